@@ -11,9 +11,14 @@ BASELINE.json configs[1] (12L/768d/12h, 36 regions + 128 tokens, V=250002, 19 ma
 tokens/sequence, ITM BCE, dropout 0.1, adam_inverse_sqrt + clip 5, bf16 compute with fp32
 master weights): jointfwd -> MLM + ITM losses -> backward (+ bucketed RCCL all-reduce for
 N>1) -> clip -> Adam.  Weak scaling: the per-GPU batch is fixed.
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     the dominant MFMA GEMM timed live with HIP events on its own stream
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, pre-warms, runs the
+--warmup steps, times the --steps steps and prints the headline (sequences/s, ms_per_step).  --full adds the
+measurements beside it, each at the cost of events or extra steps:
+  roofline     the dominant MFMA GEMM timed live with HIP events on its own stream (+ the sustained clock, 5 extra steps)
+  also.cfg3    the same step at 1024 sequences per GPU (default configuration only)
   cpu_baseline the oracle (plain PyTorch fp32 CPU restatement) on the host cores, bounded sample
+  comm         N > 1: exposed collective wait and per-collective bus bandwidth (3 extra steps)
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -175,6 +180,41 @@ def also_config(name, dropout, steps):
                 step_frac=round(value * fl / 1e12 / PEAK_BF16_TFLOPS, 4), step_frac_peak=PEAK_BF16_TFLOPS)
 
 
+DUMP_BYTES = 48 << 20     # --dump-outputs stays below this (the contract allows 64 MB)
+
+
+def dump_outputs(path, trainer, loss, rank, multi):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy - the step's total loss ('loss'),
+    each head's loss ('loss.<stat key>', e.g. 'loss.CMLM-google') and the model's fp32 parameters after the update
+    ('param.<name>').  A parameter larger than `cap` elements is sampled at sorted positions drawn from a generator seeded by
+    its name (the same positions for every build); `cap` is halved until the whole dump fits in DUMP_BYTES."""
+    import zlib
+    import numpy as np
+    from m3p_amd.trainer import _unwrap
+    if multi:       # zero1 keeps the fp32 master of the big matrices on its owner rank: gather it (a collective)
+        trainer._sync_master()
+    if rank != 0:
+        return
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    out = {'loss': loss.detach().float().reshape(-1).cpu().numpy()}
+    for key, vals in trainer.stats.items():
+        if isinstance(vals, list) and vals and torch.is_tensor(vals[-1]):
+            out['loss.' + key] = vals[-1].detach().float().reshape(-1).cpu().numpy()
+    named = sorted(_unwrap(trainer.model).named_parameters(), key=lambda kv: kv[0])
+    cap = 1 << 16
+    while 4 * sum(min(p.numel(), cap) for _, p in named) > DUMP_BYTES:
+        cap //= 2
+    for name, p in named:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).randint(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out['param.' + name] = flat.float().cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a.astype(np.float32))
+
+
 def _self_launch(args):
     """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU."""
     import socket
@@ -199,10 +239,15 @@ def main():
                          'cfg3 = configs[2] (the same model at 1024 sequences per GPU = global batch 8192 on 8 GPUs), '
                          'cfg4 = configs[3] (24L/1024d, 100 + 256; use --batch 64 --fp8), cfg5 = configs[4] shapes')
     ap.add_argument('--dropout', type=float, default=0.1)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline + sustained clock, the cfg3 line of the default '
+                         'configuration, the CPU baseline, and for N > 1 the "comm" block')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the losses and (sampled) updated parameters of the last timed step as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--instances', action='store_true',
                     help='add "gemm_instances": every GEMM instance of the step with its in-step median time (HIP events of the warm-up steps)')
-    ap.add_argument('--no-also', action='store_true', help='skip the second measurement (cfg3: 1024 sequences per GPU) of the default line')
+    ap.add_argument('--no-also', action='store_true', help='with --full: skip the second measurement (cfg3: 1024 sequences per GPU) of the default line')
     ap.add_argument('--ragged', action='store_true',
                     help='text lengths ~ U[T/2, T] with padding (the second throughput run of SURVEY 8d) instead of all = T')
     ap.add_argument('--refine-layers', type=int, default=0,
@@ -247,41 +292,30 @@ def main():
     if dp is not None:
         dp.uniform_tokens = not args.ragged      # every rank's batch has the same token-row count: no count exchange at all
 
+    last = {}
+
     def step():
-        trainer.pretrain_under_step(tup, 'google', 't2i', 'en', 1.0, 1.0, 1.0, 1.0)
+        last['loss'] = trainer.pretrain_under_step(tup, 'google', 't2i', 'en', 1.0, 1.0, 1.0, 1.0).detach()
         trainer.n_iter += 1
 
-    # Pre-warm OUTSIDE the counted warm-up until the step time is stable (the engine clock ramps up from idle over a
-    # few hundred ms, lazy allocations settle): two consecutive 3-step groups within 2 %, at most 12 groups - so the
-    # result does not depend on the caller's --warmup.
-    def timed_group(n=3):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(n):
-            step()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t) / n
-    prev, groups = timed_group(), 1
-    while groups < 12:
-        cur = timed_group()
-        groups += 1
-        stable = abs(cur - prev) <= 0.02 * prev
-        if multi:      # ranks must leave the loop together
-            flag = torch.tensor([1.0 if stable else 0.0], device='cuda')
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            stable = bool(flag.item())
-        prev = cur
-        if stable:
-            break
+    # Pre-warm OUTSIDE the counted warm-up (the engine clock ramps up from idle over a few hundred ms, lazy allocations
+    # settle), so that the result does not depend on the caller's --warmup.  A fixed count, so that the step
+    # --dump-outputs records is the same step of the same training run every time: 36 steps, where two 3-step groups
+    # agree within 2 % after 6-15.
+    groups = 12
+    for _ in range(3 * groups):
+        step()
+    torch.cuda.synchronize()
 
-    # Warm-up steps time EVERY GEMM launch with HIP events (on the launch stream) to find the dominant
+    # --full: the warm-up steps time EVERY GEMM launch with HIP events (on the launch stream) to find the dominant
     # instance; the timed region then brackets only that instance's launches (the events of all ~100
-    # GEMMs per step cost 0.9 ms of a 42-ms step).
-    ops.PROFILE = {}
+    # GEMMs per step cost 0.9 ms of a 42-ms step).  A plain run records no events.
+    profile = args.full or args.instances
+    ops.PROFILE = {} if profile else None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    warm_prof = ops.PROFILE
+    warm_prof = ops.PROFILE or {}
     # per instance: median launch time x launches - one outlier among the warm-up launches (a first launch, a clock ramp)
     # must not decide which instance the timed region brackets
     def _robust_total(evs):
@@ -299,12 +333,12 @@ def main():
                                   median_us=round(med * 1e3, 1), tflops=round(2.0 * M_ * N_ * K_ / (med * 1e-3) / 1e12, 0)))
     gemm_ms_per_step = sum(warm_agg.values()) / max(args.warmup, 1)
     ops.PROFILE_ONLY = max(warm_agg.items(), key=lambda kv: kv[1])[0] if warm_agg else None
-    if dp is not None:
+    if dp is not None and args.full:
         dp.exposed_events = []
     if multi:
         dist.barrier()
         torch.cuda.synchronize()
-    ops.PROFILE = {}
+    ops.PROFILE = {} if args.full else None
     t0 = time.perf_counter()
     host_ms = []
     for _ in range(args.steps):
@@ -317,11 +351,14 @@ def main():
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof, ops.PROFILE = ops.PROFILE, None
-    comm = None
     if multi:
         t = torch.tensor([dt], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:      # before any further step changes the model
+        dump_outputs(args.dump_outputs, trainer, last['loss'], rank, multi)
+    comm = None
+    if multi and args.full:
         evs = dp.exposed_events or []
         exposed = [a.elapsed_time(b) for a, b, _, _ in evs]
         payload = [n for _, _, n, _ in evs]
@@ -390,7 +427,7 @@ def main():
     # is the matrix peak at the 2.4 GHz ceiling; clock x 256 CUs x 4096 FLOP/clk is what the chip could do at the clock its
     # power budget actually let it hold (MI355X_MICROARCH.md, DVFS section)
     clock = None
-    if rank == 0 and not multi:
+    if rank == 0 and not multi and args.full:
         import threading
         samples, stop = [], threading.Event()
 
@@ -475,8 +512,9 @@ def main():
                                            + (', fp8 layer projections + data gradients' if args.fp8 else '')),
                                per_gpu_batch=cfg['B'], global_batch=cfg['B'] * world, seq_len=cfg['T'] + cfg['R'],
                                parallelism='dp%d' % world, flops_train_per_seq=fl, prewarm_steps=3 * groups,
-                               host_enqueue_ms_per_step=round(sorted(host_ms)[len(host_ms) // 2], 2)),
-                   roofline=roof)
+                               host_enqueue_ms_per_step=round(sorted(host_ms)[len(host_ms) // 2], 2)))
+        if args.full:
+            out['roofline'] = roof
         if instances is not None:
             out['gemm_instances'] = instances
         if comm is not None:
@@ -487,14 +525,14 @@ def main():
             out['config']['parallelism'] = 'dp1 wrapped (M3P_DP_FORCE: one rank running its collectives over RCCL; development run)'
         plain_default = (world == 1 and not forced and args.config == 'cfg2' and args.batch is None and not args.fp8
                          and not args.ragged and not args.refine_layers)
-        if plain_default and not args.no_also:
+        if args.full and plain_default and not args.no_also:
             #  the 0.40-of-roofline target is stated on 1024 sequences per GPU (BASELINE configs[2]'s per-GPU share):
             # the default line carries that number too, so that it is not a builder-only measurement.  Same model, same step,
             # B = 1024; its own pre-warm, then 20 timed steps between synchronisations (~2.5 s).
-            del trainer, tup, step, timed_group
+            del trainer, tup, step, last
             torch.cuda.empty_cache()
             out['also'] = dict(cfg3=also_config('cfg3', args.dropout, 20))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             trainer = None
             torch.cuda.empty_cache()
             out['cpu_baseline'] = cpu_baseline(cfg, args.dropout)
