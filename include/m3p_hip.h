@@ -18,7 +18,7 @@
  *   - the library never allocates and keeps no per-call state: re-entrant (the autograd engine calls from its
  *     own thread).  What IS process-global: idempotent one-time initialisation (the CU count, the dynamic-LDS
  *     attribute of each kernel), the two schedule setters m3p_set_persistent_grid / m3p_set_tile_queue and the developer
- *     switch m3p_debug_set_variant (A/B runs of kernel generations; never called by the product).
+ *     switches m3p_debug_set_variant / m3p_debug_attn_variant (tests and A/B tools; never called by the product).
  */
 #ifndef M3P_HIP_H
 #define M3P_HIP_H
@@ -490,13 +490,13 @@ enum {
 M3P_API int m3p_gemm_nt_plan(int M, int N, int K, int epilogue);
 M3P_API int m3p_gemm_wgrad_plan(int M, int N, int K);
 
-/* Developer switch (process-wide, NEVER called by the product; tools/ab_*.py and M3P_VARIANT in m3p_amd/lib.py use it for A/B
- * runs of kernel generations): low byte 0 = force the 128 x 128 kernels, 1 = the tables above (default), 2 = four-wave NT
- * wherever it applies, 3 = ring kernels, 6 = eight-wave NT, 7 = round 1's choice, 9 = default without the skinny kernel; the
- * higher bits are ablation flags of the timeline builds.  Every launch reads it: set it only with no GEMM call in flight. */
+/* Developer switch (process-wide, NEVER called by the product; tests/test_gemm.py and tools/ab_*.py use it): 1 = the tables
+ * above (default), 2 = four-wave NT wherever it applies, 6 = eight-wave NT wherever it applies; any other value means 1.
+ * Every launch reads it: set it only with no GEMM call in flight. */
 M3P_API void m3p_debug_set_variant(int v);
-/* The same kind of switch for the attention kernels: bit 0 = the two-phase backward (scores recomputed in both phases,
- * rounds 1-4) instead of the one-pass form for the M3P sequence (tools/ab_attn.py). */
+/* The same kind of switch for the attention backward of the M3P sequence (tests/test_attention.py, tools/ab_attn.py):
+ * 0 = the persistent one-pass form (default), bit 0 = the two-phase form (scores recomputed in both phases, rounds 1-4),
+ * bit 1 = the plain one-pass form. */
 M3P_API void m3p_debug_attn_variant(int v);
 
 /* ------------------------------------------------------------------------------------

@@ -17,60 +17,17 @@
 //   * output is token-major [M, d] (head-interleaved) so out_lin consumes it directly.
 #include "common.hpp"
 
-#ifndef M3P_ATTN_SKIP_PAD
-#define M3P_ATTN_SKIP_PAD 1
-#endif
-#ifndef M3P_ATTN_WL_BATCH
-#define M3P_ATTN_WL_BATCH 1     // forward: a key tile's four keep words written by one statement (one s_nop 3 instead of four)
-#endif
 
 namespace {
 
-// -DM3P_ATTN_TL: debug build that stamps s_memtime at the forward kernel's phase boundaries
-// (tools/attn_timeline.py reads them back through m3p_debug_attn_timeline).
-#ifdef M3P_ATTN_TL
-__device__ unsigned long long g_attn_tl[4096 * 4 * 16];
-#define ATL(k) do { if (blockIdx.x < 4096 && lane == 0 && wid < 4) g_attn_tl[(blockIdx.x * 4 + wid) * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-// backward kernel (the last launch wins the buffer): 0 start, 1 D / lse done, 2 Q / dO staged (barrier passed), 3 phase A loop done,
-// 4 barrier passed, 5 K / V staged (barrier passed), 6 phase B loop done, 7 end; sums: 8 waiting for the owned block's K / V rows (A),
-// 9 the same for Q / dO rows (B), 10 phase A output stores issued, 11 phase B output stores issued
-#define BTL(i) do { tl[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#define BTL_SUM(i, t0) do { tl[i] += __builtin_amdgcn_s_memtime() - (t0); } while (0)
-#else
-#define ATL(k) do { } while (0)
-#define BTL(k) do { } while (0)
-#define BTL_SUM(i, t0) do { } while (0)
-#endif
+// the two-phase backward of the M3P sequence (36 regions + 128 tokens: 11 tiles, 6 steps): four-wave workgroups, and the waves
+// per SIMD their register allocation must leave room for
+constexpr int ATTN_BWD_NW = 4;
+constexpr int ATTN_BWD_WPS = 3;
 
-// -DM3P_ATTN_BWDP_ABL=<bits>: timing ablations of the persistent backward's phase A (results are garbage): 1 no softmax / dropout
-// arithmetic, 2 the Q / dO row fragments are not read from LDS (registers stand in), 4 likewise
-// the transposed Q / dO fragments, 8 no dS^T store, 16 no MFMA in phase A
-#ifndef M3P_ATTN_BWDP_FLUSH16
-#define M3P_ATTN_BWDP_FLUSH16 0   // 1: the persistent backward's bias sums by four full butterflies per value (round 5)
-#endif
-#ifndef M3P_ATTN_BWDP_ABL
-#define M3P_ATTN_BWDP_ABL 0
-#endif
-#ifndef M3P_ATTN_BWD_NEXTFRAG
-#define M3P_ATTN_BWD_NEXTFRAG 1
-#endif
-#ifndef M3P_ATTN_BWD_TRPRE
-#define M3P_ATTN_BWD_TRPRE 0
-#endif
-#ifndef M3P_ATTN_BWD_KB
-#define M3P_ATTN_BWD_KB 1
-#endif
-#ifndef M3P_ATTN_BWD_KBQ
-#define M3P_ATTN_BWD_KBQ M3P_ATTN_BWD_KB
-#endif
-#ifndef M3P_ATTN_BWD_WPS
-#define M3P_ATTN_BWD_WPS 3      // waves per SIMD the register allocation must leave room for (four-wave workgroups)
-#endif
-#ifndef M3P_ATTN_BWD_NW
-#define M3P_ATTN_BWD_NW 4
-#endif
-
-static int g_attn_variant = 0;      // developer switch (m3p_debug_attn_variant): bit 0 = the two-phase backward for the M3P sequence (A/B runs)
+// developer switch (m3p_debug_attn_variant, tests/test_attention.py): bit 0 = the two-phase backward for the M3P sequence,
+// bit 1 = the plain one-pass backward instead of the persistent one
+static int g_attn_variant = 0;
 
 template <int DH> struct AttnCfg {
   static constexpr int ROWB = DH * 2;        // bytes per K/V row in LDS
@@ -210,10 +167,6 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
   const bf16* Vg = Qg + 2 * dmodel;
   char* sK = smem;
   char* sV = smem + nt * 16 * Cf::ROWB;
-  ATL(0);
-#ifdef M3P_ATTN_TL
-  if (blockIdx.x < 4096 && lane == 0 && wid < 4) g_attn_tl[(blockIdx.x * 4 + wid) * 16 + 14] = __builtin_amdgcn_s_memrealtime();
-#endif
   stage_rows<DH>(Kg, ld, S, nt * 16, sK, wid, lane, NW);
   stage_rows<DH>(Vg, ld, S, nk * 32, sV, wid, lane, NW);
   const int fq = lane & 15, fg = lane >> 4;
@@ -228,9 +181,7 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       qnext[kk] = *reinterpret_cast<const bf16x8*>(Qg + (size_t)qc0 * ld + 32 * kk + 8 * fg);
   }
   const int klen = keylen[b];
-  ATL(1);
   __syncthreads();
-  ATL(2);
 
   // K fragment: row 16t + fq, chunk (4kk + fg) swizzled with row & 7 == fq & 7
   int k_off[Cf::KK];
@@ -269,7 +220,6 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
           s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[t], 0, 0, 0);
         }
     }
-    if (qb == wrot) ATL(3);
     // ---- softmax over keys (key = 16t + 4fg + r) for query column fq; tiles t >= nt are padding
     constexpr float kLog2e = 1.4426950408889634f;
     float mx = -INFINITY;
@@ -305,7 +255,6 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.0f / sum;
-    if (qb == wrot) ATL(4);
     const uint32_t rbase = (uint32_t)((b * H + h) * S + qc) * (uint32_t)S;
     // one hash per PAIR of keys (common.hpp): key k of query row q is element rbase + k; with an even row length S every
     // row starts on an even element and the lane's four consecutive keys 16 t + 4 fg + r are two whole pairs
@@ -361,23 +310,13 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
           if (t < nt) {
             v = s[t][r] * invk;
             if (DROP) {
-#if defined(M3P_ATTN_ABL) && (M3P_ATTN_ABL & 2)       // (timing ablation: no hash - a keep decision that costs nothing)
-              const bool keep = ((lane + j) & 15) != 0;
-#else
               const bool keep = kq[j];
-#endif
               kw[r] = __builtin_amdgcn_ballot_w64(keep);
-#if !M3P_ATTN_WL_BATCH
-              asm("s_nop 3\n\tv_writelane_b32 %0, %2, %4\n\tv_writelane_b32 %1, %3, %4"
-                  : "+v"(mlo[(4 * t + r) >> 6]), "+v"(mhi[(4 * t + r) >> 6])
-                  : "s"((uint32_t)kw[r]), "s"((uint32_t)(kw[r] >> 32)), "i"((4 * t + r) & 63));
-#endif
               v = keep ? v : 0.f;
             }
           }
           p[j] = v;
         }
-#if M3P_ATTN_WL_BATCH && !(defined(M3P_ATTN_ABL) && (M3P_ATTN_ABL & 1))     // (timing ablation bit 0: no ballot words - backward would read garbage)
         if (DROP && t < nt) {
           // the four ballots of a key tile dropped into lanes 4 t .. 4 t + 3 of the word registers by ONE statement: a
           // v_writelane that reads an SGPR a v_cmp has just written gets the stale value without wait states (measured; the
@@ -389,7 +328,6 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
                 "s"((uint32_t)kw[2]), "s"((uint32_t)(kw[2] >> 32)), "s"((uint32_t)kw[3]), "s"((uint32_t)(kw[3] >> 32)),
                 "i"((4 * t) & 63), "i"((4 * t + 1) & 63), "i"((4 * t + 2) & 63), "i"((4 * t + 3) & 63));
         }
-#endif
       }
       pf[kk] = bf16x8{(bf16)p[0], (bf16)p[1], (bf16)p[2], (bf16)p[3], (bf16)p[4], (bf16)p[5], (bf16)p[6], (bf16)p[7]};
     }
@@ -398,7 +336,6 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       for (int g = 0; g < MW; ++g)
         if (64 * g + lane < 4 * nt) mrow[64 * g + lane] = ((unsigned long long)mhi[g] << 32) | mlo[g];
     }
-    if (qb == wrot) ATL(5);
     // ---- O^T[d][q] = sum_key V[key][d] P[q][key]
     f32x4 o[Cf::NT];
 #pragma unroll
@@ -414,7 +351,6 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
         }
       }
     }
-    if (qb == wrot) ATL(6);
     {
       bf16x4 ob[Cf::NT];
 #pragma unroll
@@ -422,12 +358,7 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       store_row_widened<Cf::NT>(ctx + (size_t)(b * S + min(q, S - 1)) * dmodel + h * DH, fg, q < S, ob);      // (16-byte stores)
       if (q < S && fg == 0) lse[(size_t)(b * H + h) * S + q] = mx + __logf(sum);
     }
-    if (qb == wrot) ATL(7);
   }
-  ATL(8);
-#ifdef M3P_ATTN_TL
-  if (blockIdx.x < 4096 && lane == 0 && wid < 4) g_attn_tl[(blockIdx.x * 4 + wid) * 16 + 15] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -459,7 +390,7 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
 // are fetched once: 516 MB per launch instead of 813), and phase B is four MFMAs per 32-key step, dQ^T = K^T dS^T, both
 // operands through transposing LDS reads - no second QK^T / dO V^T, no second softmax, no V tile, no Q / dO fragments.
 template <int DH, int KT, bool DROP, bool MASK, int NKC, int NTC, int NW = 4, int KB = 1, int KBQ = KB, bool ONEPASS = false>
-__global__ __launch_bounds__(NW * 64, NTC == 11 ? M3P_ATTN_BWD_WPS : ((NW == 8 || KB == 2) ? 2 : 3))   // NW = 4: three 49-KB workgroups per CU; 8: one ~100-KB workgroup (long S); 12 (ONEPASS): one 143-KB workgroup, three waves per SIMD
+__global__ __launch_bounds__(NW * 64, NTC == 11 ? ATTN_BWD_WPS : ((NW == 8 || KB == 2) ? 2 : 3))   // NW = 4: three 49-KB workgroups per CU; 8: one ~100-KB workgroup (long S); 12 (ONEPASS): one 143-KB workgroup, three waves per SIMD
 void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keylen, const bf16* __restrict__ ctx,
                      const bf16* __restrict__ dctx, const float* __restrict__ lse,
                      const unsigned long long* __restrict__ keepmask, bf16* __restrict__ dqkv,
@@ -477,11 +408,7 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
   const int nt = NTC ? NTC : ((S + 15) >> 4);
   const int nk = NKC ? NKC : ((S + 31) >> 5);
   const size_t ld = 3 * (size_t)dmodel;
-#ifdef M3P_ATTN_ALIAS      // experiment: every workgroup reads the operands of batch rows 0..3 (cache-resident), writes its own
-  const int b_rd = b & 3;
-#else
   const int b_rd = b;
-#endif
   const bf16* Qg = qkv + (size_t)b_rd * S * ld + h * DH;
   const bf16* Kg = Qg + dmodel;
   const bf16* Vg = Qg + 2 * dmodel;
@@ -548,15 +475,9 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
   // 16-row tile t lies wholly behind the sequence (S = 164: the 12th tile, rows 176..191, of the six 32-row steps):
   // with the tile count known at compile time the code for it simply is not generated; as a run-time test it was
   // only worth it without the keep-bit words (measured slower with them)
-#define PAD_TILE(t) (NTC ? (t) >= NTC : (M3P_ATTN_SKIP_PAD && !MASK && (t) >= nt))
+#define PAD_TILE(t) (NTC ? (t) >= NTC : (!MASK && (t) >= nt))
   constexpr float kLog2e = 1.4426950408889634f;
   constexpr float kMasked = -1.0e30f;    // score of a masked key: exp2 of it is exactly 0
-#ifdef M3P_ATTN_TL
-  unsigned long long tl[16];
-  for (int i = 0; i < 16; ++i) tl[i] = 0;
-  unsigned long long tw;
-#endif
-  BTL(0);
   // Q and dO tiles are requested first (LDS-DMA, asynchronous), then this wave's first K / V fragments (they do not depend on
   // LDS).  D[q] = rowsum(dO * O) is taken from the dO rows THIS wave staged (a wave may read its own LDS-DMA rows after its own
   // vmcnt(0), no barrier needed) times the matching O chunks fetched from global beside them: dO is read from HBM once
@@ -586,7 +507,7 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
     }
   };
   // (not with dropout re-hashed instead of read from the forward's keep bits: that variant has no registers to spare)
-  constexpr bool kNextFrag = M3P_ATTN_BWD_NEXTFRAG && NKC != 0 && NTC != 0 && !(DROP && !MASK);      // (nor the less specialised instantiations: they spill with 16 more)
+  constexpr bool kNextFrag = NKC != 0 && NTC != 0 && !(DROP && !MASK);      // (nor the less specialised instantiations: they spill with 16 more)
   bf16x8 kfn[KB][Cf::KK], vfn[KB][Cf::KK];     // the next owned block's, in flight while this one is computed
   auto load_kv_next = [&](int u, int kb) {
     const int keyc = min(kb * 16 + fq, S - 1);
@@ -641,10 +562,8 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       }
     }
   }
-  BTL(1);
   // ================= phase A: dV, dK (wave owns key blocks) =================
   __syncthreads();
-  BTL(2);
 
   // keep-bit words of a step are requested two steps ahead (unrolled steps only: the buffers alternate at compile time): the
   // words are read once per launch, so every one of them is an L2 miss the step would otherwise wait for in full
@@ -680,11 +599,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
         load_kv(u, kb0 + u);
       }
     }
-#ifdef M3P_ATTN_TL
-    tw = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    BTL_SUM(8, tw);
-#endif
     // dV^T[d][key] = sum_q dO[q][d] Pd[q][key] ; dK^T[d][key] = sum_q Q[q][d] dS[q][key]
     // streamed over 32-query steps: P / dS of a step are produced (lane = key column, query
     // 16t + 4fg + r) and consumed as MFMA B operands at once — nothing S x S is held
@@ -697,13 +611,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
     for (int kq = 0; kq < nk; ++kq) {
       // the MFMA chains of a step (scores and dPd of both 16-query tiles, of every owned block) are issued interleaved,
       // k-step outermost, so that no MFMA waits on the one just issued
-#ifdef M3P_ATTN_TL
-      __builtin_amdgcn_sched_barrier(0);
-      unsigned long long ts0 = __builtin_amdgcn_s_memtime(), ts1;
-#define STEP_SEG(i) do { __builtin_amdgcn_sched_barrier(0); ts1 = __builtin_amdgcn_s_memtime(); tl[i] += ts1 - ts0; ts0 = ts1; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define STEP_SEG(i) do { } while (0)
-#endif
       f32x4 scA[KB][2], dpA[KB][2], dnegA[2];
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
@@ -732,20 +639,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
             dpA[u][hf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, vf[u][kk], dpA[u][hf], 0, 0, 0);   // dPd[q][key]
           }
         }
-      }
-      STEP_SEG(12);      // 12: fragments read, score / dPd MFMAs issued
-      // the transposed Q / dO fragments of the first d-tiles are requested before the softmax arithmetic instead of behind it
-      constexpr int kTrPre = M3P_ATTN_BWD_TRPRE;
-      bf16x8 qTp[kTrPre ? kTrPre : 1], dTp[kTrPre ? kTrPre : 1];
-      if (kTrPre) {
-#pragma unroll
-        for (int n = 0; n < kTrPre; ++n) {
-          const char* pq = s0 + kq * 32 * Cf::ROWB + t_off[n];
-          const char* pdo = s1 + kq * 32 * Cf::ROWB + t_off[n];
-          qTp[n] = cat8(lds_tr16(pq), lds_tr16(pq + 16 * Cf::ROWB));
-          dTp[n] = cat8(lds_tr16(pdo), lds_tr16(pdo + 16 * Cf::ROWB));
-        }
-        __builtin_amdgcn_sched_barrier(0);
       }
       bf16x8 pfrag[KB], sfrag[KB];
 #pragma unroll
@@ -804,7 +697,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
           }
         }
       }
-      STEP_SEG(13);      // 13: P / dS built (waits for the MFMA results, the keep words, lse / D)
       if (kPreA) {      // (behind the last step of a block: the first steps of the next owned block, clamped on the last one)
         if (kq + 2 < nk) mask_words_A(kb0, kq + 2, kq & 1);
         else mask_words_A(kb0 + NW * KB, kq + 2 - nk, kq & 1);
@@ -813,20 +705,16 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       for (int n = 0; n < Cf::NT; ++n) {
         const char* pq = s0 + kq * 32 * Cf::ROWB + t_off[n];
         const char* pdo = s1 + kq * 32 * Cf::ROWB + t_off[n];
-        const bf16x8 qT = (n < kTrPre) ? qTp[n < kTrPre ? n : 0] : cat8(lds_tr16(pq), lds_tr16(pq + 16 * Cf::ROWB));
-        const bf16x8 dT = (n < kTrPre) ? dTp[n < kTrPre ? n : 0] : cat8(lds_tr16(pdo), lds_tr16(pdo + 16 * Cf::ROWB));
+        const bf16x8 qT = cat8(lds_tr16(pq), lds_tr16(pq + 16 * Cf::ROWB));
+        const bf16x8 dT = cat8(lds_tr16(pdo), lds_tr16(pdo + 16 * Cf::ROWB));
 #pragma unroll
         for (int u = 0; u < KB; ++u) {
           dv[u][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dT, pfrag[u], dv[u][n], 0, 0, 0);
           dk[u][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT, sfrag[u], dk[u][n], 0, 0, 0);
         }
       }
-      STEP_SEG(14);      // 14: transposed fragments read, dV / dK MFMAs issued
       if (NKC) __builtin_amdgcn_sched_barrier(0);   // unrolled steps stay in order: no register blow-up from hoisted loads
     }
-#ifdef M3P_ATTN_TL
-    tw = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
     for (int u = 0; u < KB; ++u) {
       bf16x4 kb4[Cf::NT], vb4[Cf::NT];
@@ -843,19 +731,15 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       store_row_widened<Cf::NT>(dKg + (size_t)keyc[u] * ld, fg, ok, kb4);      // (16-byte stores: see store_row_widened)
       store_row_widened<Cf::NT>(dVg + (size_t)keyc[u] * ld, fg, ok, vb4);
     }
-    BTL_SUM(10, tw);
   }
-  BTL(3);
   if (dbias_qkv) bias_flush(2);
   __syncthreads();   // everyone done with Q / dO tiles
-  BTL(4);
 
   if constexpr (ONEPASS) {
     // ================= phase B, one-pass form: dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q] =================
     // A operand: K^T through transposing reads of the K tile (rows = keys), B operand: dS^T through transposing reads of the
     // tile phase A left (rows = keys, this wave's 16 query columns) - lane fq holds query column fq, keys 4 fg + r of both
     // 16-key tiles of the step, exactly the contraction order of the K^T fragment.
-    BTL(5);
     for (int qb = wid; qb < nt; qb += NW) {
       f32x4 dq[Cf::NT];
 #pragma unroll
@@ -884,7 +768,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       }
       store_row_widened<Cf::NT>(dQg + (size_t)min(q, S - 1) * ld, fg, q < S, qb4);
     }
-    BTL(6);
   } else {
   // ================= phase B: dQ (wave owns query blocks) =================
   stage_rows<DH>(Kg, ld, S, nk * 32, s0, wid, lane, NW);
@@ -912,7 +795,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
     for (int u = 0; u < KBQ; ++u) load_qd(u, wrot * KBQ + u);
   }
   __syncthreads();
-  BTL(5);
 
   for (int qb0 = wrot * KBQ; qb0 < nt; qb0 += NW * KBQ) {
     int q[KBQ], qc[KBQ];
@@ -936,11 +818,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       dq_[u] = in ? sD[min(q[u], nk * 32 - 1)] : 0.f;
       rbase[u] = (uint32_t)((b * H + h) * S + qc[u]) * (uint32_t)S;
     }
-#ifdef M3P_ATTN_TL
-    tw = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    BTL_SUM(9, tw);
-#endif
     int klen_it = klen;
     asm volatile("" : "+s"(klen_it));   // opaque per query block: keeps the key-mask tests inside the loop
     // keep-bit words (wave-uniform: scalar loads, one s_load_dwordx16 per step) are requested one step ahead.  (They share
@@ -1043,9 +920,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       }
       if (NKC) __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef M3P_ATTN_TL
-    tw = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
     for (int u = 0; u < KBQ; ++u) {
       bf16x4 qb4[Cf::NT];
@@ -1059,9 +933,7 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       }
       store_row_widened<Cf::NT>(dQg + (size_t)qc[u] * ld, fg, ok, qb4);
     }
-    BTL_SUM(11, tw);
   }
-  BTL(6);
   }      // (two-phase form)
 
   // ---- bias gradients: column sums of the bf16 dQ / dV rows this block wrote (k: zero, see above)
@@ -1078,11 +950,6 @@ void attn_bwd_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keyle
       }
     }
   }
-#ifdef M3P_ATTN_TL
-  BTL(7);
-  if (lane == 0 && blockIdx.x < 4096 && wid < 4)
-    for (int i = 0; i < 16; ++i) g_attn_tl[(blockIdx.x * 4 + wid) * 16 + i] = tl[i];
-#endif
 }
 
 #undef PAD_TILE
@@ -1105,8 +972,7 @@ __global__ __launch_bounds__(768, 3)
 void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ keylen, const bf16* __restrict__ ctx,
                        const bf16* __restrict__ dctx, const float* __restrict__ lse,
                        const unsigned long long* __restrict__ keepmask, bf16* __restrict__ dqkv,
-                       float* __restrict__ dbias_qkv, int S, int H, int dmodel, int nheads, float qscale, float inv_keep,
-                       int stagger) {
+                       float* __restrict__ dbias_qkv, int S, int H, int dmodel, int nheads, float qscale, float inv_keep) {
   constexpr int DH = 64, NW = 12, NKC = 6, NTC = 11, NR = NKC * 32;
   using Cf = AttnCfg<DH>;
   constexpr int DSP = NTC * 32;                      // row pitch of dS^T: 352 B (see attn_bwd_kernel, ONEPASS)
@@ -1181,16 +1047,6 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
   // half-mirror) - one bank-masked v_add_f32_dpp per kept value and side; the last two stages are plain quad butterflies on the
   // four values left.  16 + 8 + 4 + 4 adds instead of 64 + 32; lanes 0 / 4 / 8 / 12 of a row end with tiles 0 / 1 / 2 / 3.
   auto bias_flush = [&](float* slot, int part) {
-#if M3P_ATTN_BWDP_FLUSH16
-#pragma unroll
-    for (int n = 0; n < Cf::NT; ++n) {
-      f32x4 x = bsum[n];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) x[r] = row16_sum(x[r]);
-      if (fq == 0) *reinterpret_cast<f32x4*>(slot + part * DH + 16 * n + 4 * fg) = x;
-      bsum[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#else
     float t[2][4], u[4];
 #pragma unroll
     for (int n = 0; n < 2; ++n)
@@ -1217,7 +1073,6 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
     if ((fq & 3) == 0) *reinterpret_cast<f32x4*>(slot + part * DH + 16 * (fq >> 2) + 4 * fg) = x;
 #pragma unroll
     for (int n = 0; n < Cf::NT; ++n) bsum[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
   };
   auto bias_reduce = [&](const float* slots, int h) {
     for (int i = tid; i < 3 * DH; i += NW * 64) {
@@ -1248,19 +1103,10 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
   // staggered start: the workgroups of a launch all fetch, then all compute.  Four phases a fraction of a head apart spread the
   // fetch bursts (183.1 -> 180.5 us at 2 x 1024 clocks per phase, nothing beyond: tools/ab_attn.py, profiles/r05_attn_bwd_ab.txt);
   // the late starters' tail is 1 / 12 of what it was in the GEMMs (twelve heads per workgroup).
-  for (int i = 0; i < (int)((blockIdx.x >> 3) & 3) * stagger; ++i) __builtin_amdgcn_s_sleep(16);
+  constexpr int kStagger = 2;
+  for (int i = 0; i < (int)((blockIdx.x >> 3) & 3) * kStagger; ++i) __builtin_amdgcn_s_sleep(16);
   request_head(hd);
   int par = 0, prev_h = -1;
-  // -DM3P_ATTN_TL: s_memtime sums per segment over this workgroup's heads (tools/attn_bwd_p_timeline.py): 0 wait for the head's
-  // requests, 1 D / lse + barrier 1, 2 previous head's bias sums + stores, K request, 3 phase A, 4 bias flush + barrier 2,
-  // 5 next head's requests, 6 phase B, 7 heads
-#ifdef M3P_ATTN_TL
-  unsigned long long ptl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long pt0 = __builtin_amdgcn_s_memtime(), pt1;
-#define PSEG(k) do { __builtin_amdgcn_sched_barrier(0); pt1 = __builtin_amdgcn_s_memtime(); ptl[k] += pt1 - pt0; pt0 = pt1; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define PSEG(k) do { } while (0)
-#endif
   for (;;) {
     const int b = hd / H, h = hd - b * H;
     bf16* dQg = dqkv + (size_t)b * S * ld + h * DH;
@@ -1274,7 +1120,6 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
     //  behind the NEXT head's first barrier, with a whole phase A to complete in before anything waits for vmcnt again.)
     __builtin_amdgcn_s_waitcnt(0x0F70);                               // vmcnt(0)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // (the tiles' transfers are invisible to the compiler: this one cannot be dropped)
-    PSEG(0);
 #pragma unroll
     for (int j = 0; j < kNIW; ++j) {
       const int i = wid + j * NW;
@@ -1293,12 +1138,10 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                  // B1: Q, dO, D, lse in place; phase B of the previous head over
     asm volatile("" ::: "memory");
-    PSEG(1);
     if (prev_h >= 0 && dbias_qkv) bias_reduce(sB + (par ^ 1) * (NW * 3 * DH), prev_h);
     if (prev_h >= 0) store_head(dQg_prev);
     dQg_prev = dQg;
     stage_rows_hidden<DH>(Kg, ld, S, NR, sK, wid, lane, NW);       // lands under phase A
-    PSEG(2);
     // ================= phase A: dV, dK, dS^T (this wave: key block `wid`) =================
     if (wid < NTC) {
       const float kbias = (key < klen) ? 0.f : kMasked;
@@ -1321,13 +1164,8 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
           for (int hf = 0; hf < 2; ++hf) {
             const int t = 2 * kq + hf;
             if (PAD_TILE(t)) continue;
-            const bf16x8 qf = (M3P_ATTN_BWDP_ABL & 2) ? kf[kk ^ 1] : *reinterpret_cast<const bf16x8*>(s0 + t * 16 * Cf::ROWB + r_off[kk]);
-            const bf16x8 df = (M3P_ATTN_BWDP_ABL & 2) ? vf[kk ^ 1] : *reinterpret_cast<const bf16x8*>(s1 + t * 16 * Cf::ROWB + r_off[kk]);
-            if (M3P_ATTN_BWDP_ABL & 16) {
-              scA[hf] += f32x4{(float)qf[0], (float)qf[1], (float)kf[kk][0], (float)kf[kk][1]};
-              dpA[hf] += f32x4{(float)df[0], (float)df[1], (float)vf[kk][0], (float)vf[kk][1]};
-              continue;
-            }
+            const bf16x8 qf = *reinterpret_cast<const bf16x8*>(s0 + t * 16 * Cf::ROWB + r_off[kk]);
+            const bf16x8 df = *reinterpret_cast<const bf16x8*>(s1 + t * 16 * Cf::ROWB + r_off[kk]);
             scA[hf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf[kk], scA[hf], 0, 0, 0);   // S[q][key]
             dpA[hf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, vf[kk], dpA[hf], 0, 0, 0);   // dPd[q][key]
           }
@@ -1345,11 +1183,6 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int q = 16 * t + 4 * fg + r;
-            if (M3P_ATTN_BWDP_ABL & 1) {
-              pd2[hf][r] = scA[hf][r];
-              ds2[hf][r] = dpA[hf][r];
-              continue;
-            }
             const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(scA[hf][r], kLog2e, -sL[q]));   // padded q: lse = +inf -> 0
             if (DROP) {      // p = P / keep here, dneg = -D keep
               const float pd = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, p) & bit_to_mask(kbits, r));
@@ -1368,7 +1201,7 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
         // dS^T[key][query]: this lane's four values of a tile are four consecutive queries of its key row
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-          if (PAD_TILE(2 * kq + hf) || (M3P_ATTN_BWDP_ABL & 8)) continue;
+          if (PAD_TILE(2 * kq + hf)) continue;
           *reinterpret_cast<bf16x4*>(sDS + key * DSP + (32 * kq + 16 * hf + 4 * fg) * 2) =
               hf ? bf16x4{sfrag[4], sfrag[5], sfrag[6], sfrag[7]} : bf16x4{sfrag[0], sfrag[1], sfrag[2], sfrag[3]};
         }
@@ -1376,13 +1209,8 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
         for (int n = 0; n < Cf::NT; ++n) {
           const char* pq = s0 + kq * 32 * Cf::ROWB + t_off[n];
           const char* pdo = s1 + kq * 32 * Cf::ROWB + t_off[n];
-          const bf16x8 qT = (M3P_ATTN_BWDP_ABL & 4) ? kf[n & 1] : cat8(lds_tr16(pq), lds_tr16(pq + 16 * Cf::ROWB));
-          const bf16x8 dT = (M3P_ATTN_BWDP_ABL & 4) ? vf[n & 1] : cat8(lds_tr16(pdo), lds_tr16(pdo + 16 * Cf::ROWB));
-          if (M3P_ATTN_BWDP_ABL & 16) {
-            dv[n] += f32x4{(float)dT[0], (float)pfrag[0], (float)dT[4], (float)pfrag[4]};
-            dk[n] += f32x4{(float)qT[0], (float)sfrag[0], (float)qT[4], (float)sfrag[4]};
-            continue;
-          }
+          const bf16x8 qT = cat8(lds_tr16(pq), lds_tr16(pq + 16 * Cf::ROWB));
+          const bf16x8 dT = cat8(lds_tr16(pdo), lds_tr16(pdo + 16 * Cf::ROWB));
           dv[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dT, pfrag, dv[n], 0, 0, 0);
           dk[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT, sfrag, dk[n], 0, 0, 0);
         }
@@ -1395,17 +1223,14 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
         if (dbias_qkv) bias_acc(n, key < S ? vb4[n] : bf16x4{0, 0, 0, 0});
       }
     }
-    PSEG(3);
     if (dbias_qkv) bias_flush(sBh + wid * 3 * DH, 2);
     // B2: dS^T complete, the K tile landed (each wave waits for its own pieces; no store is outstanding - dK / dV go out below)
     __builtin_amdgcn_s_waitcnt(0);                       // vmcnt(0) expcnt(0) lgkmcnt(0)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    PSEG(4);
     const int next = hd + gridDim.x;
     if (next < nheads) request_head(next);             // Q / dO tiles are free: everyone is past phase A
-    PSEG(5);
     // ================= phase B: dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q] (this wave: query block `wid`) =================
     if (wid < NTC) {
       f32x4 dq[Cf::NT];
@@ -1431,10 +1256,6 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
       }
     }
     if (dbias_qkv) bias_flush(sBh + wid * 3 * DH, 0);
-    PSEG(6);
-#ifdef M3P_ATTN_TL
-    ptl[7] += 1;
-#endif
     prev_h = h;
     par ^= 1;
     if (next >= nheads) break;
@@ -1445,11 +1266,6 @@ void attn_bwd_p_kernel(const bf16* __restrict__ qkv, const int* __restrict__ key
     __syncthreads();
     bias_reduce(sB + (par ^ 1) * (NW * 3 * DH), prev_h);
   }
-#ifdef M3P_ATTN_TL
-  if (lane == 0 && wid < 4 && blockIdx.x < 4096)
-    for (int k = 0; k < 8; ++k) g_attn_tl[(blockIdx.x * 4 + wid) * 16 + k] = ptl[k];
-#endif
-#undef PSEG
 #undef PAD_TILE
 }
 
@@ -1486,14 +1302,11 @@ int launch_bwd(const bf16* qkv, const int* keylen, const bf16* ctx, const bf16* 
                uint32_t seed, uint32_t thresh24, float inv_keep, hipStream_t st) {
   const int nk = (S + 31) / 32;
   const bool wide = (size_t)2 * ((size_t)2 * nk * 32 * DH * 2) > 160 * 1024;   // one workgroup per CU anyway: eight waves
-  // the M3P sequence (36 regions + 128 tokens: 11 tiles, 6 steps): M3P_ATTN_BWD_KB blocks per wave pass, M3P_ATTN_BWD_NW waves
+  // the M3P sequence (36 regions + 128 tokens: 11 tiles, 6 steps): one block per wave pass, ATTN_BWD_NW waves
   const bool m3p_seq = nk == 6 && (S + 15) / 16 == 11;
-#ifndef M3P_ATTN_BWD_ONEPASS
-#define M3P_ATTN_BWD_ONEPASS 1
-#endif
   // the one-pass form: 64-wide heads of the M3P sequence, keep bits from the forward pass or no dropout
-  const bool onepass = M3P_ATTN_BWD_ONEPASS && m3p_seq && DH == 64 && (!thresh24 || keepmask) && !(g_attn_variant & 1);
-  const int nwaves = wide ? 8 : (onepass ? 12 : (m3p_seq ? M3P_ATTN_BWD_NW : 4));
+  const bool onepass = m3p_seq && DH == 64 && (!thresh24 || keepmask) && !(g_attn_variant & 1);
+  const int nwaves = wide ? 8 : (onepass ? 12 : (m3p_seq ? ATTN_BWD_NW : 4));
   const size_t lds = (size_t)2 * nk * 32 * DH * 2 + (size_t)2 * nk * 32 * sizeof(float) + 3 * nwaves * DH * sizeof(float) +
                      (onepass ? (size_t)nk * 32 * DH * 2 + (size_t)11 * 16 * 11 * 32 : 0);
 #define M3P_ATTN_BWD(KT, DROP, MASK)                                                                            \
@@ -1501,7 +1314,7 @@ int launch_bwd(const bf16* qkv, const int* keylen, const bf16* ctx, const bf16* 
     auto kern = attn_bwd_kernel<DH, KT, DROP, MASK, 0, 0>;                                                      \
     if (wide) kern = attn_bwd_kernel<DH, KT, DROP, MASK, 0, 0, 8>;                                              \
     if (nk == 6) kern = attn_bwd_kernel<DH, KT, DROP, MASK, 6, 0>;                                              \
-    if (m3p_seq) kern = attn_bwd_kernel<DH, KT, DROP, MASK, 6, 11, M3P_ATTN_BWD_NW, M3P_ATTN_BWD_KB, M3P_ATTN_BWD_KBQ>;           \
+    if (m3p_seq) kern = attn_bwd_kernel<DH, KT, DROP, MASK, 6, 11, ATTN_BWD_NW, 1, 1>;                                \
     if constexpr (DH == 64 && (MASK || !DROP)) { if (onepass) kern = attn_bwd_kernel<DH, KT, DROP, MASK, 6, 11, 12, 1, 1, true>; } \
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     if (e != hipSuccess) return (int)e;                                                                         \
@@ -1521,7 +1334,7 @@ int launch_bwd(const bf16* qkv, const int* keylen, const bf16* ctx, const bf16* 
       if (hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp) == hipSuccess) {
         const int nheads = B * H;
         hipLaunchKernelGGL(kp, dim3(nheads < n_cu ? nheads : n_cu), dim3(768), ldsp, st, qkv, keylen, ctx, dctx, lse, keepmask, dqkv, dbias,
-                           S, H, dmodel, nheads, qscale, inv_keep, (g_attn_variant >> 8) ? ((g_attn_variant >> 8) & 0xff) - 1 : 2);   // (bits 8..: stagger + 1; default 2 x 1024 clocks per phase)
+                           S, H, dmodel, nheads, qscale, inv_keep);
         M3P_CHECK_LAUNCH();
         return M3P_OK;
       }
@@ -1542,17 +1355,6 @@ int launch_bwd(const bf16* qkv, const int* keylen, const bf16* ctx, const bf16* 
 extern "C" {
 
 void m3p_debug_attn_variant(int v) { g_attn_variant = v; }
-
-// debug (only with -DM3P_ATTN_TL): copies the forward kernel's phase stamps ([4096 WGs][4 waves][16] u64)
-__attribute__((visibility("default"))) int m3p_debug_attn_timeline(void* out, size_t bytes) {
-#ifdef M3P_ATTN_TL
-  if (bytes > sizeof(g_attn_tl)) return M3P_EINVAL;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_tl), bytes);
-#else
-  (void)out; (void)bytes;
-  return M3P_EINVAL;
-#endif
-}
 
 int m3p_attn_fwd(const void* qkv, const int32_t* keylen, void* ctx, float* lse, uint64_t* keepmask, int B, int S, int H, int dh,
                  uint32_t seed, uint32_t thresh24, float inv_keep, void* stream) {

@@ -13,11 +13,10 @@
 #include "common.hpp"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-#ifndef M3P_EMB_BWD_BLOCKS
-#define M3P_EMB_BWD_BLOCKS 512
-#endif
-
 namespace {
+
+// the backward splits the batch until about this many blocks are in flight
+constexpr int EMB_BWD_BLOCKS = 512;
 
 constexpr float kEps = 1e-12f;
 
@@ -443,7 +442,7 @@ int m3p_embed_assemble_bwd(const void* dh, const void* z, const float* mean_emb,
                            uint32_t thresh24, float inv_keep, int phase, void* stream) {
   if (B <= 0 || T < 0 || R < 0 || d <= 0 || (d % 4) != 0 || d > 1024 || phase < 0 || phase > 2) return M3P_EINVAL;
   int bsplit = 1;
-  while (bsplit < 16 && (R + T) * bsplit < M3P_EMB_BWD_BLOCKS && B / (4 * bsplit) >= 8) bsplit *= 2;
+  while (bsplit < 16 && (R + T) * bsplit < EMB_BWD_BLOCKS && B / (4 * bsplit) >= 8) bsplit *= 2;
   EmbedBwdArgs a = {(const bf16*)dh, (const bf16*)z, mean_emb, rstd_emb, g_emb, (const bf16*)e, mean_img, rstd_img, g_img,
                     tok, totlen, loc, (bf16*)dz_scratch, (bf16*)de, d_g_emb, d_be_emb, d_pos, d_emb,
                     (bf16*)d_tok_rows, d_g_img, d_be_img, d_b_img, d_b_loc, d_w_loc, B, T, R, d, pad_index, bsplit,

@@ -25,11 +25,10 @@
 #include "../../include/m3p_hip.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-static int g_variant = 1;  // debug: 0 = force the 128x128 2-stage kernel, 1 = auto (skinny for M <= 128, eight-wave 256x256 for full tiles, ring otherwise),
-                           // 2 = force the four-wave 256x256 kernel, 3 = force ring, 6 = force eight-wave 256x256, 7 = the round-1 auto choice (w4 / ring), 9 = auto without the skinny kernel
-static int g_ablate = 0;  // debug: timeline kernels only (bit0 = no fragment reads, bit1 = no LDS-DMA)
-static int g_w8_strip = 0; // debug: eight-wave kernel's strip rule (bits 0-3: strip width in tiles, 0 = the default rule; bit 4: odd strips walk M backwards)
-extern "C" void m3p_debug_set_variant(int v) { g_variant = v & 0xff; g_ablate = (v >> 8) & 0xff; g_w8_strip = (v >> 16) & 0xff; }     // (declared in the header's developer section)
+// debug: 1 = the dispatch tables (nt_plan / wgrad_plan), 2 = force the four-wave 256x256 NT kernel where it applies, 6 = force
+// the eight-wave 256x256 NT kernel; any other value means 1
+static int g_variant = 1;
+extern "C" void m3p_debug_set_variant(int v) { g_variant = (v == 2 || v == 6) ? v : 1; }     // (declared in the header's developer section)
 
 namespace {
 
@@ -269,9 +268,6 @@ __device__ __forceinline__ V4 flip_halves(const V4& t, bool flip) {
 // per staged piece.  The staging buffers never alias the stages; with these the waits are ours (lgkm_wait ties the wait to
 // the values it is for, so that their uses cannot be scheduled in front of it).
 typedef unsigned int u32x4_lds __attribute__((ext_vector_type(4)));
-#ifndef M3P_EPI_ALDS
-#define M3P_EPI_ALDS 0       // 1: the eight-wave kernel's epilogues stage through these too.  Measured neutral there (two waves per
-#endif                       // SIMD: the partner wave runs under the vmcnt(0)) - QKV 150 / 150 us, lin1 + GELU + byte 246 / 243, byte dgrad 214 / 216
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
 __device__ __forceinline__ void lds_w64(uint32_t a, const bf16x4& v) { asm volatile("ds_write_b64 %0, %1" :: "v"(a), "v"(v)); }
 __device__ __forceinline__ void lds_w128(uint32_t a, const u32x4_lds& v) { asm volatile("ds_write_b128 %0, %1" :: "v"(a), "v"(v)); }
@@ -282,30 +278,6 @@ __device__ __forceinline__ void lds_r128(uint32_t a, u32x4_lds& v) { asm volatil
 // evaluating erf/exp (~20 exposed VALU instructions per element).  The table covers |u| in
 // [2^-15, 8) (exponents -15..2 x 128 mantissas = 2304 fp32 entries, 9 KB of LDS), built from what
 // gelu_erf_grad_f returns for that bf16 value; gelu'(-u) = 1 - gelu'(u).
-// M3P_GQ_TRIM: the leaner form of the lin1 + GELU + byte epilogue (1, default since late round 4): |x| as a source modifier of
-// the first multiply, Phi(x) = 1/2 + copysign(1/2 - tail, x), and the code converted AND packed by v_cvt_pk_u8_f32.
-// What is established: the instruction rounds to nearest (tests/test_gemm.py: the form with an extra +0.5 fails the codes'
-// bias check, this one passes), and ONE in-process A/B of the three edits TOGETHER: 240.5 -> 231.8 us on the 41984 x 3072 x 768
-// product (tools/ab_gemm.py).  Not established: which of the three edits the 8.7 us come from (never built separately), and
-// the effect on the step.  0 = the first round-4 form, kept for A/B builds (tools/build_variant.sh).
-#ifndef M3P_GQ_TRIM
-#define M3P_GQ_TRIM 1
-#endif
-#ifndef M3P_W8_SPARE_EPILOGUE
-#define M3P_W8_SPARE_EPILOGUE 1
-#endif
-#ifndef M3P_MQ_PREFETCH
-#define M3P_MQ_PREFETCH 0
-#endif
-#ifndef M3P_MQ_EARLYREQ
-#define M3P_MQ_EARLYREQ 0
-#endif
-#ifndef M3P_LSE_NT
-#define M3P_LSE_NT 1      // the 2.4 GB of logits leave with non-temporal stores: 1883 -> 1847 us (profiles/r06_lse_nt.txt)
-#endif
-#ifndef M3P_DGELU_LUT
-#define M3P_DGELU_LUT 1
-#endif
 constexpr int GELU_TAB_LO = 0x3800, GELU_TAB_HI = 0x4100, GELU_TAB_N = GELU_TAB_HI - GELU_TAB_LO;
 // The table holds gelu'(|u|) - 1/2, an odd function of u: gelu'(u) = 1/2 + copysign(tab[|u|], u).  Seven VALU
 // instructions and one LDS read per element (and, sub, med3, lshl_add, bfi, add, + the multiply); the first table
@@ -352,24 +324,10 @@ __device__ __forceinline__ void load_aux(const M3PEpilogue& ep, int mrow0, int n
 // residual epilogues unchanged (the aux tile costs ~60 us per 41984 x 3072 GEMM either way - see DESIGN.md).
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // (HIP's uint4 is a struct: arrays of it passed by reference end up in scratch)
 
-// 16-byte output-row store.  M3P_ST_POLICY (A/B builds): 0 plain, 1 nt, 2 sc1 (write-through, line dropped from this XCD's L2),
-// 3 sc0 sc1, 4 sc1 nt
-#ifndef M3P_ST_POLICY
-#define M3P_ST_POLICY 0
-#endif
+// 16-byte output-row store (plain: the store policies sc1 / sc0 sc1 / sc1 nt were measured against it)
 template <class P>
 __device__ __forceinline__ void st16(P* p, const u32x4& v) {
-#if M3P_ST_POLICY == 0
   *reinterpret_cast<u32x4*>(p) = v;
-#elif M3P_ST_POLICY == 1
-  __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
-#elif M3P_ST_POLICY == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-#elif M3P_ST_POLICY == 3
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-#else
-  asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-#endif
 }
 template <bool NT>
 __device__ __forceinline__ void st16p(void* p, const u32x4& v) {
@@ -384,11 +342,7 @@ __device__ __forceinline__ void load_aux_rows_issue(const M3PEpilogue& ep, int m
   const bf16* X = reinterpret_cast<const bf16*>(ep.aux) + (size_t)(mrow0 + srow) * ep.ld_aux + nw + sch * 8;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
-#ifdef M3P_ABL_NOAUX      // (timing ablation: what the aux tile's trip from memory costs the epilogue - results are garbage)
-    t[it] = u32x4{(uint32_t)lane, 0x3f803f80u, 0x3f803f80u, (uint32_t)it};
-#else
     t[it] = *reinterpret_cast<const u32x4*>(X + (size_t)(it * 8) * ep.ld_aux);
-#endif
   }
 }
 template <int EPI, bool SW = false, bool ALDS = false>
@@ -417,11 +371,11 @@ __device__ __forceinline__ void load_aux_rows_finish(int lane, char* r1, const u
     for (int j = 0; j < 4; ++j)
       auxv[ii][j] = *reinterpret_cast<const bf16x4*>(r1 + ep_off8<SW>(ii * 16 + fr, (j * 16 + fg * 4) * 2));
 }
-template <int EPI, bool SW = false, bool ALDS = false>
+template <int EPI, bool SW = false>
 __device__ __forceinline__ void load_aux_rows(const M3PEpilogue& ep, int mrow0, int nw, int lane, char* r1, bf16x4 (&auxv)[2][4]) {
   u32x4 t[4];
   load_aux_rows_issue<EPI>(ep, mrow0, nw, lane, t);
-  load_aux_rows_finish<EPI, SW, ALDS>(lane, r1, t, auxv);
+  load_aux_rows_finish<EPI, SW>(lane, r1, t, auxv);
 }
 
 // epilogue_half in two parts: the arithmetic on a 32 x 64 piece and its staging writes (accumulator layout -> r1) ...
@@ -489,32 +443,16 @@ __device__ __forceinline__ void epilogue_half_write(const M3PEpilogue& ep, int N
     }
   }
 }
-// ... the staged piece read back as rows (16 bytes per lane, 8 lanes per 128-byte row segment) ...
-template <bool SW, bool ALDS = false>
+// ... the staged piece read back as rows (16 bytes per lane, 8 lanes per 128-byte row segment) with asm accesses, issued
+// only: the caller waits - lgkm_wait_rows - and flips the halves of rows 8-15, 24-31 then ...
+template <bool SW>
 __device__ __forceinline__ void epilogue_rows_read(const char* r1, int lane, u32x4 (&R)[4]) {
   const int srow = lane >> 3, sch = lane & 7;
-  if (ALDS) {      // (issued only: the caller waits - lgkm_wait_rows - and flips the halves of rows 8-15, 24-31 then)
-    const uint32_t la = lds_addr(r1);
-#pragma unroll
-    for (int it = 0; it < 4; ++it) lds_r128(la + ep_off<SW>(it * 8 + srow, sch * 16), R[it]);
-    return;
-  }
-#pragma unroll
-  for (int it = 0; it < 4; ++it) R[it] = flip_halves(*reinterpret_cast<const u32x4*>(r1 + ep_off<SW>(it * 8 + srow, sch * 16)), SW && (it & 1));
-}
-// (16-row pieces: two row instructions)  read + wait + store in one go, asm accesses
-__device__ __forceinline__ void epilogue_rows16_flush_alds(bf16* __restrict__ C, int ldc, int mrow0, int nw, const char* r1, int lane) {
-  const int srow = lane >> 3, sch = lane & 7;
   const uint32_t la = lds_addr(r1);
-  u32x4 R[2];
-  lds_r128(la + ep_off<true>(srow, sch * 16), R[0]);
-  lds_r128(la + ep_off<true>(8 + srow, sch * 16), R[1]);
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(R[0]), "+v"(R[1]));
-  bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
-  st16(Cp + (size_t)srow * ldc, R[0]);
-  st16(Cp + (size_t)(8 + srow) * ldc, flip_halves(R[1], true));
+#pragma unroll
+  for (int it = 0; it < 4; ++it) lds_r128(la + ep_off<SW>(it * 8 + srow, sch * 16), R[it]);
 }
-// the wait that belongs to epilogue_rows_read<SW, true>: `younger` (8 or 0) LDS instructions of this wave may stay in flight
+// the wait that belongs to epilogue_rows_read: `younger` (8 or 0) LDS instructions of this wave may stay in flight
 template <bool SW>
 __device__ __forceinline__ void lgkm_wait_rows(u32x4 (&R)[4], bool younger8) {
   if (younger8) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3]));
@@ -530,7 +468,7 @@ __device__ __forceinline__ void epilogue_rows_store(bf16* __restrict__ C, int ld
 #pragma unroll
   for (int it = 0; it < 4; ++it) st16(Cp + (size_t)(it * 8 + srow) * ldc, R[it]);
 }
-template <int EPI, bool SW = false, bool ALDS = false>
+template <int EPI, bool SW = false>
 __device__ __forceinline__ void epilogue_half(const M3PEpilogue& ep, bf16* __restrict__ C, int ldc, int N,
                                               int mrow0, int nw, char* r1, const f32x4 (&rows)[2][4],
                                               const f32x4 (&biasv)[4], const bf16x4 (&auxv)[2][4], int lane, f32x4 (&csum)[4],
@@ -538,15 +476,7 @@ __device__ __forceinline__ void epilogue_half(const M3PEpilogue& ep, bf16* __res
   const int fr = lane & 15, fg = lane >> 4;
   const int srow = lane >> 3, sch = lane & 7;
   bf16x4 ukeep[2][4];
-  constexpr bool kA = ALDS && EPI != M3P_EPI_BIAS_GELU;      // (the two-output epilogue keeps plain accesses: not on the hot path)
-  epilogue_half_write<EPI, SW, kA>(ep, N, mrow0, nw, r1, rows, biasv, auxv, lane, csum, ukeep, gtab);
-  if (kA) {
-    u32x4 R[4];
-    epilogue_rows_read<SW, true>(r1, lane, R);
-    lgkm_wait_rows<SW>(R, false);
-    epilogue_rows_store(C, ldc, mrow0, nw, lane, R);
-    return;
-  }
+  epilogue_half_write<EPI, SW>(ep, N, mrow0, nw, r1, rows, biasv, auxv, lane, csum, ukeep, gtab);
   bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
@@ -689,20 +619,6 @@ __device__ __forceinline__ void piece8_flush(uint8_t* __restrict__ o8, int ld8, 
   piece8_write(r1, w8, lane);
   piece8_store(o8, ld8, mrow0, nw, r1, lane);
 }
-// M3P_MQ_ABL (timing ablations, results are garbage): 1 = the codes are not read (the caller passes lane numbers), 2 = dU is
-// neither staged nor stored, 4 = no column sums
-#ifndef M3P_MQ_ABL
-#define M3P_MQ_ABL 0
-#endif
-#ifndef M3P_MQ_NT
-#define M3P_MQ_NT 1          // dU rows leave with non-temporal stores: 209 -> 194 us on the 41984 x 3072 x 768 product (profiles/r06_store_policy.txt)
-#endif
-#ifndef M3P_MQ_CSUMV
-#define M3P_MQ_CSUMV 1
-#endif
-#ifndef M3P_MQ_NTLOAD
-#define M3P_MQ_NTLOAD 0
-#endif
 template <int O8 = 0>      // 0: no 8-bit copy, 1: e4m3, 2: e5m2
 __device__ __forceinline__ void epilogue_pieceq(bf16* __restrict__ C, int ldc, int mrow0, int nw, char* r1, const f32x4 (&rows)[4],
                                                 const u32x4& q, int lane, f32x4 (&csum)[4], uint8_t* __restrict__ o8 = nullptr, int ld8 = 0,
@@ -717,17 +633,14 @@ __device__ __forceinline__ void epilogue_pieceq(bf16* __restrict__ C, int ldc, i
     g = g * GQ_STEP - GQ_OFF;
     const f32x4 v = rows[j] * g;
     const bf16x4 ob = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-    if (M3P_MQ_ABL & 2) asm volatile("" :: "v"(ob));
-    else if (M3P_EPI_ALDS || O8) lds_w64(lds_addr(r1) + ep_off8<true>(fr, (j * 16 + fg * 4) * 2), ob);
+    if (O8) lds_w64(lds_addr(r1) + ep_off8<true>(fr, (j * 16 + fg * 4) * 2), ob);
     else *reinterpret_cast<bf16x4*>(r1 + ep_off8<true>(fr, (j * 16 + fg * 4) * 2)) = ob;
     // column sums (lin1's bias gradient) of the fp32 products: one add per element (round 6; summing the bf16-rounded values
     // cost an unpack per element on top and is no closer to the fp32 reference's sum)
-    if (!(M3P_MQ_ABL & 4)) { if (M3P_MQ_CSUMV) csum[j] += v; else csum[j] += f32x4{(float)ob[0], (float)ob[1], (float)ob[2], (float)ob[3]}; }
+    csum[j] += v;
     if (O8) w8[j] = (O8 == 2) ? pack8<true>(v, scale8, *amax) : pack8<false>(v, scale8, *amax);
   }
   if (O8) piece8_write(r8, w8, lane);
-  if (M3P_MQ_ABL & 2) return;
-  if (M3P_EPI_ALDS) { epilogue_rows16_flush_alds(C, ldc, mrow0, nw, r1, lane); return; }
   bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
   if (O8) {
     // every staging access of this form is one the compiler does not see (no vmcnt(0) in front of each: with the 8-bit rows'
@@ -739,8 +652,8 @@ __device__ __forceinline__ void epilogue_pieceq(bf16* __restrict__ C, int ldc, i
     lds_r128(la + ep_off<true>(8 + srow, sch * 16), Rb);
     lds_r128(l8 + row8 * 64 + (c8 << 4), R8);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Ra), "+v"(Rb), "+v"(R8));
-    st16p<M3P_MQ_NT != 0>(Cp + (size_t)srow * ldc, u32x4{Ra[0], Ra[1], Ra[2], Ra[3]});
-    st16p<M3P_MQ_NT != 0>(Cp + (size_t)(8 + srow) * ldc, u32x4{Rb[2], Rb[3], Rb[0], Rb[1]});
+    st16p<true>(Cp + (size_t)srow * ldc, u32x4{Ra[0], Ra[1], Ra[2], Ra[3]});
+    st16p<true>(Cp + (size_t)(8 + srow) * ldc, u32x4{Rb[2], Rb[3], Rb[0], Rb[1]});
     st16p<true>(o8 + (size_t)(mrow0 + row8) * ld8 + nw + ((c8 ^ ((row8 >> 1) & 3)) << 4), u32x4{R8[0], R8[1], R8[2], R8[3]});
     return;
   }
@@ -753,7 +666,7 @@ __device__ __forceinline__ void epilogue_pieceq(bf16* __restrict__ C, int ldc, i
   // (the 8-bit piece has staging rows of its own, r8: its writes were issued with the bf16 piece's - below - and its row read
   //  shares the wait of theirs; the first version took a second, serialised trip through r1: 277 against 207 us per launch)
 #pragma unroll
-  for (int it = 0; it < 2; ++it) st16p<M3P_MQ_NT != 0>(Cp + (size_t)(it * 8 + srow) * ldc, R2[it]);
+  for (int it = 0; it < 2; ++it) st16p<true>(Cp + (size_t)(it * 8 + srow) * ldc, R2[it]);
   if (O8) piece8_store(o8, ld8, mrow0, nw, r8, lane);
 }
 
@@ -775,8 +688,7 @@ __device__ __forceinline__ void epilogue_half_lse(bf16* __restrict__ C, int ldc,
     for (int j = 0; j < 4; ++j) {
       x[j] = (ii ? rows1[j] : rows0[j]) + biasv[j];
       const bf16x4 xb = bf16x4{(bf16)x[j][0], (bf16)x[j][1], (bf16)x[j][2], (bf16)x[j][3]};
-      if (M3P_EPI_ALDS) lds_w64(lds_addr(r1) + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2), xb);
-      else *reinterpret_cast<bf16x4*>(r1 + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2)) = xb;
+      *reinterpret_cast<bf16x4*>(r1 + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2)) = xb;
       // the statistics are taken on the ROUNDED logits - the very values the cross-entropy's gradient pass and its target term
       // read back - so that softmax rows sum to one and the gradient rows to zero exactly as with a statistics pass over the
       // stored logits (one shift per element)
@@ -811,125 +723,19 @@ __device__ __forceinline__ void epilogue_half_lse(bf16* __restrict__ C, int ldc,
     sm += __shfl_xor(sm, 32, 64);
     if (fg == 0) stats[mrow0 + ii * 16 + fr] = float2{m, sm};
   }
-  if (M3P_EPI_ALDS) {
-    u32x4 R[4];
-    epilogue_rows_read<true, true>(r1, lane, R);
-    lgkm_wait_rows<true>(R, false);
-    epilogue_rows_store(C, ldc, mrow0, nw, lane, R);
-    return;
-  }
   bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int row = it * 8 + srow;
-    st16p<M3P_LSE_NT != 0>(Cp + (size_t)row * ldc, flip_halves(*reinterpret_cast<const u32x4*>(r1 + ep_off<true>(row, sch * 16)), it & 1));
+    st16p<true>(Cp + (size_t)row * ldc, flip_halves(*reinterpret_cast<const u32x4*>(r1 + ep_off<true>(row, sch * 16)), it & 1));
   }
 }
-
-// 32-row piece of the FFN1 epilogue that leaves BOTH things the layer needs of u = acc + bias (M3P_EPI_BIAS_GELUQ):
-// h = gelu_erf(u) staged to row order like any output tile, and gelu_erf'(u) as one byte per element written
-// straight from the accumulator layout in fragment order (16 bytes per lane and 16-row block: 1 KB per wave instruction,
-// no staging) - what M3P_EPI_MULQ reads back the same way.  u itself is never stored.  The arithmetic is written on
-// four-element vectors so that the polynomial runs on packed f32 instructions (the epilogue has the VALU to itself).
-// M3P_GQ_ABL (timing ablations of this epilogue, results are garbage): 1 = no arithmetic (h = x, code = bits of x),
-// 2 = the codes are not stored, 4 = h is neither staged nor stored
-#ifndef M3P_GQ_ABL
-#define M3P_GQ_ABL 0
-#endif
-__device__ __forceinline__ void epilogue_half_geluq(bf16* __restrict__ C, int ldc, uint8_t* __restrict__ qout, int mrow0, int nw,
-                                                    char* r1, const f32x4 (&rows0)[4], const f32x4 (&rows1)[4],
-                                                    const f32x4 (&biasv)[4], int lane) {
-  const int fr = lane & 15, fg = lane >> 4;
-  const int srow = lane >> 3, sch = lane & 7;
-#pragma unroll
-  for (int ii = 0; ii < 2; ++ii) {
-    u32x4 code;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      // (x stays fp32: with u never stored there is no bf16 copy anything else would have to agree with)
-      const f32x4 x = (ii ? rows1[j] : rows0[j]) + biasv[j];
-#if M3P_GQ_ABL & 1
-      {
-        code[j] = __builtin_bit_cast(uint32_t, x[0]);
-        const bf16x4 hb = bf16x4{(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3]};
-        if (M3P_GQ_ABL & 4) asm volatile("" :: "v"(hb));
-        else *reinterpret_cast<bf16x4*>(r1 + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2)) = hb;
-        continue;
-      }
-#endif
-      // gelu_parts (common.hpp) on a vector: Phi(|x|) = 1 - (poly(t) t e) / 2, t = 1 / (1 + p z), z = |x| / sqrt 2, e = exp(-z^2)
-      f32x4 z, t, e;
-#if M3P_GQ_TRIM
-#pragma unroll
-      for (int r = 0; r < 4; ++r) z[r] = fabsf(x[r]) * 0.70710678118654752440f;      // (one v_mul with the |x| modifier)
-#else
-#pragma unroll
-      for (int r = 0; r < 4; ++r) z[r] = fabsf(x[r]);
-      z *= 0.70710678118654752440f;
-#endif
-      const f32x4 den = z * 0.3275911f + 1.0f;
-      const f32x4 ez = z * z * -1.4426950408889634f;          // exp(-z^2) = exp2(-z^2 log2 e)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { t[r] = __builtin_amdgcn_rcpf(den[r]); e[r] = __builtin_amdgcn_exp2f(ez[r]); }
-      f32x4 poly = t * 1.061405429f - 1.453152027f;
-      poly = poly * t + 1.421413741f;
-      poly = poly * t - 0.284496736f;
-      poly = poly * t + 0.254829592f;
-      const f32x4 tail = poly * t * e * 0.5f;                 // 1 - Phi(|x|)
-      f32x4 cdf;
-#if M3P_GQ_TRIM
-      {       // Phi(x) = 1/2 + copysign(1/2 - tail, x): one packed subtract, a bit-field insert of x's sign, one packed add
-        const f32x4 half = 0.5f - tail;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cdf[r] = __builtin_copysignf(half[r], x[r]);
-        cdf += 0.5f;
-      }
-#else
-#pragma unroll
-      for (int r = 0; r < 4; ++r) cdf[r] = (x[r] >= 0.f) ? 1.0f - tail[r] : tail[r];
-#endif
-      const f32x4 hv = x * cdf;
-      const f32x4 gd = x * e * 0.39894228040143267794f + cdf;                  // gelu'(x) = Phi + x phi
-#if M3P_GQ_TRIM
-      // v_cvt_pk_u8_f32 converts AND drops the byte into place: one instruction per element where the other form has a
-      // conversion plus a shift / or.  It rounds to nearest - pinned by tests/test_gemm.py (with +0.5 added the codes' rms
-      // error fails the 0.4-step bar), hence no +0.5 here (M3P_GQ_TRIM == 2 is the failing form, kept so the test can be re-run)
-      const f32x4 qf = gd * GQ_INV + (GQ_OFF * GQ_INV + (M3P_GQ_TRIM == 2 ? 0.5f : 0.0f));
-      uint32_t cw = 0;
-      cw = __builtin_amdgcn_cvt_pk_u8_f32(qf[0], 0, cw); cw = __builtin_amdgcn_cvt_pk_u8_f32(qf[1], 1, cw);
-      cw = __builtin_amdgcn_cvt_pk_u8_f32(qf[2], 2, cw); cw = __builtin_amdgcn_cvt_pk_u8_f32(qf[3], 3, cw);
-      code[j] = cw;
-#else
-      const f32x4 qf = gd * GQ_INV + (GQ_OFF * GQ_INV + 0.5f);                 // in [1.7, 253.3): truncation = round to nearest
-      code[j] = (uint32_t)qf[0] | ((uint32_t)qf[1] << 8) | ((uint32_t)qf[2] << 16) | ((uint32_t)qf[3] << 24);
-#endif
-      if (M3P_GQ_ABL & 4) { const bf16x4 hb = bf16x4{(bf16)hv[0], (bf16)hv[1], (bf16)hv[2], (bf16)hv[3]}; asm volatile("" :: "v"(hb)); }
-      else if (M3P_EPI_ALDS) lds_w64(lds_addr(r1) + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2), bf16x4{(bf16)hv[0], (bf16)hv[1], (bf16)hv[2], (bf16)hv[3]});
-      else *reinterpret_cast<bf16x4*>(r1 + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2)) = bf16x4{(bf16)hv[0], (bf16)hv[1], (bf16)hv[2], (bf16)hv[3]};
-    }
-    if (M3P_GQ_ABL & 2) asm volatile("" :: "v"(code));
-    else st16(qout + ii * 1024 + lane * 16, code);
-  }
-  if (M3P_GQ_ABL & 4) return;
-  if (M3P_EPI_ALDS) {
-    u32x4 R[4];
-    epilogue_rows_read<true, true>(r1, lane, R);
-    lgkm_wait_rows<true>(R, false);
-    epilogue_rows_store(C, ldc, mrow0, nw, lane, R);
-    return;
-  }
-  bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = it * 8 + srow;
-    st16(Cp + (size_t)row * ldc, flip_halves(*reinterpret_cast<const u32x4*>(r1 + ep_off<true>(row, sch * 16)), it & 1));
-  }
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 6: the lin1 + GELU + byte epilogue from ONE table read per element (M3P_GQ_LUT, default).
-// The round-4 form above evaluates erf and the Gaussian on the VALU - ~17 issue slots and two quarter-rate
+// The lin1 + GELU + byte epilogue (M3P_EPI_BIAS_GELUQ) from ONE table read per element (round 6).  h = gelu_erf(u) is staged
+// to row order like any output tile; gelu_erf'(u) leaves as one byte per element straight from the accumulator layout in
+// fragment order - what M3P_EPI_MULQ reads back the same way; u itself is never stored.
+// The round-4 form evaluated erf and the Gaussian on the VALU - ~17 issue slots and two quarter-rate
 // transcendentals per element, with the matrix pipe idle: measured (profiles/r06_gq_ablation.txt) the arithmetic alone is
 // 46-64 us of the 232-us launch.  Both results are functions of x, and to the accuracy a bf16 output and a one-byte code can
 // carry they are functions of the upper 16 bits of x:
@@ -945,12 +751,6 @@ __device__ __forceinline__ void epilogue_half_geluq(bf16* __restrict__ C, int ld
 // read; the bias rides in the accumulators (they start an output tile at the bias instead of zero), so there is no add.
 // 16-row pieces: staging 2 KB per wave + 1 KB for the 8-bit copy, the 7-KB table beside them (31 of the 32 KB the two stages leave).
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef M3P_GQ_LUT
-#define M3P_GQ_LUT 1
-#endif
-#ifndef M3P_GQ_NT
-#define M3P_GQ_NT 1          // h rows and codes leave with non-temporal stores (r06_store_policy.txt)
-#endif
 // |x| in [2^-11, 8): 14 exponents x 128 mantissas = 1792 words, 7 KB (below 2^-11 the first entry serves: T = 0.4998 against
 // 1/2 - 0.4 |x|, an error of 4e-4 relative in h, a fifth of its bf16 rounding; gelu' = 1/2 +- 4e-4 -> codes 128 / 127 either way).
 // The 2 KB this saves against the dGELU table's range [2^-15, 8) are what lets the 8-bit copy of h have staging rows of its own.
@@ -1014,7 +814,7 @@ __device__ __forceinline__ void epilogue_piece_geluq_lut(bf16* __restrict__ C, i
     lds_w64(la + ep_off8<true>(fr, (j * 16 + fg * 4) * 2), bf16x4{(bf16)hv[0], (bf16)hv[1], (bf16)hv[2], (bf16)hv[3]});
     if (O8) w8[j] = pack8<false>(hv, scale8, *amax);
   }
-  st16p<M3P_GQ_NT != 0>(qout + lane * 16, code);
+  st16p<true>(qout + lane * 16, code);
   if (O8) piece8_write(r8, w8, lane);      // (staging rows of its own: its round trip shares the bf16 piece's wait)
   u32x4 R[2];
   u32x4_lds R8;
@@ -1028,15 +828,11 @@ __device__ __forceinline__ void epilogue_piece_geluq_lut(bf16* __restrict__ C, i
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(R[0]), "+v"(R[1]));
   }
   bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
-  st16p<M3P_GQ_NT != 0>(Cp + (size_t)srow * ldc, R[0]);
-  st16p<M3P_GQ_NT != 0>(Cp + (size_t)(8 + srow) * ldc, flip_halves(R[1], true));
+  st16p<true>(Cp + (size_t)srow * ldc, R[0]);
+  st16p<true>(Cp + (size_t)(8 + srow) * ldc, flip_halves(R[1], true));
   if (O8) st16p<true>(o8 + (size_t)(mrow0 + row8) * ld8 + nw + ((c8 ^ ((row8 >> 1) & 3)) << 4), u32x4{R8[0], R8[1], R8[2], R8[3]});
 }
 
-#if defined(M3P_RING_TL) || defined(M3P_W8_TL) || defined(M3P_WG_TL)
-__device__ unsigned long long g_ring_tl[256 * 8 * 16];  // debug build: per-wave cycle sums of the eight-wave kernel's segments
-                                                        // ([256][8][8] segments, then [256][8][8] K-tile phases of the w8 kernel)
-#endif
 
 // ---------------------------------------------------------------------------------
 // NT kernel, persistent ring version (the production path): one 8-wave workgroup per CU walks
@@ -1058,7 +854,7 @@ template <int EPI>
 __global__ __launch_bounds__(512)
 void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
                          bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
-                         int tiles_m, int tiles_n, int m_fast) {
+                         int tiles_m, int tiles_n) {
   constexpr int BM = 256, BN = 128, NWAVES = 8;
   constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB, STAGE = A_BYTES + B_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1067,16 +863,15 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = tiles_m * tiles_n;
   // tile id -> (tm, tn): n-fastest shares the A row-panel between neighbours (weights small
-  // enough for L2/MALL); m-fastest shares the W panel instead (vocabulary projection: W = 384 MB)
-  // strips pay off once a full row of n-tiles no longer fits beside the A panels (measured:
+  // enough for L2/MALL); strips pay off once a full row of n-tiles no longer fits beside the A panels (measured:
   // 24 n-tiles 805 -> 914 TF with 8-wide strips; 18 n-tiles lose ~5 %, so those stay n-fastest)
   const int n_strips = (tiles_n >= 24) ? (tiles_n + 7) / 8 : 1;
   const int strip_w = (tiles_n + n_strips - 1) / n_strips;
   // (default order: strips of ~8 n-tiles walked m-major, so the 32 consecutive tiles an XCD
   //  holds in one round form a ~4 x 8 block: 4 A row-panels + 8 W panels are live per XCD
-  //  instead of 1.3 + 24 -> fewer unique bytes per step in the 4-MB L2)
+  //  instead of 1.3 + 24 -> fewer unique bytes per step in the 4-MB L2.  m-fastest order for a huge W used to win; with the
+  //  strips the vocabulary projection went 2.20 -> 2.05 ms, 9.3 -> ~2 GB of reads)
   auto split_tile = [&](int t, int& tm, int& tn) {
-    if (m_fast) { tn = t / tiles_m; tm = t - tn * tiles_m; return; }
     const int strip = t / (tiles_m * strip_w);
     const int rem = t - strip * tiles_m * strip_w;
     const int bn = min(strip_w, tiles_n - strip * strip_w);
@@ -1091,8 +886,8 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
   const int my_tiles = (ntiles > slot) ? (ntiles - slot + nwg - 1) / nwg : 0;
   if (my_tiles == 0) return;
   // dGELU: derivative table behind the three stages (visible to everyone after the first K-tile barrier)
-  float* gtab = (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) ? reinterpret_cast<float*>(smem + 3 * STAGE) : nullptr;
-  if (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) gelu_grad_table_fill(gtab, tid, 512);
+  float* gtab = (EPI == M3P_EPI_DGELU) ? reinterpret_cast<float*>(smem + 3 * STAGE) : nullptr;
+  if (EPI == M3P_EPI_DGELU) gelu_grad_table_fill(gtab, tid, 512);
   const int nk = K / BK;
   const int total = my_tiles * nk;
 
@@ -1206,13 +1001,6 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
         csum[j][r] = 0.f;
       }
   };
-#ifdef M3P_RING_TL
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tl0 = __builtin_amdgcn_s_memtime(), tl1;
-#define RING_TSEG(k) do { tl1 = __builtin_amdgcn_s_memtime(); tacc[k] += tl1 - tl0; tl0 = tl1; } while (0)
-#else
-#define RING_TSEG(k) do { } while (0)
-#endif
   for (int step = 0; step < total; ++step) {
     const int nxt = (cur == 2) ? 0 : cur + 1;
     const int nx2 = (nxt == 2) ? 0 : nxt + 1;
@@ -1235,7 +1023,6 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
     M3P_LGKM0();
 
     if (++c_kt == nk) {
-      RING_TSEG(0);
       // ---- epilogue of output tile c_q; stage `cur` is free (all waves passed the barrier above)
       c_kt = 0;
       const int t = tile_of(c_q);
@@ -1268,14 +1055,8 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
           f32x4 biasv[4];
           bf16x4 auxv[2][4];
           load_bias4<EPI>(ep, nw, lane, biasv);
-          RING_TSEG(1);
           load_aux_rows_finish<EPI>(lane, r1, auxt, auxv);
-#ifdef M3P_RING_TL
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-          RING_TSEG(2);
           epilogue_half<EPI>(ep, C, ldc, N, mw + 32 * hf, nw, r1, rows, biasv, auxv, lane, csum, gtab);
-          RING_TSEG(3);
         };
         do_half(0, auxt0);
         do_half(1, auxt1);
@@ -1286,7 +1067,6 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
           for (int j = 0; j < 4; ++j)
             epilogue_store<EPI>(ep, C, ldc, M, N, mw + i * 16 + fr, nw + j * 16 + fg * 4, acc[i][j], csum[j]);
       }
-      RING_TSEG(4);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1298,17 +1078,10 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
-      RING_TSEG(5);
     }
     cur = nxt;
   }
   if ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) && ep.colsum && csum_nw >= 0) flush_csum();
-#ifdef M3P_RING_TL
-  RING_TSEG(0);
-  if (lane == 0 && EPI == M3P_EPI_DGELU)
-    for (int k = 0; k < 8; ++k) g_ring_tl[(blockIdx.x * 8 + wid) * 8 + k] = tacc[k];
-#endif
-#undef RING_TSEG
 #undef M3P_DSR
 #undef M3P_LGKM0
 }
@@ -1316,7 +1089,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
 
 // ---------------------------------------------------------------------------------
 // NT kernel, "w8" version: 256x256 output tile, EIGHT waves (2 x 4), 128x64 per wave, two 64-KB LDS stages.
-// tools/gemm_timeline.py on the four-wave kernel: a wave alone on its SIMD loses ~32 clocks of matrix pipe to each of its
+// The four-wave kernel's timeline: a wave alone on its SIMD loses ~32 clocks of matrix pipe to each of its
 // 16 LDS-DMA instructions per K-tile and issues 16x16x32 MFMAs every ~18 clocks instead of 16 - 29 % of the K loop - and
 // pays the whole epilogue (20 % of a K = 768 launch) with the pipe idle; neither depends on the MFMA shape.  With two
 // waves per SIMD the partner's MFMAs fill those holes.  What made the earlier eight-wave kernels LDS-bound was 64x64 per
@@ -1338,7 +1111,7 @@ template <int EPI, bool DYN = false, bool O8 = false>      // O8: BIAS_GELUQ / M
 __global__ __launch_bounds__(512)
 void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
                        bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
-                       int tiles_m, int tiles_n, int* __restrict__ tile_ctr, int strip_arg) {
+                       int tiles_m, int tiles_n, int* __restrict__ tile_ctr) {
   constexpr int BM = 256, BN = 256, NWAVES = 8;
   constexpr int A_BYTES = BM * ROWB, STAGE = (BM + BN) * ROWB;      // 32 KB, 64 KB
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1346,19 +1119,16 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = tiles_m * tiles_n;
-  const int strip_req = strip_arg & 15;
   // (round 6: nine n-tiles - the QKV projection - in three strips of three instead of one row of nine: 131.4 -> 124.1 us on
   //  one box, 132 -> 131 on two others - never slower; profiles/r06_qkv_strips.txt)
-  const int n_strips = strip_req ? (tiles_n + strip_req - 1) / strip_req : ((tiles_n >= 9) ? (tiles_n + 3) / 4 : 1);
+  const int n_strips = (tiles_n >= 9) ? (tiles_n + 3) / 4 : 1;
   const int strip_w = (tiles_n + n_strips - 1) / n_strips;
-  const bool serpentine = (strip_arg & 16) != 0;
   auto split_tile = [&](int t, int& tm, int& tn) {
     const int strip = t / (tiles_m * strip_w);
     const int rem = t - strip * tiles_m * strip_w;
     const int bn = min(strip_w, tiles_n - strip * strip_w);
     tm = rem / bn;
     tn = strip * strip_w + (rem - tm * bn);
-    if (serpentine && (strip & 1)) tm = tiles_m - 1 - tm;
   };
   const int nwg = gridDim.x;
   const int per_xcd = nwg >> 3;
@@ -1380,99 +1150,52 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   int t_ld = slot, t_cmp = slot, t_next = -1;               // (dynamic schedule: tiles being loaded / computed, the popped one)
   int pop_state = 0;        // 1: popped this K-tile (wave 0 publishes after the barrier), 2: published (everyone reads after the next)
   unsigned popped = 0;
-  // kSpare: the epilogue stages through the 32 KB beside the two stages (swizzled 128-byte rows: 4 KB per wave, or 2 KB
-  // for the 16-row pieces of the multiply epilogues, whose derivative table lives there too) instead of the stage the
-  // output tile's last K-tile vacated: the next tile's K-tile 1 is then requested on schedule and nobody has to meet at a
-  // barrier after the epilogue.
-  constexpr bool kSpare = M3P_W8_SPARE_EPILOGUE;
+  // The epilogue stages through the 32 KB beside the two stages (swizzled 128-byte rows: 4 KB per wave, or 2 KB for the
+  // 16-row pieces of the multiply epilogues, whose derivative table lives there too) instead of the stage the output tile's
+  // last K-tile vacated: the next tile's K-tile 1 is then requested on schedule and nobody has to meet at a barrier after
+  // the epilogue.
   constexpr bool kMulE = (EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL || EPI == M3P_EPI_MULQ);
   constexpr bool kAuxE = (EPI == M3P_EPI_BIAS_DROP_RES || EPI == M3P_EPI_RES || kMulE);
-  constexpr bool kGqLut = (EPI == M3P_EPI_BIAS_GELUQ) && M3P_GQ_LUT;
-  constexpr int kTabBytes = (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) ? GELU_TAB_N * (int)sizeof(float) : (kGqLut ? GQ_TAB_BYTES : 0);
-  float* gtab = (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) ? reinterpret_cast<float*>(smem + 2 * STAGE) : nullptr;
-  if (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) gelu_grad_table_fill(gtab, tid, 512);
+  constexpr bool kGqLut = (EPI == M3P_EPI_BIAS_GELUQ);
+  constexpr int kTabBytes = (EPI == M3P_EPI_DGELU) ? GELU_TAB_N * (int)sizeof(float) : (kGqLut ? GQ_TAB_BYTES : 0);
+  float* gtab = (EPI == M3P_EPI_DGELU) ? reinterpret_cast<float*>(smem + 2 * STAGE) : nullptr;
+  if (EPI == M3P_EPI_DGELU) gelu_grad_table_fill(gtab, tid, 512);
   if (kGqLut) geluq_table_fill(reinterpret_cast<uint32_t*>(smem + 2 * STAGE), tid, 512);      // (the prologue's barrier publishes it)
   int* const mbox = reinterpret_cast<int*>(smem + 2 * STAGE + kTabBytes);
 
-  // ---- load cursor: one LDS-DMA = 8 rows x 128 B; piece i of wave w covers row group w + 8 i of an operand
-  //      (lane -> row l >> 3, LDS slot l & 7, source chunk slot ^ (row & 7)); groups are 64 rows apart
+  // ---- load cursor: one LDS-DMA = 8 rows x 128 B (lane -> row l >> 3, LDS slot l & 7, source chunk slot ^ (row & 7)).  A wave
+  //      stages 32 CONSECUTIVE rows of each operand (pieces 1 KB apart in LDS) as buffer_load_dwordx4 ... lds: resource = the
+  //      wave's slice of the operand tile, scalar offset = K-tile + piece, one 32-bit lane offset per operand, the destination
+  //      picked by the immediate offset, which moves the source by the same bytes (tools/probe_dma_offset.py; the four-wave
+  //      kernels do the same).  Per LDS-DMA that saves the M0 write and its hazard nop (probe_issue.py: ~32 of the ~70 ticks a
+  //      piece costs).
   const int sr = lane >> 3, sc = (lane & 7) ^ sr;
-  const bf16* a_src;
-  const bf16* w_src;
-  const size_t a_step = (size_t)64 * lda, w_step = (size_t)64 * ldw;
   int l_kt = 0, l_q = 0;
   bool l_alive = true;      // (dynamic) the load cursor points at a K-tile of this workgroup's stream
-#ifndef M3P_W8_IMM
-#define M3P_W8_IMM 1
-#endif
-#ifndef M3P_W8_SADDR
-#define M3P_W8_SADDR 1
-#endif
-  // M3P_W8_IMM: a wave stages 32 CONSECUTIVE rows of each operand (pieces 1 KB apart in LDS) and the four pieces of an operand
-  // share one M0: the destination is picked by the instruction's immediate offset (-2048 .. +1024), which moves the global
-  // source by the same bytes - compensated in the source pointer (tools/probe_dma_offset.py; the four-wave kernels do the
-  // same).  Per LDS-DMA that saves the M0 write and its hazard nop (probe_issue.py: ~32 of the ~70 ticks a piece costs).
-#ifndef M3P_W8_BUFDMA
-#define M3P_W8_BUFDMA 1     // the transfers as buffer_load_dwordx4 ... lds (resource = the wave's slice of the operand tile, scalar offset = K-tile + piece)
-#endif
   __amdgpu_buffer_rsrc_t a_rsrc, w_rsrc;
   auto set_load_tile = [&](int t) {
     int tm, tn;
     split_tile(t, tm, tn);
-    if (M3P_W8_IMM) {       // (uniform: the lane's part is a_lane / w_lane)
-      a_src = A + (size_t)(tm * BM + wid * 32) * lda;
-      w_src = W + (size_t)(tn * BN + wid * 32) * ldw;
-      if (M3P_W8_BUFDMA) {
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_src)), 0, 0xffffffff, 0x00020000);
-        w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_src)), 0, 0xffffffff, 0x00020000);
-      }
-    } else {
-      a_src = A + (size_t)(tm * BM + wid * 8 + sr) * lda + sc * 8;
-      w_src = W + (size_t)(tn * BN + wid * 8 + sr) * ldw + sc * 8;
-    }
+    const bf16* a_src = A + (size_t)(tm * BM + wid * 32) * lda;
+    const bf16* w_src = W + (size_t)(tn * BN + wid * 32) * ldw;
+    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_src)), 0, 0xffffffff, 0x00020000);
+    w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_src)), 0, 0xffffffff, 0x00020000);
   };
-  const size_t a_step8 = (size_t)8 * lda, w_step8 = (size_t)8 * ldw;
-  // scalar base + 32-bit lane offset: the address form the LDS-DMA takes without any per-piece vector arithmetic
   const uint32_t a_lane = (uint32_t)(sr * lda + sc * 8) * 2u, w_lane = (uint32_t)(sr * ldw + sc * 8) * 2u;
   auto issue_load = [&](int s, int piece) {
     char* sa = smem + s * STAGE;
     const int k0 = l_kt * BK;
-    if (M3P_W8_IMM && M3P_W8_BUFDMA) {
-      const int pc = piece & 3;
-      char* base = sa + (piece < 4 ? 0 : A_BYTES) + wid * 4096;
-      const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)k0 * 2u + (uint32_t)pc * (uint32_t)((piece < 4 ? lda : ldw) * 16) - (uint32_t)pc * 1024u);
+    const int pc = piece & 3;
+    char* base = sa + (piece < 4 ? 0 : A_BYTES) + wid * 4096;
+    const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)k0 * 2u + (uint32_t)pc * (uint32_t)((piece < 4 ? lda : ldw) * 16) - (uint32_t)pc * 1024u);
 #define W8_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 4 ? a_rsrc : w_rsrc, LDS_PTR(base), 16, piece < 4 ? a_lane : w_lane, soff, IMM, 0)
-      switch (pc) {
-        case 0: W8_LDB(0); break;
-        case 1: W8_LDB(1024); break;
-        case 2: W8_LDB(2048); break;
-        default: W8_LDB(3072); break;
-      }
+    switch (pc) {
+      case 0: W8_LDB(0); break;
+      case 1: W8_LDB(1024); break;
+      case 2: W8_LDB(2048); break;
+      default: W8_LDB(3072); break;
+    }
 #undef W8_LDB
-      return;
-    }
-    if (M3P_W8_IMM) {
-      const int pc = piece & 3;
-      char* base = sa + (piece < 4 ? 0 : A_BYTES) + wid * 4096 + 2048;
-      // (source compensated by the immediate: (pc - 2) * 1024 bytes = (pc - 2) * 512 elements)
-      // (uniform_ptr keeps the sum scalar: otherwise the lane offset is folded in first, loop-invariantly, and every piece pays
-      //  a 64-bit vector add again)
-      const bf16* row = uniform_ptr((piece < 4 ? a_src + pc * a_step8 : w_src + pc * w_step8) + k0 - (pc - 2) * 512);
-      uint32_t lane_off = piece < 4 ? a_lane : w_lane;
-      if (M3P_W8_SADDR) asm volatile("" : "+v"(lane_off));      // (the zero-extension has to sit beside the DMA for the scalar-base form to be selected)
-      const char* src = reinterpret_cast<const char*>(row) + lane_off;
-      switch (pc) {
-        case 0: __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(base), 16, -2048, 0); break;
-        case 1: __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(base), 16, -1024, 0); break;
-        case 2: __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(base), 16, 0, 0); break;
-        default: __builtin_amdgcn_global_load_lds(GLB_PTR(src), LDS_PTR(base), 16, 1024, 0); break;
-      }
-      return;
-    }
-    if (piece < 4)
-      __builtin_amdgcn_global_load_lds(GLB_PTR(a_src + piece * a_step + k0), LDS_PTR(sa + (wid + piece * NWAVES) * 1024), 16, 0, 0);
-    else
-      __builtin_amdgcn_global_load_lds(GLB_PTR(w_src + (piece - 4) * w_step + k0), LDS_PTR(sa + A_BYTES + (wid + (piece - 4) * NWAVES) * 1024), 16, 0, 0);
   };
   auto load_done = [&]() {
     if constexpr (!dyn) {
@@ -1539,66 +1262,23 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       for (int i = 0; i < 8; ++i) acc[i][j] = b;
     }
   }
-#ifndef M3P_W8_SETPRIO
-#define M3P_W8_SETPRIO 1
-#endif
-#ifndef M3P_W8_SPREAD
-#define M3P_W8_SPREAD 1
-#endif
-#ifndef M3P_W8_INTERLEAVE
-#define M3P_W8_INTERLEAVE 0
-#endif
-  // (ld_s, ld_p0, ld_n): with M3P_W8_INTERLEAVE the quarter's LDS-DMA pieces ld_p0 .. ld_p0 + ld_n - 1 (stage ld_s) are
-  //  issued one after every fourth MFMA instead of in front of the cluster
-  auto mfma_q = [&](auto half_c, const bf16x8 (&af)[4], const bf16x8 (&wf)[4], int ld_s = 0, int ld_p0 = 0, int ld_n = 0) {
+  // (raised priority around every MFMA cluster; a static priority for the younger half of the workgroup was the
+  //  alternative measured - DESIGN.md)
+  auto mfma_q = [&](auto half_c, const bf16x8 (&af)[4], const bf16x8 (&wf)[4]) {
     constexpr int I0 = 4 * decltype(half_c)::value;
-    if (M3P_W8_SETPRIO == 1) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc[I0 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[I0 + i][j], 0, 0, 0);
-      if (M3P_W8_INTERLEAVE && i < ld_n) {
-        __builtin_amdgcn_sched_barrier(0);
-        issue_load(ld_s, ld_p0 + i);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (M3P_W8_SETPRIO == 1) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
   };
-  // M3P_W8_SETPRIO == 2 (A/B build): static priority for the younger half of the workgroup instead of flips around every
-  // MFMA cluster (MI355X_MICROARCH.md "Two waves per SIMD", item 4)
-  if (M3P_W8_SETPRIO == 2 && wid >= 4) __builtin_amdgcn_s_setprio(1);
   using H0 = std::integral_constant<int, 0>;
   using H1 = std::integral_constant<int, 1>;
 
-#ifdef M3P_W8_TL
-  // debug build: s_memtime sums per segment (0 K loop, 1 bias + aux fetch / wait, 2 epilogue pieces, 3 restart after the
-  // epilogue, 4 prologue) and the absolute start / end stamps (5, 6) of every wave  (tools/w8_timeline.py)
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tl0 = __builtin_amdgcn_s_memtime(), tl1;
-  tacc[5] = tl0;
-#define W8_TSEG(k) do { tl1 = __builtin_amdgcn_s_memtime(); tacc[k] += tl1 - tl0; tl0 = tl1; } while (0)
-  // phases of a K-tile: stamps are issued (not waited for) in front of each quarter's closing lgkmcnt wait, behind the vmcnt
-  // wait and behind the barrier; the sums are taken behind quarter 3's wait, when all of them have returned
-  unsigned long long kq[8] = {0, 0, 0, 0, 0, 0, 0, 0}, kst[7];
-#define W8_KSTAMP(i) asm volatile("s_memtime %0" : "=s"(kst[i]))
-#define W8_KSTAMP0() do { W8_KSTAMP(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); } while (0)
-#else
-#define W8_TSEG(k) do { } while (0)
-#define W8_KSTAMP(i) do { } while (0)
-#define W8_KSTAMP0() do { } while (0)
-#endif
   // ---- prologue: K-tiles 0 and 1 into stages 0 and 1
   set_load_tile(slot);
-#if M3P_MQ_PREFETCH
-  if (EPI == M3P_EPI_MULQ) {       // (the first output tile's codes: see the epilogue)
-    int tm2, tn2;
-    split_tile(slot, tm2, tn2);
-    const uint8_t* pf = reinterpret_cast<const uint8_t*>(ep.aux) + gq_block_offset(tm2, tn2, tiles_n, wid, 0) + lane * 128;
-    __builtin_amdgcn_global_load_lds(GLB_PTR(pf), LDS_PTR(smem + 2 * STAGE + 8 * 2048 + wid * 256), 4, 0, 0);
-  }
-#endif
   stage_next(0);
 #define W8_H1 (dyn ? h1d : (step + 1 < total))
 #define W8_MORE2 (dyn ? l_alive : more2)
@@ -1641,45 +1321,36 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   float amax_run = 0.f;       // (BIAS_GELUQ with an 8-bit copy: this lane's max |output| over the launch; MULQ keeps it in LDS)
   if constexpr (O8 && EPI == M3P_EPI_MULQ) reinterpret_cast<float*>(smem + 2 * STAGE + 8 * 2048)[tid] = 0.f;
   bool spread_pending = false;
-#ifdef M3P_W8_TL
-  W8_TSEG(4);
-#endif
-  W8_KSTAMP0();
   for (int step = 0; dyn || step < total; ++step) {
     const int cur = step & 1, nxt = cur ^ 1;
     const bool last_kt = (c_kt + 1 == nk);
     // K-tile step + 2 exists (it is requested during this step).  Dynamic: known once quarter 1 has advanced the load cursor
     const bool more2 = dyn ? false : (step + 2 < total);
     const uint32_t so = cur * STAGE;
-    const bool pend = M3P_W8_SPREAD && spread_pending;      // the request for K-tile +1 started in the previous quarter 3
+    const bool pend = spread_pending;      // the request for K-tile +1 started in the previous quarter 3
     // quarter 0: k-step 0, rows 0-63 | fetch k-step 0, rows 64-127
-    if (pend && !M3P_W8_INTERLEAVE) { issue_load(nxt, 3); issue_load(nxt, 4); issue_load(nxt, 5); }
+    if (pend) { issue_load(nxt, 3); issue_load(nxt, 4); issue_load(nxt, 5); }
     read_a_hi(a_addr[0] + so, fa1);
     __builtin_amdgcn_sched_barrier(0);
-    mfma_q(H0{}, fa0, fw0, nxt, 3, pend ? 3 : 0);
-    W8_KSTAMP(1);
+    mfma_q(H0{}, fa0, fw0);
     W8_LGKM0();
     // quarter 1: k-step 0, rows 64-127 | fetch k-step 1: W and rows 0-63
-    if (pend && !M3P_W8_INTERLEAVE) { issue_load(nxt, 6); issue_load(nxt, 7); }
+    if (pend) { issue_load(nxt, 6); issue_load(nxt, 7); }
     read_w(b_addr[1] + so, fw1);
     read_a_lo(a_addr[1] + so, fa0);
     __builtin_amdgcn_sched_barrier(0);
-    mfma_q(H1{}, fa1, fw0, nxt, 6, pend ? 2 : 0);
+    mfma_q(H1{}, fa1, fw0);
     if (pend) { load_done(); spread_pending = false; }
-    W8_KSTAMP(2);
     W8_LGKM0();
     // quarter 2: k-step 1, rows 0-63 | fetch k-step 1, rows 64-127 (the last LDS read of this K-tile)
     read_a_hi(a_addr[1] + so, fa1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(H0{}, fa0, fw1);
-    W8_KSTAMP(3);
     // every LDS read of this K-tile is complete and K-tile +1, requested one K-tile ago, has landed for this wave
     W8_LGKM0();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    W8_KSTAMP(4);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    W8_KSTAMP(5);
     __builtin_amdgcn_sched_barrier(0);
     if (dyn && pop_state) {
       if (pop_state == 1) {
@@ -1699,32 +1370,21 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     // (on an output tile's last K-tile both wait for the epilogue, which stages through that stage and wants the registers)
     // (epilogues with an aux tile ask for it FIRST: vmcnt retires in order, so a load issued behind the three LDS-DMAs
     //  would wait for them too - on an output tile's last K-tile the request moves into the epilogue, behind the aux loads)
-    // (M3P_MQ_EARLYREQ, A/B: the byte-decode epilogue asks for K-tile + 2 on schedule and fetches its codes BEHIND the transfers)
-    constexpr bool kReqLate = kAuxE && !(M3P_MQ_EARLYREQ && EPI == M3P_EPI_MULQ);
-    const bool req = W8_MORE2 && (!last_kt || (kSpare && !kReqLate));
+    const bool req = W8_MORE2 && (!last_kt || !kAuxE);
     if (req) {
-      if (!M3P_W8_SPREAD) stage_next(cur);
-      else if (!M3P_W8_INTERLEAVE) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); }
-      if (M3P_W8_SPREAD) spread_pending = true;
+      issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2);
+      spread_pending = true;
     }
     if (W8_H1 && !last_kt) {
       read_w(b_addr[0] + nxt * STAGE, fw0);
       read_a_lo(a_addr[0] + nxt * STAGE, fa0);
     }
     __builtin_amdgcn_sched_barrier(0);
-    mfma_q(H1{}, fa1, fw1, cur, 0, (req && M3P_W8_SPREAD) ? 3 : 0);
-    W8_KSTAMP(6);
+    mfma_q(H1{}, fa1, fw1);
     W8_LGKM0();
-#ifdef M3P_W8_TL
-#pragma unroll
-    for (int i = 0; i < 6; ++i) kq[i] += kst[i + 1] - kst[i];
-    kq[6] += 1;
-    kst[0] = kst[6];
-#endif
 
     if (++c_kt == nk) {
       // ---- epilogue of output tile c_q through the vacated stage `cur`
-      W8_TSEG(0);
       c_kt = 0;
       // (dynamic, nk >= 8: the loader moved on to the next tile two K-tiles ago; -1 behind the last one)
       const int t = dyn ? t_cmp : tile_of(c_q);
@@ -1753,7 +1413,6 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        W8_TSEG(2);
       } else if constexpr (kGqLut) {
         // (the launcher admits whole, aligned tiles only: `fast` always holds)
         f32x4 bnext[4];
@@ -1790,21 +1449,6 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
         for (int i = 0; i < 8; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j) acc[i][j] = bnext[j];
-        W8_TSEG(2);
-      } else if constexpr (EPI == M3P_EPI_BIAS_GELUQ) {
-        if (fast) {
-          char* r1 = smem + 2 * STAGE + wid * 4096;
-          f32x4 biasv[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) biasv[j] = *reinterpret_cast<const f32x4*>(ep.bias + nw + j * 16 + (lane >> 4) * 4);
-          uint8_t* qo = reinterpret_cast<uint8_t*>(ep.out2) + gq_block_offset(tm, tn, tiles_n, wid, 0);
-#pragma unroll
-          for (int hf = 0; hf < 4; ++hf) {
-            epilogue_half_geluq(C, ldc, qo + 2048 * hf, mw + 32 * hf, nw, r1, acc[2 * hf], acc[2 * hf + 1], biasv, lane);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-        W8_TSEG(2);
       } else if constexpr (EPI == M3P_EPI_MULQ) {
         // byte derivative in fragment order: one 16-byte load per lane and 16-row piece, two pieces ahead (the launcher admits
         // whole tiles only, so `fast` always holds).  Measured and removed: all eight code loads
@@ -1814,14 +1458,10 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
         if (fast) {
           const uint8_t* qp = reinterpret_cast<const uint8_t*>(ep.aux) + gq_block_offset(tm, tn, tiles_n, wid, 0) + lane * 16;
           char* r1 = smem + 2 * STAGE + wid * 2048;
-#if M3P_MQ_ABL & 1
-#define MQ_LD(off) u32x4{(uint32_t)lane * 0x01010101u, 0x40404040u + (off), 0x80808080u, 0xc0c0c0c0u}
-#else
-#define MQ_LD(off) (M3P_MQ_NTLOAD ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(qp + (off))) : *reinterpret_cast<const u32x4*>(qp + (off)))
-#endif
+#define MQ_LD(off) (*reinterpret_cast<const u32x4*>(qp + (off)))
           u32x4 qa = MQ_LD(0), qb = MQ_LD(1024);
           __builtin_amdgcn_sched_barrier(0);
-          if (W8_MORE2 && !M3P_MQ_EARLYREQ) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
+          if (W8_MORE2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
           __builtin_amdgcn_sched_barrier(0);
           if constexpr (O8) {      // + the 8-bit copy of dU for an fp8 dx1 product
             const float sc8 = ep.scale8 ? *ep.scale8 : 1.f;
@@ -1854,19 +1494,8 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           }
           }
 #undef MQ_LD
-#if M3P_MQ_PREFETCH
-          // the NEXT output tile's codes (this wave's 8 KB = 64 lines) pulled towards this XCD's L2 a whole K loop ahead: one
-          // 4-byte LDS-DMA per lane, each touching another 128-byte line, into 256 idle bytes behind the staging rows
-          if (dyn ? (t_cmp >= 0) : (c_q < my_tiles)) {
-            int tm2, tn2;
-            split_tile(dyn ? t_cmp : tile_of(c_q), tm2, tn2);
-            const uint8_t* pf = reinterpret_cast<const uint8_t*>(ep.aux) + gq_block_offset(tm2, tn2, tiles_n, wid, 0) + lane * 128;
-            __builtin_amdgcn_global_load_lds(GLB_PTR(pf), LDS_PTR(smem + 2 * STAGE + 8 * 2048 + wid * 256), 4, 0, 0);
-          }
-#endif
         }
-        W8_TSEG(2);
-      } else if (fast && kSpare && kMulE) {
+      } else if (fast && kMulE) {
         // 16-row pieces, the aux rows of the next piece in flight while this one is computed
         char* r1 = smem + 2 * STAGE + kTabBytes + wid * 2048;
         u32x4 ta[2], tb[2];
@@ -1883,13 +1512,12 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           epilogue_piece16<EPI>(ep, C, ldc, mw + 16 * (hp + 1), nw, r1, acc[hp + 1], tb, lane, csum, gtab);
           __builtin_amdgcn_sched_barrier(0);
         }
-        W8_TSEG(2);
       } else if (fast) {
-        char* r1 = kSpare ? smem + 2 * STAGE + wid * 4096 : smem + cur * STAGE + wid * 6144;
+        char* r1 = smem + 2 * STAGE + wid * 4096;
         f32x4 biasv[4];
         load_bias4<EPI>(ep, nw, lane, biasv);
         u32x4 aux0[4];
-        if (kSpare && kAuxE) {
+        if (kAuxE) {
           load_aux_rows_issue<EPI>(ep, mw, nw, lane, aux0);
           __builtin_amdgcn_sched_barrier(0);
           if (W8_MORE2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
@@ -1903,19 +1531,13 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) rows[ii][j] = acc[2 * hf + ii][j];
           bf16x4 auxv[2][4];
-          constexpr bool kAlds = M3P_EPI_ALDS && kSpare;      // (staging accesses the compiler does not see: no vmcnt(0) per piece)
-          if (kSpare && kAuxE && hf == 0) load_aux_rows_finish<EPI, kSpare, kAlds>(lane, r1, aux0, auxv);
-          else load_aux_rows<EPI, kSpare, kAlds>(ep, mw + 32 * hf, nw, lane, r1, auxv);
-#ifdef M3P_W8_TL
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          W8_TSEG(1);
-#endif
-          epilogue_half<EPI, kSpare, kAlds>(ep, C, ldc, N, mw + 32 * hf, nw, r1, rows, biasv, auxv, lane, csum, gtab);
-          W8_TSEG(2);
+          if (kAuxE && hf == 0) load_aux_rows_finish<EPI, true>(lane, r1, aux0, auxv);
+          else load_aux_rows<EPI, true>(ep, mw + 32 * hf, nw, lane, r1, auxv);
+          epilogue_half<EPI, true>(ep, C, ldc, N, mw + 32 * hf, nw, r1, rows, biasv, auxv, lane, csum, gtab);
           __builtin_amdgcn_sched_barrier(0);      // one piece at a time: hoisted loads of the next piece cost registers
         }
       } else {
-        if (kSpare && kAuxE && W8_MORE2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
+        if (kAuxE && W8_MORE2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1929,19 +1551,10 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       if (W8_H1) {
-        if (!kSpare) {
-          // the staging rows are where K-tile +2 goes: nobody requests it before every wave is done with its round trip
-          W8_LGKM0();
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          if (W8_MORE2) stage_next(cur);
-        }
         read_w(b_addr[0] + nxt * STAGE, fw0);
         read_a_lo(a_addr[0] + nxt * STAGE, fa0);
         W8_LGKM0();
       }
-      W8_TSEG(3);
-      W8_KSTAMP0();
     }
     if (dyn) {
       if (!h1d) break;
@@ -1968,19 +1581,8 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       }
     }
   }
-#ifdef M3P_W8_TL
-  tacc[6] = __builtin_amdgcn_s_memtime();
-  if (lane == 0)
-    for (int k = 0; k < 8; ++k) {
-      g_ring_tl[(blockIdx.x * 8 + wid) * 8 + k] = tacc[k];
-      g_ring_tl[256 * 8 * 8 + (blockIdx.x * 8 + wid) * 8 + k] = kq[k];
-    }
-#endif
 #undef W8_H1
 #undef W8_MORE2
-#undef W8_TSEG
-#undef W8_KSTAMP
-#undef W8_KSTAMP0
 #undef W8_DSR
 #undef W8_LGKM0
 }
@@ -2010,18 +1612,14 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = tiles_m * tiles_n;
-  constexpr int strip_arg = 0;
-  const int strip_req = strip_arg & 15;
-  const int n_strips = strip_req ? (tiles_n + strip_req - 1) / strip_req : ((tiles_n >= 12) ? (tiles_n + 3) / 4 : 1);
+  const int n_strips = (tiles_n >= 12) ? (tiles_n + 3) / 4 : 1;
   const int strip_w = (tiles_n + n_strips - 1) / n_strips;
-  const bool serpentine = (strip_arg & 16) != 0;
   auto split_tile = [&](int t, int& tm, int& tn) {
     const int strip = t / (tiles_m * strip_w);
     const int rem = t - strip * tiles_m * strip_w;
     const int bn = min(strip_w, tiles_n - strip * strip_w);
     tm = rem / bn;
     tn = strip * strip_w + (rem - tm * bn);
-    if (serpentine && (strip & 1)) tm = tiles_m - 1 - tm;
   };
   const int nwg = gridDim.x;
   const int per_xcd = nwg >> 3;
@@ -2030,13 +1628,12 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
   const int my_tiles = (ntiles > slot) ? (ntiles - slot + nwg - 1) / nwg : 0;
   if (my_tiles == 0) return;
   // the epilogue stages through the 32 KB beside the two stages, like the bf16 kernel (see there)
-  constexpr bool kSpare = M3P_W8_SPARE_EPILOGUE;
   constexpr bool kMulE = (EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL);
   constexpr bool kAuxE = (EPI == M3P_EPI_BIAS_DROP_RES || EPI == M3P_EPI_RES || kMulE);
-  constexpr bool kGqLut = (EPI == M3P_EPI_BIAS_GELUQ) && M3P_GQ_LUT;
-  constexpr int kTabBytes = (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) ? GELU_TAB_N * (int)sizeof(float) : (kGqLut ? GQ_TAB_BYTES : 0);
-  float* gtab = (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) ? reinterpret_cast<float*>(smem + 2 * STAGE) : nullptr;
-  if (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT) gelu_grad_table_fill(gtab, tid, 512);
+  constexpr bool kGqLut = (EPI == M3P_EPI_BIAS_GELUQ);
+  constexpr int kTabBytes = (EPI == M3P_EPI_DGELU) ? GELU_TAB_N * (int)sizeof(float) : (kGqLut ? GQ_TAB_BYTES : 0);
+  float* gtab = (EPI == M3P_EPI_DGELU) ? reinterpret_cast<float*>(smem + 2 * STAGE) : nullptr;
+  if (EPI == M3P_EPI_DGELU) gelu_grad_table_fill(gtab, tid, 512);
   if (kGqLut) geluq_table_fill(reinterpret_cast<uint32_t*>(smem + 2 * STAGE), tid, 512);      // (the prologue's barrier publishes it)
   const int nk = K / BK8;
   const int total = my_tiles * nk;
@@ -2188,7 +1785,7 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (!LAST || (kSpare && !kAuxE)) {
+    if (!LAST || !kAuxE) {
       if (more2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
     }
     if (!LAST) read_a(Q0{}, nxt * STAGE, fa0);           // (stale bytes after the very last K-tile: never used)
@@ -2228,7 +1825,7 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
         csum_nw = nw;
       }
       const bool fast = io_aligned && (m0 + BM <= M) && (n0 + BN <= N);
-      if (fast && kSpare && kMulE) {
+      if (fast && kMulE) {
         char* r1 = smem + 2 * STAGE + kTabBytes + wid * 2048;
         u32x4 ta[2], tb[2];
         aux16_issue(ep, mw, nw, lane, ta);
@@ -2250,11 +1847,11 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
           __builtin_amdgcn_sched_barrier(0);
         }
       } else if (fast) {
-        char* r1 = kSpare ? smem + 2 * STAGE + wid * 4096 : smem + cur * STAGE + wid * 6144;
+        char* r1 = smem + 2 * STAGE + wid * 4096;
         f32x4 biasv[4];
         load_bias4<EPI>(ep, nw, lane, biasv);
         u32x4 aux0[4];
-        if (kSpare && kAuxE) {
+        if (kAuxE) {
           load_aux_rows_issue<EPI>(ep, mw, nw, lane, aux0);
           __builtin_amdgcn_sched_barrier(0);
           if (more2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
@@ -2268,13 +1865,13 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
 #pragma unroll
             for (int j = 0; j < 4; ++j) rows[ii][j] = acc[2 * hf + ii][j] * dsc;
           bf16x4 auxv[2][4];
-          if (kSpare && kAuxE && hf == 0) load_aux_rows_finish<EPI, kSpare>(lane, r1, aux0, auxv);
-          else load_aux_rows<EPI, kSpare>(ep, mw + 32 * hf, nw, lane, r1, auxv);
-          epilogue_half<EPI, kSpare>(ep, C, ldc, N, mw + 32 * hf, nw, r1, rows, biasv, auxv, lane, csum, gtab);
+          if (kAuxE && hf == 0) load_aux_rows_finish<EPI, true>(lane, r1, aux0, auxv);
+          else load_aux_rows<EPI, true>(ep, mw + 32 * hf, nw, lane, r1, auxv);
+          epilogue_half<EPI, true>(ep, C, ldc, N, mw + 32 * hf, nw, r1, rows, biasv, auxv, lane, csum, gtab);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
-        if (kSpare && kAuxE && more2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
+        if (kAuxE && more2) { issue_load(cur, 0); issue_load(cur, 1); issue_load(cur, 2); spread_pending = true; }
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -2286,12 +1883,6 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (more1) {
-        if (!kSpare) {
-          F8_LGKM0();
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          if (more2) stage_next(cur);
-        }
         read_w(nxt * STAGE, fw);
         read_a(Q0{}, nxt * STAGE, fa0);
         F8_LGKM0();
@@ -2518,31 +2109,21 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
 // K-tiles are 64 deep with full 128-B rows: the first version of this kernel staged 32-deep
 // tiles (64-B row segments) and stalled on L2 ingest - tools/probe_ingest.py measures
 // 33 B/clk/CU for LDS-DMA with 64-B segments against 64 B/clk/CU with 128-B segments.
-// Pipeline (two 64-KB stages, one s_barrier per 128 MFMAs):
-//   phase 1 of K-tile j: 64 MFMAs on k-step 0 (registers) | ds_read k-step 1 of tile j
-//                        | the last LDS-DMAs of tile j+1
-//   mid:  lgkmcnt(0), vmcnt -> tile j+1 has landed, s_barrier (everyone is done with stage j)
-//   phase 2: 64 MFMAs on k-step 1 | ds_read k-step 0 of tile j+1 | first LDS-DMAs of tile j+2
-//            into stage j
-// The 16 LDS-DMAs of a K-tile are spread over phase 2 and the start of the next phase 1: issued
-// back to back in phase 2 alone they ask the texture path for its full 64 B/clk and the issuing
-// waves (alone on their SIMDs, nothing else to run) stall on the queue.  Memory instructions
+// Pipeline: two 64-KB stages, 128 MFMAs per K-tile with every fragment read and LDS-DMA in their shadow
+// (the schedule is at ktile below).  The 16 LDS-DMAs of a K-tile are spread out: issued back to back
+// they ask the texture path for its full 64 B/clk and the issuing waves (alone on their SIMDs,
+// nothing else to run) stall on the queue.  Memory instructions
 // themselves are free in the shadow of an MFMA (tools/probe_issue2.py: +1 clock per 8 MFMAs).
-// One M0 per operand and K-tile: LDS destinations are selected by the immediate offset, which
-// moves source and destination together (tools/probe_dma_offset.py).
+// LDS destinations are selected by the immediate offset, which moves source and destination
+// together (tools/probe_dma_offset.py).
 // The epilogue runs from a private 4.5-KB staging area per wave; the loads of the next
 // output tile are already in flight under it.
 // ---------------------------------------------------------------------------------
-template <int EPI, bool TL = false, int ABL = 0>
+template <int EPI>
 __global__ __launch_bounds__(256)
 void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
                        bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
-                       int tiles_m, int tiles_n, int m_fast, unsigned long long* __restrict__ dbg = nullptr) {
-  // TL: debug instantiation that accumulates s_memtime per pipeline segment (tools/gemm_timeline.py);
-  // ABL (TL only): bit 0 = no fragment reads, bit 1 = no LDS-DMA, bit 2 = every K-tile re-reads the first
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tl0 = TL ? __builtin_amdgcn_s_memtime() : 0, tl1;
-#define W4_TSEG(k) do { if (TL) { tl1 = __builtin_amdgcn_s_memtime(); tacc[k] += tl1 - tl0; tl0 = tl1; } } while (0)
+                       int tiles_m, int tiles_n, int m_fast) {
   constexpr int BM = 256, BN = 256, KT = 64;
   constexpr int A_BYTES = BM * KT * 2, STAGE = (BM + BN) * KT * 2;     // 32 KB, 64 KB
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2571,77 +2152,43 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 
   // ---- load cursor.  One LDS-DMA instruction = 1 KB = 8 tile rows of 128 B; lane l fills slot
   // (l & 7) of row (l >> 3), which must hold 16-B chunk slot ^ (row & 7).  Wave w stages rows
-  // [64w, 64w + 64) of each operand = one contiguous 8-KB slice per operand: M0 = slice + 4096,
-  // the eight instructions differ only in the immediate -4096..3072 (sources pre-compensated:
-  // the +2048 elements in the base pointers and the -512 per row group undo the immediates).
+  // [64w, 64w + 64) of each operand = one contiguous 8-KB slice per operand.
   const int l_row = lane >> 3;
   const int l_col = ((lane & 7) ^ l_row) * 8;
   // (only full tiles come here - the launcher sends ragged shapes to the ring kernel - so the
-  //  eight row groups of a slice are a uniform stride apart and two pointers are enough)
-  // Source of piece p = (wave-uniform pointer: this K-tile's slice + 8 p rows, less what the immediate adds) + (the lane's 32-bit
-  // byte offset, one register per operand for the whole kernel): the LDS-DMA's scalar-base address form, no vector arithmetic
-  // per piece and no per-piece address registers.  (Sixteen 64-bit lane addresses live across the K-tile made the compiler
-  // park values in the AGPRs - which are this kernel's accumulators.)
+  //  eight row groups of a slice are a uniform stride apart)
+  // The transfer is buffer_load_dwordx4 ... lds: resource = this wave's slice of the operand tile, scalar offset = K-tile +
+  // piece, one 32-bit lane offset per operand for the whole kernel - no vector arithmetic per piece and no per-piece address
+  // registers.  (Sixteen 64-bit lane addresses live across the K-tile made the compiler park values in the AGPRs - which are
+  // this kernel's accumulators.)  The immediate of the buffer form is unsigned 12-bit: pieces 0-3 and 4-7 of an operand get
+  // an M0 each (slice, slice + 4 KB), immediates 0..3072.
   const uint32_t a_lane = (uint32_t)(l_row * lda + l_col) * 2u, w_lane = (uint32_t)(l_row * ldw + l_col) * 2u;
-  const size_t a_step8 = (size_t)8 * lda, w_step8 = (size_t)8 * ldw;
-  const bf16* a_tile;       // this wave's slice of the tile the load cursor points at, K-tile 0
-  const bf16* w_tile;
-  const bf16* a_base;       // ... at the cursor's K-tile
-  const bf16* w_base;
-#ifndef M3P_W4_BUFDMA
-#define M3P_W4_BUFDMA 1
-#endif
   __amdgpu_buffer_rsrc_t a_rsrc, w_rsrc;
   int l_q = 0, l_kt = 0;
   auto set_load_tile = [&](int q) {
     int tm, tn;
     split_tile(tile_of(q), tm, tn);
-    a_base = a_tile = A + (size_t)(tm * BM + wid * 64) * lda;
-    w_base = w_tile = W + (size_t)(tn * BN + wid * 64) * ldw;
-    if (M3P_W4_BUFDMA) {
-      a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_tile)), 0, 0xffffffff, 0x00020000);
-      w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_tile)), 0, 0xffffffff, 0x00020000);
-    }
+    const bf16* a_tile = A + (size_t)(tm * BM + wid * 64) * lda;      // this wave's slice of the tile, K-tile 0
+    const bf16* w_tile = W + (size_t)(tn * BN + wid * 64) * ldw;
+    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_tile)), 0, 0xffffffff, 0x00020000);
+    w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_tile)), 0, 0xffffffff, 0x00020000);
   };
-#define W4_LD1(PTR, IMM) __builtin_amdgcn_global_load_lds(GLB_PTR(PTR), LDS_PTR(sl), 16, IMM, 0)
 #define W4_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 8 ? a_rsrc : w_rsrc, LDS_PTR(sl), 16, piece < 8 ? a_lane : w_lane, soff, IMM, 0)
-  // M3P_W4_BUFDMA: the transfer as buffer_load_dwordx4 ... lds (resource = this wave's slice of the operand tile, scalar offset
-  // = K-tile + piece, one 32-bit lane offset for the whole kernel) instead of global_load_lds_dwordx4.  The immediate of the
-  // buffer form is unsigned 12-bit: pieces 0-3 and 4-7 of an operand get an M0 each (slice, slice + 4 KB), immediates 0..3072.
   auto issue_load = [&](int s, int piece) {
     const int pc = piece & 7;
-    if (M3P_W4_BUFDMA) {
-      char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + (pc >> 2) * 4096;
-      const uint32_t k_off = (ABL & 4) ? 0u : (uint32_t)l_kt * (KT * 2);
-      const uint32_t soff = __builtin_amdgcn_readfirstlane(k_off + (uint32_t)pc * (uint32_t)((piece < 8 ? lda : ldw) * 16) - (uint32_t)(pc & 3) * 1024u);
-      switch (pc & 3) {
-        case 0: W4_LDB(0); break;
-        case 1: W4_LDB(1024); break;
-        case 2: W4_LDB(2048); break;
-        default: W4_LDB(3072); break;
-      }
-      return;
-    }
-    char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + 4096;
-    const bf16* row = uniform_ptr((piece < 8 ? a_base + pc * a_step8 : w_base + pc * w_step8) - (pc - 4) * 512);
-    uint32_t lane_off = piece < 8 ? a_lane : w_lane;
-    asm volatile("" : "+v"(lane_off));      // (the zero-extension has to sit beside the DMA for the scalar-base form to be selected)
-    const char* src = reinterpret_cast<const char*>(row) + lane_off;
-    switch (pc) {
-      case 0: W4_LD1(src, -4096); break;
-      case 1: W4_LD1(src, -3072); break;
-      case 2: W4_LD1(src, -2048); break;
-      case 3: W4_LD1(src, -1024); break;
-      case 4: W4_LD1(src, 0); break;
-      case 5: W4_LD1(src, 1024); break;
-      case 6: W4_LD1(src, 2048); break;
-      default: W4_LD1(src, 3072); break;
+    char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + (pc >> 2) * 4096;
+    const uint32_t k_off = (uint32_t)l_kt * (KT * 2);
+    const uint32_t soff = __builtin_amdgcn_readfirstlane(k_off + (uint32_t)pc * (uint32_t)((piece < 8 ? lda : ldw) * 16) - (uint32_t)(pc & 3) * 1024u);
+    switch (pc & 3) {
+      case 0: W4_LDB(0); break;
+      case 1: W4_LDB(1024); break;
+      case 2: W4_LDB(2048); break;
+      default: W4_LDB(3072); break;
     }
   };
   auto load_done = [&]() {
     // (past the end of the stream the last tile's K-tiles are requested again into stages nobody reads)
     if (++l_kt == nk) { l_kt = 0; ++l_q; if (l_q < my_tiles) set_load_tile(l_q); }
-    if (!(ABL & 4)) { a_base = a_tile + l_kt * KT; w_base = w_tile + l_kt * KT; }
   };
 
   // ---- fragment addressing (as in the ring kernel: 128-B rows, chunk ^= row & 7)
@@ -2658,7 +2205,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     a_addr1[ks] = a_addr[ks] + STAGE;
     b_addr1[ks] = b_addr[ks] + STAGE;
   }
-#define W4_DSR(dst, addr, off) do { if (!(ABL & 1)) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr)); } while (0)
+#define W4_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
 #define W4_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   // The 256 accumulator registers live in a[0:255] under OUR control: every MFMA and every
@@ -2671,18 +2218,13 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 #define W4_ACC(I, J) "a[((" #I ")*8+(" #J "))*4:((" #I ")*8+(" #J "))*4+3]"
 #define W4_M(FA, FW, I, J) do { if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 " W4_ACC(I, J) ", %1, %0, 0" :: "v"(FA[I]), "v"(FW[J])); \
                                 else asm volatile("v_mfma_f32_16x16x32_bf16 " W4_ACC(I, J) ", %1, %0, " W4_ACC(I, J) :: "v"(FA[I]), "v"(FW[J])); } while (0)
-#define W4_L(PIECE) do { if (!(ABL & 2)) issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_LP(PIECE) do { if (!(ABL & 2) && PEND) issue_load(s_cur ^ 1, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define W4_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   bf16x8 fa0[8], fw0[8], fa1[8], fw1[8];
-#ifndef M3P_W4_SCHED2
-#define M3P_W4_SCHED2 1
-#endif
 #define W4_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#if M3P_W4_SCHED2
   // One K-tile (tile j in stage s, tile j+1 landing in stage s^1) = 128 MFMAs with every memory instruction in their shadow.
   // What decides the schedule is the time a global -> LDS transfer is given to land:
   //   MFMA   1..15  k-step 1 of tile j: W fragments out of stage s        (k-step 0 is in registers since the previous K-tile)
@@ -2691,7 +2233,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   //         50      lgkmcnt(0) + barrier: nor A                            -> A of tile j+2 (53..)
   //        107      vmcnt(16) + barrier: tile j+1 (requested one K-tile ago) has landed for everyone
   //        108..123 k-step 0 of tile j+1 into the registers k-step 0 of tile j vacated at MFMA 63
-  // so a transfer has between 1.2 and 1.7 K-tiles (2500-3500 clocks) to land where the two-phase form above gives the last
+  // so a transfer has between 1.2 and 1.7 K-tiles (2500-3500 clocks) to land where the earlier two-phase form gave the last
   // five pieces of a K-tile 46 MFMAs (740 clocks, less than an HBM miss), and the three barriers sit where their condition
   // has long been true.
   auto ktile = [&](auto first_c, auto stage_c) {
@@ -2722,7 +2264,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       W4_M(fa0, fw0, 2, 1); W4_DSR(fa1[0], ra1, 0);
       W4_M(fa0, fw0, 2, 2);
       W4_M(fa0, fw0, 2, 3); W4_DSR(fa1[1], ra1, 2048);
-      W4_M(fa0, fw0, 2, 4); W4_WAIT_LGKM(2); W4_BAR(); W4_TSEG(0);
+      W4_M(fa0, fw0, 2, 4); W4_WAIT_LGKM(2); W4_BAR();
       W4_M(fa0, fw0, 2, 5); W4_L(8);
       W4_M(fa0, fw0, 2, 6);
       W4_M(fa0, fw0, 2, 7); W4_DSR(fa1[2], ra1, 4096);
@@ -2752,7 +2294,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       W4_M(fa0, fw0, 5, 7);
       W4_M(fa0, fw0, 6, 0);
       W4_M(fa0, fw0, 6, 1);
-      W4_M(fa0, fw0, 6, 2); W4_WAIT_LGKM(0); W4_BAR(); W4_TSEG(1);
+      W4_M(fa0, fw0, 6, 2); W4_WAIT_LGKM(0); W4_BAR();
       W4_M(fa0, fw0, 6, 3);
       W4_M(fa0, fw0, 6, 4); W4_L(14);
       W4_M(fa0, fw0, 6, 5);
@@ -2812,7 +2354,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       W4_M(fa1, fw1, 5, 0);
       W4_M(fa1, fw1, 5, 1);
       W4_M(fa1, fw1, 5, 2);
-      W4_M(fa1, fw1, 5, 3); W4_TSEG(2); W4_WAIT_VM(16); W4_TSEG(3); W4_BAR(); W4_TSEG(4);
+      W4_M(fa1, fw1, 5, 3); W4_WAIT_VM(16); W4_BAR();
       W4_M(fa1, fw1, 5, 4); W4_DSR(fw0[0], rb0n, 0);
       W4_M(fa1, fw1, 5, 5); W4_DSR(fw0[1], rb0n, 2048);
       W4_M(fa1, fw1, 5, 6); W4_DSR(fw0[2], rb0n, 4096);
@@ -2832,160 +2374,10 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       W4_M(fa1, fw1, 7, 4);
       W4_M(fa1, fw1, 7, 5);
       W4_M(fa1, fw1, 7, 6);
-      W4_M(fa1, fw1, 7, 7); W4_WAIT_LGKM(0); W4_TSEG(5);
+      W4_M(fa1, fw1, 7, 7); W4_WAIT_LGKM(0);
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-#else
-  // phase 1: k-step 0 of the current K-tile from registers; fetch its k-step 1 fragments; finish
-  // the LDS-DMA list phase 2 of the previous iteration started (`pend`)
-  auto phase1 = [&](auto first_c, auto stage_c, auto pend_c) {
-    constexpr bool FIRST = decltype(first_c)::value;   // first K-tile of an output tile: C operand = 0
-    constexpr int s_cur = decltype(stage_c)::value;
-    constexpr bool PEND = decltype(pend_c)::value;     // (false in a workgroup's very first step only)
-    const uint32_t ra1 = s_cur ? a_addr1[1] : a_addr[1], rb1 = s_cur ? b_addr1[1] : b_addr[1];
-    __builtin_amdgcn_sched_barrier(0);
-    W4_M(fa0, fw0, 0, 0);
-    W4_M(fa0, fw0, 0, 1); W4_DSR(fw1[0], rb1, 0);
-    W4_M(fa0, fw0, 0, 2); W4_LP(11);
-    W4_M(fa0, fw0, 0, 3); W4_DSR(fw1[1], rb1, 2048);
-    W4_M(fa0, fw0, 0, 4);
-    W4_M(fa0, fw0, 0, 5); W4_DSR(fw1[2], rb1, 4096);
-    W4_M(fa0, fw0, 0, 6); W4_LP(12);
-    W4_M(fa0, fw0, 0, 7); W4_DSR(fw1[3], rb1, 6144);
-    W4_M(fa0, fw0, 1, 0);
-    W4_M(fa0, fw0, 1, 1); W4_DSR(fw1[4], rb1, 8192);
-    W4_M(fa0, fw0, 1, 2); W4_LP(13);
-    W4_M(fa0, fw0, 1, 3); W4_DSR(fw1[5], rb1, 10240);
-    W4_M(fa0, fw0, 1, 4);
-    W4_M(fa0, fw0, 1, 5); W4_DSR(fw1[6], rb1, 12288);
-    W4_M(fa0, fw0, 1, 6); W4_LP(14);
-    W4_M(fa0, fw0, 1, 7); W4_DSR(fw1[7], rb1, 14336);
-    W4_M(fa0, fw0, 2, 0);
-    W4_M(fa0, fw0, 2, 1); W4_DSR(fa1[0], ra1, 0);
-    W4_M(fa0, fw0, 2, 2); W4_LP(15);
-    W4_M(fa0, fw0, 2, 3); W4_DSR(fa1[1], ra1, 2048);
-    W4_M(fa0, fw0, 2, 4);
-    W4_M(fa0, fw0, 2, 5); W4_DSR(fa1[2], ra1, 4096);
-    W4_M(fa0, fw0, 2, 6);
-    W4_M(fa0, fw0, 2, 7); W4_DSR(fa1[3], ra1, 6144);
-    W4_M(fa0, fw0, 3, 0);
-    W4_M(fa0, fw0, 3, 1); W4_DSR(fa1[4], ra1, 8192);
-    W4_M(fa0, fw0, 3, 2);
-    W4_M(fa0, fw0, 3, 3); W4_DSR(fa1[5], ra1, 10240);
-    W4_M(fa0, fw0, 3, 4);
-    W4_M(fa0, fw0, 3, 5); W4_DSR(fa1[6], ra1, 12288);
-    W4_M(fa0, fw0, 3, 6);
-    W4_M(fa0, fw0, 3, 7); W4_DSR(fa1[7], ra1, 14336);
-    W4_M(fa0, fw0, 4, 0);
-    W4_M(fa0, fw0, 4, 1);
-    W4_M(fa0, fw0, 4, 2);
-    W4_M(fa0, fw0, 4, 3);
-    W4_M(fa0, fw0, 4, 4);
-    W4_M(fa0, fw0, 4, 5);
-    W4_M(fa0, fw0, 4, 6);
-    W4_M(fa0, fw0, 4, 7);
-    W4_M(fa0, fw0, 5, 0);
-    W4_M(fa0, fw0, 5, 1);
-    W4_M(fa0, fw0, 5, 2);
-    W4_M(fa0, fw0, 5, 3);
-    W4_M(fa0, fw0, 5, 4);
-    W4_M(fa0, fw0, 5, 5);
-    W4_M(fa0, fw0, 5, 6);
-    W4_M(fa0, fw0, 5, 7);
-    W4_M(fa0, fw0, 6, 0);
-    W4_M(fa0, fw0, 6, 1);
-    W4_M(fa0, fw0, 6, 2);
-    W4_M(fa0, fw0, 6, 3);
-    W4_M(fa0, fw0, 6, 4);
-    W4_M(fa0, fw0, 6, 5);
-    W4_M(fa0, fw0, 6, 6);
-    W4_M(fa0, fw0, 6, 7);
-    W4_M(fa0, fw0, 7, 0);
-    W4_M(fa0, fw0, 7, 1);
-    W4_M(fa0, fw0, 7, 2);
-    W4_M(fa0, fw0, 7, 3);
-    W4_M(fa0, fw0, 7, 4);
-    W4_M(fa0, fw0, 7, 5);
-    W4_M(fa0, fw0, 7, 6);
-    W4_M(fa0, fw0, 7, 7);
-    __builtin_amdgcn_sched_barrier(0);
-    if (PEND) load_done();
-  };
-  // phase 2: k-step 1; the stage just vacated by everyone (barrier) starts receiving K-tile +2,
-  // and k-step 0 of the next K-tile comes out of the other stage
-  auto phase2 = [&](auto stage_c) {
-    constexpr bool FIRST = false;
-    constexpr int s_cur = decltype(stage_c)::value;
-    const uint32_t ra0n = s_cur ? a_addr[0] : a_addr1[0], rb0n = s_cur ? b_addr[0] : b_addr1[0];
-    __builtin_amdgcn_sched_barrier(0);
-    W4_M(fa1, fw1, 0, 0); W4_L(0);
-    W4_M(fa1, fw1, 0, 1); W4_DSR(fw0[0], rb0n, 0);
-    W4_M(fa1, fw1, 0, 2);
-    W4_M(fa1, fw1, 0, 3); W4_DSR(fw0[1], rb0n, 2048);
-    W4_M(fa1, fw1, 0, 4);
-    W4_M(fa1, fw1, 0, 5); W4_DSR(fw0[2], rb0n, 4096);
-    W4_M(fa1, fw1, 0, 6); W4_L(1);
-    W4_M(fa1, fw1, 0, 7); W4_DSR(fw0[3], rb0n, 6144);
-    W4_M(fa1, fw1, 1, 0);
-    W4_M(fa1, fw1, 1, 1); W4_DSR(fw0[4], rb0n, 8192);
-    W4_M(fa1, fw1, 1, 2);
-    W4_M(fa1, fw1, 1, 3); W4_DSR(fw0[5], rb0n, 10240);
-    W4_M(fa1, fw1, 1, 4); W4_L(2);
-    W4_M(fa1, fw1, 1, 5); W4_DSR(fw0[6], rb0n, 12288);
-    W4_M(fa1, fw1, 1, 6);
-    W4_M(fa1, fw1, 1, 7); W4_DSR(fw0[7], rb0n, 14336);
-    W4_M(fa1, fw1, 2, 0);
-    W4_M(fa1, fw1, 2, 1); W4_DSR(fa0[0], ra0n, 0);
-    W4_M(fa1, fw1, 2, 2); W4_L(3);
-    W4_M(fa1, fw1, 2, 3); W4_DSR(fa0[1], ra0n, 2048);
-    W4_M(fa1, fw1, 2, 4);
-    W4_M(fa1, fw1, 2, 5); W4_DSR(fa0[2], ra0n, 4096);
-    W4_M(fa1, fw1, 2, 6);
-    W4_M(fa1, fw1, 2, 7); W4_DSR(fa0[3], ra0n, 6144);
-    W4_M(fa1, fw1, 3, 0); W4_L(4);
-    W4_M(fa1, fw1, 3, 1); W4_DSR(fa0[4], ra0n, 8192);
-    W4_M(fa1, fw1, 3, 2);
-    W4_M(fa1, fw1, 3, 3); W4_DSR(fa0[5], ra0n, 10240);
-    W4_M(fa1, fw1, 3, 4);
-    W4_M(fa1, fw1, 3, 5); W4_DSR(fa0[6], ra0n, 12288);
-    W4_M(fa1, fw1, 3, 6); W4_L(5);
-    W4_M(fa1, fw1, 3, 7); W4_DSR(fa0[7], ra0n, 14336);
-    W4_M(fa1, fw1, 4, 0);
-    W4_M(fa1, fw1, 4, 1);
-    W4_M(fa1, fw1, 4, 2);
-    W4_M(fa1, fw1, 4, 3);
-    W4_M(fa1, fw1, 4, 4); W4_L(6);
-    W4_M(fa1, fw1, 4, 5);
-    W4_M(fa1, fw1, 4, 6);
-    W4_M(fa1, fw1, 4, 7);
-    W4_M(fa1, fw1, 5, 0);
-    W4_M(fa1, fw1, 5, 1);
-    W4_M(fa1, fw1, 5, 2); W4_L(7);
-    W4_M(fa1, fw1, 5, 3);
-    W4_M(fa1, fw1, 5, 4);
-    W4_M(fa1, fw1, 5, 5);
-    W4_M(fa1, fw1, 5, 6);
-    W4_M(fa1, fw1, 5, 7);
-    W4_M(fa1, fw1, 6, 0); W4_L(8);
-    W4_M(fa1, fw1, 6, 1);
-    W4_M(fa1, fw1, 6, 2);
-    W4_M(fa1, fw1, 6, 3);
-    W4_M(fa1, fw1, 6, 4);
-    W4_M(fa1, fw1, 6, 5);
-    W4_M(fa1, fw1, 6, 6); W4_L(9);
-    W4_M(fa1, fw1, 6, 7);
-    W4_M(fa1, fw1, 7, 0);
-    W4_M(fa1, fw1, 7, 1);
-    W4_M(fa1, fw1, 7, 2);
-    W4_M(fa1, fw1, 7, 3);
-    W4_M(fa1, fw1, 7, 4);
-    W4_M(fa1, fw1, 7, 5);
-    W4_M(fa1, fw1, 7, 6); W4_L(10);
-    W4_M(fa1, fw1, 7, 7);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#endif
 
   // ---- prologue: K-tiles 0 and 1 into stages 0 and 1
   set_load_tile(0);
@@ -3023,31 +2415,10 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
         load_bias4<EPI>(ep, btn * BN + wn * 128, lane, bias_lo);
         load_bias4<EPI>(ep, btn * BN + wn * 128 + 64, lane, bias_hi);
       }
-#if M3P_W4_SCHED2
       ktile(std::true_type{}, stage_c);
     } else {
       ktile(std::false_type{}, stage_c);
     }
-#else
-      if (step == 0) phase1(std::true_type{}, stage_c, std::false_type{});
-      else phase1(std::true_type{}, stage_c, std::true_type{});
-    } else {
-      phase1(std::false_type{}, stage_c, std::true_type{});
-    }
-    W4_TSEG(0);
-    W4_LGKM0();
-    W4_TSEG(1);
-    // everything this wave has in flight is K-tile step+1 (and older epilogue stores)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    W4_TSEG(2);
-    __builtin_amdgcn_s_barrier();      // K-tile step+1 visible to all; stage s_cur fully read by all
-    asm volatile("" ::: "memory");
-    W4_TSEG(3);
-    phase2(stage_c);
-    W4_TSEG(0);
-    W4_LGKM0();
-    W4_TSEG(1);
-#endif
     if (++c_kt == nk) {
       // ---- epilogue of output tile c_q out of the wave-private staging area
       c_kt = 0;
@@ -3073,15 +2444,12 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 #define W4_SLICE(RG, CH)                                                                      \
   W4_RD(0, 0, 2 * RG, 4 * CH); W4_RD(0, 1, 2 * RG, 4 * CH + 1); W4_RD(0, 2, 2 * RG, 4 * CH + 2); W4_RD(0, 3, 2 * RG, 4 * CH + 3); \
   W4_RD(1, 0, 2 * RG + 1, 4 * CH); W4_RD(1, 1, 2 * RG + 1, 4 * CH + 1); W4_RD(1, 2, 2 * RG + 1, 4 * CH + 2); W4_RD(1, 3, 2 * RG + 1, 4 * CH + 3)
-#ifndef M3P_W4_PIPE_EPI
-#define M3P_W4_PIPE_EPI 1
-#endif
       // The plain epilogues with LDS accesses the compiler does not see (see lds_w64 ...): with transfers for the next output
       // tile in flight it puts s_waitcnt vmcnt(0) in front of every staging access it knows of, i.e. every piece waits for the
       // previous piece's global stores (~1150 clocks a piece, 9.2 k per output tile, a fifth of a K = 768 launch -
-      // tools/gemm_timeline.py).  One swizzled 4-KB buffer inside each wave's 4.5-KB staging area (146 KB of LDS in all: a
+      // timeline in DESIGN.md).  One swizzled 4-KB buffer inside each wave's 4.5-KB staging area (146 KB of LDS in all: a
       // collective's kernel can still share the CU).
-      constexpr bool kPipe = M3P_W4_PIPE_EPI && (EPI == M3P_EPI_NONE || EPI == M3P_EPI_BIAS || EPI == M3P_EPI_RES || EPI == M3P_EPI_BIAS_DROP_RES);
+      constexpr bool kPipe = (EPI == M3P_EPI_NONE || EPI == M3P_EPI_BIAS || EPI == M3P_EPI_RES || EPI == M3P_EPI_BIAS_DROP_RES);
       if (kPipe && fast) {
         char* rb = smem + 2 * STAGE + wid * EP_HALF;      // (one swizzled 4-KB buffer inside the wave's 4.5-KB staging area)
         u32x4 tq[4];
@@ -3111,7 +2479,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           //  destination registers can slip in between; what the asm accesses buy is the absence of vmcnt(0) - the stores of
           //  piece p are in flight under piece p + 1)
           u32x4 R[4];
-          epilogue_rows_read<true, true>(rc, lane, R);
+          epilogue_rows_read<true>(rc, lane, R);
           lgkm_wait_rows<true>(R, false);
           epilogue_rows_store(C, ldc, mw + 32 * rg, nw + 64 * ch, lane, R);
         }
@@ -3169,7 +2537,6 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       }
 #undef W4_SLICE
 #undef W4_RD
-      W4_TSEG(M3P_W4_SCHED2 ? 6 : 4);
     }
   };
   for (int step = 0; step < total; step += 2) {
@@ -3177,20 +2544,12 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     if (step + 1 < total) kstep(std::integral_constant<int, 1>{}, step + 1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
-  if (TL) {
-    W4_TSEG(M3P_W4_SCHED2 ? 7 : 6);
-    if (lane == 0)
-      for (int k = 0; k < 8; ++k) dbg[((size_t)blockIdx.x * 8 + wid) * 8 + k] = tacc[k];
-  }
-#undef W4_TSEG
-#undef W4_LD1
 #undef W4_LDB
 #undef W4_ACC
 #undef W4_DSR
 #undef W4_LGKM0
 #undef W4_M
 #undef W4_L
-#undef W4_LP
 #undef W4_WAIT_LGKM
 #undef W4_WAIT_VM
 #undef W4_BAR
@@ -3305,12 +2664,9 @@ static int* tq_acquire(hipStream_t st, hipError_t* err) {
   return g_tq_pool + 8 * g_tq_next++;
 }
 
-#ifndef M3P_W8_MAX_W_BYTES
-#define M3P_W8_MAX_W_BYTES (1LL << 40)      // (no limit: the vocabulary projection - W = 384 MB - measured 2.18 -> 1.85 ms on this kernel)
-#endif
-#ifndef M3P_W4_MIN_K
-#define M3P_W4_MIN_K 2048
-#endif
+// the four-wave kernel takes contractions from this depth on (table below); the eight-wave kernel has no limit on the size of
+// W (the vocabulary projection - W = 384 MB - measured 2.18 -> 1.85 ms on it)
+constexpr int W4_MIN_K = 2048;
 static bool tq_enabled() {
   std::lock_guard<std::mutex> lk(g_tq_mu);
   return g_tq_pool != nullptr;
@@ -3334,20 +2690,20 @@ static bool tq_enabled() {
 //   M >= 1024 otherwise (ragged M or N, N < 512)          ring 256x128, 3 stages     any shape; strip order for the vocabulary matrices
 //   M < 1024                                              128x128, 2 stages          small-M fallback (cfg1, tests)
 //
-// Developer overrides (m3p_debug_set_variant, never set by the product): 0 forces the last row, 2 the four-wave kernel wherever it
-// applies, 3 the ring kernel, 6 the eight-wave kernel, 7 round 1's choice (four-wave / ring), 9 = auto without the skinny kernel.
+// Developer overrides (m3p_debug_set_variant, never set by the product): 2 forces the four-wave kernel wherever it applies,
+// 6 the eight-wave kernel.
 // ---------------------------------------------------------------------------------------------------------------------
 static int nt_plan(int epi, int M, int N, int K, int* queue) {
   if (queue) *queue = 0;
   const bool whole = M >= 1024 && (M % 256) == 0 && (N % 256) == 0 && N >= 512 && (K % 64) == 0;
   if (epi == M3P_EPI_MULQ || epi == M3P_EPI_BIAS_GELUQ || epi == M3P_EPI_BIAS_LSE) return whole ? M3P_KERN_NT_W8 : M3P_EINVAL;
   const bool mul_epi = epi == M3P_EPI_DGELU || epi == M3P_EPI_MUL;
-  if (M <= 128 && g_variant >= 1 && g_variant != 9 && (K % 128) == 0 && !mul_epi) return M3P_KERN_NT_SKINNY;
+  if (M <= 128 && (K % 128) == 0 && !mul_epi) return M3P_KERN_NT_SKINNY;
   // (dGELU epilogue on the four-wave kernel: 240 VGPRs, measured slower in the step)
   const bool deep = N >= 512 && 2LL * N * K <= (64LL << 20) && epi != M3P_EPI_DGELU;
   const bool armed = tq_enabled();     // (the tile queue of data parallelism lives in the eight-wave kernel)
-  const bool w4_first = g_variant == 1 && deep && K >= M3P_W4_MIN_K && epi != M3P_EPI_MUL && !armed;
-  if (whole && (g_variant == 1 || g_variant == 6) && !w4_first && 2LL * N * K <= M3P_W8_MAX_W_BYTES) {
+  const bool w4_first = g_variant == 1 && deep && K >= W4_MIN_K && epi != M3P_EPI_MUL && !armed;
+  if (whole && g_variant != 2 && !w4_first) {
     // dynamic tile queue only where a workgroup takes several tiles (not for the multiply epilogues: with the queue's
     // bookkeeping on top of their aux pieces and column sums the instantiation spills ~100 bytes per lane)
     int grid = num_cus();
@@ -3356,9 +2712,9 @@ static int nt_plan(int epi, int M, int N, int K, int* queue) {
     if (queue) *queue = (!mul_epi && armed && ntiles > grid && K >= 8 * BK) ? 1 : 0;
     return M3P_KERN_NT_W8;
   }
-  if (M >= 1024 && (M % 256) == 0 && (N % 256) == 0 && (g_variant == 2 || ((g_variant == 1 || g_variant == 7) && deep)))
+  if (M >= 1024 && (M % 256) == 0 && (N % 256) == 0 && (g_variant == 2 || (g_variant == 1 && deep)))
     return M3P_KERN_NT_W4;
-  if (M >= 1024 && g_variant >= 1) return M3P_KERN_NT_RING;
+  if (M >= 1024) return M3P_KERN_NT_RING;
   return M3P_KERN_NT_128;
 }
 
@@ -3377,8 +2733,8 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
   }
   if (plan == M3P_KERN_NT_W8) {
     const int tiles_m = M / 256, tiles_n = N / 256;
-    const size_t lds = 2 * 512 * ROWB + (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT ? GELU_TAB_N * sizeof(float) : 0) +
-                       (M3P_W8_SPARE_EPILOGUE ? ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) ? 8 * 2048 : 8 * 4096) : 0);
+    const size_t lds = 2 * 512 * ROWB + (EPI == M3P_EPI_DGELU ? GELU_TAB_N * sizeof(float) : 0) +
+                       ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) ? 8 * 2048 : 8 * 4096);
     auto kern = gemm_nt_w8_kernel<EPI>;
     static bool attr_set8 = false;
     if (!attr_set8) {
@@ -3407,11 +2763,11 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
         if (e != hipSuccess) return (int)e;
         attr_set8d = true;
       }
-      hipLaunchKernelGGL(kern_d, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, ctr, g_w8_strip);
+      hipLaunchKernelGGL(kern_d, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, ctr);
       M3P_CHECK_LAUNCH();
       return M3P_OK;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, ctr, g_w8_strip);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, ctr);
     M3P_CHECK_LAUNCH();
     return M3P_OK;
   }
@@ -3419,7 +2775,7 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     constexpr int BM = 256, BN = 256;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     const size_t lds = 2 * (BM + BN) * 128 + 4 * EP_HALF;
-    auto kern = gemm_nt_w4_kernel<EPI, false>;
+    auto kern = gemm_nt_w4_kernel<EPI>;
     static bool attr_set = false;
     if (!attr_set) {
       hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -3431,14 +2787,14 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
     const long long wbytes = 2LL * N * K, abytes = 2LL * M * K;
     const int m_fast = (wbytes > (64LL << 20) && abytes < wbytes) ? 1 : 0;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, m_fast, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, m_fast);
     M3P_CHECK_LAUNCH();
     return M3P_OK;
   }
   if (plan == M3P_KERN_NT_RING) {
     constexpr int BM = 256, BN = 128;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    const size_t lds = 3 * (BM + BN) * ROWB + (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT ? GELU_TAB_N * sizeof(float) : 0);
+    const size_t lds = 3 * (BM + BN) * ROWB + (EPI == M3P_EPI_DGELU ? GELU_TAB_N * sizeof(float) : 0);
     auto kern = gemm_nt_ring_kernel<EPI>;
     static bool attr_set = false;
     if (!attr_set) {
@@ -3449,11 +2805,7 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     int grid = num_cus();                       // one persistent workgroup per CU
     const int ntiles = tiles_m * tiles_n;
     if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
-    const long long wbytes = 2LL * N * K, abytes = 2LL * M * K;
-    // (m-fastest order for a huge W used to win; with the 8-wide strips an XCD's 32 tiles are a 4 x 8 block
-    //  whose A and W panels fit its L2 together: vocabulary projection 2.20 -> 2.05 ms, 9.3 -> ~2 GB of reads)
-    const int m_fast = ((g_ablate & 8) && wbytes > (64LL << 20) && abytes < wbytes) ? 1 : 0;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, m_fast);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n);
     M3P_CHECK_LAUNCH();
     return M3P_OK;
   }
@@ -3485,7 +2837,7 @@ static int launch_nt_gq(const bf16* A, int lda, const bf16* W, int ldw, bf16* C,
     return M3P_EINVAL;
   if (EPI == M3P_EPI_BIAS_LSE && (ep.ld_out2 <= 0 || ep.ld_out2 > N)) return M3P_EINVAL;
   const int tiles_m = M / 256, tiles_n = N / 256;
-  const size_t lds = 2 * 512 * ROWB + ((EPI == M3P_EPI_BIAS_GELUQ && M3P_GQ_LUT) ? GQ_TAB_BYTES + 8 * 2048 + 8 * 1024 : 8 * (EPI != M3P_EPI_MULQ ? 4096 : 2048)) +
+  const size_t lds = 2 * 512 * ROWB + ((EPI == M3P_EPI_BIAS_GELUQ) ? GQ_TAB_BYTES + 8 * 2048 + 8 * 1024 : 8 * (EPI != M3P_EPI_MULQ ? 4096 : 2048)) +
                      (EPI == M3P_EPI_MULQ ? 2048 + 8 * 1024 : 0);      // (MULQ: behind the staging rows 2 KB - the 8-bit copy's running maxima / the
                                                                        //  prefetch experiment - and the 8-bit copy's own staging rows, 1 KB per wave)
   int grid = num_cus();
@@ -3503,7 +2855,7 @@ static int launch_nt_gq(const bf16* A, int lda, const bf16* W, int ldw, bf16* C,
         if (e != hipSuccess) return (int)e;
         attr_set8 = true;
       }
-      hipLaunchKernelGGL(kern8, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, (int*)nullptr, g_w8_strip);
+      hipLaunchKernelGGL(kern8, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, (int*)nullptr);
       M3P_CHECK_LAUNCH();
       return M3P_OK;
     }
@@ -3515,7 +2867,7 @@ static int launch_nt_gq(const bf16* A, int lda, const bf16* W, int ldw, bf16* C,
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, (int*)nullptr, g_w8_strip);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, (int*)nullptr);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
@@ -3662,8 +3014,8 @@ void gemm_wgrad_kernel(const bf16* __restrict__ dY, int lddy, const bf16* __rest
 // Weight-gradient kernel, four-wave version of the stream-K ring kernel below/above:
 // dW[i,j] += alpha * sum_m dY[m,i] X[m,j] with 256(i) x 256(j) output tiles, 128x128 per wave
 // (accumulators pinned in AGPRs as in gemm_nt_w4_kernel), 64-row K-tiles of M in two 64-KB LDS
-// stages ([64 m][256 cols] bf16, 512-B rows for both operands), the same two-phase schedule
-// (one s_barrier per 128 MFMAs, LDS-DMAs of K-tile +2 spread over phase 2 and the next phase 1).
+// stages ([64 m][256 cols] bf16, 512-B rows for both operands), the same one-piece K-tile schedule
+// (wktile below).
 // Both operands are contraction-strided, so fragments come out of LDS through
 // ds_read_b64_tr_b16 with the 32-B-segment swizzle of the ring kernel.  Stream-K bookkeeping
 // (chunk == one workgroup's share, round-robin for many tiles) is the ring kernel's; a segment
@@ -3681,7 +3033,7 @@ __global__ __launch_bounds__(256)
 void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16* __restrict__ X_a, int ldx_a,
                           float* __restrict__ dW_a, int lddw_a, int M, int N, int K, float alpha,
                           int tiles_i, int tiles_j_a, int WR_CHUNK, float* __restrict__ ws, int* __restrict__ ws_tile,
-                          int dbg_flags, int overwrite, WgradProblem pb) {
+                          int overwrite, WgradProblem pb) {
   // Two products over the same M in one launch (pb.tiles != 0; one-segment-per-workgroup mode only): the tiles of product b
   // follow those of product a in the tile numbering, every workgroup picks its product once, before the K loop.  36 tiles of
   // out_lin + q/k/v then share one launch, one end-of-kernel flush and one reduction instead of 9 tiles x 28 chunks beside
@@ -3753,29 +3105,14 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   int l_issued = 0;
   const int l_hi = lane >> 5, l_pos = lane & 31;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  int y_off[8], x_off[8];      // element offsets of this lane's 16 bytes inside the K-tile, immediates compensated
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    const int row = wid * 16 + 2 * p + l_hi;
-    const int f = (row & 3) | (((row >> 3) & 1) << 2);
-    const int gc = l_pos ^ (f << 1);
-    y_off[p] = row * lddy + gc * 8 - (-4096 + 1024 * p) / 2;
-    x_off[p] = row * ldx + gc * 8 - (-4096 + 1024 * p) / 2;
-    if (YROWS) {      // piece p of wave w = rows 64 w + 8 p .. + 7 of the 256-row panel, 128 B each: lane -> (row l >> 3, slot l & 7)
-      const int yrow = wid * 64 + 8 * p + (lane >> 3);
-      y_off[p] = yrow * lddy + (((lane & 7) ^ (yrow & 7)) * 8) - (-4096 + 1024 * p) / 2;
-    }
-  }
   const bf16* y_base;
   const bf16* x_base;
-#ifndef M3P_WG_BUFDMA
-#define M3P_WG_BUFDMA 1
-#endif
-  // M3P_WG_BUFDMA: the transfers as buffer_load_dwordx4 ... lds - resource = the K-tile's base, scalar offset = the piece's
-  // rows, a 32-bit lane offset (four per operand: the swizzle of a row depends on the piece's parity and half) - instead of
+  // The transfers are buffer_load_dwordx4 ... lds - resource = the K-tile's base, scalar offset = the piece's rows, a 32-bit
+  // lane offset (four per operand: the swizzle of a row depends on the piece's parity and half) - rather than
   // global_load_lds_dwordx4 with a 64-bit lane address per piece.  In the NT kernel the buffer form costs the issuing wave
-  // ~16 clocks a piece where the global form costs ~37 (tools/gemm_timeline.py).  The buffer form's immediate is unsigned
-  // 12-bit: pieces 0-3 and 4-7 of an operand get an M0 each.
+  // ~16 clocks a piece where the global form costs ~37.  The buffer form's immediate is unsigned 12-bit: pieces 0-3 and 4-7
+  // of an operand get an M0 each.  (YROWS: piece p of wave w = rows 64 w + 8 p .. + 7 of the 256-row panel, 128 B each:
+  // lane -> (row l >> 3, slot l & 7).)
   __amdgpu_buffer_rsrc_t y_rsrc, x_rsrc;
   uint32_t y_voff[4], x_voff[4];
 #pragma unroll
@@ -3787,10 +3124,8 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     if (YROWS) y_voff[k] = (uint32_t)((lane >> 3) * lddy + (((lane & 7) ^ (lane >> 3)) * 8)) * 2u;
   }
   auto set_rsrc = [&]() {
-    if (M3P_WG_BUFDMA) {
-      y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(y_base)), 0, 0xffffffff, 0x00020000);
-      x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(x_base)), 0, 0xffffffff, 0x00020000);
-    }
+    y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(y_base)), 0, 0xffffffff, 0x00020000);
+    x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(x_base)), 0, 0xffffffff, 0x00020000);
   };
   auto set_load_ktile = [&]() {
     const int ti = lc.t / tiles_j, tj = lc.t - ti * tiles_j;
@@ -3800,36 +3135,18 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     set_rsrc();
   };
   set_load_ktile();
-  // (written as instructions in the scalar-base form - SGPR pair + 32-bit lane offset, no 64-bit vector add per piece - the
-  //  global loads measured the same, 6.88 against 6.80 ms: the adds fit the free issue slots between two MFMAs.)
-#define WG_LD1(PTR, IMM) __builtin_amdgcn_global_load_lds(GLB_PTR(PTR), LDS_PTR(sl), 16, IMM, 0)
 #define WG_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 8 ? y_rsrc : x_rsrc, LDS_PTR(sl), 16, voff, soff, IMM, 0)
   auto issue_load = [&](int s, int piece) {
-    if (M3P_WG_BUFDMA) {
-      const int pc = piece & 7, k = (pc & 1) + 2 * (pc >> 2);
-      char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + (pc >> 2) * 4096;
-      const uint32_t voff = piece < 8 ? y_voff[YROWS ? 0 : k] : x_voff[k];
-      const uint32_t rows = (piece < 8 && YROWS) ? (uint32_t)(wid * 64 + 8 * pc) : (uint32_t)(wid * 16 + 2 * pc);
-      const uint32_t soff = __builtin_amdgcn_readfirstlane(rows * (uint32_t)((piece < 8 ? lddy : ldx) * 2) - (uint32_t)(pc & 3) * 1024u);
-      switch (pc & 3) {
-        case 0: WG_LDB(0); break;
-        case 1: WG_LDB(1024); break;
-        case 2: WG_LDB(2048); break;
-        default: WG_LDB(3072); break;
-      }
-      return;
-    }
-    char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + 4096;
-    const bf16* src = (piece < 8) ? y_base + y_off[piece & 7] : x_base + x_off[piece & 7];
-    switch (piece & 7) {
-      case 0: WG_LD1(src, -4096); break;
-      case 1: WG_LD1(src, -3072); break;
-      case 2: WG_LD1(src, -2048); break;
-      case 3: WG_LD1(src, -1024); break;
-      case 4: WG_LD1(src, 0); break;
-      case 5: WG_LD1(src, 1024); break;
-      case 6: WG_LD1(src, 2048); break;
-      default: WG_LD1(src, 3072); break;
+    const int pc = piece & 7, k = (pc & 1) + 2 * (pc >> 2);
+    char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + (pc >> 2) * 4096;
+    const uint32_t voff = piece < 8 ? y_voff[YROWS ? 0 : k] : x_voff[k];
+    const uint32_t rows = (piece < 8 && YROWS) ? (uint32_t)(wid * 64 + 8 * pc) : (uint32_t)(wid * 16 + 2 * pc);
+    const uint32_t soff = __builtin_amdgcn_readfirstlane(rows * (uint32_t)((piece < 8 ? lddy : ldx) * 2) - (uint32_t)(pc & 3) * 1024u);
+    switch (pc & 3) {
+      case 0: WG_LDB(0); break;
+      case 1: WG_LDB(1024); break;
+      case 2: WG_LDB(2048); break;
+      default: WG_LDB(3072); break;
     }
   };
   const size_t y_step = YROWS ? (size_t)KT : (size_t)KT * lddy, x_step = (size_t)KT * ldx;
@@ -3896,15 +3213,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #define WG_ACC(B, A) "a[((" #B ")*8+(" #A "))*4:((" #B ")*8+(" #A "))*4+3]"
 #define WG_M(YF, XF, B, A) do { if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 " WG_ACC(B, A) ", %0, %1, 0" :: "v"(YF[A]), "v"(XF[B])); \
                                 else asm volatile("v_mfma_f32_16x16x32_bf16 " WG_ACC(B, A) ", %0, %1, " WG_ACC(B, A) :: "v"(YF[A]), "v"(XF[B])); } while (0)
-  // (the ablation switches of tools/gemm_timeline.py are compile-time: as run-time tests they were a scalar compare + branch per
-  //  LDS-DMA - 21 per K-tile - in a wave that has no partner on its SIMD to issue around them)
-#ifdef M3P_WG_DBG
-#define WG_DBG(bit) (dbg_flags & (bit))
-#else
-#define WG_DBG(bit) 0
-#endif
-#define WG_L(PIECE) do { if (!WG_DBG(2)) issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_LP(PIECE) do { if (PEND && !WG_DBG(2)) issue_load(s_cur ^ 1, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define WG_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
   auto frag = [](const s16x4& lo, const s16x4& hi) {
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
@@ -3913,161 +3222,13 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   bf16x8 yq[8];                         // (YROWS: the first operand's fragments arrive whole)
   auto yfrag = [&](int c) { if constexpr (YROWS) return yq[c]; else return frag(yl[c], yh[c]); };
   bf16x8 yf0[8], xf0[8], yf1[8], xf1[8];
-  // the stage is a compile-time fact of each phase body (the K loop is unrolled by two): fragment addresses and LDS-DMA
-  // destinations are then plain registers / immediates
-  auto phase1 = [&](auto first_c, auto stage_c, auto pend_c) {
-    constexpr bool FIRST = decltype(first_c)::value;
-    constexpr int s_cur = decltype(stage_c)::value;
-    constexpr bool PEND = decltype(pend_c)::value;     // (false in a workgroup's very first step only: nothing to top up yet)
-    __builtin_amdgcn_sched_barrier(0);
-    WG_M(yf0, xf0, 0, 0);
-    WG_M(yf0, xf0, 0, 1); WG_YRD(0, s_cur, 1);
-    WG_M(yf0, xf0, 0, 2); WG_LP(11);
-    WG_M(yf0, xf0, 0, 3);
-    WG_M(yf0, xf0, 0, 4);
-    WG_M(yf0, xf0, 0, 5); WG_YRD(1, s_cur, 1);
-    WG_M(yf0, xf0, 0, 6); WG_LP(12);
-    WG_M(yf0, xf0, 0, 7);
-    WG_M(yf0, xf0, 1, 0);
-    WG_M(yf0, xf0, 1, 1); WG_YRD(2, s_cur, 1);
-    WG_M(yf0, xf0, 1, 2); WG_LP(13);
-    WG_M(yf0, xf0, 1, 3);
-    WG_M(yf0, xf0, 1, 4);
-    WG_M(yf0, xf0, 1, 5); WG_YRD(3, s_cur, 1);
-    WG_M(yf0, xf0, 1, 6); WG_LP(14);
-    WG_M(yf0, xf0, 1, 7);
-    WG_M(yf0, xf0, 2, 0);
-    WG_M(yf0, xf0, 2, 1); WG_YRD(4, s_cur, 1);
-    WG_M(yf0, xf0, 2, 2); WG_LP(15);
-    WG_M(yf0, xf0, 2, 3);
-    WG_M(yf0, xf0, 2, 4);
-    WG_M(yf0, xf0, 2, 5); WG_YRD(5, s_cur, 1);
-    WG_M(yf0, xf0, 2, 6);
-    WG_M(yf0, xf0, 2, 7);
-    WG_M(yf0, xf0, 3, 0);
-    WG_M(yf0, xf0, 3, 1); WG_YRD(6, s_cur, 1);
-    WG_M(yf0, xf0, 3, 2);
-    WG_M(yf0, xf0, 3, 3);
-    WG_M(yf0, xf0, 3, 4);
-    WG_M(yf0, xf0, 3, 5); WG_YRD(7, s_cur, 1);
-    WG_M(yf0, xf0, 3, 6);
-    WG_M(yf0, xf0, 3, 7);
-    WG_M(yf0, xf0, 4, 0);
-    WG_M(yf0, xf0, 4, 1); WG_TR2(xl[0], xh[0], x_addr[s_cur][0], 16384);
-    WG_M(yf0, xf0, 4, 2);
-    WG_M(yf0, xf0, 4, 3);
-    WG_M(yf0, xf0, 4, 4);
-    WG_M(yf0, xf0, 4, 5); WG_TR2(xl[1], xh[1], x_addr[s_cur][1], 16384);
-    WG_M(yf0, xf0, 4, 6);
-    WG_M(yf0, xf0, 4, 7);
-    WG_M(yf0, xf0, 5, 0);
-    WG_M(yf0, xf0, 5, 1); WG_TR2(xl[2], xh[2], x_addr[s_cur][2], 16384);
-    WG_M(yf0, xf0, 5, 2);
-    WG_M(yf0, xf0, 5, 3);
-    WG_M(yf0, xf0, 5, 4);
-    WG_M(yf0, xf0, 5, 5); WG_TR2(xl[3], xh[3], x_addr[s_cur][3], 16384);
-    WG_M(yf0, xf0, 5, 6);
-    WG_M(yf0, xf0, 5, 7);
-    WG_M(yf0, xf0, 6, 0);
-    WG_M(yf0, xf0, 6, 1); WG_TR2(xl[4], xh[4], x_addr[s_cur][4], 16384);
-    WG_M(yf0, xf0, 6, 2);
-    WG_M(yf0, xf0, 6, 3);
-    WG_M(yf0, xf0, 6, 4);
-    WG_M(yf0, xf0, 6, 5); WG_TR2(xl[5], xh[5], x_addr[s_cur][5], 16384);
-    WG_M(yf0, xf0, 6, 6);
-    WG_M(yf0, xf0, 6, 7);
-    WG_M(yf0, xf0, 7, 0);
-    WG_M(yf0, xf0, 7, 1); WG_TR2(xl[6], xh[6], x_addr[s_cur][6], 16384);
-    WG_M(yf0, xf0, 7, 2);
-    WG_M(yf0, xf0, 7, 3);
-    WG_M(yf0, xf0, 7, 4);
-    WG_M(yf0, xf0, 7, 5); WG_TR2(xl[7], xh[7], x_addr[s_cur][7], 16384);
-    WG_M(yf0, xf0, 7, 6);
-    WG_M(yf0, xf0, 7, 7);
-    __builtin_amdgcn_sched_barrier(0);
-    if (PEND) load_done();
-  };
-  auto phase2 = [&](auto stage_c) {
-    constexpr bool FIRST = false;
-    constexpr int s_cur = decltype(stage_c)::value;
-    __builtin_amdgcn_sched_barrier(0);
-    WG_M(yf1, xf1, 0, 0); WG_L(0);
-    WG_M(yf1, xf1, 0, 1); WG_YRD(0, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 0, 2);
-    WG_M(yf1, xf1, 0, 3);
-    WG_M(yf1, xf1, 0, 4);
-    WG_M(yf1, xf1, 0, 5); WG_YRD(1, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 0, 6); WG_L(1);
-    WG_M(yf1, xf1, 0, 7);
-    WG_M(yf1, xf1, 1, 0);
-    WG_M(yf1, xf1, 1, 1); WG_YRD(2, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 1, 2);
-    WG_M(yf1, xf1, 1, 3);
-    WG_M(yf1, xf1, 1, 4); WG_L(2);
-    WG_M(yf1, xf1, 1, 5); WG_YRD(3, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 1, 6);
-    WG_M(yf1, xf1, 1, 7);
-    WG_M(yf1, xf1, 2, 0);
-    WG_M(yf1, xf1, 2, 1); WG_YRD(4, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 2, 2); WG_L(3);
-    WG_M(yf1, xf1, 2, 3);
-    WG_M(yf1, xf1, 2, 4);
-    WG_M(yf1, xf1, 2, 5); WG_YRD(5, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 2, 6);
-    WG_M(yf1, xf1, 2, 7);
-    WG_M(yf1, xf1, 3, 0); WG_L(4);
-    WG_M(yf1, xf1, 3, 1); WG_YRD(6, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 3, 2);
-    WG_M(yf1, xf1, 3, 3);
-    WG_M(yf1, xf1, 3, 4);
-    WG_M(yf1, xf1, 3, 5); WG_YRD(7, s_cur ^ 1, 0);
-    WG_M(yf1, xf1, 3, 6); WG_L(5);
-    WG_M(yf1, xf1, 3, 7);
-    WG_M(yf1, xf1, 4, 0);
-    WG_M(yf1, xf1, 4, 1); WG_TR2(xl[0], xh[0], x_addr[s_cur ^ 1][0], 0);
-    WG_M(yf1, xf1, 4, 2);
-    WG_M(yf1, xf1, 4, 3);
-    WG_M(yf1, xf1, 4, 4); WG_L(6);
-    WG_M(yf1, xf1, 4, 5); WG_TR2(xl[1], xh[1], x_addr[s_cur ^ 1][1], 0);
-    WG_M(yf1, xf1, 4, 6);
-    WG_M(yf1, xf1, 4, 7);
-    WG_M(yf1, xf1, 5, 0);
-    WG_M(yf1, xf1, 5, 1); WG_TR2(xl[2], xh[2], x_addr[s_cur ^ 1][2], 0);
-    WG_M(yf1, xf1, 5, 2); WG_L(7);
-    WG_M(yf1, xf1, 5, 3);
-    WG_M(yf1, xf1, 5, 4);
-    WG_M(yf1, xf1, 5, 5); WG_TR2(xl[3], xh[3], x_addr[s_cur ^ 1][3], 0);
-    WG_M(yf1, xf1, 5, 6);
-    WG_M(yf1, xf1, 5, 7);
-    WG_M(yf1, xf1, 6, 0); WG_L(8);
-    WG_M(yf1, xf1, 6, 1); WG_TR2(xl[4], xh[4], x_addr[s_cur ^ 1][4], 0);
-    WG_M(yf1, xf1, 6, 2);
-    WG_M(yf1, xf1, 6, 3);
-    WG_M(yf1, xf1, 6, 4);
-    WG_M(yf1, xf1, 6, 5); WG_TR2(xl[5], xh[5], x_addr[s_cur ^ 1][5], 0);
-    WG_M(yf1, xf1, 6, 6); WG_L(9);
-    WG_M(yf1, xf1, 6, 7);
-    WG_M(yf1, xf1, 7, 0);
-    WG_M(yf1, xf1, 7, 1); WG_TR2(xl[6], xh[6], x_addr[s_cur ^ 1][6], 0);
-    WG_M(yf1, xf1, 7, 2);
-    WG_M(yf1, xf1, 7, 3);
-    WG_M(yf1, xf1, 7, 4);
-    WG_M(yf1, xf1, 7, 5); WG_TR2(xl[7], xh[7], x_addr[s_cur ^ 1][7], 0);
-    WG_M(yf1, xf1, 7, 6); WG_L(10);
-    WG_M(yf1, xf1, 7, 7);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-#ifndef M3P_WG_SCHED2
-#define M3P_WG_SCHED2 1
-#endif
 #define WG_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_SET1() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf1[c] = yfrag(c); xf1[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_SET0() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
-  // M3P_WG_SCHED2: the K-tile in one piece, as in gemm_nt_w4_kernel - the first operand's region of the stage is released by
+  // The K-tile in one piece, as in gemm_nt_w4_kernel (the stage is a compile-time fact: the K loop is unrolled by two) - the first operand's region of the stage is released by
   // a barrier as soon as its k-step-1 fragments are in registers (MFMA 20), the second's at MFMA 50, the next K-tile is waited
   // for at MFMA 107 (vmcnt(16): this K-tile's own sixteen transfers stay in flight): a transfer has 1.2-1.7 K-tiles to land
   // where the two-phase form gives the last five of a K-tile 46 MFMAs and waits ~200-270 clocks per K-tile at its vmcnt(0).
@@ -4234,47 +3395,10 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   WgCursor cc = locate(g0);
   bool first = true;
   int n_seg = 0;
-  // -DM3P_WG_TL: s_memtime sums per segment of a K-tile (tools/wgrad_timeline.py): 0 phase 1 (64 MFMAs + reads + LDS-DMAs issued),
-  // 1 its closing lgkmcnt(0), 2 vmcnt(0), 3 s_barrier, 4 phase 2, 5 its closing lgkmcnt(0), 6 step tail / flush, 7 K-tiles
-#ifdef M3P_WG_TL
-  unsigned long long wtl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long wt0 = __builtin_amdgcn_s_memtime(), wt1;
-#define WG_TSEG(k) do { __builtin_amdgcn_sched_barrier(0); wt1 = __builtin_amdgcn_s_memtime(); wtl[k] += wt1 - wt0; wt0 = wt1; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define WG_TSEG(k) do { } while (0)
-#endif
   auto kstep = [&](auto stage_c, int step) {
-#if M3P_WG_SCHED2
     if (first) wktile(std::true_type{}, stage_c);
     else wktile(std::false_type{}, stage_c);
     first = false;
-#else
-    WG_TSEG(6);
-    if (step == 0) phase1(std::true_type{}, stage_c, std::false_type{});
-    else if (first) phase1(std::true_type{}, stage_c, std::true_type{});
-    else phase1(std::false_type{}, stage_c, std::true_type{});
-    first = false;
-    WG_TSEG(0);
-    WG_LGKM0();
-    WG_TSEG(1);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { yf1[c] = yfrag(c); xf1[c] = frag(xl[c], xh[c]); }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WG_TSEG(2);
-    __builtin_amdgcn_s_barrier();      // K-tile step+1 visible to all; stage s_cur fully read by all
-    asm volatile("" ::: "memory");
-    WG_TSEG(3);
-    phase2(stage_c);
-    WG_TSEG(4);
-    WG_LGKM0();
-    WG_TSEG(5);
-#ifdef M3P_WG_TL
-    wtl[7] += 1;
-#endif
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); }
-
-#endif
 
     const bool last_of_tile = (cc.mt + 1 == cc.len) || (step + 1 == total);
     if (last_of_tile) {
@@ -4353,7 +3477,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
               // overwrite (whole-tile round-robin mode on a gradient the caller knows to be zero: the vocabulary matrix's
               // first product of a step): a plain store - the atomic is a read-modify-write of 768 MB that is not in any cache
               if (overwrite) dcol[(size_t)(a * 16 + r) * lddw] = alpha * v[a * 4 + r];
-              else if (!WG_DBG(1)) unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
+              else unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
         }
       }
       if (to_ws && tid == 0) ws_tile[slot] = tile_id0 + cc.t;
@@ -4367,13 +3491,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     if (step + 1 < total) kstep(std::integral_constant<int, 1>{}, step + 1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
-#ifdef M3P_WG_TL
-  WG_TSEG(6);
-  if (lane == 0)
-    for (int k = 0; k < 8; ++k) g_ring_tl[(blockIdx.x * 4 + wid) * 8 + k] = wtl[k];
-#endif
-#undef WG_TSEG
-#undef WG_LD1
 #undef WG_LDB
 #undef WG_TR2
 #undef WG_YRD
@@ -4381,8 +3498,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #undef WG_ACC
 #undef WG_M
 #undef WG_L
-#undef WG_DBG
-#undef WG_LP
 }
 
 // dW[tile] += alpha * sum of the workspace slots that hold a partial of that tile.
@@ -4637,8 +3752,8 @@ template <int EPI, bool A_BF8>
 int launch_nt_fp8(const uint8_t* A, int lda, const uint8_t* W, int ldw, bf16* C, int ldc, int M, int N, int K,
                          const M3PEpilogue& ep, hipStream_t st) {
   const int tiles_m = M / 256, tiles_n = N / 256;
-  const size_t lds = 2 * 512 * ROWB + (EPI == M3P_EPI_DGELU && M3P_DGELU_LUT ? GELU_TAB_N * sizeof(float) : 0) +
-                     (M3P_W8_SPARE_EPILOGUE ? ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) ? 8 * 2048 : 8 * 4096) : 0);
+  const size_t lds = 2 * 512 * ROWB + (EPI == M3P_EPI_DGELU ? GELU_TAB_N * sizeof(float) : 0) +
+                     ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) ? 8 * 2048 : 8 * 4096);
   auto kern = gemm_nt_w8f8_kernel<EPI, A_BF8>;
   static bool attr_set = false;
   if (!attr_set) {
@@ -4713,39 +3828,6 @@ int m3p_gemm_nt_fp8(const void* A, int lda, int a_is_bf8, const void* W, int ldw
 #undef M3P_F8_CASE
 }
 
-// debug (only with -DM3P_RING_TL): per-wave cycle sums of the last dGELU launch of the eight-wave kernel
-// [256 workgroups][8 waves][8 segments]: 0 K loop, 1 bias / row copies, 2 aux fetch + wait, 3 epilogue half (compute,
-// staging, stores), 4 column sums, 5 zeroing + end barrier  (tools/ring_timeline.py)
-__attribute__((visibility("default"))) int m3p_debug_ring_timeline(void* out, size_t bytes) {
-#if defined(M3P_RING_TL) || defined(M3P_W8_TL) || defined(M3P_WG_TL)
-  if (bytes > sizeof(g_ring_tl)) return M3P_EINVAL;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ring_tl), bytes);
-#else
-  (void)out; (void)bytes;
-  return M3P_EINVAL;
-#endif
-}
-
-__attribute__((visibility("default"))) int m3p_debug_gemm_timeline(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
-                                                                   int M, int N, int K, unsigned long long* dbg, void* stream) {
-  // (only the four-wave kernel carries timeline instrumentation; full 256x256 tiles, K % 64 == 0)
-  if ((M % 256) || (N % 256) || (K % 64)) return M3P_EINVAL;
-  M3PEpilogue ep = {};
-  const int tm = M / 256, tn = N / 256;
-  const size_t lds4 = 2 * 512 * 128 + 4 * EP_HALF;
-  auto k4 = gemm_nt_w4_kernel<M3P_EPI_NONE, true, 0>;
-  if (g_ablate == 1) k4 = gemm_nt_w4_kernel<M3P_EPI_NONE, true, 1>;
-  if (g_ablate == 2) k4 = gemm_nt_w4_kernel<M3P_EPI_NONE, true, 2>;
-  if (g_ablate == 3) k4 = gemm_nt_w4_kernel<M3P_EPI_NONE, true, 3>;
-  if (g_ablate == 4) k4 = gemm_nt_w4_kernel<M3P_EPI_NONE, true, 4>;
-  hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-  hipLaunchKernelGGL(k4, dim3(num_cus()), dim3(256), lds4, (hipStream_t)stream, (const bf16*)A, lda, (const bf16*)W, ldw,
-                     (bf16*)C, ldc, M, N, K, ep, tm, tn, 0, dbg);
-  return (int)hipGetLastError();
-}
-
-
-
 static int launch_streamk(const void* A, int lda, const void* W, int ldw, float* C, int ldc, int M, int N, int K, float alpha,
                           bool w_kn, int k_valid, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || (lda % 8) != 0 || (ldw % 8) != 0) return M3P_EINVAL;
@@ -4810,7 +3892,7 @@ size_t m3p_gemm_wgrad_workspace_bytes(void) {
 
 // four-wave kernel + reduction; pb: optional second product over the same M (paired launch), nullptr = none
 static bool wgrad_w4_ok(int M, int N, int K, int lddy, int ldx, const void* dY, const void* X) {
-  return g_variant >= 1 && g_variant != 3 && (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 &&
+  return (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 &&
          (lddy % 8) == 0 && (ldx % 8) == 0 && !((uintptr_t)dY & 15) && !((uintptr_t)X & 15);
 }
 extern "C++" {
@@ -4845,7 +3927,7 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
     ws = (float*)workspace;
   int* ws_tile = ws ? (int*)(ws + (size_t)grid * (65536 + 272)) : nullptr;
   hipLaunchKernelGGL(gemm_wgrad_w4_kernel<YROWS>, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const bf16*)dY, lddy,
-                     (const bf16*)X, ldx, dW, lddw, M, N, K, alpha, ti, tj, chunk, ws, ws_tile, g_ablate, store ? 1 : 0, pb);
+                     (const bf16*)X, ldx, dW, lddw, M, N, K, alpha, ti, tj, chunk, ws, ws_tile, store ? 1 : 0, pb);
   M3P_CHECK_LAUNCH();
   if (ws) {
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(16, ntile), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
@@ -4872,10 +3954,9 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
 //   anything else                                          128x128 split-M (atomics)                small M (cfg1, tests)
 // ---------------------------------------------------------------------------------------------------------------------
 static int wgrad_plan(int M, int N, int K, bool aligned) {
-  if (aligned && g_variant >= 1 && g_variant != 3 && (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 &&
-      (N / 256) * (K / 256) >= ((g_ablate & 16) ? 1 : 9))
+  if (aligned && (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 && (N / 256) * (K / 256) >= 9)
     return ((long long)(N / 256) * (K / 256) >= 4LL * num_cus()) ? M3P_KERN_WGRAD_W4_TILES : M3P_KERN_WGRAD_W4_CHUNKS;
-  if (g_variant >= 1 && (M % BK) == 0 && M >= 4096) return M3P_KERN_WGRAD_RING;
+  if ((M % BK) == 0 && M >= 4096) return M3P_KERN_WGRAD_RING;
   return M3P_KERN_WGRAD_128;
 }
 
@@ -4897,7 +3978,7 @@ int m3p_gemm_nn_w4_f32(const void* A, int lda, const void* W, int ldw, float* C,
                        void* workspace, size_t workspace_bytes, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C) return M3P_EINVAL;
   if ((K % 64) || K < 4096 || (M % 256) || (N % 256) || (lda % 8) || (ldw % 8) || lda < K || ldw < N || ldc < N ||
-      ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || g_variant < 1 || g_variant == 3)
+      ((uintptr_t)A & 15) || ((uintptr_t)W & 15))
     return M3P_ENOTIMPL;
   return launch_wgrad_w4<true>(A, lda, W, ldw, C, ldc, K, M, N, alpha, workspace, workspace_bytes, stream, nullptr);
 }

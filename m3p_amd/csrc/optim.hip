@@ -69,9 +69,6 @@ __global__ __launch_bounds__(256) void sumsq_ranges_kernel(SumsqRanges a, double
   if (threadIdx.x == 0) unsafeAtomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
-#ifndef M3P_ADAM_STREAM
-#define M3P_ADAM_STREAM 1
-#endif
 struct AdamArgs {
   float* p; float* g; float* m; float* v; bf16* w16;
   size_t n4;
@@ -91,7 +88,6 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
     coef *= (c < 1.f) ? c : 1.f;
   }
   const float ob1 = 1.f - a.beta1, ob2 = 1.f - a.beta2, wdl = a.weight_decay * a.lr;
-#if M3P_ADAM_STREAM
   // Nine streams (4 read, 5 written) of data touched once per step: non-temporal accesses keep them out of the way
   // of the bf16 weights / activations the next forward re-reads, and two 16-byte quads per thread and iteration put
   // eight loads in flight before the first use.
@@ -132,25 +128,6 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
       }
     }
   }
-#else
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 p = Vec4<float>::load(a.p + 4 * i);
-    const f32x4 g = Vec4<float>::load(a.g + 4 * i) * coef;
-    f32x4 m = Vec4<float>::load(a.m + 4 * i) * a.beta1 + g * ob1;
-    f32x4 v = Vec4<float>::load(a.v + 4 * i) * a.beta2 + g * g * ob2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float denom = sqrtf(v[j]) + a.eps;
-      if (wdl != 0.f) p[j] -= wdl * p[j];
-      p[j] -= a.step_size * (m[j] / denom);
-    }
-    Vec4<float>::store(a.p + 4 * i, p);
-    Vec4<float>::store(a.m + 4 * i, m);
-    Vec4<float>::store(a.v + 4 * i, v);
-    if (a.w16) Vec4<bf16>::store(a.w16 + 4 * i, p);
-    if (a.zero_grad) Vec4<float>::store(a.g + 4 * i, f32x4{0.f, 0.f, 0.f, 0.f});
-  }
-#endif
 }
 
 // bf16 -> fp8 (e4m3) / bf8 (e5m2) with a per-tensor scale, saturating, + running max |x| for the next step's scale
@@ -588,12 +565,9 @@ struct AdamRanges {
   int blk0[ADAM_MAX_RANGES + 1];
   int n;
 };
-#ifndef M3P_ADAM_Q
-#define M3P_ADAM_Q 2          // 16-byte quads per thread and trip (x 4 read streams = loads in flight before the first use)
-#endif
-#ifndef M3P_ADAM_MAXBLK
-#define M3P_ADAM_MAXBLK 4096
-#endif
+// loop shape of the fused update over the arena: every shape swept measured the same 6.1 TB/s (profiles/r05_adam_sweep.txt)
+constexpr int ADAM_Q = 2;            // 16-byte quads per thread and trip (x 4 read streams = loads in flight before the first use)
+constexpr int ADAM_MAXBLK = 4096;    // blocks per launch at most
 __global__ __launch_bounds__(256) void adam_ranges_kernel(AdamRanges a) {
   int r = 0;
   while (r + 1 < a.n && (int)blockIdx.x >= a.blk0[r + 1]) ++r;
@@ -610,7 +584,7 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(AdamRanges a) {
   float* const P = a.c.p + 4 * base; float* const G = a.c.g + 4 * base; float* const M = a.c.m + 4 * base; float* const V = a.c.v + 4 * base;
   bf16* const W = a.c.w16 ? a.c.w16 + 4 * base : nullptr;
   const size_t stride = (size_t)(a.blk0[r + 1] - a.blk0[r]) * blockDim.x;
-  constexpr int Q = M3P_ADAM_Q;
+  constexpr int Q = ADAM_Q;
   for (size_t i0 = (size_t)((int)blockIdx.x - a.blk0[r]) * blockDim.x + threadIdx.x; i0 < n4; i0 += Q * stride) {
     f32x4 p[Q], g[Q], m[Q], v[Q];
 #pragma unroll
@@ -672,7 +646,7 @@ int m3p_adam_step_ranges(float* p, float* g, float* m, float* v, void* w16, cons
     }
     if (a.n == 0) continue;
     long long want = (total4 + 255) / 256;      // one quad per thread and trip like m3p_adam_step, at most 4096 blocks, at least one per piece
-    if (want > M3P_ADAM_MAXBLK) want = M3P_ADAM_MAXBLK;
+    if (want > ADAM_MAXBLK) want = ADAM_MAXBLK;
     if (want < a.n) want = a.n;
     int b = 0;
     for (int r = 0; r < a.n; ++r) {

@@ -122,10 +122,6 @@ def load():
         fn.restype = res
         fn.argtypes = args
     _lib_tq = os.environ.get('M3P_TILE_QUEUE', '0') != '0'     # developer switch: dynamic tile queues without data parallelism
-    if os.environ.get('M3P_VARIANT'):      # developer switch between GEMM kernel generations (A/B runs)
-        lib.m3p_debug_set_variant(int(os.environ['M3P_VARIANT']))
-    if os.environ.get('M3P_ATTN_VARIANT'):
-        lib.m3p_debug_attn_variant(int(os.environ['M3P_ATTN_VARIANT']))
     _lib = lib
     if _lib_tq and torch.cuda.is_available():
         from . import ops

@@ -15,13 +15,13 @@ HIPCC = '/opt/rocm/bin/hipcc'
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_w4_gemm_accumulators_are_ours(tmp_path):
+def test_w4_gemm_accumulators_are_ours_in_every_epilogue(tmp_path):
     out = tmp_path / 'gemm.s'
     cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
            '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', 'gemm.hip'), '-o', str(out)]
     subprocess.run(cmd, check=True, capture_output=True, timeout=600)
     text = out.read_text().splitlines()
-    starts = [i for i, l in enumerate(text) if re.match(r'^_ZN\S*gemm_nt_w4_kernelILi\dELb0ELi0E\S*:', l)]
+    starts = [i for i, l in enumerate(text) if re.match(r'^_ZN\S*gemm_nt_w4_kernelILi\dEE\S*:', l)]
     assert len(starts) == 7, 'expected the seven epilogue instantiations of the production kernel'
     for st in starts:
         name = text[st].split(':')[0]

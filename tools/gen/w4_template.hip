@@ -10,31 +10,21 @@
 // K-tiles are 64 deep with full 128-B rows: the first version of this kernel staged 32-deep
 // tiles (64-B row segments) and stalled on L2 ingest - tools/probe_ingest.py measures
 // 33 B/clk/CU for LDS-DMA with 64-B segments against 64 B/clk/CU with 128-B segments.
-// Pipeline (two 64-KB stages, one s_barrier per 128 MFMAs):
-//   phase 1 of K-tile j: 64 MFMAs on k-step 0 (registers) | ds_read k-step 1 of tile j
-//                        | the last LDS-DMAs of tile j+1
-//   mid:  lgkmcnt(0), vmcnt -> tile j+1 has landed, s_barrier (everyone is done with stage j)
-//   phase 2: 64 MFMAs on k-step 1 | ds_read k-step 0 of tile j+1 | first LDS-DMAs of tile j+2
-//            into stage j
-// The 16 LDS-DMAs of a K-tile are spread over phase 2 and the start of the next phase 1: issued
-// back to back in phase 2 alone they ask the texture path for its full 64 B/clk and the issuing
-// waves (alone on their SIMDs, nothing else to run) stall on the queue.  Memory instructions
+// Pipeline: two 64-KB stages, 128 MFMAs per K-tile with every fragment read and LDS-DMA in their shadow
+// (the schedule is at ktile below).  The 16 LDS-DMAs of a K-tile are spread out: issued back to back
+// they ask the texture path for its full 64 B/clk and the issuing waves (alone on their SIMDs,
+// nothing else to run) stall on the queue.  Memory instructions
 // themselves are free in the shadow of an MFMA (tools/probe_issue2.py: +1 clock per 8 MFMAs).
-// One M0 per operand and K-tile: LDS destinations are selected by the immediate offset, which
-// moves source and destination together (tools/probe_dma_offset.py).
+// LDS destinations are selected by the immediate offset, which moves source and destination
+// together (tools/probe_dma_offset.py).
 // The epilogue runs from a private 4.5-KB staging area per wave; the loads of the next
 // output tile are already in flight under it.
 // ---------------------------------------------------------------------------------
-template <int EPI, bool TL = false, int ABL = 0>
+template <int EPI>
 __global__ __launch_bounds__(256)
 void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
                        bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
-                       int tiles_m, int tiles_n, int m_fast, unsigned long long* __restrict__ dbg = nullptr) {
-  // TL: debug instantiation that accumulates s_memtime per pipeline segment (tools/gemm_timeline.py);
-  // ABL (TL only): bit 0 = no fragment reads, bit 1 = no LDS-DMA, bit 2 = every K-tile re-reads the first
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tl0 = TL ? __builtin_amdgcn_s_memtime() : 0, tl1;
-#define W4_TSEG(k) do { if (TL) { tl1 = __builtin_amdgcn_s_memtime(); tacc[k] += tl1 - tl0; tl0 = tl1; } } while (0)
+                       int tiles_m, int tiles_n, int m_fast) {
   constexpr int BM = 256, BN = 256, KT = 64;
   constexpr int A_BYTES = BM * KT * 2, STAGE = (BM + BN) * KT * 2;     // 32 KB, 64 KB
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -63,77 +53,43 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 
   // ---- load cursor.  One LDS-DMA instruction = 1 KB = 8 tile rows of 128 B; lane l fills slot
   // (l & 7) of row (l >> 3), which must hold 16-B chunk slot ^ (row & 7).  Wave w stages rows
-  // [64w, 64w + 64) of each operand = one contiguous 8-KB slice per operand: M0 = slice + 4096,
-  // the eight instructions differ only in the immediate -4096..3072 (sources pre-compensated:
-  // the +2048 elements in the base pointers and the -512 per row group undo the immediates).
+  // [64w, 64w + 64) of each operand = one contiguous 8-KB slice per operand.
   const int l_row = lane >> 3;
   const int l_col = ((lane & 7) ^ l_row) * 8;
   // (only full tiles come here - the launcher sends ragged shapes to the ring kernel - so the
-  //  eight row groups of a slice are a uniform stride apart and two pointers are enough)
-  // Source of piece p = (wave-uniform pointer: this K-tile's slice + 8 p rows, less what the immediate adds) + (the lane's 32-bit
-  // byte offset, one register per operand for the whole kernel): the LDS-DMA's scalar-base address form, no vector arithmetic
-  // per piece and no per-piece address registers.  (Sixteen 64-bit lane addresses live across the K-tile made the compiler
-  // park values in the AGPRs - which are this kernel's accumulators.)
+  //  eight row groups of a slice are a uniform stride apart)
+  // The transfer is buffer_load_dwordx4 ... lds: resource = this wave's slice of the operand tile, scalar offset = K-tile +
+  // piece, one 32-bit lane offset per operand for the whole kernel - no vector arithmetic per piece and no per-piece address
+  // registers.  (Sixteen 64-bit lane addresses live across the K-tile made the compiler park values in the AGPRs - which are
+  // this kernel's accumulators.)  The immediate of the buffer form is unsigned 12-bit: pieces 0-3 and 4-7 of an operand get
+  // an M0 each (slice, slice + 4 KB), immediates 0..3072.
   const uint32_t a_lane = (uint32_t)(l_row * lda + l_col) * 2u, w_lane = (uint32_t)(l_row * ldw + l_col) * 2u;
-  const size_t a_step8 = (size_t)8 * lda, w_step8 = (size_t)8 * ldw;
-  const bf16* a_tile;       // this wave's slice of the tile the load cursor points at, K-tile 0
-  const bf16* w_tile;
-  const bf16* a_base;       // ... at the cursor's K-tile
-  const bf16* w_base;
-#ifndef M3P_W4_BUFDMA
-#define M3P_W4_BUFDMA 1
-#endif
   __amdgpu_buffer_rsrc_t a_rsrc, w_rsrc;
   int l_q = 0, l_kt = 0;
   auto set_load_tile = [&](int q) {
     int tm, tn;
     split_tile(tile_of(q), tm, tn);
-    a_base = a_tile = A + (size_t)(tm * BM + wid * 64) * lda;
-    w_base = w_tile = W + (size_t)(tn * BN + wid * 64) * ldw;
-    if (M3P_W4_BUFDMA) {
-      a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_tile)), 0, 0xffffffff, 0x00020000);
-      w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_tile)), 0, 0xffffffff, 0x00020000);
-    }
+    const bf16* a_tile = A + (size_t)(tm * BM + wid * 64) * lda;      // this wave's slice of the tile, K-tile 0
+    const bf16* w_tile = W + (size_t)(tn * BN + wid * 64) * ldw;
+    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_tile)), 0, 0xffffffff, 0x00020000);
+    w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_tile)), 0, 0xffffffff, 0x00020000);
   };
-#define W4_LD1(PTR, IMM) __builtin_amdgcn_global_load_lds(GLB_PTR(PTR), LDS_PTR(sl), 16, IMM, 0)
 #define W4_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 8 ? a_rsrc : w_rsrc, LDS_PTR(sl), 16, piece < 8 ? a_lane : w_lane, soff, IMM, 0)
-  // M3P_W4_BUFDMA: the transfer as buffer_load_dwordx4 ... lds (resource = this wave's slice of the operand tile, scalar offset
-  // = K-tile + piece, one 32-bit lane offset for the whole kernel) instead of global_load_lds_dwordx4.  The immediate of the
-  // buffer form is unsigned 12-bit: pieces 0-3 and 4-7 of an operand get an M0 each (slice, slice + 4 KB), immediates 0..3072.
   auto issue_load = [&](int s, int piece) {
     const int pc = piece & 7;
-    if (M3P_W4_BUFDMA) {
-      char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + (pc >> 2) * 4096;
-      const uint32_t k_off = (ABL & 4) ? 0u : (uint32_t)l_kt * (KT * 2);
-      const uint32_t soff = __builtin_amdgcn_readfirstlane(k_off + (uint32_t)pc * (uint32_t)((piece < 8 ? lda : ldw) * 16) - (uint32_t)(pc & 3) * 1024u);
-      switch (pc & 3) {
-        case 0: W4_LDB(0); break;
-        case 1: W4_LDB(1024); break;
-        case 2: W4_LDB(2048); break;
-        default: W4_LDB(3072); break;
-      }
-      return;
-    }
-    char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + 4096;
-    const bf16* row = uniform_ptr((piece < 8 ? a_base + pc * a_step8 : w_base + pc * w_step8) - (pc - 4) * 512);
-    uint32_t lane_off = piece < 8 ? a_lane : w_lane;
-    asm volatile("" : "+v"(lane_off));      // (the zero-extension has to sit beside the DMA for the scalar-base form to be selected)
-    const char* src = reinterpret_cast<const char*>(row) + lane_off;
-    switch (pc) {
-      case 0: W4_LD1(src, -4096); break;
-      case 1: W4_LD1(src, -3072); break;
-      case 2: W4_LD1(src, -2048); break;
-      case 3: W4_LD1(src, -1024); break;
-      case 4: W4_LD1(src, 0); break;
-      case 5: W4_LD1(src, 1024); break;
-      case 6: W4_LD1(src, 2048); break;
-      default: W4_LD1(src, 3072); break;
+    char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + (pc >> 2) * 4096;
+    const uint32_t k_off = (uint32_t)l_kt * (KT * 2);
+    const uint32_t soff = __builtin_amdgcn_readfirstlane(k_off + (uint32_t)pc * (uint32_t)((piece < 8 ? lda : ldw) * 16) - (uint32_t)(pc & 3) * 1024u);
+    switch (pc & 3) {
+      case 0: W4_LDB(0); break;
+      case 1: W4_LDB(1024); break;
+      case 2: W4_LDB(2048); break;
+      default: W4_LDB(3072); break;
     }
   };
   auto load_done = [&]() {
     // (past the end of the stream the last tile's K-tiles are requested again into stages nobody reads)
     if (++l_kt == nk) { l_kt = 0; ++l_q; if (l_q < my_tiles) set_load_tile(l_q); }
-    if (!(ABL & 4)) { a_base = a_tile + l_kt * KT; w_base = w_tile + l_kt * KT; }
   };
 
   // ---- fragment addressing (as in the ring kernel: 128-B rows, chunk ^= row & 7)
@@ -150,7 +106,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     a_addr1[ks] = a_addr[ks] + STAGE;
     b_addr1[ks] = b_addr[ks] + STAGE;
   }
-#define W4_DSR(dst, addr, off) do { if (!(ABL & 1)) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr)); } while (0)
+#define W4_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
 #define W4_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   // The 256 accumulator registers live in a[0:255] under OUR control: every MFMA and every
@@ -163,18 +119,13 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 #define W4_ACC(I, J) "a[((" #I ")*8+(" #J "))*4:((" #I ")*8+(" #J "))*4+3]"
 #define W4_M(FA, FW, I, J) do { if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 " W4_ACC(I, J) ", %1, %0, 0" :: "v"(FA[I]), "v"(FW[J])); \
                                 else asm volatile("v_mfma_f32_16x16x32_bf16 " W4_ACC(I, J) ", %1, %0, " W4_ACC(I, J) :: "v"(FA[I]), "v"(FW[J])); } while (0)
-#define W4_L(PIECE) do { if (!(ABL & 2)) issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_LP(PIECE) do { if (!(ABL & 2) && PEND) issue_load(s_cur ^ 1, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define W4_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   bf16x8 fa0[8], fw0[8], fa1[8], fw1[8];
-#ifndef M3P_W4_SCHED2
-#define M3P_W4_SCHED2 1
-#endif
 #define W4_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#if M3P_W4_SCHED2
   // One K-tile (tile j in stage s, tile j+1 landing in stage s^1) = 128 MFMAs with every memory instruction in their shadow.
   // What decides the schedule is the time a global -> LDS transfer is given to land:
   //   MFMA   1..15  k-step 1 of tile j: W fragments out of stage s        (k-step 0 is in registers since the previous K-tile)
@@ -183,7 +134,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   //         50      lgkmcnt(0) + barrier: nor A                            -> A of tile j+2 (53..)
   //        107      vmcnt(16) + barrier: tile j+1 (requested one K-tile ago) has landed for everyone
   //        108..123 k-step 0 of tile j+1 into the registers k-step 0 of tile j vacated at MFMA 63
-  // so a transfer has between 1.2 and 1.7 K-tiles (2500-3500 clocks) to land where the two-phase form above gives the last
+  // so a transfer has between 1.2 and 1.7 K-tiles (2500-3500 clocks) to land where the earlier two-phase form gave the last
   // five pieces of a K-tile 46 MFMAs (740 clocks, less than an HBM miss), and the three barriers sit where their condition
   // has long been true.
   auto ktile = [&](auto first_c, auto stage_c) {
@@ -202,30 +153,6 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-#else
-  // phase 1: k-step 0 of the current K-tile from registers; fetch its k-step 1 fragments; finish
-  // the LDS-DMA list phase 2 of the previous iteration started (`pend`)
-  auto phase1 = [&](auto first_c, auto stage_c, auto pend_c) {
-    constexpr bool FIRST = decltype(first_c)::value;   // first K-tile of an output tile: C operand = 0
-    constexpr int s_cur = decltype(stage_c)::value;
-    constexpr bool PEND = decltype(pend_c)::value;     // (false in a workgroup's very first step only)
-    const uint32_t ra1 = s_cur ? a_addr1[1] : a_addr[1], rb1 = s_cur ? b_addr1[1] : b_addr[1];
-    __builtin_amdgcn_sched_barrier(0);
-@PHASE1@
-    __builtin_amdgcn_sched_barrier(0);
-    if (PEND) load_done();
-  };
-  // phase 2: k-step 1; the stage just vacated by everyone (barrier) starts receiving K-tile +2,
-  // and k-step 0 of the next K-tile comes out of the other stage
-  auto phase2 = [&](auto stage_c) {
-    constexpr bool FIRST = false;
-    constexpr int s_cur = decltype(stage_c)::value;
-    const uint32_t ra0n = s_cur ? a_addr[0] : a_addr1[0], rb0n = s_cur ? b_addr[0] : b_addr1[0];
-    __builtin_amdgcn_sched_barrier(0);
-@PHASE2@
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#endif
 
   // ---- prologue: K-tiles 0 and 1 into stages 0 and 1
   set_load_tile(0);
@@ -263,31 +190,10 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
         load_bias4<EPI>(ep, btn * BN + wn * 128, lane, bias_lo);
         load_bias4<EPI>(ep, btn * BN + wn * 128 + 64, lane, bias_hi);
       }
-#if M3P_W4_SCHED2
       ktile(std::true_type{}, stage_c);
     } else {
       ktile(std::false_type{}, stage_c);
     }
-#else
-      if (step == 0) phase1(std::true_type{}, stage_c, std::false_type{});
-      else phase1(std::true_type{}, stage_c, std::true_type{});
-    } else {
-      phase1(std::false_type{}, stage_c, std::true_type{});
-    }
-    W4_TSEG(0);
-    W4_LGKM0();
-    W4_TSEG(1);
-    // everything this wave has in flight is K-tile step+1 (and older epilogue stores)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    W4_TSEG(2);
-    __builtin_amdgcn_s_barrier();      // K-tile step+1 visible to all; stage s_cur fully read by all
-    asm volatile("" ::: "memory");
-    W4_TSEG(3);
-    phase2(stage_c);
-    W4_TSEG(0);
-    W4_LGKM0();
-    W4_TSEG(1);
-#endif
     if (++c_kt == nk) {
       // ---- epilogue of output tile c_q out of the wave-private staging area
       c_kt = 0;
@@ -313,15 +219,12 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 #define W4_SLICE(RG, CH)                                                                      \
   W4_RD(0, 0, 2 * RG, 4 * CH); W4_RD(0, 1, 2 * RG, 4 * CH + 1); W4_RD(0, 2, 2 * RG, 4 * CH + 2); W4_RD(0, 3, 2 * RG, 4 * CH + 3); \
   W4_RD(1, 0, 2 * RG + 1, 4 * CH); W4_RD(1, 1, 2 * RG + 1, 4 * CH + 1); W4_RD(1, 2, 2 * RG + 1, 4 * CH + 2); W4_RD(1, 3, 2 * RG + 1, 4 * CH + 3)
-#ifndef M3P_W4_PIPE_EPI
-#define M3P_W4_PIPE_EPI 1
-#endif
       // The plain epilogues with LDS accesses the compiler does not see (see lds_w64 ...): with transfers for the next output
       // tile in flight it puts s_waitcnt vmcnt(0) in front of every staging access it knows of, i.e. every piece waits for the
       // previous piece's global stores (~1150 clocks a piece, 9.2 k per output tile, a fifth of a K = 768 launch -
-      // tools/gemm_timeline.py).  One swizzled 4-KB buffer inside each wave's 4.5-KB staging area (146 KB of LDS in all: a
+      // timeline in DESIGN.md).  One swizzled 4-KB buffer inside each wave's 4.5-KB staging area (146 KB of LDS in all: a
       // collective's kernel can still share the CU).
-      constexpr bool kPipe = M3P_W4_PIPE_EPI && (EPI == M3P_EPI_NONE || EPI == M3P_EPI_BIAS || EPI == M3P_EPI_RES || EPI == M3P_EPI_BIAS_DROP_RES);
+      constexpr bool kPipe = (EPI == M3P_EPI_NONE || EPI == M3P_EPI_BIAS || EPI == M3P_EPI_RES || EPI == M3P_EPI_BIAS_DROP_RES);
       if (kPipe && fast) {
         char* rb = smem + 2 * STAGE + wid * EP_HALF;      // (one swizzled 4-KB buffer inside the wave's 4.5-KB staging area)
         u32x4 tq[4];
@@ -351,7 +254,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           //  destination registers can slip in between; what the asm accesses buy is the absence of vmcnt(0) - the stores of
           //  piece p are in flight under piece p + 1)
           u32x4 R[4];
-          epilogue_rows_read<true, true>(rc, lane, R);
+          epilogue_rows_read<true>(rc, lane, R);
           lgkm_wait_rows<true>(R, false);
           epilogue_rows_store(C, ldc, mw + 32 * rg, nw + 64 * ch, lane, R);
         }
@@ -409,7 +312,6 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       }
 #undef W4_SLICE
 #undef W4_RD
-      W4_TSEG(M3P_W4_SCHED2 ? 6 : 4);
     }
   };
   for (int step = 0; step < total; step += 2) {
@@ -417,20 +319,12 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     if (step + 1 < total) kstep(std::integral_constant<int, 1>{}, step + 1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
-  if (TL) {
-    W4_TSEG(M3P_W4_SCHED2 ? 7 : 6);
-    if (lane == 0)
-      for (int k = 0; k < 8; ++k) dbg[((size_t)blockIdx.x * 8 + wid) * 8 + k] = tacc[k];
-  }
-#undef W4_TSEG
-#undef W4_LD1
 #undef W4_LDB
 #undef W4_ACC
 #undef W4_DSR
 #undef W4_LGKM0
 #undef W4_M
 #undef W4_L
-#undef W4_LP
 #undef W4_WAIT_LGKM
 #undef W4_WAIT_VM
 #undef W4_BAR

@@ -2,8 +2,8 @@
 // Weight-gradient kernel, four-wave version of the stream-K ring kernel below/above:
 // dW[i,j] += alpha * sum_m dY[m,i] X[m,j] with 256(i) x 256(j) output tiles, 128x128 per wave
 // (accumulators pinned in AGPRs as in gemm_nt_w4_kernel), 64-row K-tiles of M in two 64-KB LDS
-// stages ([64 m][256 cols] bf16, 512-B rows for both operands), the same two-phase schedule
-// (one s_barrier per 128 MFMAs, LDS-DMAs of K-tile +2 spread over phase 2 and the next phase 1).
+// stages ([64 m][256 cols] bf16, 512-B rows for both operands), the same one-piece K-tile schedule
+// (wktile below).
 // Both operands are contraction-strided, so fragments come out of LDS through
 // ds_read_b64_tr_b16 with the 32-B-segment swizzle of the ring kernel.  Stream-K bookkeeping
 // (chunk == one workgroup's share, round-robin for many tiles) is the ring kernel's; a segment
@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256)
 void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16* __restrict__ X_a, int ldx_a,
                           float* __restrict__ dW_a, int lddw_a, int M, int N, int K, float alpha,
                           int tiles_i, int tiles_j_a, int WR_CHUNK, float* __restrict__ ws, int* __restrict__ ws_tile,
-                          int dbg_flags, int overwrite, WgradProblem pb) {
+                          int overwrite, WgradProblem pb) {
   // Two products over the same M in one launch (pb.tiles != 0; one-segment-per-workgroup mode only): the tiles of product b
   // follow those of product a in the tile numbering, every workgroup picks its product once, before the K loop.  36 tiles of
   // out_lin + q/k/v then share one launch, one end-of-kernel flush and one reduction instead of 9 tiles x 28 chunks beside
@@ -93,29 +93,14 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   int l_issued = 0;
   const int l_hi = lane >> 5, l_pos = lane & 31;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  int y_off[8], x_off[8];      // element offsets of this lane's 16 bytes inside the K-tile, immediates compensated
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    const int row = wid * 16 + 2 * p + l_hi;
-    const int f = (row & 3) | (((row >> 3) & 1) << 2);
-    const int gc = l_pos ^ (f << 1);
-    y_off[p] = row * lddy + gc * 8 - (-4096 + 1024 * p) / 2;
-    x_off[p] = row * ldx + gc * 8 - (-4096 + 1024 * p) / 2;
-    if (YROWS) {      // piece p of wave w = rows 64 w + 8 p .. + 7 of the 256-row panel, 128 B each: lane -> (row l >> 3, slot l & 7)
-      const int yrow = wid * 64 + 8 * p + (lane >> 3);
-      y_off[p] = yrow * lddy + (((lane & 7) ^ (yrow & 7)) * 8) - (-4096 + 1024 * p) / 2;
-    }
-  }
   const bf16* y_base;
   const bf16* x_base;
-#ifndef M3P_WG_BUFDMA
-#define M3P_WG_BUFDMA 1
-#endif
-  // M3P_WG_BUFDMA: the transfers as buffer_load_dwordx4 ... lds - resource = the K-tile's base, scalar offset = the piece's
-  // rows, a 32-bit lane offset (four per operand: the swizzle of a row depends on the piece's parity and half) - instead of
+  // The transfers are buffer_load_dwordx4 ... lds - resource = the K-tile's base, scalar offset = the piece's rows, a 32-bit
+  // lane offset (four per operand: the swizzle of a row depends on the piece's parity and half) - rather than
   // global_load_lds_dwordx4 with a 64-bit lane address per piece.  In the NT kernel the buffer form costs the issuing wave
-  // ~16 clocks a piece where the global form costs ~37 (tools/gemm_timeline.py).  The buffer form's immediate is unsigned
-  // 12-bit: pieces 0-3 and 4-7 of an operand get an M0 each.
+  // ~16 clocks a piece where the global form costs ~37.  The buffer form's immediate is unsigned 12-bit: pieces 0-3 and 4-7
+  // of an operand get an M0 each.  (YROWS: piece p of wave w = rows 64 w + 8 p .. + 7 of the 256-row panel, 128 B each:
+  // lane -> (row l >> 3, slot l & 7).)
   __amdgpu_buffer_rsrc_t y_rsrc, x_rsrc;
   uint32_t y_voff[4], x_voff[4];
 #pragma unroll
@@ -127,10 +112,8 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     if (YROWS) y_voff[k] = (uint32_t)((lane >> 3) * lddy + (((lane & 7) ^ (lane >> 3)) * 8)) * 2u;
   }
   auto set_rsrc = [&]() {
-    if (M3P_WG_BUFDMA) {
-      y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(y_base)), 0, 0xffffffff, 0x00020000);
-      x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(x_base)), 0, 0xffffffff, 0x00020000);
-    }
+    y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(y_base)), 0, 0xffffffff, 0x00020000);
+    x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(x_base)), 0, 0xffffffff, 0x00020000);
   };
   auto set_load_ktile = [&]() {
     const int ti = lc.t / tiles_j, tj = lc.t - ti * tiles_j;
@@ -140,36 +123,18 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     set_rsrc();
   };
   set_load_ktile();
-  // (written as instructions in the scalar-base form - SGPR pair + 32-bit lane offset, no 64-bit vector add per piece - the
-  //  global loads measured the same, 6.88 against 6.80 ms: the adds fit the free issue slots between two MFMAs.)
-#define WG_LD1(PTR, IMM) __builtin_amdgcn_global_load_lds(GLB_PTR(PTR), LDS_PTR(sl), 16, IMM, 0)
 #define WG_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 8 ? y_rsrc : x_rsrc, LDS_PTR(sl), 16, voff, soff, IMM, 0)
   auto issue_load = [&](int s, int piece) {
-    if (M3P_WG_BUFDMA) {
-      const int pc = piece & 7, k = (pc & 1) + 2 * (pc >> 2);
-      char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + (pc >> 2) * 4096;
-      const uint32_t voff = piece < 8 ? y_voff[YROWS ? 0 : k] : x_voff[k];
-      const uint32_t rows = (piece < 8 && YROWS) ? (uint32_t)(wid * 64 + 8 * pc) : (uint32_t)(wid * 16 + 2 * pc);
-      const uint32_t soff = __builtin_amdgcn_readfirstlane(rows * (uint32_t)((piece < 8 ? lddy : ldx) * 2) - (uint32_t)(pc & 3) * 1024u);
-      switch (pc & 3) {
-        case 0: WG_LDB(0); break;
-        case 1: WG_LDB(1024); break;
-        case 2: WG_LDB(2048); break;
-        default: WG_LDB(3072); break;
-      }
-      return;
-    }
-    char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + 4096;
-    const bf16* src = (piece < 8) ? y_base + y_off[piece & 7] : x_base + x_off[piece & 7];
-    switch (piece & 7) {
-      case 0: WG_LD1(src, -4096); break;
-      case 1: WG_LD1(src, -3072); break;
-      case 2: WG_LD1(src, -2048); break;
-      case 3: WG_LD1(src, -1024); break;
-      case 4: WG_LD1(src, 0); break;
-      case 5: WG_LD1(src, 1024); break;
-      case 6: WG_LD1(src, 2048); break;
-      default: WG_LD1(src, 3072); break;
+    const int pc = piece & 7, k = (pc & 1) + 2 * (pc >> 2);
+    char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + (pc >> 2) * 4096;
+    const uint32_t voff = piece < 8 ? y_voff[YROWS ? 0 : k] : x_voff[k];
+    const uint32_t rows = (piece < 8 && YROWS) ? (uint32_t)(wid * 64 + 8 * pc) : (uint32_t)(wid * 16 + 2 * pc);
+    const uint32_t soff = __builtin_amdgcn_readfirstlane(rows * (uint32_t)((piece < 8 ? lddy : ldx) * 2) - (uint32_t)(pc & 3) * 1024u);
+    switch (pc & 3) {
+      case 0: WG_LDB(0); break;
+      case 1: WG_LDB(1024); break;
+      case 2: WG_LDB(2048); break;
+      default: WG_LDB(3072); break;
     }
   };
   const size_t y_step = YROWS ? (size_t)KT : (size_t)KT * lddy, x_step = (size_t)KT * ldx;
@@ -236,15 +201,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #define WG_ACC(B, A) "a[((" #B ")*8+(" #A "))*4:((" #B ")*8+(" #A "))*4+3]"
 #define WG_M(YF, XF, B, A) do { if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 " WG_ACC(B, A) ", %0, %1, 0" :: "v"(YF[A]), "v"(XF[B])); \
                                 else asm volatile("v_mfma_f32_16x16x32_bf16 " WG_ACC(B, A) ", %0, %1, " WG_ACC(B, A) :: "v"(YF[A]), "v"(XF[B])); } while (0)
-  // (the ablation switches of tools/gemm_timeline.py are compile-time: as run-time tests they were a scalar compare + branch per
-  //  LDS-DMA - 21 per K-tile - in a wave that has no partner on its SIMD to issue around them)
-#ifdef M3P_WG_DBG
-#define WG_DBG(bit) (dbg_flags & (bit))
-#else
-#define WG_DBG(bit) 0
-#endif
-#define WG_L(PIECE) do { if (!WG_DBG(2)) issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_LP(PIECE) do { if (PEND && !WG_DBG(2)) issue_load(s_cur ^ 1, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define WG_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
   auto frag = [](const s16x4& lo, const s16x4& hi) {
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
@@ -253,35 +210,13 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   bf16x8 yq[8];                         // (YROWS: the first operand's fragments arrive whole)
   auto yfrag = [&](int c) { if constexpr (YROWS) return yq[c]; else return frag(yl[c], yh[c]); };
   bf16x8 yf0[8], xf0[8], yf1[8], xf1[8];
-  // the stage is a compile-time fact of each phase body (the K loop is unrolled by two): fragment addresses and LDS-DMA
-  // destinations are then plain registers / immediates
-  auto phase1 = [&](auto first_c, auto stage_c, auto pend_c) {
-    constexpr bool FIRST = decltype(first_c)::value;
-    constexpr int s_cur = decltype(stage_c)::value;
-    constexpr bool PEND = decltype(pend_c)::value;     // (false in a workgroup's very first step only: nothing to top up yet)
-    __builtin_amdgcn_sched_barrier(0);
-@PHASE1@
-    __builtin_amdgcn_sched_barrier(0);
-    if (PEND) load_done();
-  };
-  auto phase2 = [&](auto stage_c) {
-    constexpr bool FIRST = false;
-    constexpr int s_cur = decltype(stage_c)::value;
-    __builtin_amdgcn_sched_barrier(0);
-@PHASE2@
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-#ifndef M3P_WG_SCHED2
-#define M3P_WG_SCHED2 1
-#endif
 #define WG_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_SET1() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf1[c] = yfrag(c); xf1[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_SET0() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
-  // M3P_WG_SCHED2: the K-tile in one piece, as in gemm_nt_w4_kernel - the first operand's region of the stage is released by
+  // The K-tile in one piece, as in gemm_nt_w4_kernel (the stage is a compile-time fact: the K loop is unrolled by two) - the first operand's region of the stage is released by
   // a barrier as soon as its k-step-1 fragments are in registers (MFMA 20), the second's at MFMA 50, the next K-tile is waited
   // for at MFMA 107 (vmcnt(16): this K-tile's own sixteen transfers stay in flight): a transfer has 1.2-1.7 K-tiles to land
   // where the two-phase form gives the last five of a K-tile 46 MFMAs and waits ~200-270 clocks per K-tile at its vmcnt(0).
@@ -322,47 +257,10 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   WgCursor cc = locate(g0);
   bool first = true;
   int n_seg = 0;
-  // -DM3P_WG_TL: s_memtime sums per segment of a K-tile (tools/wgrad_timeline.py): 0 phase 1 (64 MFMAs + reads + LDS-DMAs issued),
-  // 1 its closing lgkmcnt(0), 2 vmcnt(0), 3 s_barrier, 4 phase 2, 5 its closing lgkmcnt(0), 6 step tail / flush, 7 K-tiles
-#ifdef M3P_WG_TL
-  unsigned long long wtl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long wt0 = __builtin_amdgcn_s_memtime(), wt1;
-#define WG_TSEG(k) do { __builtin_amdgcn_sched_barrier(0); wt1 = __builtin_amdgcn_s_memtime(); wtl[k] += wt1 - wt0; wt0 = wt1; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define WG_TSEG(k) do { } while (0)
-#endif
   auto kstep = [&](auto stage_c, int step) {
-#if M3P_WG_SCHED2
     if (first) wktile(std::true_type{}, stage_c);
     else wktile(std::false_type{}, stage_c);
     first = false;
-#else
-    WG_TSEG(6);
-    if (step == 0) phase1(std::true_type{}, stage_c, std::false_type{});
-    else if (first) phase1(std::true_type{}, stage_c, std::true_type{});
-    else phase1(std::false_type{}, stage_c, std::true_type{});
-    first = false;
-    WG_TSEG(0);
-    WG_LGKM0();
-    WG_TSEG(1);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { yf1[c] = yfrag(c); xf1[c] = frag(xl[c], xh[c]); }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WG_TSEG(2);
-    __builtin_amdgcn_s_barrier();      // K-tile step+1 visible to all; stage s_cur fully read by all
-    asm volatile("" ::: "memory");
-    WG_TSEG(3);
-    phase2(stage_c);
-    WG_TSEG(4);
-    WG_LGKM0();
-    WG_TSEG(5);
-#ifdef M3P_WG_TL
-    wtl[7] += 1;
-#endif
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); }
-
-#endif
 
     const bool last_of_tile = (cc.mt + 1 == cc.len) || (step + 1 == total);
     if (last_of_tile) {
@@ -441,7 +339,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
               // overwrite (whole-tile round-robin mode on a gradient the caller knows to be zero: the vocabulary matrix's
               // first product of a step): a plain store - the atomic is a read-modify-write of 768 MB that is not in any cache
               if (overwrite) dcol[(size_t)(a * 16 + r) * lddw] = alpha * v[a * 4 + r];
-              else if (!WG_DBG(1)) unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
+              else unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
         }
       }
       if (to_ws && tid == 0) ws_tile[slot] = tile_id0 + cc.t;
@@ -455,13 +353,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     if (step + 1 < total) kstep(std::integral_constant<int, 1>{}, step + 1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
-#ifdef M3P_WG_TL
-  WG_TSEG(6);
-  if (lane == 0)
-    for (int k = 0; k < 8; ++k) g_ring_tl[(blockIdx.x * 4 + wid) * 8 + k] = wtl[k];
-#endif
-#undef WG_TSEG
-#undef WG_LD1
 #undef WG_LDB
 #undef WG_TR2
 #undef WG_YRD
@@ -469,8 +360,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #undef WG_ACC
 #undef WG_M
 #undef WG_L
-#undef WG_DBG
-#undef WG_LP
 }
 
 // dW[tile] += alpha * sum of the workspace slots that hold a partial of that tile.
