@@ -3,10 +3,13 @@ import pytest
 import torch
 
 from tests.util import randn_bf16, randn_f32, rel_l2, max_abs
+from tests.util import (F32_OUT, ROW_FLOOR, ROW_RTOL_BF16, assert_block_bound, assert_exact_zero, assert_gemm_bound,
+                        poison_outputs)  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
+@pytest.mark.usefixtures('poison_outputs')
 @pytest.mark.parametrize('rows,d', [(37, 128), (1000, 768), (513, 1024), (64, 2048), (5, 64)])
 @pytest.mark.parametrize('masked', [False, True])
 def test_layernorm_fwd_bwd(rows, d, masked):
@@ -39,6 +42,23 @@ def test_layernorm_fwd_bwd(rows, d, masked):
     assert rel_l2(dg, gr.grad) < 1e-4
     assert rel_l2(db, br.grad) < 1e-4
     assert rel_l2(dbias, dx.float().sum(0)) < 1e-5   # column sum of the bf16 dx it wrote
+    # against fp64 on the device: y and dx row by row (bf16 outputs of an fp32 computation on exact inputs), mean (a depth-d
+    # sum) and rstd (relative error half that of a depth-d sum of squares) element by element, masked rows exactly zero
+    x64, g64, b64 = x.double(), g.double(), b.double()
+    mu64 = x64.mean(-1)
+    rs64 = 1.0 / torch.sqrt((x64 - mu64[:, None]).pow(2).mean(-1) + 1e-12)
+    xhat = (x64 - mu64[:, None]) * rs64[:, None]
+    keep = rmc.cuda().double()[:, None]
+    assert_block_bound(y, (xhat * g64 + b64) * keep, ('row',), ROW_RTOL_BF16, ROW_FLOOR, 'layernorm y')
+    assert_gemm_bound(mean, mu64, x64.abs().mean(-1), d, F32_OUT, what='layernorm mean')
+    assert_gemm_bound(rstd, rs64, rs64, d, F32_OUT, what='layernorm rstd')
+    gdy = (dya.double() + dyb.double()) * g64
+    dx64 = rs64[:, None] * (gdy - gdy.mean(-1, keepdim=True) - xhat * (gdy * xhat).mean(-1, keepdim=True)) * keep
+    assert_block_bound(dx, dx64, ('row',), ROW_RTOL_BF16, ROW_FLOOR, 'layernorm dx')
+    if masked:
+        off = (rmc == 0).cuda()
+        assert_exact_zero(y[off], 'layernorm y of masked rows')
+        assert_exact_zero(dx[off], 'layernorm dx of masked rows')
 
 
 def test_layernorm_bwd_dropout_branch():

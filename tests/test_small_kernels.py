@@ -7,6 +7,8 @@ import torch
 import torch.nn.functional as F
 
 from tests.util import randn_bf16, randn_f32, rel_l2, max_abs
+from tests.util import (F32_OUT, ROW_FLOOR, ROW_RTOL_BF16, assert_block_bound, assert_gemm_bound,
+                        poison_outputs)  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -40,6 +42,22 @@ def test_gather_scatter_colsum():
     assert rel_l2(cs, 0.5 * xc[:, :1000].sum(0)) < 1e-5
 
 
+def _ce_bounds(row_loss, grad, lc, y, V, n, what):
+    """Row losses element by element against an fp64 log-sum-exp: a sum of V positive terms with fp32 exp (a depth-V sum
+    of O(1) relative error), 2^-20 absolute for __expf / __logf, and the fp32 rounding of lse and of the target logit the
+    loss is their difference of.  The gradient (bf16, fp32 softmax) row by row."""
+    x64 = lc[:, :V].cuda().double()
+    yy = y.cuda()
+    lse = torch.logsumexp(x64, -1)
+    xt = x64[torch.arange(n, device='cuda'), yy]
+    assert_gemm_bound(row_loss, lse - xt, torch.ones_like(lse), V, F32_OUT, F32_OUT * (lse.abs() + xt.abs()) + 2.0 ** -20,
+                      what=what + ' row loss')
+    gref = torch.softmax(x64, -1)
+    gref[torch.arange(n, device='cuda'), yy] -= 1.0
+    assert_block_bound(grad, gref / n, ('row',), ROW_RTOL_BF16, ROW_FLOOR, what + ' gradient')
+
+
+@pytest.mark.usefixtures('poison_outputs')
 @pytest.mark.parametrize('n,V', [(9, 1000), (40, 250002), (3, 64)])
 def test_cross_entropy_fwd_bwd(n, V):
     from m3p_amd import ops
@@ -54,6 +72,7 @@ def test_cross_entropy_fwd_bwd(n, V):
     assert rel_l2(row_loss, F.cross_entropy(lc[:, :V], y, reduction='none')) < 1e-5
     assert rel_l2(logits[:, :V].float(), x.grad) < 5e-3      # bf16 gradient storage
     assert bool((logits[:, V:] == 0).all())
+    _ce_bounds(row_loss, logits[:, :V], lc, y, V, n, 'ce_fwd_bwd')
 
 
 @pytest.mark.parametrize('n,V', [(9, 1000), (70, 250002), (33, 4100), (1, 64)])
@@ -74,6 +93,7 @@ def test_cross_entropy_with_fused_bias_gradient(n, V):
     ref = F.cross_entropy(lc[:, :V], y, reduction='mean')
     assert abs(float(loss_sum) - float(ref)) < 2e-4 * max(1.0, float(ref))
     assert cs.shape == (ld,) and rel_l2(cs, logits.float().sum(0)) < 1e-5 and float(cs[V:].abs().max()) == 0.0
+    _ce_bounds(row_loss, logits[:, :V], lc, y, V, n, 'ce_fwd_bwd_colsum')
 
 
 def test_adam_step_over_ranges_in_one_launch():
