@@ -13,7 +13,8 @@ import torch
 
 from m3p_amd import synth
 from oracle import ref_cpu
-from tests.util import rel_l2
+from tests.util import (ATTN_CTX_RTOL, ATTN_DS_FLOOR, ATTN_DS_RTOL, ROW_FLOOR, assert_block_bound, assert_exact_zero, poisoned_outputs,
+                        rel_l2)
 
 G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'decoder.npz'))
 TAGS = list(synth.DECODER_CASES)
@@ -191,20 +192,29 @@ def test_generate_beam_vs_reference(tag):
     assert n_equal >= n_total - 1, (n_equal, n_total)
 
 
+def _heads(x, B, T, H, dh):
+    """[B*T, H*dh] or [B, T, H*dh] -> [B, H, T, dh]: one block per (sequence, head, row)."""
+    return x.reshape(B, T, H, dh).transpose(1, 2)
+
+
 @pytest.mark.gpu
 def test_attn_query_kernel_vs_torch():
     from m3p_amd import ops
     g = torch.Generator(device='cuda').manual_seed(3)
+    # (the last two: the most keys the launcher admits, QA_MAX_KEYS of csrc/decode.hip, and one key beside all of them)
     for B, Tq, H, dh, Lk, causal, pos0 in ((3, 1, 4, 32, 37, True, 36), (2, 5, 12, 64, 9, True, 4), (4, 3, 2, 64, 200, False, 0),
-                                            (1, 1, 16, 64, 700, False, 0)):
+                                            (1, 1, 16, 64, 700, False, 0), (2, 3, 4, 64, 1024, False, 0), (2, 2, 4, 32, 1024, True, 1022)):
         d = H * dh
         q = torch.randn(B * Tq, d, device='cuda', generator=g).to(torch.bfloat16)
         kv = torch.randn(B, Lk + 3, 2 * d, device='cuda', generator=g).to(torch.bfloat16)
         klen = None if causal else torch.randint(1, Lk + 1, (B,), device='cuda', generator=g).to(torch.int32)
-        ctx = ops.attn_query_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=causal, pos0=pos0)
-        qf = q.float().view(B, Tq, H, dh).transpose(1, 2)
-        kf = kv[:, :Lk, :d].float().reshape(B, Lk, H, dh).transpose(1, 2)
-        vf = kv[:, :Lk, d:].float().reshape(B, Lk, H, dh).transpose(1, 2)
+        if Lk == 1024 and not causal:
+            klen[0], klen[1] = 1, Lk
+        with poisoned_outputs():
+            ctx = ops.attn_query_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=causal, pos0=pos0)
+        qf = q.double().view(B, Tq, H, dh).transpose(1, 2)
+        kf = kv[:, :Lk, :d].double().reshape(B, Lk, H, dh).transpose(1, 2)
+        vf = kv[:, :Lk, d:].double().reshape(B, Lk, H, dh).transpose(1, 2)
         s = qf @ kf.transpose(2, 3)
         j = torch.arange(Lk, device='cuda')
         if causal:
@@ -214,6 +224,8 @@ def test_attn_query_kernel_vs_torch():
             s = s.masked_fill(~(j[None, :] < klen[:, None])[:, None, None, :], float('-inf'))
         ref = (torch.softmax(s, -1) @ vf).transpose(1, 2).reshape(B * Tq, d)
         assert rel_l2(ctx.float(), ref) < 5e-3, (B, Tq, H, dh, Lk)
+        assert_block_bound(_heads(ctx, B, Tq, H, dh), _heads(ref, B, Tq, H, dh), ('b', 'h', 'row'), ATTN_CTX_RTOL, ROW_FLOOR,
+                           'attn_query_fwd ctx %s' % ((B, Tq, H, dh, Lk),))
 
 
 def test_language_ids_need_a_multilingual_model():
@@ -227,7 +239,8 @@ def test_language_ids_need_a_multilingual_model():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('B,Tq,H,dh,Lk,causal,p', [(3, 9, 4, 32, 9, True, 0.0), (2, 17, 12, 64, 17, True, 0.1),
-                                                   (4, 6, 2, 64, 50, False, 0.1), (2, 33, 4, 32, 137, False, 0.0)])
+                                                   (4, 6, 2, 64, 50, False, 0.1), (2, 33, 4, 32, 137, False, 0.0),
+                                                   (2, 5, 4, 64, 1024, False, 0.1), (2, 3, 2, 32, 1024, False, 0.0)])
 def test_attn_rows_training_kernels_vs_autograd(B, Tq, H, dh, Lk, causal, p):
     """Forward with dropout (keep mask regenerated by the RNG twin) + log-sum-exp, and the backward (dq of the unscaled
     projection, dk / dv accumulated in fp32) against torch autograd on the same bf16 operands."""
@@ -238,13 +251,16 @@ def test_attn_rows_training_kernels_vs_autograd(B, Tq, H, dh, Lk, causal, p):
     q = (torch.randn(B * Tq, d, device='cuda', generator=g) * qscale).to(torch.bfloat16)       # the scaled projection output
     kv = torch.randn(B, Lk, 2 * d, device='cuda', generator=g).to(torch.bfloat16)
     klen = None if causal else torch.randint(1, Lk + 1, (B,), device='cuda', generator=g).to(torch.int32)
+    if Lk == 1024:                  # QA_MAX_KEYS of csrc/decode.hip: the most keys the launcher admits; one key beside all of them
+        klen[0], klen[1] = 1, Lk
     dctx = torch.randn(B * Tq, d, device='cuda', generator=g).to(torch.bfloat16)
     seed = 4242
-    ctx, lse = ops.attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=causal, seed=seed, p_drop=p)
+    with poisoned_outputs():
+        ctx, lse = ops.attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=causal, seed=seed, p_drop=p)
     keep = torch.from_numpy(rng.keep_mask(B * H * Tq * Lk, seed, p, (B, H, Tq, Lk))).cuda() if p > 0 else None
-    qf = q.float().view(B, Tq, H, dh).transpose(1, 2).requires_grad_(True)
-    kf = kv[:, :, :d].float().reshape(B, Lk, H, dh).transpose(1, 2).requires_grad_(True)
-    vf = kv[:, :, d:].float().reshape(B, Lk, H, dh).transpose(1, 2).requires_grad_(True)
+    qf = q.double().view(B, Tq, H, dh).transpose(1, 2).requires_grad_(True)
+    kf = kv[:, :, :d].double().reshape(B, Lk, H, dh).transpose(1, 2).requires_grad_(True)
+    vf = kv[:, :, d:].double().reshape(B, Lk, H, dh).transpose(1, 2).requires_grad_(True)
     s = qf @ kf.transpose(2, 3)
     j = torch.arange(Lk, device='cuda')
     if causal:
@@ -257,11 +273,23 @@ def test_attn_rows_training_kernels_vs_autograd(B, Tq, H, dh, Lk, causal, p):
     ref = (pr @ vf).transpose(1, 2).reshape(B * Tq, d)
     assert rel_l2(ctx.float(), ref) < 5e-3
     assert rel_l2(lse, torch.logsumexp(s, -1)) < 1e-4
-    ref.backward(dctx.float())
-    dq, dkv = ops.attn_rows_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, causal=causal, seed=seed, p_drop=p)
+    ref.backward(dctx.double())
+    with poisoned_outputs():
+        dq, dkv = ops.attn_rows_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, causal=causal, seed=seed, p_drop=p)
     assert rel_l2(dq.float(), (qf.grad * qscale).transpose(1, 2).reshape(B * Tq, d)) < 1e-2
     assert rel_l2(dkv[:, :, :d], kf.grad.transpose(1, 2).reshape(B, Lk, d)) < 1e-2
     assert rel_l2(dkv[:, :, d:], vf.grad.transpose(1, 2).reshape(B, Lk, d)) < 1e-2
+    # Per row, with the bars of the encoder attention (tests/util.py).  They follow a fortiori: these kernels keep P and dS in
+    # fp32 where the encoder's round them to bf16 for the matrix instructions; only ctx and dq are rounded to bf16 when stored,
+    # dk and dv are fp32 sums.
+    what = 'attn_rows %s' % ((B, Tq, H, dh, Lk, causal, p),)
+    assert_block_bound(_heads(ctx, B, Tq, H, dh), _heads(ref.detach(), B, Tq, H, dh), ('b', 'h', 'row'), ATTN_CTX_RTOL, ROW_FLOOR, what + ' ctx')
+    assert_block_bound(_heads(dq, B, Tq, H, dh), qf.grad * qscale, ('b', 'h', 'row'), ATTN_DS_RTOL, ATTN_DS_FLOOR, what + ' dq')
+    assert_block_bound(_heads(dkv[:, :, :d], B, Lk, H, dh), kf.grad, ('b', 'h', 'key'), ATTN_DS_RTOL, ATTN_DS_FLOOR, what + ' dk')
+    assert_block_bound(_heads(dkv[:, :, d:], B, Lk, H, dh), vf.grad, ('b', 'h', 'key'), ATTN_CTX_RTOL, ROW_FLOOR, what + ' dv')
+    if klen is not None:
+        past = torch.arange(Lk, device='cuda')[None, :] >= klen[:, None]
+        assert_exact_zero(dkv[past], what + ' dk, dv of keys past the sequence')
 
 
 def _mt_model(extra=None):

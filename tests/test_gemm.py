@@ -6,6 +6,7 @@ import torch
 
 from tests.util import randn_bf16, randn_f32, rel_l2, max_abs
 from tests.util import BF16_OUT, F32_OUT, GLOBAL_GEMM, assert_gemm_bound, poison_outputs  # noqa: F401  (poison_outputs: a fixture)
+from tests.util import EPS_DGELU, EPS_ERF, _dgelu64, _gelu64
 
 pytestmark = pytest.mark.gpu
 
@@ -17,27 +18,14 @@ def _tol(K):
     return GLOBAL_GEMM
 
 
-# Elementwise bounds (tests/util.py: gemm_bound) against fp64 products on the device.  The dGELU epilogue looks gelu' up
-# in a table of fp32 values that is exact to fp32 except below |u| = 2^-15, where the first entry serves: 2.4e-5
-# (csrc/gemm.hip:284).  The GELU epilogue evaluates erf with |error| <= 1.5e-7 (csrc/common.hpp:83).
-EPS_DGELU = 2.4e-5
-EPS_ERF = 1.5e-7
+# Elementwise bounds (tests/util.py: gemm_bound) against fp64 products on the device; EPS_DGELU, EPS_ERF and the fp64 GELU
+# live in tests/util.py, which the streaming GELU kernels' tests share.
 
 
 def _prod64(a, w):
     """fp64 A W^T and |A| |W|^T of the bf16 operands, on the device."""
     a64, w64 = a.cuda().double(), w.cuda().double()
     return a64 @ w64.t(), a64.abs() @ w64.abs().t()
-
-
-def _gelu64(x):
-    x = x.cuda().double()
-    return 0.5 * x * (1 + torch.erf(x / math.sqrt(2)))
-
-
-def _dgelu64(x):
-    x = x.cuda().double()
-    return 0.5 * (1 + torch.erf(x / math.sqrt(2))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2 * math.pi)
 
 
 def _bias64(p64, ap64, bias, scale_cols=0, scale=1.0):

@@ -162,3 +162,351 @@ def test_bounds_count_nan_as_a_failure():
     assert U.block_bound(got, ref, ('row',), U.ROW_RTOL_BF16, U.ROW_FLOOR)[1] == {'row': 2}
     with pytest.raises(AssertionError):
         U.assert_exact_zero(torch.tensor([0.0, float('nan')]), 'nan')
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Streaming kernels: fused Adam update, sum of squares, elementwise bf16 functions, embedding rows.
+# ---------------------------------------------------------------------------------------------------------------------
+import numpy as np  # noqa: E402
+
+F32 = np.float32
+ADAM_GLOBAL_PM, ADAM_GLOBAL_V = 2e-6, 5e-6      # the rel_l2 bars of test_adam_step_matches_oracle
+FAULT_QUAD = 2_000_001                          # the quad the Adam faults hit (elements 4 q .. 4 q + 3)
+
+
+def _adam_f32(p, g, m, v, hp, swap=False, clip_v_once=False, no_wd=False):
+    """adam_kernel of csrc/optim.hip restated in NumPy fp32, one rounding per operation in the kernel's order (no FMA).  The
+    keyword faults are what the rejecting tests inject on one quad."""
+    b1, b2, eps, lr = F32(hp['beta1']), F32(hp['beta2']), F32(hp['eps']), F32(hp['lr'])
+    if swap:
+        b1, b2 = b2, b1
+    gs = F32(hp['grad_scale']) if hp['grad_scale'] else F32(1)
+    coef = gs
+    if hp.get('gnorm_sq') is not None and hp['max_norm'] > 0:
+        norm = F32(math.sqrt(hp['gnorm_sq'])) * gs
+        c = F32(hp['max_norm']) / (norm + F32(1e-6))
+        coef = coef * (c if c < 1 else F32(1))
+    ob1, ob2 = F32(1) - b1, F32(1) - b2
+    wdl = F32(0) if no_wd else F32(hp['weight_decay']) * lr
+    gc = g * coef
+    mn = m * b1 + gc * ob1
+    vn = v * b2 + (gc * (g * gs if clip_v_once else gc)) * ob2
+    den = np.sqrt(vn) + eps
+    pn = p - wdl * p if wdl != 0 else p
+    pn = pn - F32(hp['step_size']) * (mn / den)
+    assert pn.dtype == mn.dtype == vn.dtype == F32
+    return pn, mn, vn
+
+
+def _adam_state(n, seed, zeros=True):
+    """Gradient scales 1e-4 .. 30 and second moments 1e-10 .. 1, log-uniform per element, with zero g, m, v entries."""
+    rs = np.random.RandomState(seed)
+    gscale = 10.0 ** rs.uniform(-4, math.log10(30), n)
+    p = rs.standard_normal(n).astype(F32)
+    g = (gscale * rs.standard_normal(n)).astype(F32)
+    m = (0.5 * gscale * rs.standard_normal(n)).astype(F32)
+    v = (10.0 ** rs.uniform(-10, 0, n)).astype(F32)
+    if zeros:
+        for k, a in enumerate((g, m, v)):
+            a[rs.randint(0, n, n // 64)] = 0
+            a[1000 * (k + 1):1000 * (k + 1) + 64] = 0
+        g[5000:5064] = 0; m[5000:5064] = 0; v[5000:5064] = 0          # all three at once: the update is 0 / eps
+    return p, g, m, v
+
+
+def _hp(g, clip, wd, grad_scale=1.0, step=3):
+    gn = float((g.astype(np.float64) ** 2).sum())
+    b1, b2, lr = 0.9, 0.98, 1e-2
+    return dict(lr=lr, beta1=b1, beta2=b2, eps=1e-8, weight_decay=wd, step_size=lr * math.sqrt(1 - b2 ** step) / (1 - b1 ** step),
+                gnorm_sq=gn, max_norm=(0.5 if clip else 2.0) * math.sqrt(gn) * grad_scale, grad_scale=grad_scale)
+
+
+def _t(*arrays):
+    return tuple(torch.from_numpy(a) for a in arrays)
+
+
+@pytest.mark.parametrize('clip', [True, False])
+@pytest.mark.parametrize('wd', [0.0, 0.01])
+def test_adam_bound_accepts_the_fp32_restatement(clip, wd):
+    """4 M elements.  The restatement reaches 2.4 u (m), 3.7 u (v) and 5.1 u (p) of the 8, 12 and 16 u of the bounds."""
+    state = _adam_state(1 << 22, 11 + clip + 2 * (wd > 0))
+    hp = _hp(state[1], clip, wd, grad_scale=0.5 if clip else 1.0)
+    out = _adam_f32(*state, hp)
+    worst = U.assert_adam_bound(_t(*out), _t(*state), hp, what='fp32 restatement')
+    assert worst['m'] > 0.15 and worst['v'] > 0.15 and worst['p'] > 0.15, worst       # (the bounds are not vacuous)
+
+
+@pytest.fixture(scope='module')
+def adam12m():
+    n = 12 << 20
+    state = _adam_state(n, 5, zeros=False)
+    q = slice(4 * FAULT_QUAD, 4 * FAULT_QUAD + 4)
+    # the faulted quad belongs to a parameter with small gradients and moments: its errors vanish in a global norm that
+    # the parameters with large ones dominate
+    state[1][q] = F32(1e-3) * np.array([1.0, -2.0, 0.5, 3.0], dtype=F32)
+    state[2][q] = F32(1e-3) * np.array([-0.7, 1.5, 2.0, -0.4], dtype=F32)
+    state[3][q] = F32(1e-4) * np.array([1.0, 0.3, 2.0, 0.8], dtype=F32)
+    hp = _hp(state[1], True, 0.01)
+    clean = _adam_f32(*state, hp)
+    refs, _ = U.adam_ref64(*_t(*state), hp)
+    return state, hp, clean, refs
+
+
+@pytest.mark.parametrize('fault', ['quad_not_updated', 'quad_updated_twice', 'betas_swapped', 'clip_once_in_v', 'no_weight_decay'])
+def test_adam_bound_rejects_one_wrong_quad_in_12m_elements(adam12m, fault):
+    state, hp, clean, refs = adam12m
+    q = slice(4 * FAULT_QUAD, 4 * FAULT_QUAD + 4)
+    got = [a.copy() for a in clean]
+    before = [a[q] for a in state]
+    if fault == 'quad_not_updated':
+        new = (before[0], before[2], before[3])
+    elif fault == 'quad_updated_twice':
+        once = _adam_f32(*before, hp)
+        new = _adam_f32(once[0], before[1], once[1], once[2], hp)
+    elif fault == 'betas_swapped':
+        new = _adam_f32(*before, hp, swap=True)
+    elif fault == 'clip_once_in_v':
+        new = _adam_f32(*before, hp, clip_v_once=True)
+    else:
+        new = _adam_f32(*before, hp, no_wd=True)
+    for a, x in zip(got, new):
+        a[q] = x
+    for a, ref, bar in zip(got, refs, (ADAM_GLOBAL_PM, ADAM_GLOBAL_PM, ADAM_GLOBAL_V)):
+        assert U.rel_l2(torch.from_numpy(a), ref) < bar                 # the present global bars let it through
+    worst = U.adam_bound(_t(*got), _t(*state), hp)
+    w, at = max(worst.values())
+    assert w > 2.0 and at // 4 == FAULT_QUAD, worst
+    with pytest.raises(AssertionError, match='quad %d' % FAULT_QUAD):
+        U.assert_adam_bound(_t(*got), _t(*state), hp, what=fault)
+
+
+def test_adam_bound_wants_exact_zeros_where_every_term_is_zero():
+    z = np.zeros(8, dtype=F32)
+    p = np.ones(8, dtype=F32)
+    hp = _hp(np.ones(8, dtype=F32), False, 0.0)
+    assert max(w for w, _ in U.adam_bound(_t(p, z, z), _t(p, z, z, z), hp).values()) == 0.0
+    m = z.copy(); m[5] = 1e-30
+    assert U.adam_bound(_t(p, m, z), _t(p, z, z, z), hp)['m'] == (math.inf, 5)
+
+
+SUMSQ_MAXBLK, SUMSQ_QUADS_PER_BLOCK = 2048, 1024      # m3p_sumsq_f32: blocks = clamp(ceil(n4 / 1024), 1, 2048) of 256 threads
+
+
+def _sumsq_f32(x, threads, skip_quad=None, drop_tail=False):
+    """sumsq_kernel restated: thread k adds the quads k, k + threads, ... in fp32, each quad as (a^2 + b^2) + (c^2 + d^2); a
+    butterfly over the 64 lanes of a wave in fp32; the waves in fp64.  Faults: one quad skipped; the quads the 4 x unrolled
+    loop leaves to the tail loop dropped."""
+    sq = x.reshape(-1, 4) * x.reshape(-1, 4)
+    quad = (sq[:, 0] + sq[:, 1]) + (sq[:, 2] + sq[:, 3])
+    n4 = quad.size
+    if skip_quad is not None:
+        quad[skip_quad] = 0
+    t = -(-n4 // threads)
+    if drop_tail:
+        quad[(n4 // (4 * threads)) * 4 * threads:] = 0
+    quad = np.concatenate([quad, np.zeros(t * threads - n4, dtype=F32)]).reshape(t, threads)
+    acc = np.zeros(threads, dtype=F32)
+    for row in quad:
+        acc = acc + row
+    acc = acc.reshape(-1, 64)
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lanes ^ o]
+    assert acc.dtype == F32
+    return float(acc[:, 0].astype(np.float64).sum()), t
+
+
+def _sumsq_threads(n4):
+    return 256 * min(max(-(-n4 // SUMSQ_QUADS_PER_BLOCK), 1), SUMSQ_MAXBLK)
+
+
+@pytest.mark.parametrize('n4,threads', [(3 * SUMSQ_MAXBLK * 256 * 4 + 77, None), (256 * 2000 + 3, 256), (1, None)])
+def test_sumsq_bound_accepts_the_fp32_restatement(n4, threads):
+    """At the launcher's grid (t = 13) and with one block walking 2001 quads per thread: the bound is linear in t."""
+    x = (np.random.RandomState(n4 % 1000).standard_normal(4 * n4) * 3).astype(F32)
+    got, t = _sumsq_f32(x, threads or _sumsq_threads(n4))
+    U.assert_sumsq_bound(got, float((x.astype(np.float64) ** 2).sum()), t, what='fp32 restatement')
+
+
+def test_sumsq_bound_rejects_a_skipped_quad_and_a_dropped_tail():
+    n4 = SUMSQ_MAXBLK * 256 * 4                        # t = 4: every thread of the full grid runs the unrolled loop once
+    x = np.random.RandomState(3).standard_normal(4 * n4).astype(F32)
+    x[4 * 777_777 + 2] = 3.5                           # one large gradient element: 12 of a sum of 8.4 M
+    ref = float((x.astype(np.float64) ** 2).sum())
+    got, t = _sumsq_f32(x, _sumsq_threads(n4), skip_quad=777_777)
+    assert t == 4 and abs(math.sqrt(got) - math.sqrt(ref)) < 1e-6 * math.sqrt(ref)      # the present bar (on the norm) lets it through
+    assert U.sumsq_bound(got, ref, t) > 1.5
+    with pytest.raises(AssertionError, match='sum of squares'):
+        U.assert_sumsq_bound(got, ref, t, what='skipped quad')
+    n4 = 3 * SUMSQ_MAXBLK * 256 * 4 + 77               # the unrolled loop three times, then 77 quads for the tail loop
+    x = np.random.RandomState(4).standard_normal(4 * n4).astype(F32)
+    got, t = _sumsq_f32(x, _sumsq_threads(n4), drop_tail=True)
+    assert t == 13 and U.sumsq_bound(got, float((x.astype(np.float64) ** 2).sum()), t) > 5.0
+    assert U.sumsq_bound(float('nan'), 1.0, 4) == math.inf
+
+
+# --- rows of the embedding assembly ------------------------------------------------------------------------------------
+EMB_B, EMB_S, EMB_R, EMB_D = 64, 40, 12, 768
+EMBED_GLOBAL_H, EMBED_GLOBAL_GRAD = 6e-3, 1.5e-2        # the rel_l2 bars of test_embed_assemble_fwd_bwd
+EMBED_BENCH_ROWS = 256 * 164                            # rows of h at the benchmarked size; de has 36 x 256
+
+
+def _ln(x, g, b):
+    mu = x.mean(-1, keepdim=True)
+    rs = 1.0 / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + 1e-12)
+    return (x - mu) * rs * g + b, (x - mu) * rs, rs
+
+
+def _ln_bwd(dy, g, xh, rs):
+    gd = dy * g
+    return (gd - gd.mean(-1, keepdim=True) - xh * (gd * xh).mean(-1, keepdim=True)) * rs
+
+
+@pytest.fixture(scope='module')
+def embed_rows():
+    """h = LN_emb(z) from a bf16 z, and de = LN_img backward of the image rows of dz = LN_emb backward of dh: exact in fp64,
+    and restated with the roundings the kernels make (fp32 arithmetic, h and de stored in bf16, dz stored in bf16 between
+    the two backward kernels)."""
+    gen = torch.Generator().manual_seed(9)
+    rnd = lambda *s: torch.randn(s, generator=gen, dtype=torch.float64)      # noqa: E731
+    z, e, dh = _bf16(rnd(EMB_B, EMB_S, EMB_D) * 0.6), _bf16(rnd(EMB_B, EMB_R, EMB_D)), _bf16(rnd(EMB_B, EMB_S, EMB_D))
+    g_emb, be_emb, g_img = (1 + 0.1 * rnd(EMB_D)).float().double(), (0.1 * rnd(EMB_D)).float().double(), (1 + 0.1 * rnd(EMB_D)).float().double()
+    out = {}
+    for name, f in (('exact', lambda t: t), ('kernel', lambda t: t.float().double())):
+        h, xh, rs = _ln(z, g_emb, be_emb)
+        dz = f(_ln_bwd(dh, g_emb, f(xh), f(rs)))
+        _, xh_i, rs_i = _ln(e, g_img, 0.0)
+        if name == 'kernel':
+            h, dz = _bf16(f(h)), _bf16(dz)
+        de = _ln_bwd(dz[:, :EMB_R], g_img, f(xh_i), f(rs_i))
+        out[name] = dict(h=h, dz=dz, de=_bf16(f(de)) if name == 'kernel' else de)
+    return out
+
+
+def test_row_bounds_accept_the_embedding_rows_with_their_roundings(embed_rows):
+    """One bf16 rounding (h) reaches 0.48 of ROW_RTOL_BF16 on these 2560 rows, two with a LayerNorm backward between them
+    (de) 0.68 on 768 rows: the bar of de is sqrt(2) ROW_RTOL_BF16."""
+    exact, kern = embed_rows['exact'], embed_rows['kernel']
+    h = U.assert_block_bound(kern['h'], exact['h'], ('b', 's'), U.ROW_RTOL_BF16, U.ROW_FLOOR, 'h')
+    de = U.assert_block_bound(kern['de'], exact['de'], ('b', 'r'), U.EMBED_DE_RTOL, U.ROW_FLOOR, 'de')
+    assert 0.4 * U.ROW_RTOL_BF16 < h < 0.6 * U.ROW_RTOL_BF16 and 0.45 * U.EMBED_DE_RTOL < de, (h, de)     # about 2 x room
+
+
+@pytest.mark.parametrize('fault', ['row_without_its_last_64_columns', 'row_2_percent', 'last_sequence_unwritten'])
+def test_row_bounds_reject_wrong_embedding_rows(embed_rows, fault):
+    exact, kern = embed_rows['exact'], embed_rows['kernel']
+    for name, rtol, bar, n_bench in (('h', U.ROW_RTOL_BF16, EMBED_GLOBAL_H, EMBED_BENCH_ROWS), ('de', U.EMBED_DE_RTOL, EMBED_GLOBAL_GRAD, 36 * 256)):
+        got = kern[name].clone()
+        if fault == 'row_without_its_last_64_columns':
+            got[EMB_B - 1, 3, -64:] = 0
+        elif fault == 'row_2_percent':
+            got[EMB_B - 1, 3] = _bf16(got[EMB_B - 1, 3] * 1.02)
+        else:
+            got[EMB_B - 1] = float('nan')                  # what a poisoned output reads where a batch slice stopped early
+        if fault != 'last_sequence_unwritten':
+            assert _global_at(got, kern[name], exact[name], n_bench * EMB_D) < bar
+        worst, at, _ = U.block_bound(got, exact[name], ('b', 'row'), rtol, U.ROW_FLOOR)
+        assert worst > 2 * rtol and at['b'] == EMB_B - 1, (name, worst, at)
+
+
+def test_accum_bound_on_sums_gathered_in_any_order():
+    """d_pos-like sums of B fp32 terms: an fp32 sum in a shuffled order passes; one lost term of 256 fails although the global
+    bar of the gradient tests lets it through."""
+    gen = torch.Generator().manual_seed(4)
+    terms = torch.randn((256, 40, 64), generator=gen).double()           # fp32 values
+    ref, absref = terms.sum(0), terms.abs().sum(0)
+    acc = torch.zeros((40, 64))
+    for b in torch.randperm(256, generator=gen).tolist():
+        acc = acc + terms[b].float()
+    worst, _ = U.accum_bound(acc, ref, absref, 256)
+    assert worst < 0.5
+    lost = acc.clone()
+    lost[17] = (ref[17] - terms[255, 17]).float()
+    assert U.rel_l2(lost, ref) < EMBED_GLOBAL_GRAD
+    worst, at = U.accum_bound(lost, ref, absref, 256)
+    assert worst > 100 and at['row'] == 17
+    with pytest.raises(AssertionError, match='accumulation bound at row 17'):
+        U.assert_accum_bound(lost, ref, absref, 256, what='lost term')
+    n = torch.tensor([[1.0]] * 20 + [[256.0]] * 20, dtype=torch.float64)      # rows that gather different numbers of terms
+    assert U.accum_bound(acc, ref, absref, n)[0] > worst * 0 and U.accum_bound(acc, ref, absref, n)[1]['row'] < 20
+
+
+# --- elementwise bf16 kernels -----------------------------------------------------------------------------------------
+GELU_BENCH = 41984 * 3072            # elements of the benchmarked GELU call
+GELU_GLOBAL = 4e-3                   # the rel_l2 bar of test_gelu_fwd_and_batched_transpose
+
+
+def _gelu_parts_f32(x):
+    """gelu_parts of csrc/common.hpp in NumPy fp32 (IEEE division and libm exp where the kernel has v_rcp_f32 / v_exp_f32)."""
+    z = np.abs(x) * F32(0.70710678118654752440)
+    t = F32(1) / (F32(1) + F32(0.3275911) * z)
+    with np.errstate(over="ignore"):
+        e = np.exp(-z * z)
+    poly = F32(1.061405429)
+    for c in (-1.453152027, 1.421413741, -0.284496736, 0.254829592):
+        poly = poly * t + F32(c)
+    cdf_abs = F32(0.5) + F32(0.5) * (F32(1) - poly * t * e)
+    cdf = np.where(x >= 0, cdf_abs, F32(1) - cdf_abs)
+    assert cdf.dtype == F32
+    return cdf, F32(0.39894228040143267794) * e
+
+
+@pytest.fixture(scope='module')
+def gelu():
+    rs = np.random.RandomState(8)
+    x = torch.from_numpy((rs.standard_normal(1 << 20) * 2).astype(F32)).to(torch.bfloat16)
+    x[:10] = torch.tensor([0.0, -0.0, 2.0 ** -20, -2.0 ** -20, 8.0, -8.0, 40.0, -40.0, 3.3895313892515355e38, -3.3895313892515355e38])
+    cdf, pdf = _gelu_parts_f32(x.float().numpy())
+    xf = x.float().numpy()
+    with np.errstate(over='ignore', invalid='ignore'):
+        h, dh = torch.from_numpy(xf * cdf).to(torch.bfloat16), torch.from_numpy(cdf + xf * pdf).to(torch.bfloat16)
+    x64 = x.double()
+    return x64, h, dh, U._gelu64(x, 'cpu'), U._dgelu64(x, 'cpu')
+
+
+def test_elementwise_bound_accepts_the_fp32_gelu(gelu):
+    x, h, dh, ref, dref = gelu
+    zero = torch.zeros_like(ref)
+    U.assert_gemm_bound(h, ref, zero, 0, U.BF16_OUT, 2 * U.EPS_ERF * x.abs(), what='gelu')
+    U.assert_gemm_bound(dh, dref, zero, 0, U.BF16_OUT, U.EPS_DGELU, what="gelu'")
+
+
+@pytest.mark.parametrize('fault', ['two_bf16_ulps', 'eight_elements_unwritten', 'eight_elements_of_the_neighbour'])
+def test_elementwise_bound_rejects_what_the_global_bar_lets_through(gelu, fault):
+    x, h, dh, ref, dref = gelu
+    got = h.double()
+    i = 8 * 5000
+    if fault == 'two_bf16_ulps':
+        i = int(ref.abs().argmax())
+        got[i] = float(got[i]) * (1 + 2 * 2.0 ** -7)
+    elif fault == 'eight_elements_unwritten':
+        got[i:i + 8] = 0                    # (what the allocator handed back; under poisoned_outputs() it reads NaN)
+    else:
+        got[i:i + 8] = got[i + 8:i + 16]
+    assert _global_at(got, h.double(), ref, GELU_BENCH) < GELU_GLOBAL
+    worst, at = U.gemm_bound(got, ref, torch.zeros_like(ref), 0, U.BF16_OUT, 2 * U.EPS_ERF * x.abs())
+    assert worst > 1.5 and i <= at['row'] < i + 8, (worst, at)
+
+
+def test_glu_terms_hold_the_fp32_restatement():
+    """The fp32 restatement reaches 0.50 (y, da) and 0.31 (db) of the approximation terms alone (no output rounding), and
+    stays inside the whole bound once its outputs are rounded to bf16."""
+    rs = np.random.RandomState(12)
+    bf = lambda a: torch.from_numpy(a.astype(F32)).to(torch.bfloat16)      # noqa: E731
+    a, b, g = bf(rs.standard_normal(1 << 20) * 1.5), bf(rs.standard_normal(1 << 20) * 3), bf(rs.standard_normal(1 << 20))
+    b[:6] = torch.tensor([0.0, 20.0, -20.0, 60.0, -60.0, 9.0])
+    an, bn, gn = (t.float().numpy() for t in (a, b, g))
+    s = F32(1) / (F32(1) + np.exp(-bn))
+    y, da, db = an * s, gn * s, gn * an * s * (F32(1) - s)
+    assert db.dtype == F32
+    a64, b64, g64 = a.double(), b.double(), g.double()
+    s64 = torch.sigmoid(b64)
+    refs = (a64 * s64, g64 * s64, g64 * a64 * s64 * (1 - s64))
+    eps = (U.glu_eps(a, b),) + U.glu_eps(a, b, g)
+    zero = torch.zeros_like(a64)
+    reached = 0.0
+    for got, ref, e in zip((y, da, db), refs, eps):
+        got = torch.from_numpy(got)
+        reached = max(reached, U.gemm_bound(got, ref, zero, 0, 0.0, e)[0])
+        U.assert_gemm_bound(got.to(torch.bfloat16), ref, zero, 0, U.BF16_OUT, e, what='glu')
+    assert 0.45 < reached <= 1.0, reached                  # (2 x room)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from m3p_amd import synth
-from tests.util import rel_l2, max_abs, randn_bf16
+from tests.util import BF16_OUT, assert_gemm_bound, glu_eps, rel_l2, max_abs, randn_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -56,6 +56,13 @@ def test_glu_fwd_bwd():
     ref.backward(dyc)
     dab = ops.glu_bwd(ab, dy)
     assert rel_l2(dab.float(), x.grad) < 6e-3
+    # every element: the bf16 store and the accuracy of the gate's exp and reciprocal (tests/util.py: glu_eps)
+    a64, b64, g64 = ab[:, :d].double(), ab[:, d:].double(), dy.double()
+    s64, zero = torch.sigmoid(b64), torch.zeros_like(g64)
+    eps_da, eps_db = glu_eps(ab[:, :d], ab[:, d:], dy)
+    assert_gemm_bound(y, a64 * s64, zero, 0, BF16_OUT, glu_eps(ab[:, :d], ab[:, d:]), what='glu_fwd')
+    assert_gemm_bound(dab[:, :d], g64 * s64, zero, 0, BF16_OUT, eps_da, what='glu_bwd da')
+    assert_gemm_bound(dab[:, d:], g64 * a64 * s64 * (1 - s64), zero, 0, BF16_OUT, eps_db, what='glu_bwd db')
 
 
 def _check_refiner_grads(own_grads, ref_grads, tol_1d=5e-2, tol_2d=5e-2):

@@ -9,6 +9,7 @@ import torch.nn.functional as F
 from tests.util import randn_bf16, randn_f32, rel_l2, max_abs
 from tests.util import (F32_OUT, ROW_FLOOR, ROW_RTOL_BF16, assert_block_bound, assert_gemm_bound,
                         poison_outputs)  # noqa: F401  (a fixture)
+from tests.util import BF16_OUT, EPS_DGELU, EPS_ERF, _dgelu64, _gelu64, assert_adam_bound, assert_sumsq_bound
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -147,7 +148,11 @@ def test_adam_step_matches_oracle():
         lr = 1e-2
         b1, b2 = 0.9, 0.98
         step_size = lr * math.sqrt(1 - b2 ** step) / (1 - b1 ** step)
+        before = tuple(t.clone() for t in (p, g, m, v))
+        assert_sumsq_bound(float(gn), float((gc.double() ** 2).sum()), 3, 'sumsq')        # (1040 quads on 2 blocks: up to 3 per thread)
         ops.adam_step(p, g, m, v, w16, lr, b1, b2, 1e-8, 0.01, step_size, gnorm_sq=gn, max_norm=5.0, grad_scale=1.0)
+        assert_adam_bound((p, m, v), before, dict(lr=lr, beta1=b1, beta2=b2, eps=1e-8, weight_decay=0.01, step_size=step_size,
+                                                  gnorm_sq=float(gn), max_norm=5.0, grad_scale=1.0), what='adam_step %d' % step)
         (gcl,), _ = O.clip_grad_norm([gc], 5.0)
         pc, mc, vc = O.adam_step(pc, gcl, mc, vc, step, lr, b1, b2, 1e-8, 0.01)
         assert rel_l2(p, pc) < 2e-6
@@ -204,6 +209,14 @@ def test_embed_assemble_fwd_bwd(B, T, R, d, p_drop):
     z = (z + leaves['pos'][:S][None]) * mask[..., None]
     href = O._drop(O.layer_norm(z, leaves['g_emb'], leaves['be_emb']), keep_e, p_drop)
     assert rel_l2(h.float().view(B, S, d), href) < 6e-3
+    # per row: h against the fp64 LayerNorm of the saved bf16 z, one rounding away (tests/test_stream_kernels.py holds z and e
+    # to the stages before them)
+    z64 = saved[0].double().view(B, S, d)
+    mu64 = z64.mean(-1, keepdim=True)
+    h64 = (z64 - mu64) / torch.sqrt(((z64 - mu64) ** 2).mean(-1, keepdim=True) + 1e-12) * g_emb.double() + be_emb.double()
+    if keep_e is not None:
+        h64 = h64 * keep_e.cuda().double() / (1.0 - p_drop)
+    assert_block_bound(h.view(B, S, d), h64, ('b', 's'), ROW_RTOL_BF16, ROW_FLOOR, 'h')
     # backward
     dh, dhc = randn_bf16((B * S, d), 20)
     grads = {k: torch.zeros(s, device='cuda') for k, s in dict(
@@ -233,6 +246,8 @@ def test_gelu_fwd_and_batched_transpose():
     u, uc = randn_bf16((1000, 64), 1, 2.0)
     h = ops.gelu_fwd(u)
     assert rel_l2(h.float(), O.gelu_erf(uc)) < 4e-3
+    zero = torch.zeros(u.shape, dtype=torch.float64, device='cuda')
+    assert_gemm_bound(h, _gelu64(u), zero, 0, BF16_OUT, 2 * EPS_ERF * u.double().abs(), what='gelu_fwd')
     # same pass with the derivative written over u (what the training path saves for backward)
     u2 = u.clone()
     h2 = ops.gelu_fwd(u2, grad_inplace=True)
@@ -240,6 +255,7 @@ def test_gelu_fwd_and_batched_transpose():
     x = uc.double().requires_grad_(True)
     (0.5 * x * (1 + torch.erf(x / 2 ** 0.5))).sum().backward()
     assert rel_l2(u2.float(), x.grad) < 4e-3
+    assert_gemm_bound(u2, _dgelu64(u), zero, 0, BF16_OUT, EPS_DGELU, what="gelu_fwd's derivative copy")
     a, ac = randn_bf16((130, 200), 2)
     b, bc = randn_bf16((64, 64), 3)
     da = torch.zeros((200, 130), dtype=BF16, device='cuda'); db = torch.zeros((64, 64), dtype=BF16, device='cuda')
@@ -283,6 +299,8 @@ def test_gelu_bwd_and_mse_kernels():
     x = uc.double().requires_grad_(True)
     (0.5 * x * (1 + torch.erf(x / 2 ** 0.5))).backward(dyc.double())
     assert rel_l2(du.float(), x.grad) < 4e-3
+    dy64 = dy.double()
+    assert_gemm_bound(du, dy64 * _dgelu64(u), torch.zeros_like(dy64), 0, BF16_OUT, EPS_DGELU * dy64.abs(), what='gelu_bwd')
     pred, pc = randn_bf16((23, 2048), 3)
     tgt, tc = randn_f32((23, 2048), 4)
     sq, dpred = ops.mse_fwd_bwd(pred, tgt, 1.0 / (23 * 2048))
@@ -291,6 +309,9 @@ def test_gelu_bwd_and_mse_kernels():
     ref.backward()
     assert abs(float(sq) / (23 * 2048) - float(ref)) < 1e-5 * float(ref)
     assert rel_l2(dpred.float(), p.grad) < 4e-3
+    # 2 (pred - tgt) gscale: a difference and a product in fp32, relative to |pred| + |tgt|, then the bf16 store
+    e64 = pred.double() - tgt.double()
+    assert_gemm_bound(dpred, 2 * e64 / (23 * 2048), (pred.double().abs() + tgt.double().abs()) * 2 / (23 * 2048), 1, BF16_OUT, what='mse gradient')
 
 
 # ---- host-glue kernels (csrc/glue.hip): each against the chain of tensor ops it replaces ----

@@ -28,6 +28,7 @@ GLOBAL_ATTN_GRAD = 1.5e-2       # attention dq / dk / dv
 # Accumulation error of a depth-K fp32 dot product, in units of sqrt(K) 2^-24 sum_k |a_k w_k|: the worst case grows like K,
 # rounding errors of random sign like sqrt(K) with a spread of a few units.  Chosen once from the model, not per test.
 KAPPA = 8.0
+U32 = 2.0 ** -24                # unit roundoff of fp32
 BF16_OUT = 2.0 ** -8            # out_rounding of a bf16 output: its unit roundoff (8 significant bits), the most
                                 # round-to-nearest moves a value relative to itself
 F32_OUT = 4 * 2.0 ** -24        # out_rounding of an fp32 output: a few fp32 roundings of the epilogue
@@ -49,6 +50,10 @@ ATTN_DS_RTOL = 2.0 ** -3
 ROW_FLOOR = 0.25
 ATTN_DS_FLOOR = 1.0
 ROW_RTOL_BF16 = 2.0 ** -8       # rows of a bf16 output computed in fp32 from exact inputs (LayerNorm, softmax gradients)
+# de of the embedding assembly: two bf16 roundings (the stored dz, then de) with a LayerNorm backward between them, which
+# keeps the relative size of the first; independent over a row, they add in quadrature.  The CPU restatement reaches 0.68 of
+# ROW_RTOL_BF16 on 768 rows (tests/test_parity_bounds.py), one rounding alone 0.48; the kernels 0.72 on 9216 rows.
+EMBED_DE_RTOL = math.sqrt(2.0) * ROW_RTOL_BF16
 
 _TINY = 1e-300
 _CHUNK = 1 << 24                # elements compared at once: a few hundred MB of fp64 temporaries at most
@@ -119,6 +124,155 @@ def assert_block_bound(got, ref, blocks, rtol, floor=ROW_FLOOR, what=''):
     worst, at, _ = block_bound(got, ref, blocks, rtol, floor)
     assert worst <= rtol, '%s: block %s has relative error %.3g > %.3g' % (what, at, worst, rtol)
     return worst
+
+
+# The GELU of csrc/common.hpp (gelu_parts), shared by the GEMM epilogues and the streaming GELU kernels.  The dGELU epilogue
+# looks gelu' up in a table of fp32 values that is exact to fp32 except below |u| = 2^-15, where the first entry serves:
+# 2.4e-5 (csrc/gemm.hip:284).  The GELU epilogue evaluates erf with |error| <= 1.5e-7 (csrc/common.hpp:83).
+EPS_DGELU = 2.4e-5
+EPS_ERF = 1.5e-7
+
+
+def _gelu64(x, device='cuda'):
+    x = x.to(device).double()
+    return 0.5 * x * (1 + torch.erf(x / math.sqrt(2)))
+
+
+def _dgelu64(x, device='cuda'):
+    x = x.to(device).double()
+    return 0.5 * (1 + torch.erf(x / math.sqrt(2))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2 * math.pi)
+
+
+# The gate of nn.GLU (csrc/refiner.hip: sigmoid_f = v_rcp_f32(1 + __expf(-b))).  v_exp_f32 and v_rcp_f32 are accurate to 1 ulp
+# = 2 u each; __expf rounds its argument -b log2(e) once, which moves the exponential by |b| u relative; the sum 1 + e rounds
+# once.  The relative error of the sigmoid is within (2 + |b|) u e / (1 + e) + u + 2 u <= (5 + |b|) u.  Forward y = a s: one
+# more product.  Backward db = g a s (1 - s): the error d of s enters as g a s d (1 - 2 s), and four more roundings of
+# products and the difference: within |g a| s (9 + |b|) u.  The fp32 restatement of tests/test_parity_bounds.py (libm exp,
+# IEEE division) reaches 0.50 of the forward and da terms and 0.31 of the db term.
+def glu_eps(a, b, g=None):
+    """Approximation terms (eps_epi of gemm_bound) of GLU forward, or with the output gradient g of its backward (da, db)."""
+    a, b = a.double(), b.double()
+    s = torch.sigmoid(b)
+    if g is None:
+        return a.abs() * s * (6.0 + b.abs()) * U32
+    g = g.double()
+    return g.abs() * s * (6.0 + b.abs()) * U32, (g * a).abs() * s * (9.0 + b.abs()) * U32
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Streaming kernels: the fused Adam update, the sum of squares, fp32 sums gathered with atomics.
+# ---------------------------------------------------------------------------------------------------------------------
+# Roundings of the fused update (csrc/optim.hip: adam_kernel), counted: the clip coefficient costs about 3 (square root,
+# division, product with grad_scale) and enters m once and v twice; then the products, the sum, the correctly rounded sqrtf
+# and division, the two subtractions.  Contraction to FMA only removes roundings.  The fp32 restatement of
+# tests/test_parity_bounds.py reaches 2.4, 3.7 and 5.1 u against these, the kernels 2.7, 4.3 and 4.7 u at 12.6 M elements.
+ADAM_M_U, ADAM_V_U, ADAM_P_U = 8.0, 12.0, 16.0
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def adam_ref64(p, g, m, v, hp):
+    """The fused Adam update in fp64 from fp32 state and the fp32 values of the scalars, with the bounds of its three
+    outputs.  hp: lr, beta1, beta2, eps, weight_decay, step_size, max_norm, grad_scale, gnorm_sq (a number read from the
+    device scalar the kernel is handed, or None).  With gc = g coef, A_m = |beta1 m| + |(1 - beta1) gc|, den = sqrt(v_new)
+    + eps:  |m_new - ref| <= 8 u A_m,  |v_new - ref| <= 12 u v_ref,  |p_new - ref| <= 16 u (|p| + step_size A_m / den).
+    Returns (p_ref, m_ref, v_ref), (p_bound, m_bound, v_bound), all fp64 on the device of p."""
+    b1, b2, eps, lr = _f32(hp['beta1']), _f32(hp['beta2']), _f32(hp['eps']), _f32(hp['lr'])
+    wdl = _f32(hp['weight_decay']) * lr
+    step_size, max_norm = _f32(hp['step_size']), _f32(hp['max_norm'])
+    gs = _f32(hp['grad_scale']) or 1.0                       # (the launcher reads 0 as 1)
+    coef = gs
+    if hp.get('gnorm_sq') is not None and max_norm > 0:
+        c = max_norm / (math.sqrt(float(hp['gnorm_sq'])) * gs + _f32(1e-6))
+        coef *= min(c, 1.0)
+    p, g, m, v = (t.double() for t in (p, g, m, v))
+    gc = g * coef
+    a_m = (b1 * m).abs() + ((1.0 - b1) * gc).abs()
+    m_ref = b1 * m + (1.0 - b1) * gc
+    v_ref = b2 * v + (1.0 - b2) * gc * gc
+    den = v_ref.sqrt() + eps
+    p_ref = (p - wdl * p) - step_size * (m_ref / den)
+    return (p_ref, m_ref, v_ref), (ADAM_P_U * U32 * (p.abs() + step_size * a_m / den), ADAM_M_U * U32 * a_m,
+                                   ADAM_V_U * U32 * v_ref)
+
+
+def adam_bound(got, before, hp, start=0):
+    """Largest |got - ref| / bound of the parameters, first and second moments after one fused Adam step, over every element,
+    and where.  got = (p, m, v) after the step, before = (p, g, m, v) before it (fp32, same length).  An element whose
+    bound is 0 (all of its terms are 0) must be exact; NaN counts as infinite.  Compared in chunks; start = the index of
+    element 0 in the whole arena, for the report.  Returns {'p' | 'm' | 'v': (worst, index)}."""
+    n = before[0].numel()
+    worst = {k: (-1.0, start) for k in 'pmv'}
+    for i0 in range(0, n, _CHUNK):
+        sl = slice(i0, i0 + _CHUNK)
+        refs, bounds = adam_ref64(*(t.reshape(-1)[sl] for t in before), hp)
+        for k, x, ref, bnd in zip('pmv', got, refs, bounds):
+            err = (x.reshape(-1)[sl].to(ref.device, torch.float64) - ref).abs()
+            r = torch.nan_to_num(torch.where(err == 0, torch.zeros_like(err), err / bnd), nan=math.inf, posinf=math.inf)   # (0 / 0 = 0; x / 0 = inf)
+            w, i = r.max(0)
+            if float(w) > worst[k][0]:
+                worst[k] = (float(w), start + i0 + int(i))
+    return worst
+
+
+def assert_adam_bound(got, before, hp, what='', start=0):
+    worst = adam_bound(got, before, hp, start)
+    for k, name in zip('pmv', ('parameter', 'first moment', 'second moment')):
+        assert worst[k][0] <= 1.0, '%s: the %s at element %d (quad %d) is off by %.3g x its bound' % (
+            what, name, worst[k][1], worst[k][1] // 4, worst[k][0])
+    return {k: w for k, (w, _) in worst.items()}
+
+
+def sumsq_bound(got, ref64, t):
+    """|got - ref| / ((t + 8) u ref) of a sum of squares accumulated in fp32: t = the number of 4-element quads one thread
+    adds up (its running sum rounds once per quad; the 8 covers the squares and sums inside a quad and the reduction across
+    the wave).  All terms are non-negative, so the worst case is linear in t and relative to the result."""
+    got, ref64 = float(got), float(ref64)
+    if math.isnan(got):
+        return math.inf
+    return abs(got - ref64) / ((t + 8) * U32 * ref64 + _TINY)
+
+
+def assert_sumsq_bound(got, ref64, t, what=''):
+    worst = sumsq_bound(got, ref64, t)
+    assert worst <= 1.0, '%s: sum of squares %r against %r is off by %.3g x the bound (t = %d)' % (what, float(got), float(ref64), worst, t)
+    return worst
+
+
+def accum_bound(got, ref64, abssum64, n_terms, extra=0.0):
+    """Elements of an fp32 sum of n_terms addends gathered in any order (atomics):  |got - ref| <= KAPPA sqrt(n_terms) u
+    sum|terms| + extra, the accumulation model of gemm_bound.  abssum64 = the same sum over the absolute values of every
+    operand of every term; n_terms a number or a tensor that broadcasts against the output (rows that gather different
+    numbers of terms); extra = what is not accumulation (a bf16 rounding upstream), same shape or a number.
+    Returns (worst, {'row', 'col', ...}) like gemm_bound."""
+    n = torch.as_tensor(n_terms, dtype=torch.float64, device=ref64.device).clamp(min=1.0)
+    bound = KAPPA * n.sqrt() * U32 * abssum64 + extra
+    if bound.dim() < ref64.dim() or bound.shape != ref64.shape:
+        bound = bound.expand_as(ref64)
+    return gemm_bound(got, ref64, torch.zeros_like(ref64), 0, 0.0, bound.contiguous())
+
+
+def assert_accum_bound(got, ref64, abssum64, n_terms, extra=0.0, what=''):
+    worst, at = accum_bound(got, ref64, abssum64, n_terms, extra)
+    assert worst <= 1.0, '%s: the error reaches %.3g x the accumulation bound at row %d, column %d' % (what, worst, at['row'], at['col'])
+    return worst
+
+
+def assert_bits_equal(got, ref, what=''):
+    """Bit-for-bit equality of two tensors of one dtype and shape (signed zeros and NaN payloads included), naming the first
+    element that differs."""
+    assert got.dtype == ref.dtype and got.shape == ref.shape, (what, got.dtype, ref.dtype, got.shape, ref.shape)
+    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    a, b = got.contiguous().view(view).reshape(-1), ref.to(got.device).contiguous().view(view).reshape(-1)
+    for i0 in range(0, a.numel(), 1 << 27):
+        bad = a[i0:i0 + (1 << 27)] != b[i0:i0 + (1 << 27)]
+        if bool(bad.any()):
+            i = i0 + int(bad.nonzero()[0, 0])
+            assert False, '%s: %d elements differ; the first is element %d (row %s): %r against %r' % (
+                what, int((a != b).sum()), i, i // got.shape[-1] if got.dim() > 1 else '-', got.reshape(-1)[i].item(),
+                ref.reshape(-1)[i].item())
 
 
 def assert_exact_zero(t, where):
