@@ -94,6 +94,10 @@ typedef struct M3PEpilogue {
   float* amax8;
   int32_t ld_out8;
   int32_t out8_bf8;
+  /* BIAS_DROP_RES on a row subset: rng_rows[m] (int32 [M], device) is the number row m of this launch has in the full
+   * tensor the dropout stream is indexed by - the keep decision of element (m, n) is that of element rng_rows[m] * N + n,
+   * so a launch over gathered rows drops exactly what the launch over all rows drops there.  NULL = m itself. */
+  const int32_t* rng_rows;
 } M3PEpilogue;
 
 /* C[M,N] (bf16, row pitch ldc) = epilogue( A[M,K] (bf16, pitch lda) x W[N,K]^T (bf16, pitch ldw) ).
@@ -197,6 +201,13 @@ M3P_API int m3p_layernorm_bwd(const void* dy_a, const void* dy_b, const void* x,
                               const float* mean, const float* rstd, const uint8_t* rowmask,
                               void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dbias_drop,
                               int rows, int d, uint32_t seed, uint32_t thresh24, float inv_keep, void* stream);
+/* The same on a row subset of a larger tensor: the dropout stream of dx_drop is indexed by rng_rows[r]*d+c (int32 [rows],
+ * device; NULL = r) - M3PEpilogue::rng_rows of the forward launch that drew the mask. */
+M3P_API int m3p_layernorm_bwd_rows(const void* dy_a, const void* dy_b, const void* x, const float* gamma,
+                                   const float* mean, const float* rstd, const uint8_t* rowmask,
+                                   void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dbias_drop,
+                                   int rows, int d, uint32_t seed, uint32_t thresh24, float inv_keep,
+                                   const int32_t* rng_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused multi-head self-attention (transformer.py:149-210, self-attention branch)
@@ -319,6 +330,11 @@ M3P_API int m3p_embed_assemble_bwd(const void* dh, const void* z, const float* m
 
 /* dst[i,:] = src[idx[i],:] — the boolean-mask gather of :1208 with precomputed row indices */
 M3P_API int m3p_gather_rows(const void* src, const int32_t* idx, void* dst, int n, int d, void* stream);
+/* dst[r,:] (bf16 [rows, d]) = src[inv[r],:] where inv[r] >= 0 (bf16 [n, d]), else the bf16 bit pattern fill_bits (0 = zero,
+ * 0x7FC0 = NaN): a filled full-size tensor with n compact rows placed in it, written in one pass (inv = the inverse of the
+ * row list; entries outside [0, n) count as "not selected").  d % 8 == 0, 16-byte aligned bases. */
+M3P_API int m3p_place_rows(const void* src, const int32_t* inv, void* dst, int rows, int d, int n, uint32_t fill_bits,
+                           void* stream);
 /* dst[idx[i],:] += src[i,:] (idx unique) — its backward */
 M3P_API int m3p_scatter_add_rows(const void* src, const int32_t* idx, void* dst, int n, int d, void* stream);
 /* dst[ids[i],:] (fp32 [V,d]) += rows[i,:] (bf16 [n,d], row pitch ld_rows elements); ids may repeat (atomics), rows with

@@ -72,7 +72,8 @@ __device__ __forceinline__ void epilogue_store(const M3PEpilogue& ep, bf16* __re
   }
   if (EPI == M3P_EPI_BIAS_DROP_RES) {
     if (ep.thresh24) {
-      const uint32_t base = (uint32_t)m * (uint32_t)N + (uint32_t)n;
+      const uint32_t mr = ep.rng_rows ? (uint32_t)ep.rng_rows[m] : (uint32_t)m;      // (row of the full tensor: M3PEpilogue)
+      const uint32_t base = mr * (uint32_t)N + (uint32_t)n;
       bool kp[4];
       m3p_keep_run<4>(base, ep.seed, ep.thresh24, kp);        // (any N: the run may start on an odd element)
 #pragma unroll
@@ -379,13 +380,26 @@ __device__ __forceinline__ void load_aux_rows(const M3PEpilogue& ep, int mrow0, 
 }
 
 // epilogue_half in two parts: the arithmetic on a 32 x 64 piece and its staging writes (accumulator layout -> r1) ...
-template <int EPI, bool SW = false, bool ALDS = false>
+// (internal epilogue number of the four-wave kernel's row-mapped BIAS_DROP_RES instantiation: see gemm_nt_w4_kernel)
+constexpr int M3P_EPI_DROP_RES_ROWS = 10;
+// NOROWS: M3PEpilogue::rng_rows is known to be NULL at compile time (no lookup, no branch)
+template <int EPI, bool SW = false, bool ALDS = false, bool NOROWS = false>
 __device__ __forceinline__ void epilogue_half_write(const M3PEpilogue& ep, int N, int mrow0, int nw, char* r1, const f32x4 (&rows)[2][4],
                                                     const f32x4 (&biasv)[4], const bf16x4 (&auxv)[2][4], int lane, f32x4 (&csum)[4],
                                                     bf16x4 (&ukeep)[2][4], const float* gtab = nullptr) {
   const int fr = lane & 15, fg = lane >> 4;
   constexpr bool kAux = (EPI == M3P_EPI_BIAS_DROP_RES || EPI == M3P_EPI_RES || EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL);
   const float alpha = (ep.alpha == 0.f) ? 1.f : ep.alpha;
+  // dropout: the two rows of this lane as the stream numbers them - the row itself, or with M3PEpilogue::rng_rows (a launch
+  // over gathered rows) its number in the full tensor: one uniform branch in front of the piece.  Precondition of every
+  // caller (as for their row-wise aux loads): the piece's 32 rows mrow0 .. mrow0 + 31 lie inside M - whole tiles in the
+  // eight-wave kernel, the whole-tile branches of the four-wave, ring and fp8 kernels; ragged tiles go through epilogue_store,
+  // which checks m < M before it reads the map
+  uint32_t drow[2] = {(uint32_t)(mrow0 + fr), (uint32_t)(mrow0 + 16 + fr)};
+  if (EPI == M3P_EPI_BIAS_DROP_RES && !NOROWS && ep.rng_rows != nullptr) {
+    drow[0] = (uint32_t)ep.rng_rows[mrow0 + fr];
+    drow[1] = (uint32_t)ep.rng_rows[mrow0 + 16 + fr];
+  }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int n = nw + j * 16 + fg * 4;
@@ -413,7 +427,7 @@ __device__ __forceinline__ void epilogue_half_write(const M3PEpilogue& ep, int N
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf_f((float)ukeep[ii][j][r]);
       }
       if (EPI == M3P_EPI_BIAS_DROP_RES && ep.thresh24) {
-        const uint32_t base = (uint32_t)mrow * (uint32_t)N + (uint32_t)n;      // (whole tiles: N and n are multiples of 4)
+        const uint32_t base = drow[ii] * (uint32_t)N + (uint32_t)n;      // (whole tiles: N and n are multiples of 4)
         bool kp[4];
         m3p_keep_even<4>(base, ep.seed, ep.thresh24, kp);
 #pragma unroll
@@ -2119,11 +2133,17 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
 // The epilogue runs from a private 4.5-KB staging area per wave; the loads of the next
 // output tile are already in flight under it.
 // ---------------------------------------------------------------------------------
-template <int EPI>
+// EPIX = the epilogue, or M3P_EPI_DROP_RES_ROWS: BIAS_DROP_RES that reads M3PEpilogue::rng_rows.  The lookup is compiled
+// into that instantiation alone: a uniform branch on the pointer in front of each pipelined piece brought the compiler's
+// wait for all vector memory operations with it - the previous piece's stores included - and cost every launch WITHOUT a
+// map 7-10 us of 168 (profiles/last_layer_rows_ab.txt)
+template <int EPIX>
 __global__ __launch_bounds__(256)
 void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
                        bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
                        int tiles_m, int tiles_n, int m_fast) {
+  constexpr bool kRows = (EPIX == M3P_EPI_DROP_RES_ROWS);
+  constexpr int EPI = kRows ? (int)M3P_EPI_BIAS_DROP_RES : EPIX;
   constexpr int BM = 256, BN = 256, KT = 64;
   constexpr int A_BYTES = BM * KT * 2, STAGE = (BM + BN) * KT * 2;     // 32 KB, 64 KB
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2474,7 +2494,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           load_aux_rows_finish<EPI, true, true>(lane, rc, tq, aux_cur);
           if (p + 1 < 8) load_aux_rows_issue<EPI>(ep, mw + 32 * ((p + 1) & 3), nw + 64 * ((p + 1) >> 2), lane, tq);
           bf16x4 ukeep[2][4];
-          epilogue_half_write<EPI, true, true>(ep, N, mw + 32 * rg, nw + 64 * ch, rc, rows, ch ? bias_hi : bias_lo, aux_cur, lane, csum, ukeep);
+          epilogue_half_write<EPI, true, true, !kRows>(ep, N, mw + 32 * rg, nw + 64 * ch, rc, rows, ch ? bias_hi : bias_lo, aux_cur, lane, csum, ukeep);
           // (read back at once: straight-line code between the asm reads and their wait, so that no compiler-made copy of the
           //  destination registers can slip in between; what the asm accesses buy is the absence of vmcnt(0) - the stores of
           //  piece p are in flight under piece p + 1)
@@ -2775,8 +2795,11 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     constexpr int BM = 256, BN = 256;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     const size_t lds = 2 * (BM + BN) * 128 + 4 * EP_HALF;
-    auto kern = gemm_nt_w4_kernel<EPI>;
-    static bool attr_set = false;
+    // (a BIAS_DROP_RES launch with a row map runs the instantiation that looks the map up; every other launch compiles it out)
+    const bool rows = (EPI == M3P_EPI_BIAS_DROP_RES && ep.rng_rows != nullptr);
+    auto kern = rows ? gemm_nt_w4_kernel<(EPI == M3P_EPI_BIAS_DROP_RES ? M3P_EPI_DROP_RES_ROWS : EPI)> : gemm_nt_w4_kernel<EPI>;
+    static bool attr_set_both[2] = {false, false};
+    bool& attr_set = attr_set_both[rows ? 1 : 0];
     if (!attr_set) {
       hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return (int)e;

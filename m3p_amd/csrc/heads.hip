@@ -19,6 +19,22 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16* __restrict
         *reinterpret_cast<const bf16x4*>(src + (size_t)idx[r] * d + 4 * c);
   }
 }
+// dst[r,:] = inv[r] >= 0 ? src[inv[r],:] : fill  for every row r of dst: a zero / NaN fill and a row scatter as ONE pass over
+// dst (16-byte accesses; an index outside [0, n) is treated as "not selected": no out-of-bounds read)
+__global__ __launch_bounds__(256) void place_rows_kernel(const bf16* __restrict__ src, const int32_t* __restrict__ inv,
+                                                         bf16* __restrict__ dst, int rows, int d, int n, uint32_t fill2) {
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const int nchunk = d >> 3;
+  const size_t total = (size_t)rows * nchunk;
+  const u32x4 fv = u32x4{fill2, fill2, fill2, fill2};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / nchunk), c = (int)(i - (size_t)r * nchunk);
+    const int j = inv[r];
+    u32x4 v = fv;
+    if (j >= 0 && j < n) v = *reinterpret_cast<const u32x4*>(src + (size_t)j * d + 8 * c);
+    *reinterpret_cast<u32x4*>(dst + (size_t)r * d + 8 * c) = v;
+  }
+}
 // dst[idx[i],:] += src[i,:]  (idx unique -> plain read-modify-write)
 __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const bf16* __restrict__ src, const int32_t* __restrict__ idx,
                                                                bf16* __restrict__ dst, int n, int d) {
@@ -366,6 +382,19 @@ int m3p_gather_rows(const void* src, const int32_t* idx, void* dst, int n, int d
   const size_t total = (size_t)n * (d / 4);
   const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, idx, (bf16*)dst, n, d);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_place_rows(const void* src, const int32_t* inv, void* dst, int rows, int d, int n, uint32_t fill_bits, void* stream) {
+  if (rows <= 0) return M3P_OK;
+  if (d <= 0 || (d % 8) != 0 || n < 0 || !inv || !dst || (n > 0 && !src) || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15))
+    return M3P_EINVAL;
+  const size_t total = (size_t)rows * (d / 8);
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  const uint32_t f = fill_bits & 0xFFFFu;
+  hipLaunchKernelGGL(place_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, inv, (bf16*)dst, rows, d, n,
+                     f | (f << 16));
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }

@@ -71,7 +71,8 @@ void ln_bwd_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy_b,
                    const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
                    const uint8_t* __restrict__ rowmask, bf16* __restrict__ dx, bf16* __restrict__ dx_drop,
                    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dbias_drop,
-                   int rows, int d, uint32_t seed, uint32_t thresh24, float inv_keep) {
+                   int rows, int d, uint32_t seed, uint32_t thresh24, float inv_keep,
+                   const int32_t* __restrict__ rng_rows) {
   __shared__ float red[4][NI * 256];   // [wave][column], reused per quantity
   const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -122,7 +123,7 @@ void ln_bwd_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy_b,
           // bias gradient is the column sum of exactly those values
           bf16x4 ob = bf16x4{(bf16)o[0], (bf16)o[1], (bf16)o[2], (bf16)o[3]};
           f32x4 od;
-          const uint32_t base = (uint32_t)r * (uint32_t)d + 4u * (uint32_t)c;      // (d % 4 == 0: even)
+          const uint32_t base = (uint32_t)(rng_rows ? rng_rows[r] : r) * (uint32_t)d + 4u * (uint32_t)c;      // (d % 4 == 0: even)
           bool kp[4] = {true, true, true, true};
           if (thresh24) m3p_keep_even<4>(base, seed, thresh24, kp);
 #pragma unroll
@@ -163,7 +164,8 @@ void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy
                       const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
                       const uint8_t* __restrict__ rowmask, bf16* __restrict__ dx, bf16* __restrict__ dx_drop,
                       float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dbias_drop,
-                      int rows, uint32_t seed, uint32_t thresh24, float inv_keep) {
+                      int rows, uint32_t seed, uint32_t thresh24, float inv_keep,
+                      const int32_t* __restrict__ rng_rows) {
   constexpr int D = 256 * NC;
   __shared__ float red[8][D];
   const int sub = threadIdx.x & 31, hw = threadIdx.x >> 5;   // 8 half-waves per block
@@ -188,6 +190,7 @@ void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy
     const size_t ro = (size_t)r * D;
     const float mu = mean[r], rs = rstd[r];
     const float mk = rowmask ? (rowmask[r] ? 1.f : 0.f) : 1.f;
+    const uint32_t rr = rng_rows ? (uint32_t)rng_rows[r] : (uint32_t)r;      // row of the tensor the dropout stream indexes
     float dyv[NC][8], xh[NC][8];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -219,7 +222,7 @@ void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy
       for (int e = 0; e < 8; ++e) ob[e] = (bf16)((dyv[i][e] * g[i][e] - c1 - xh[i][e] * c2) * rs);
       *reinterpret_cast<bf16x8*>(dx + ro + c) = ob;
       if (dx_drop || dbias_drop) {
-        const uint32_t base = (uint32_t)r * (uint32_t)D + (uint32_t)c;
+        const uint32_t base = rr * (uint32_t)D + (uint32_t)c;
         bool kp[8] = {true, true, true, true, true, true, true, true};
         if (thresh24) m3p_keep_even<8>(base, seed, thresh24, kp);
 #pragma unroll
@@ -279,10 +282,10 @@ int m3p_layernorm_fwd(const void* x, const float* gamma, const float* beta, cons
   return M3P_OK;
 }
 
-int m3p_layernorm_bwd(const void* dy_a, const void* dy_b, const void* x, const float* gamma, const float* mean,
-                      const float* rstd, const uint8_t* rowmask, void* dx, void* dx_drop, float* dgamma,
-                      float* dbeta, float* dbias_drop, int rows, int d, uint32_t seed, uint32_t thresh24,
-                      float inv_keep, void* stream) {
+int m3p_layernorm_bwd_rows(const void* dy_a, const void* dy_b, const void* x, const float* gamma, const float* mean,
+                           const float* rstd, const uint8_t* rowmask, void* dx, void* dx_drop, float* dgamma,
+                           float* dbeta, float* dbias_drop, int rows, int d, uint32_t seed, uint32_t thresh24,
+                           float inv_keep, const int32_t* rng_rows, void* stream) {
   if (rows <= 0 || d <= 0 || (d % 4) != 0 || d > 2048) return M3P_EINVAL;
   if (!dy_a || !x || !dx || !dgamma || !dbeta) return M3P_EINVAL;
   if (((uintptr_t)x & 7) || ((uintptr_t)dy_a & 7) || ((uintptr_t)dx & 7) || ((uintptr_t)gamma & 15)) return M3P_EINVAL;
@@ -292,11 +295,11 @@ int m3p_layernorm_bwd(const void* dy_a, const void* dy_b, const void* x, const f
     if (d == 768)
       hipLaunchKernelGGL(ln_bwd_hw_kernel<3>, dim3(blocks_hw), dim3(256), 0, st, (const bf16*)dy_a, (const bf16*)dy_b,
                          (const bf16*)x, gamma, mean, rstd, rowmask, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta, dbias_drop,
-                         rows, seed, thresh24, inv_keep);
+                         rows, seed, thresh24, inv_keep, rng_rows);
     else
       hipLaunchKernelGGL(ln_bwd_hw_kernel<4>, dim3(blocks_hw), dim3(256), 0, st, (const bf16*)dy_a, (const bf16*)dy_b,
                          (const bf16*)x, gamma, mean, rstd, rowmask, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta, dbias_drop,
-                         rows, seed, thresh24, inv_keep);
+                         rows, seed, thresh24, inv_keep, rng_rows);
     M3P_CHECK_LAUNCH();
     return M3P_OK;
   }
@@ -304,7 +307,7 @@ int m3p_layernorm_bwd(const void* dy_a, const void* dy_b, const void* x, const f
 #define M3P_LN_BWD(NI)                                                                                     \
   hipLaunchKernelGGL(ln_bwd_kernel<NI>, dim3(blocks), dim3(256), 0, st, (const bf16*)dy_a,                 \
                      (const bf16*)dy_b, (const bf16*)x, gamma, mean, rstd, rowmask, (bf16*)dx,              \
-                     (bf16*)dx_drop, dgamma, dbeta, dbias_drop, rows, d, seed, thresh24, inv_keep)
+                     (bf16*)dx_drop, dgamma, dbeta, dbias_drop, rows, d, seed, thresh24, inv_keep, rng_rows)
   switch (ln_ni(d)) {
     case 1: M3P_LN_BWD(1); break;
     case 2: M3P_LN_BWD(2); break;
@@ -315,6 +318,14 @@ int m3p_layernorm_bwd(const void* dy_a, const void* dy_b, const void* x, const f
 #undef M3P_LN_BWD
   M3P_CHECK_LAUNCH();
   return M3P_OK;
+}
+
+int m3p_layernorm_bwd(const void* dy_a, const void* dy_b, const void* x, const float* gamma, const float* mean,
+                      const float* rstd, const uint8_t* rowmask, void* dx, void* dx_drop, float* dgamma,
+                      float* dbeta, float* dbias_drop, int rows, int d, uint32_t seed, uint32_t thresh24,
+                      float inv_keep, void* stream) {
+  return m3p_layernorm_bwd_rows(dy_a, dy_b, x, gamma, mean, rstd, rowmask, dx, dx_drop, dgamma, dbeta, dbias_drop, rows, d,
+                                seed, thresh24, inv_keep, nullptr, stream);
 }
 
 }  // extern "C"

@@ -511,7 +511,74 @@ def first_rows_sink(model, tensor):
     return sink, base, rows
 
 
-N_ENC_ARGS = 16     # positional arguments of EncoderFn.forward (backward returns one None per argument)
+N_ENC_ARGS = 17     # positional arguments of EncoderFn.forward (backward returns one None per argument)
+
+ROW_TILE = 256          # the compact row set is whole 256-row GEMM tiles (the byte-GELU epilogues take nothing else)
+COMPACT_MIN_ROWS = 4096     # below this the weight-gradient launcher leaves the four-wave kernel (m3p_gemm_wgrad_plan)
+
+
+def compact_rows_eligible(n_rows, M):
+    """Does a last layer restricted to ``n_rows`` selected rows (before padding) of the M rows of an encoder pass run on
+    the compact path?  -> the padded row count, or 0 for the full path.  Padded to whole tiles the set must keep the
+    row-wise GEMMs on the kernels the full pass uses (>= COMPACT_MIN_ROWS) and leave at least half of the rows out (less is
+    not worth the gathers and the split weight-gradient launch).
+    EncoderFn adds conditions of the pass itself: it is differentiated, runs on the bf16 GEMMs, and the FFN takes the same
+    form at n rows as at M (ops.gq_eligible: backward keeps ONE flag for how gelu'(u) was saved in all layers) - so at the
+    usual widths (4 d >= 512) a pass whose M = B * S is not a multiple of 256 keeps the full path whatever the set."""
+    if n_rows <= 0:
+        return 0
+    n = _round_up(n_rows, ROW_TILE)
+    return n if (n >= COMPACT_MIN_ROWS and 2 * n <= M) else 0
+
+
+class OutputRows:
+    """The rows of an encoder pass's [M, d] output (row b * S + s) that its caller will read - built on the HOST from the
+    masks of the batch, so that its size is known without a device synchronisation.  EncoderFn computes the last layer's
+    row-wise part (everything after attention) on these rows only and returns NaN everywhere else.
+
+    idx  int32 [n]: the selected rows in ascending order, padded to a multiple of ROW_TILE with rows OUTSIDE the set (forward
+         computes them, nobody places or reads them; no head reads them, so the gradient sink holds exact zeros there and
+         they add nothing to any gradient); idx64: the same as int64, for indexing;
+    inv  int32 [M]: position of row r in idx, -1 for rows outside the set (pad entries included)."""
+
+    def __init__(self, flags):
+        flags = torch.as_tensor(flags).reshape(-1).cpu()
+        if flags.dtype != torch.bool:
+            flags = flags != 0
+        self.flags = flags
+        self.M = int(flags.numel())
+        sel = torch.nonzero(flags).view(-1)
+        self.n_rows = int(sel.numel())
+        self.n = compact_rows_eligible(self.n_rows, self.M)
+        self.idx = self.idx64 = self.inv = None
+        if self.n:
+            pad = torch.nonzero(~flags).view(-1)[:self.n - self.n_rows]       # (2 n <= M: there are enough)
+            idx = torch.cat([sel, pad]).to(torch.int32)
+            inv = torch.full((self.M,), -1, dtype=torch.int32)
+            inv[sel] = torch.arange(self.n_rows, dtype=torch.int32)
+            self._host = (idx, inv)
+
+    @classmethod
+    def from_masks(cls, B, S, R, first=True, pred_mask=None, region_labels=None):
+        """Union of: the first row of every sequence (the relation heads), the True entries of ``pred_mask`` (T, B) (MLM: text
+        position t is row R + t) and the regions whose ``region_labels`` (B, R) are not -1 (MRM / MRFR)."""
+        flags = torch.zeros((B, S), dtype=torch.bool)
+        if first:
+            flags[:, 0] = True
+        if pred_mask is not None:
+            flags[:, R:] |= torch.as_tensor(pred_mask).cpu().reshape(S - R, B).t() != 0
+        if region_labels is not None and R > 0:
+            flags[:, :R] |= torch.as_tensor(region_labels).cpu().reshape(B, R) != -1
+        return cls(flags)
+
+    def to(self, device):
+        if self.n and self.idx is None:
+            from .utils import to_cuda
+            with torch.cuda.device(device):
+                self.idx, self.inv = to_cuda(*self._host)
+            self.idx64 = self.idx.long()
+        assert self.idx is None or self.idx.device == torch.device(device), 'an OutputRows serves one pass on one device'
+        return self
 
 
 class EncoderFn(torch.autograd.Function):
@@ -522,7 +589,7 @@ class EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, model, x, lengths, x_img, lengths_img, image_loc, p_drop, p_attn, seed_step, p_refine=None,
-                track=False, text_embed=None, langs=None, h0=None, positions=None):
+                track=False, text_embed=None, langs=None, h0=None, positions=None, out_rows=None):
         ar = model.arena()
         # sharded data parallelism: the parameters of this step arrive bucket by bucket (in forward order) on the side
         # stream; wait for what the embedding stage reads now and for each layer in front of its first GEMM
@@ -629,6 +696,16 @@ class EncoderFn(torch.autograd.Function):
             w8, _, dws = st8.weights[(i, wsite)]
             return ops.gemm_nt_fp8(x8, w8, epi, descale_a=dxs, descale_b=dws, **kw)
 
+        # the caller reads only out_rows of the output (OutputRows): inside a layer only attention mixes rows, so the LAST
+        # layer's row-wise part - out_lin, LayerNorm 1, the FFN, LayerNorm 2, and their backward - runs on those rows alone
+        # (gathered into [n, d] buffers; the same launchers, the same kernels).  Only for a pass that is differentiated, on
+        # bf16 GEMMs, and where the byte-GELU form of the FFN is taken (or not) at n rows as at M
+        rows_c = None
+        if out_rows is not None and out_rows.n and track and st8 is None and nL > 0 and d % 8 == 0 \
+                and ops.gq_eligible(M, 4 * d) == ops.gq_eligible(out_rows.n, 4 * d):
+            assert out_rows.M == M, 'out_rows was built for %d rows, this pass has %d' % (out_rows.M, M)
+            rows_c = out_rows.to(dev)
+
         for i in range(nL):
             a, f = 'attentions.%d.' % i, 'ffns.%d.' % i
             ready(('layer', i))
@@ -636,16 +713,25 @@ class EncoderFn(torch.autograd.Function):
             ctxt, lse, kmask = ops.attn_fwd(qkv, totlen, B, S, H, dh, seed=seed('attn_p', i), p_drop=p_attn,
                                             want_mask=True)
             lse = (lse, kmask)      # the dropout keep bits travel with the log-sum-exp to backward
-            pre1 = lin(ctxt, i, 'ctx', 'wout', ar.w(a + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(a + 'out_lin.bias'),
-                       aux=h, seed=seed('attn_out', i), p_drop=p_drop)
+            compact = rows_c is not None and i == nL - 1
+            Mi, ctx_in, res_in, mask_i, rr, ctx_c = M, ctxt, h, rowmask, {}, None
+            if compact:
+                # the dropout streams are indexed by the element's position in the full [M, N] tensor: the launches on
+                # gathered rows are told the rows' numbers (rng_rows) and draw the same keep decisions for the same elements
+                Mi, rr = rows_c.n, dict(rng_rows=rows_c.idx)
+                ctx_in = ctx_c = ops.gather_rows(ctxt, rows_c.idx, Mi, d)
+                res_in = ops.gather_rows(h, rows_c.idx, Mi, d)
+                mask_i = rowmask[rows_c.idx64]
+            pre1 = lin(ctx_in, i, 'ctx', 'wout', ar.w(a + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(a + 'out_lin.bias'),
+                       aux=res_in, seed=seed('attn_out', i), p_drop=p_drop, **rr)
             x1, mean1, rstd1 = ops.layernorm_fwd(pre1, ar.p('layer_norm1.%d.weight' % i), ar.p('layer_norm1.%d.bias' % i))
             hact8 = None
             u_holds_grad = False     # does the pass below leave gelu'(u) in u's buffer? (backward then only multiplies)
             if (st8 is None or 'w1' not in fp8mod.FWD_SITES) and not _GELU_GRAD_IN_FWD and _GELU_BYTE_GRAD == 2 and track \
-                    and ops.gq_eligible(M, 4 * d):
+                    and ops.gq_eligible(Mi, 4 * d):
                 # lin1 + GELU in ONE launch: the epilogue writes h and, for backward, gelu'(u) as one byte per element in the
                 # dU GEMM's own fragment order (EPI_MULQ decodes it with one fma); u is never stored
-                u = torch.empty((M * 4 * d,), dtype=torch.uint8, device=dev)
+                u = torch.empty((Mi * 4 * d,), dtype=torch.uint8, device=dev)
                 o8 = {}
                 if st8 is not None and 'w2' in fp8mod.FWD_SITES:
                     # fp8 (round 6): the same epilogue leaves the e4m3 copy of h that the 8-bit lin2 product reads - no
@@ -660,14 +746,14 @@ class EncoderFn(torch.autograd.Function):
                 elif st8 is not None and 'w2' in fp8mod.FWD_SITES:
                     st8._first_use(hact, kh)
                 u_holds_grad = 'q'
-            elif M >= 1024 or st8 is not None:
+            elif Mi >= 1024 or st8 is not None:
                 # persistent GEMM: bias in the epilogue, GELU as its own HBM-speed pass
                 # The same pass leaves gelu'(u) in u's buffer: the backward dgrad then only multiplies
                 # (EPI_MUL, runs on the four-wave GEMM) instead of evaluating erf/exp in its epilogue.
                 u = lin(x1, i, 'x1', 'w1', ar.w(f + 'lin1.weight'), L.EPI_BIAS, bias=ar.p(f + 'lin1.bias'))
                 if st8 is not None and 'w2' in fp8mod.FWD_SITES and 'w2' not in fp8mod.BWD_SITES and not _GELU_GRAD_IN_FWD:
                     hact, hact8 = st8.gelu_quant(u, i)           # GELU and the 8-bit copy for lin2 in one pass
-                elif st8 is None and not _GELU_GRAD_IN_FWD and _GELU_BYTE_GRAD and track and ops.gq_eligible(M, 4 * d):
+                elif st8 is None and not _GELU_GRAD_IN_FWD and _GELU_BYTE_GRAD and track and ops.gq_eligible(Mi, 4 * d):
                     # what backward needs of u is gelu'(u): one byte per element in the dU GEMM's own fragment order
                     # (EPI_MULQ decodes it with one fma - no derivative table, no aux trip through LDS); u is dropped here
                     hact, u = ops.gelu_fwd_gq(u)
@@ -676,20 +762,25 @@ class EncoderFn(torch.autograd.Function):
                     u_holds_grad = _GELU_GRAD_IN_FWD or (st8 is not None and 'w2' in fp8mod.BWD_SITES)
                     hact = ops.gelu_fwd(u, grad_inplace=u_holds_grad)
             else:
-                u = torch.empty((M, 4 * d), dtype=BF16, device=dev)
+                u = torch.empty((Mi, 4 * d), dtype=BF16, device=dev)
                 hact = ops.gemm_nt(x1, ar.w(f + 'lin1.weight'), L.EPI_BIAS_GELU, bias=ar.p(f + 'lin1.bias'), out2=u)
             pre2 = lin(hact, i, 'hact', 'w2', ar.w(f + 'lin2.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(f + 'lin2.bias'),
-                       aux=x1, seed=seed('ffn', i), p_drop=p_drop, pre8=hact8)
+                       aux=x1, seed=seed('ffn', i), p_drop=p_drop, pre8=hact8, **rr)
             h_next, mean2, rstd2 = ops.layernorm_fwd(pre2, ar.p('layer_norm2.%d.weight' % i),
-                                                     ar.p('layer_norm2.%d.bias' % i), rowmask)
+                                                     ar.p('layer_norm2.%d.bias' % i), mask_i)
             if track:      # (inference keeps nothing: retrieval evaluation runs thousands of sequences per call)
-                saved_layers.append((h, qkv, ctxt, lse, pre1, mean1, rstd1, x1, u, hact, pre2, mean2, rstd2))
+                saved_layers.append((h, qkv, ctxt, lse, pre1, mean1, rstd1, x1, u, hact, pre2, mean2, rstd2, ctx_c, mask_i))
+            if compact:
+                # the full-size output in one pass: the selected rows in their places, NaN everywhere else - a consumer that
+                # reads a row it did not ask for fails loudly
+                h_next = ops.place_rows(h_next, rows_c.inv, M, ops.BF16_NAN_BITS)
             h = h_next
 
         ctx.model = model
         ctx.dims = (B, T, R, S, d, H, dh, nL)
         ctx.drop = (p_drop, p_attn, seed_step)
         ctx.u_holds_grad = nL > 0 and u_holds_grad
+        ctx.rows_c = rows_c
         # (backward wants the REAL token ids where they exist - pad rows, the scatter into the vocabulary matrix; with
         #  text_embed there are none and it gets the row numbers)
         ctx.saved = (tok if text_embed is not None else x, totlen, rowmask, ximg16, loc, emb_saved, saved_layers)
@@ -719,6 +810,7 @@ class EncoderFn(torch.autograd.Function):
         p_drop, p_attn, seed_step = ctx.drop
         x, totlen, rowmask, ximg16, loc, emb_saved, saved_layers = ctx.saved
         ctx.saved = None
+        rows_c = ctx.rows_c
         seed = lambda kind, i=0: rng.stream_seed(model.base_seed, seed_step, _site(kind, i))   # noqa: E731
         ref_saved, keylen_img, p_refine = ctx.refine
         ctx.refine = None
@@ -752,13 +844,20 @@ class EncoderFn(torch.autograd.Function):
 
         for i in reversed(range(nL)):
             a, f = 'attentions.%d.' % i, 'ffns.%d.' % i
-            (h_in, qkv, ctxt, lse, pre1, mean1, rstd1, x1, u, hact, pre2, mean2, rstd2) = saved_layers[i]
+            (h_in, qkv, ctxt, lse, pre1, mean1, rstd1, x1, u, hact, pre2, mean2, rstd2, ctx_c, mask_i) = saved_layers[i]
             saved_layers[i] = None
+            compact = rows_c is not None and i == nL - 1
+            rr = {}
+            if compact:
+                # the last layer ran its row-wise part on the rows the caller reads (forward): gather their gradients - every
+                # other row's is zero -, run the same launches on [n, d], hand attention's backward full-size buffers
+                rr = dict(rng_rows=rows_c.idx)
+                dh_ = ops.gather_rows(dh_.view(M, d), rows_c.idx, rows_c.n, d)
             # LayerNorm2 (+ the layer-end mask) and the FFN dropout
-            dpre2, dY2 = ops.layernorm_bwd(dh_, None, pre2, ar.p('layer_norm2.%d.weight' % i), mean2, rstd2, rowmask,
+            dpre2, dY2 = ops.layernorm_bwd(dh_, None, pre2, ar.p('layer_norm2.%d.weight' % i), mean2, rstd2, mask_i,
                                            ar.g('layer_norm2.%d.weight' % i), ar.g('layer_norm2.%d.bias' % i),
                                            dbias_drop=ar.g(f + 'lin2.bias'), want_drop=p_drop > 0,
-                                           seed=seed('ffn', i), p_drop=p_drop)
+                                           seed=seed('ffn', i), p_drop=p_drop, **rr)
             if dY2 is None:
                 dY2 = dpre2
             ops.gemm_wgrad(dY2, hact, ar.g(f + 'lin2.weight'))
@@ -786,14 +885,24 @@ class EncoderFn(torch.autograd.Function):
             dpre1, dAO = ops.layernorm_bwd(dx1, None, pre1, ar.p('layer_norm1.%d.weight' % i), mean1, rstd1, None,
                                            ar.g('layer_norm1.%d.weight' % i), ar.g('layer_norm1.%d.bias' % i),
                                            dbias_drop=ar.g(a + 'out_lin.bias'), want_drop=p_drop > 0,
-                                           seed=seed('attn_out', i), p_drop=p_drop)
+                                           seed=seed('attn_out', i), p_drop=p_drop, **rr)
             if dAO is None:
                 dAO = dpre1
             dctx = dgrad(dAO, i, 'dao', 'wout', ar.wt[('out', i)], L.EPI_NONE)
+            if compact:
+                # out_lin's weight gradient over the n rows (the paired launch needs one shared row count: q/k/v's runs alone
+                # below, over all rows); dctx and the residual gradient go back to full size, zero outside the set (pad
+                # entries hold zeros and are not placed) - the residual still enters dh through the EPI_RES epilogue
+                ops.gemm_wgrad(dAO, ctx_c, ar.g(a + 'out_lin.weight'))
+                dctx = ops.place_rows(dctx, rows_c.inv, M, 0)
+                dpre1 = ops.place_rows(dpre1, rows_c.inv, M, 0)
             dqkv = ops.attn_bwd(qkv, totlen, ctxt, dctx, lse[0], B, S, H, dh, dbias_qkv=ar.qkv_bias(i, grad=True),
                                 seed=seed('attn_p', i), p_drop=p_attn, keepmask=lse[1])
-            # out_lin's and q/k/v's weight gradients in one launch (9 + 27 output tiles fill the CUs like one FFN gradient)
-            ops.gemm_wgrad_pair(dqkv, h_in, ar.qkv_wgrad(i), dAO, ctxt, ar.g(a + 'out_lin.weight'))
+            if compact:
+                ops.gemm_wgrad(dqkv, h_in, ar.qkv_wgrad(i))
+            else:
+                # out_lin's and q/k/v's weight gradients in one launch (9 + 27 output tiles fill the CUs like one FFN gradient)
+                ops.gemm_wgrad_pair(dqkv, h_in, ar.qkv_wgrad(i), dAO, ctxt, ar.g(a + 'out_lin.weight'))
             dh_ = dgrad(dqkv, i, 'dqkv', 'wqkv', ar.wt[('qkv', i)], L.EPI_RES, aux=dpre1)
             del dqkv, dctx, dAO, dpre1, dx1
             ar.touch_layer(i)
@@ -802,7 +911,7 @@ class EncoderFn(torch.autograd.Function):
         if ctx.h0_mode is not None:       # no embedding assembly in this pass: the rows' gradient goes back to whoever made them
             if hook is not None:
                 hook.embed_done(last, ids=None, rows=None, n_max=ctx.tok_rows_max)
-            return (None,) * 14 + (dh_.to(ctx.h0_mode), None)        # (h0 is the 15th argument, positions the 16th)
+            return (None,) * 14 + (dh_.to(ctx.h0_mode), None, None)        # (h0 is the 15th argument, positions the 16th)
         # under data parallelism the token rows' gradients are exchanged as rows, not scattered here
         want_dximg, has_text_embed = ctx.input_grads
         langs, positions = ctx.langs, ctx.positions
@@ -856,7 +965,7 @@ class EncoderFn(torch.autograd.Function):
             tok_rows = None
         if hook is not None:
             hook.embed_done(last, ids=x if tok_rows is not None else None, rows=tok_rows, n_max=ctx.tok_rows_max)
-        return (None, None, None, None, d_ximg, None, None, None, None, None, None, None, d_text, None, None, None)
+        return (None, None, None, None, d_ximg, None, None, None, None, None, None, None, d_text, None, None, None, None)
 
 
 class ImageStreamFn(torch.autograd.Function):

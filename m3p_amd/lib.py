@@ -31,6 +31,7 @@ class Epilogue(C.Structure):
         ('alpha', C.c_float), ('seed', C.c_uint32), ('thresh24', C.c_uint32), ('inv_keep', C.c_float),
         ('descale_a', C.c_void_p), ('descale_b', C.c_void_p),
         ('out8', C.c_void_p), ('scale8', C.c_void_p), ('amax8', C.c_void_p), ('ld_out8', C.c_int32), ('out8_bf8', C.c_int32),
+        ('rng_rows', C.c_void_p),
     ]
 
 
@@ -52,6 +53,7 @@ SIGNATURES = {
     'm3p_gemm_wgrad_pair_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
     'm3p_layernorm_fwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
     'm3p_layernorm_bwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _u32, _u32, _f, _p]),
+    'm3p_layernorm_bwd_rows': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _u32, _u32, _f, _p, _p]),
     'm3p_attn_fwd': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _u32, _u32, _f, _p]),
     'm3p_attn_bwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _u32, _u32, _f, _p]),
     'm3p_attn_query_fwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
@@ -65,6 +67,7 @@ SIGNATURES = {
     'm3p_glu_fwd': (_i, [_p, _i, _p, _i, _i, _p]),
     'm3p_glu_bwd': (_i, [_p, _i, _p, _p, _i, _i, _p]),
     'm3p_gather_rows': (_i, [_p, _p, _p, _i, _i, _p]),
+    'm3p_place_rows': (_i, [_p, _p, _p, _i, _i, _i, _u32, _p]),
     'm3p_scatter_add_rows': (_i, [_p, _p, _p, _i, _i, _p]),
     'm3p_scatter_add_token_rows': (_i, [_p, _i, _p, _p, _i, _i, _i, _p]),
     'm3p_ce_fwd_bwd': (_i, [_p, _i, _i, _i, _p, _p, _p, _f, _f, _p]),

@@ -406,9 +406,12 @@ class TransformerModel(nn.Module):
         return self._fwd_counter
 
     def jointfwd(self, x, lengths, x_img, lengths_img, causal=False, positions=None, langs=None,
-                 image_loc=None, refine_image=False, is_latent=False, text_embed=None):
+                 image_loc=None, refine_image=False, is_latent=False, text_embed=None, out_rows=None):
         """transformer.py:878-968.  x (T,B) int64, x_img (R,B,2048), image_loc (R,B,5) ->
-        (S=R+T, B, d) (a transposed view of the batch-major activation, like the reference)."""
+        (S=R+T, B, d) (a transposed view of the batch-major activation, like the reference).
+        out_rows (functional.OutputRows, optional): the output rows the caller will read.  A training pass may then compute
+        the last layer's row-wise part on those rows only; every other row of the result holds NaN.  None: every row is
+        computed."""
         assert not causal and not is_latent, 'causal / is_latent are outside the MI355X hot path'
         T, B = x.size()
         assert lengths.size(0) == B
@@ -420,7 +423,8 @@ class TransformerModel(nn.Module):
             assert self.n_refine_layers > 0, 'refine_image=True needs params.refine_layers > 0'
             p_ref = self.refine_dropout if self.training else 0.0
         out = self._tag_pass(Fn.EncoderFn.apply(self.layer_norm_emb.weight, self, x, lengths, x_img, lengths_img, image_loc, p, pa,
-                                                self._next_seed_step(), p_ref, torch.is_grad_enabled(), text_embed))
+                                                self._next_seed_step(), p_ref, torch.is_grad_enabled(), text_embed,
+                                                None, None, None, out_rows))
         return out.view(B, R + T, self.dim).transpose(0, 1)
 
     def _tag_pass(self, out):

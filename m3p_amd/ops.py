@@ -45,9 +45,12 @@ def _chk_bf16(*ts):
 
 
 def gemm_nt(a, w, epilogue=L.EPI_NONE, bias=None, aux=None, out=None, out2=None, colsum=None,
-            scale_cols=0, scale=1.0, alpha=1.0, seed=0, p_drop=0.0, n=None, out8=None, scale8=None, amax8=None, out8_bf8=False):
+            scale_cols=0, scale=1.0, alpha=1.0, seed=0, p_drop=0.0, n=None, out8=None, scale8=None, amax8=None, out8_bf8=False,
+            rng_rows=None):
     """C[M,N] = epi(a[M,K] @ w[N,K]^T).  a, w bf16 (row pitch = stride(0)); returns C (bf16).
     ``n`` restricts the number of output columns (rows of w) used.
+    rng_rows (EPI_BIAS_DROP_RES on gathered rows): int32 [M], the number of each row in the full tensor the dropout stream
+    is indexed by - the launch then drops exactly the elements the launch over all rows drops in those rows.
     out8 (EPI_BIAS_GELUQ / EPI_MULQ): uint8 [M, N] that receives the 8-bit copy of C - sat(C * scale8) in e4m3, or e5m2 with
     out8_bf8 - for the fp8 product that consumes C; amax8 (fp32 [1], zeroed by the caller) is raised to max |C|."""
     M, K = a.shape
@@ -84,6 +87,10 @@ def gemm_nt(a, w, epilogue=L.EPI_NONE, bias=None, aux=None, out=None, out2=None,
     ep.inv_keep = 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0
     if bias is not None:
         assert bias.dtype == torch.float32
+    if rng_rows is not None:
+        assert epilogue == L.EPI_BIAS_DROP_RES and rng_rows.dtype == torch.int32 and rng_rows.is_cuda \
+            and rng_rows.is_contiguous() and rng_rows.numel() == M
+        ep.rng_rows = rng_rows.data_ptr()
     if out8 is not None:
         assert epilogue in (L.EPI_BIAS_GELUQ, L.EPI_MULQ) and out8.dtype == torch.uint8 and out8.shape == (M, N) and out8.stride(1) == 1
         ep.out8, ep.ld_out8, ep.out8_bf8 = out8.data_ptr(), out8.stride(0), 1 if out8_bf8 else 0
@@ -271,18 +278,22 @@ def layernorm_fwd(x, gamma, beta, rowmask=None, eps=1e-12):
 
 
 def layernorm_bwd(dy_a, dy_b, x, gamma, mean, rstd, rowmask, dgamma, dbeta, dbias_drop=None,
-                  want_drop=False, seed=0, p_drop=0.0):
+                  want_drop=False, seed=0, p_drop=0.0, rng_rows=None):
     """Returns (dx, dx_drop).  dx_drop is dx pushed through the residual-branch dropout
-    (None unless want_drop).  dgamma/dbeta/dbias_drop are accumulated in place (fp32)."""
+    (None unless want_drop).  dgamma/dbeta/dbias_drop are accumulated in place (fp32).
+    rng_rows: int32 [rows], the rows' numbers in the full tensor the dropout stream is indexed by (see gemm_nt)."""
     _chk_bf16(dy_a, dy_b, x)
     rows, d = x.shape
+    if rng_rows is not None:
+        assert rng_rows.dtype == torch.int32 and rng_rows.is_cuda and rng_rows.is_contiguous() and rng_rows.numel() == rows
     dx = torch.empty_like(x)
     dx_drop = torch.empty_like(x) if want_drop else None
-    rc = L.load().m3p_layernorm_bwd(dy_a.data_ptr(), L.ptr(dy_b), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
-                                    rstd.data_ptr(), L.ptr(rowmask), dx.data_ptr(), L.ptr(dx_drop),
-                                    dgamma.data_ptr(), dbeta.data_ptr(), L.ptr(dbias_drop), rows, d, seed,
-                                    L.thresh24(p_drop), 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
-    L.check(rc, 'm3p_layernorm_bwd')
+    rc = L.load().m3p_layernorm_bwd_rows(dy_a.data_ptr(), L.ptr(dy_b), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                                         rstd.data_ptr(), L.ptr(rowmask), dx.data_ptr(), L.ptr(dx_drop),
+                                         dgamma.data_ptr(), dbeta.data_ptr(), L.ptr(dbias_drop), rows, d, seed,
+                                         L.thresh24(p_drop), 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0,
+                                         L.ptr(rng_rows), L.stream())
+    L.check(rc, 'm3p_layernorm_bwd_rows')
     return dx, dx_drop
 
 
@@ -568,6 +579,21 @@ def scatter_add_token_rows(rows, ids, dst, pad_index):
 def gather_rows(src_base, idx, n, d):
     out = torch.empty((n, d), dtype=BF16, device=idx.device)
     L.check(L.load().m3p_gather_rows(src_base.data_ptr(), idx.data_ptr(), out.data_ptr(), n, d, L.stream()), 'm3p_gather_rows')
+    return out
+
+
+BF16_NAN_BITS = 0x7FC0
+
+
+def place_rows(src, inv, rows, fill_bits=0):
+    """[rows, d] bf16 = src[inv[r]] where inv[r] >= 0 (src [n, d]), else the bit pattern fill_bits (0, or BF16_NAN_BITS):
+    a fill and a row scatter written in one pass.  inv int32 [rows] = the inverse of the row list src was gathered by."""
+    _chk_bf16(src)
+    n, d = src.shape
+    assert src.is_contiguous() and inv.dtype == torch.int32 and inv.is_cuda and inv.is_contiguous() and inv.numel() == rows
+    out = torch.empty((rows, d), dtype=BF16, device=src.device)
+    L.check(L.load().m3p_place_rows(src.data_ptr(), inv.data_ptr(), out.data_ptr(), rows, d, n, int(fill_bits), L.stream()),
+            'm3p_place_rows')
     return out
 
 

@@ -725,6 +725,17 @@ class XTrainer(Trainer):
         y = _labels[_labels > 0]
         return y, pred_mask
 
+    @staticmethod
+    def _output_rows(B, R, T, pred_mask, region_labels):
+        """functional.OutputRows of a joint pass whose heads read the first row of every sequence, the True entries of
+        ``pred_mask`` (T, B) and the regions with ``region_labels`` (B, R) != -1 - or None where a mask is not a host
+        tensor (reading it would synchronise with the device: the pass then computes every row)."""
+        for t in (pred_mask, region_labels):
+            if t is not None and not (torch.is_tensor(t) and not t.is_cuda):
+                return None
+        from . import functional as Fn
+        return Fn.OutputRows.from_masks(B, R + T, R, pred_mask=pred_mask, region_labels=region_labels)
+
     def _itm_loss(self, relation_scores, pos_labels):
         """xtrainer.py:2357-2372 kept on the device: CE over groups of sample_n + BCE vs one-hot."""
         params = self.params
@@ -975,11 +986,15 @@ class XTrainer(Trainer):
         mlm_on, mrm_on, mrfr_on = (len(getattr(params, k)) > 0 for k in ('cross_mlm_steps', 'cross_mrm_steps', 'cross_mrfr_steps'))
         self._dp_plan(mlm_on, expect=[h for h, on in (('mlm', mlm_on), ('mrm', mrm_on), ('mrfr', mrfr_on)) if on])
         has_mlm = mlm_on and int(y_text.numel()) > 0
+        # the rows of the encoder output this step's heads read (masked tokens, masked regions, the first row of every
+        # sequence), from the host-side masks: the encoder computes its last layer's row-wise part on them alone
+        out_rows = self._output_rows(x1.shape[1], x_img.shape[0], x1.shape[0], pred_mask_text if has_mlm else None,
+                                     obj_labels if (mrm_on or mrfr_on) else None)
         x1, len1, x_img, img_loc, img_len, y_text, pred_mask_text = to_cuda(
             x1, len1, x_img, img_loc, img_len, y_text, pred_mask_text)
 
         encoder_outputs = model('jointfwd', x=x1, lengths=len1, x_img=x_img, lengths_img=img_len, causal=False,
-                                langs=None, image_loc=img_loc, refine_image=params.refine_image)
+                                langs=None, image_loc=img_loc, refine_image=params.refine_image, out_rows=out_rows)
         total_loss = None
         R = x_img.shape[0]
         _text_out = encoder_outputs[R:]
@@ -1006,7 +1021,8 @@ class XTrainer(Trainer):
         if task_name == 'i2t' and len(params.cross_clcm_steps) > 0:        # xtrainer.py:2379-2393
             x2c, len2c = to_cuda(x2, len2)
             encoder_outputs2 = model('jointfwd', x=x2c, lengths=len2c, x_img=x_img, lengths_img=img_len, causal=False,
-                                     langs=None, image_loc=img_loc, refine_image=params.refine_image)
+                                     langs=None, image_loc=img_loc, refine_image=params.refine_image,
+                                     out_rows=self._output_rows(x2c.shape[1], x_img.shape[0], x2c.shape[0], None, None))
             relation_scores2 = model('predict', tensor=encoder_outputs2.transpose(0, 1), is_clcm=True)
             target2 = torch.as_tensor(clcm_labels).reshape(-1).to(device=relation_scores2.device, dtype=torch.float32)
             loss = F.binary_cross_entropy_with_logits(relation_scores2.view(-1).float(), target2)

@@ -20,11 +20,17 @@
 // The epilogue runs from a private 4.5-KB staging area per wave; the loads of the next
 // output tile are already in flight under it.
 // ---------------------------------------------------------------------------------
-template <int EPI>
+// EPIX = the epilogue, or M3P_EPI_DROP_RES_ROWS: BIAS_DROP_RES that reads M3PEpilogue::rng_rows.  The lookup is compiled
+// into that instantiation alone: a uniform branch on the pointer in front of each pipelined piece brought the compiler's
+// wait for all vector memory operations with it - the previous piece's stores included - and cost every launch WITHOUT a
+// map 7-10 us of 168 (profiles/last_layer_rows_ab.txt)
+template <int EPIX>
 __global__ __launch_bounds__(256)
 void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
                        bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
                        int tiles_m, int tiles_n, int m_fast) {
+  constexpr bool kRows = (EPIX == M3P_EPI_DROP_RES_ROWS);
+  constexpr int EPI = kRows ? (int)M3P_EPI_BIAS_DROP_RES : EPIX;
   constexpr int BM = 256, BN = 256, KT = 64;
   constexpr int A_BYTES = BM * KT * 2, STAGE = (BM + BN) * KT * 2;     // 32 KB, 64 KB
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -249,7 +255,7 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
           load_aux_rows_finish<EPI, true, true>(lane, rc, tq, aux_cur);
           if (p + 1 < 8) load_aux_rows_issue<EPI>(ep, mw + 32 * ((p + 1) & 3), nw + 64 * ((p + 1) >> 2), lane, tq);
           bf16x4 ukeep[2][4];
-          epilogue_half_write<EPI, true, true>(ep, N, mw + 32 * rg, nw + 64 * ch, rc, rows, ch ? bias_hi : bias_lo, aux_cur, lane, csum, ukeep);
+          epilogue_half_write<EPI, true, true, !kRows>(ep, N, mw + 32 * rg, nw + 64 * ch, rc, rows, ch ? bias_hi : bias_lo, aux_cur, lane, csum, ukeep);
           // (read back at once: straight-line code between the asm reads and their wait, so that no compiler-made copy of the
           //  destination registers can slip in between; what the asm accesses buy is the absence of vmcnt(0) - the stores of
           //  piece p are in flight under piece p + 1)
