@@ -385,6 +385,18 @@ M3P_API int m3p_ce_fwd_bwd_colsum(void* logits, int ld, int n_rows, int V, const
                                   float* row_lse, float grad_scale, float* colsum, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* Validation scoring in one read-only pass over bf16 logits [n_rows, ld] (V valid columns): what the reference's evaluators take
+ * from predict(..., get_scores=True) per batch - `loss.item() * len(y)` and `(word_scores.max(1)[1] == y).sum()`
+ * (evaluation/xevaluator.py:433-438, :530-535, :654-659, :757-762, :861-866, :1165-1170; evaluator.py:240-270).
+ *   row_loss[r]   = logsumexp(logits[r, :V]) - logits[r, target[r]]                          (fp32)
+ *   row_argmax[r] = the LOWEST column c < V at which row r's maximum is attained              (int32)
+ * Columns [V, ld) may hold anything (the ragged projection leaves them unwritten): they enter neither the maximum, the sum
+ * nor the argmax.  The logits are not written.  No atomics: the caller reduces the per-row outputs.
+ * Preconditions of m3p_ce_fwd_bwd: ld % 8 == 0, ld >= V, logits 16-byte aligned, 0 <= target[r] < V; M3P_EINVAL otherwise
+ * (the targets are not inspected). */
+M3P_API int m3p_ce_eval(const void* logits, int ld, int n_rows, int V, const int64_t* target, float* row_loss,
+                        int32_t* row_argmax, void* stream);
+
 /* out[c] += scale * sum_r x[r,c] for c < ncols (x bf16 [n, ld]); scale read from the
  * device scalar *scale_ptr (NULL = 1): the vocabulary-bias gradient colsum(dlogits). */
 M3P_API int m3p_colsum_bf16(const void* x, int ld, int n, int ncols, float* out, const float* scale_ptr,

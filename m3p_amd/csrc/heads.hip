@@ -203,6 +203,69 @@ __device__ __forceinline__ void lse_fold(float& m, float& s, float m2, float s2)
   m = mm;
   s = a + b;
 }
+// ---- validation scoring (xevaluator.py: `loss.item() * len(y)` and `(word_scores.max(1)[1] == y).sum()` per batch): ONE
+// read-only pass over the logits gives every row's loss AND its argmax - ce_stats_kernel's stream (one 1024-thread block per
+// row, 16-byte loads, online (max, sum) rescaled once per 8 logits) with the column of the maximum carried beside it.
+// The argmax contract is the LOWEST column c < V at which the row's maximum is attained (max(1)[1] leaves ties open on a
+// GPU).  It holds at every fold: a thread visits its chunks in rising column order and replaces its index only on a strictly
+// larger value; lanes, then waves, fold (value, index) pairs with "larger value, or equal value and lower index".
+// Columns [V, ld) are replaced by -inf before anything looks at them and can never supply the index.
+constexpr int CE_NO_COL = 0x7fffffff;
+__device__ __forceinline__ void argmax_fold(float m, int& i, float m2, int i2) {
+  if (m2 > m || (m2 == m && i2 < i)) i = i2;     // (m itself is folded by the caller: fmaxf / lse_fold)
+}
+__global__ __launch_bounds__(1024) void ce_eval_kernel(const bf16* __restrict__ logits, int ld, int V, const int64_t* __restrict__ target,
+                                                       float* __restrict__ row_loss, int32_t* __restrict__ row_argmax) {
+  __shared__ float s_m[16], s_s[16];
+  __shared__ int s_i[16];
+  constexpr float kLog2e = 1.4426950408889634f;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
+  const bf16* lr = logits + (size_t)row * ld;
+  const int nchunk = ld >> 3;
+  float m = -INFINITY, s = 0.f;               // running max and sum of exp(x - m); bi = lowest column holding m
+  int bi = CE_NO_COL;
+  for (int c = tid; c < nchunk; c += 1024) {
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(lr + 8 * c);
+    float x[8];
+    float gm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x[j] = (8 * c + j < V) ? (float)v[j] : -INFINITY;
+      gm = fmaxf(gm, x[j]);
+    }
+    if (gm > m) {                              // rare after the first few groups
+      int jj = 7;
+#pragma unroll
+      for (int j = 6; j >= 0; --j) jj = (x[j] == gm) ? j : jj;       // lowest column of the group's maximum (never a pad column: those are -inf)
+      bi = 8 * c + jj;
+      s *= __builtin_amdgcn_exp2f((m - gm) * kLog2e);
+      m = gm;
+    }
+    const float mb = m * kLog2e;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += __builtin_amdgcn_exp2f(__builtin_fmaf(x[j], kLog2e, -mb));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    const int i2 = __shfl_xor(bi, o, 64);
+    argmax_fold(m, bi, m2, i2);
+    lse_fold(m, s, m2, s2);
+  }
+  if (lane == 0) { s_m[wib] = m; s_s[wib] = s; s_i[wib] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    float M = s_m[0], Ssum = s_s[0];
+    int I = s_i[0];
+    for (int w = 1; w < 16; ++w) {
+      argmax_fold(M, I, s_m[w], s_i[w]);
+      lse_fold(M, Ssum, s_m[w], s_s[w]);
+    }
+    row_loss[row] = M + __logf(Ssum) - (float)lr[target[row]];
+    row_argmax[row] = (I == CE_NO_COL) ? 0 : I;      // (a row of -inf: its maximum sits at column 0 too)
+  }
+}
+
 __global__ __launch_bounds__(256) void ce_lse_partial_kernel(const float2* __restrict__ stats, int n_blocks, int n_rows,
                                                              float2* __restrict__ part) {
   __shared__ float2 sh[4][64];
@@ -424,6 +487,15 @@ int m3p_ce_fwd_bwd(void* logits, int ld, int n_rows, int V, const int64_t* targe
   if (n_rows <= 0 || V <= 0 || ld < V || (ld % 8) != 0 || ((uintptr_t)logits & 15)) return M3P_EINVAL;
   hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(n_rows), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, V, target,
                      row_loss, loss_sum, loss_scale, grad_scale);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_ce_eval(const void* logits, int ld, int n_rows, int V, const int64_t* target, float* row_loss, int32_t* row_argmax, void* stream) {
+  if (n_rows <= 0 || V <= 0 || ld < V || (ld % 8) != 0 || !logits || ((uintptr_t)logits & 15) || !target || !row_loss || !row_argmax)
+    return M3P_EINVAL;
+  hipLaunchKernelGGL(ce_eval_kernel, dim3(n_rows), dim3(1024), 0, (hipStream_t)stream, (const bf16*)logits, ld, V, target, row_loss,
+                     row_argmax);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }

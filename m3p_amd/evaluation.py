@@ -14,12 +14,23 @@ Differences from the reference, on purpose:
 Valid-set matching accuracy (``evaluate_t2i`` / ``evaluate_i2t`` / ``evaluate_understanding_tasks``,
 xevaluator.py:1262-1417): each dataset item contributes ``sample_n`` (text, image) sequences, one of them the true
 pair; a group counts as correct when its highest relation score sits on ``pos_labels``.
+
+Valid-set perplexity and accuracy of the language-model objectives (``evaluate_mlm`` evaluator.py:240-270 / xevaluator.py:389-446,
+``evaluate_mass`` :493-539, ``evaluate_mt`` :604-677, ``evaluate_ic`` :696-780, ``evaluate_mt_ic`` :799-884, ``evaluate_ntg``
+:1119-1175) and ``run_all_evals`` (:120-235): the reference's batches and score keys, with the evaluator's own seeded masking
+(``eval_mask_out`` :89-118, ``eval_mask_sent`` :541-602).  Per batch the reference reads ``loss.item() * len(y)`` and
+``(word_scores.max(1)[1] == y).sum().item()`` back to the host; here ``predict_stats`` leaves both on the device, they are
+summed there, and a data set costs ONE host read.  Ties of the maximum count for the lowest word id (the reference leaves them
+open).  Not built: ``evaluate_clm``, the ``eval_bleu`` branches (hypothesis files, BLEU scripts), ``evaluate_slide`` and the
+test-set captioning generators.
 """
+from collections import OrderedDict
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from .utils import to_cuda
+from .utils import concat_batches, to_cuda
 
 
 @torch.no_grad()
@@ -159,4 +170,307 @@ def evaluate_understanding_tasks(model, params, iterator, scores, data_set, lang
         i2t_acc, i2t_n = i2t_acc + a, i2t_n + n
     scores['%s_%s-%s_rel_t2i_acc' % (data_set, lang1, lang2)] = 100. * t2i_acc / t2i_n
     scores['%s_%s-%s_rel_i2t_acc' % (data_set, lang1, lang2)] = 100. * i2t_acc / i2t_n
+    return scores
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# perplexity / accuracy of the language-model objectives
+# ---------------------------------------------------------------------------------------------------------------------
+def eval_mask_out(x, lengths, params, rng):
+    """The evaluator's word selection (xevaluator.py:89-118; NOT the trainer's ``masking.mask_out``): Bernoulli(word_pred)
+    per position from ``rng`` (a ``RandomState`` the caller seeds once per data set, so every epoch scores the same
+    words), never the first row nor a sentence's last symbol or padding; a sentence left without a target gets one at
+    ``rng.randint(1, len - 1)``.  Every selected word becomes <mask>.  -> (x, original ids, bool mask (slen, bs))."""
+    slen, bs = x.size()
+    sel = rng.rand(slen, bs) <= params.word_pred
+    sel[0] = 0
+    for i, n in enumerate(lengths.tolist()):
+        sel[n - 1:, i] = 0
+        if not sel[:n - 1, i].any():
+            sel[rng.randint(1, n - 1), i] = 1
+    pred_mask = torch.from_numpy(sel.astype(np.uint8)).bool()
+    real = x[pred_mask]
+    x = x.masked_fill(pred_mask, params.mask_index)
+    assert 0 <= int(x.min()) and int(x.max()) < params.n_words
+    return x, real, pred_mask
+
+
+def eval_mask_sent(x, lengths, params, rng):
+    """The evaluator's MASS span (xevaluator.py:541-602): per sentence of l symbols a span of max(1, round(l * word_mass) - 1)
+    of them starting at 1 (p >= 0.8), at the latest start (p >= 0.6) or anywhere between; inside it the encoder input
+    shows <mask> (p >= 0.2), a random word (p >= 0.05) or the word itself; the decoder reads the word BEFORE each hidden
+    one at that word's position.  RNG order: per sentence the start's draws, then one or two draws per hidden word.
+    -> (x1, len1, x2, len2, y, pred_mask, positions)."""
+    pad = params.pad_index
+    bs = lengths.size(0)
+    inputs, prevs, outs, poss = [], [], [], []
+    for i in range(bs):
+        words = x[:lengths[i], i].tolist()
+        n = len(words)
+        span = max(1, round(n * params.word_mass) - 1)
+        end = n - span + 1
+        p = rng.rand()
+        start = 1 if p >= 0.8 else (end - 1 if p >= 0.6 else rng.randint(1, end))
+        shown = list(words)
+        for j in range(start, min(start + span, n)):
+            p = rng.rand()
+            shown[j] = params.mask_index if p >= 0.2 else (rng.randint(params.n_words) if p >= 0.05 else words[j])
+        hidden = range(start, min(start + span, n))
+        inputs.append(shown)
+        outs.append([words[j] for j in hidden])
+        prevs.append([words[j - 1] for j in hidden])
+        poss.append([j - 1 for j in hidden])
+    len1 = lengths.clone()
+    len2 = torch.LongTensor([len(o) for o in outs])
+    x1 = torch.full((int(len1.max()), bs), pad, dtype=torch.long)
+    x2, y, pos = (torch.full((int(len2.max()), bs), pad, dtype=torch.long) for _ in range(3))
+    for i in range(bs):
+        x1[:len1[i], i] = torch.LongTensor(inputs[i])
+        x2[:len2[i], i] = torch.LongTensor(prevs[i])
+        y[:len2[i], i] = torch.LongTensor(outs[i])
+        pos[:len2[i], i] = torch.LongTensor(poss[i])
+    pred_mask = y != pad
+    return x1, len1, x2, len2, y.masked_select(pred_mask), pred_mask, pos
+
+
+def _host_read(t):
+    """The ONE device-to-host read of an evaluated data set (tests count the calls)."""
+    return t.tolist()
+
+
+class _LMStats:
+    """Sums of the batches' (loss_sum, n_correct) kept where ``predict_stats`` left them - device scalars - and the word
+    count, which the host knows (len(y))."""
+
+    def __init__(self):
+        self.xe = self.ok = None
+        self.n = 0
+
+    def add(self, loss_sum, n_correct, n):
+        self.xe = loss_sum.double() if self.xe is None else self.xe + loss_sum.double()
+        self.ok = n_correct.long() if self.ok is None else self.ok + n_correct.long()
+        self.n += int(n)
+
+    def write(self, scores, ppl_name, acc_name, empty=None):
+        """np.exp(xe_loss / n_words), 100 * n_valid / n_words under the reference's keys; ``empty``: the (ppl, acc) of a data
+        set without a word (evaluate_mlm only: the others divide)."""
+        if self.n == 0 and empty is not None:
+            scores[ppl_name], scores[acc_name] = empty
+            return scores
+        xe, ok = _host_read(torch.stack([self.xe, self.ok.double()]))     # (a count is exact in fp64 below 2^53)
+        scores[ppl_name] = float(np.exp(xe / self.n))
+        scores[acc_name] = 100. * int(round(ok)) / self.n
+        return scores
+
+
+class _eval_mode:
+    """``model.module`` if wrapped, in eval mode; training mode restored on exit if it was on."""
+
+    def __init__(self, model):
+        self.model = getattr(model, 'module', model)
+
+    def __enter__(self):
+        self.was_training = self.model.training
+        self.model.eval()
+        return self.model
+
+    def __exit__(self, *exc):
+        if self.was_training:
+            self.model.train()
+        return False
+
+
+def _next_word_targets(x2, len2):
+    """Predict word t + 1 from position t, nothing from a sentence's last word (xevaluator.py:636-640)."""
+    alen = torch.arange(int(len2.max()), dtype=torch.long, device=len2.device)
+    pred_mask = alen[:, None] < len2[None] - 1
+    y = x2[1:].masked_select(pred_mask[:-1])
+    assert len(y) == int((len2 - 1).sum())
+    return pred_mask, y
+
+
+def _decode_and_score(model, stats, enc1, len1, x2, len2, langs2, pred_mask, y, **kw):
+    dec2 = model('crossfwd', stream_='text', x=x2, lengths=len2, langs=langs2, causal=True, src_enc=enc1, src_len=len1, **kw)
+    stats.add(*model('predict_stats', tensor=dec2, pred_mask=pred_mask, y=y))
+
+
+@torch.no_grad()
+def evaluate_mlm(model, params, iterator, scores, data_set, lang1, lang2):
+    """xevaluator.py:389-446: masked-word perplexity and accuracy on the monolingual stream (``lang2 is None``, batches
+    (x, lengths)) or on TLM pairs (batches ((x1, len1), (x2, len2)) joined with reset positions), the same words every
+    call (RandomState(0))."""
+    assert data_set in ('valid', 'test')
+    assert lang1 in params.langs and (lang2 is None or lang2 in params.langs)
+    rng = np.random.RandomState(0)
+    lang1_id = params.lang2id[lang1]
+    lang2_id = params.lang2id[lang2] if lang2 is not None else None
+    stats = _LMStats()
+    with _eval_mode(model) as m:
+        for batch in iterator:
+            if lang2 is None:
+                x, lengths = batch
+                positions = None
+                langs = x.clone().fill_(lang1_id) if params.n_langs > 1 else None
+            else:
+                (sent1, len1), (sent2, len2) = batch
+                x, lengths, positions, langs = concat_batches(sent1, len1, lang1_id, sent2, len2, lang2_id, params.pad_index,
+                                                              params.eos_index, reset_positions=True)
+            x, y, pred_mask = eval_mask_out(x, lengths, params, rng)
+            x, y, pred_mask, lengths, positions, langs = to_cuda(x, y, pred_mask, lengths, positions, langs)
+            tensor = m('crossfwd', stream_='text', x=x, lengths=lengths, positions=positions, langs=langs, causal=False)
+            stats.add(*m('predict_stats', tensor=tensor, pred_mask=pred_mask, y=y))
+    name = '%s_%s' % (data_set, lang1) if lang2 is None else '%s_%s-%s' % (data_set, lang1, lang2)
+    return stats.write(scores, name + '_mlm_ppl', name + '_mlm_acc', empty=(1e9, 0.))
+
+
+@torch.no_grad()
+def evaluate_mass(model, params, iterator, scores, data_set, lang1, lang2=None):
+    """xevaluator.py:493-539: the hidden span of ``eval_mask_sent`` decoded over the masked sentence; the decoder may not
+    look at the source's <mask> positions (``enc_mask``) and reads its inputs at their original positions."""
+    assert data_set in ('valid', 'test') and lang1 in params.langs
+    rng = np.random.RandomState(0)
+    lang_id = params.lang2id[lang1]
+    stats = _LMStats()
+    with _eval_mode(model) as m:
+        for x1, len1 in iterator:
+            x1, len1, x2, len2, y, pred_mask, positions = eval_mask_sent(x1, len1, params, rng)
+            langs1, langs2 = x1.clone().fill_(lang_id), x2.clone().fill_(lang_id)
+            enc_mask = x1.ne(params.mask_index).transpose(0, 1)
+            x1, len1, langs1, x2, len2, langs2, y, positions, pred_mask, enc_mask = to_cuda(
+                x1, len1, langs1, x2, len2, langs2, y, positions, pred_mask, enc_mask)
+            enc1 = m('crossfwd', stream_='text', x=x1, lengths=len1, langs=langs1, causal=False).transpose(0, 1)
+            _decode_and_score(m, stats, enc1, len1, x2, len2, langs2, pred_mask, y, positions=positions, enc_mask=enc_mask)
+    name = '%s_%s-%s' % (data_set, lang1, lang1)
+    return stats.write(scores, name + '_mass_ppl', name + '_mass_acc')
+
+
+def _evaluate_text_pair(model, params, iterator, stats, lang1_id, lang2_id):
+    """The loop evaluate_mt and evaluate_ntg share: source sentence encoded, target teacher-forced over it."""
+    with _eval_mode(model) as m:
+        for (x1, len1), (x2, len2) in iterator:
+            langs1, langs2 = x1.clone().fill_(lang1_id), x2.clone().fill_(lang2_id)
+            pred_mask, y = _next_word_targets(x2, len2)
+            x1, len1, langs1, x2, len2, langs2, y, pred_mask = to_cuda(x1, len1, langs1, x2, len2, langs2, y, pred_mask)
+            enc1 = m('crossfwd', stream_='text', x=x1, lengths=len1, langs=langs1, causal=False).transpose(0, 1)
+            _decode_and_score(m, stats, enc1, len1, x2, len2, langs2, pred_mask, y)
+
+
+@torch.no_grad()
+def evaluate_mt(model, params, iterator, scores, data_set, lang1, lang2):
+    """xevaluator.py:604-677 without the BLEU branch: next-word perplexity and accuracy of the translation lang1 -> lang2."""
+    assert data_set in ('valid', 'test') and lang1 in params.langs and lang2 in params.langs
+    stats = _LMStats()
+    _evaluate_text_pair(model, params, iterator, stats, params.lang2id[lang1], params.lang2id[lang2])
+    name = '%s_%s-%s' % (data_set, lang1, lang2)
+    return stats.write(scores, name + '_mt_ppl', name + '_mt_acc')
+
+
+@torch.no_grad()
+def evaluate_ntg(model, params, iterator, scores, data_set, lang1, lang2=None):
+    """xevaluator.py:1119-1175: text-to-text generation pairs of one language (both sides carry lang1's id)."""
+    assert data_set in ('valid', 'test')
+    stats = _LMStats()
+    _evaluate_text_pair(model, params, iterator, stats, params.lang2id[lang1], params.lang2id[lang1])
+    return stats.write(scores, '%s_%s_NTG_ppl' % (data_set, lang1), '%s_%s_NTG_acc' % (data_set, lang1))
+
+
+@torch.no_grad()
+def evaluate_ic(model, params, iterator, scores, data_set, lang1, lang2):
+    """xevaluator.py:696-780 without the BLEU branch: captions decoded over the image-only encoder stream.  Batches
+    ((x2, len2, _), (x1, x1_mask, img_loc, img_id)) as caption_collate emits them; the language id of both streams is
+    ``ft_lgs[0]``'s, or 'en' without fine-tuning languages."""
+    assert data_set in ('valid', 'test')
+    ft_lgs = getattr(params, 'ft_lgs', [])
+    lang_id = params.lang2id[ft_lgs[0] if len(ft_lgs) > 0 else 'en']
+    stats = _LMStats()
+    with _eval_mode(model) as m:
+        for (x2, len2, _), (x1, x1_mask, img_loc, _ids) in iterator:
+            langs = x2.clone().fill_(lang_id)
+            pred_mask, y = _next_word_targets(x2, len2)
+            len1 = x1_mask.sum(dim=1)
+            x1, img_loc = x1.transpose(0, 1), img_loc.transpose(0, 1)
+            langs_img = x1_mask.transpose(0, 1).clone().fill_(lang_id)
+            x1, len1, img_loc, x2, len2, y, langs, langs_img, pred_mask = to_cuda(x1, len1, img_loc, x2, len2, y, langs, langs_img,
+                                                                                  pred_mask)
+            enc1 = m('crossfwd', stream_='img', x=x1, lengths=len1, langs=langs_img, causal=False, cross_modal=True,
+                     image_loc=img_loc, image_dist=None).transpose(0, 1)
+            _decode_and_score(m, stats, enc1, len1, x2, len2, langs, pred_mask, y)
+    name = '%s_%s-%s' % (data_set, lang1, lang2)
+    return stats.write(scores, name + '_IC_ppl', name + '_IC_acc')
+
+
+@torch.no_grad()
+def evaluate_mt_ic(model, params, iterator, scores, data_set, lang1, lang2):
+    """xevaluator.py:799-884 without the BLEU branch: the target decoded over jointfwd(regions | source words) - or, with
+    ``mt_only_text``, over the source's text stream alone.  Batches ((x_src, src_len, _), (x2, len2, _), (x1, x1_mask,
+    img_loc, img_id)) as mt_caption_collate emits them; languages ``ft_lgs[0]`` -> ``ft_lgs[1]``.  Same keys as evaluate_ic."""
+    assert data_set in ('valid', 'test')
+    src_id, tgt_id = params.lang2id[params.ft_lgs[0]], params.lang2id[params.ft_lgs[1]]
+    refine = getattr(params, 'refine_image', False)
+    stats = _LMStats()
+    with _eval_mode(model) as m:
+        for (x_src, src_len, _), (x2, len2, _), (x1, x1_mask, img_loc, _ids) in iterator:
+            lang_src, langs = x_src.clone().fill_(src_id), x2.clone().fill_(tgt_id)
+            pred_mask, y = _next_word_targets(x2, len2)
+            len1 = x1_mask.sum(dim=1)
+            x1, img_loc = x1.transpose(0, 1), img_loc.transpose(0, 1)
+            x1, len1, img_loc, x2, len2, y, langs, lang_src, x_src, src_len, pred_mask = to_cuda(
+                x1, len1, img_loc, x2, len2, y, langs, lang_src, x_src, src_len, pred_mask)
+            if getattr(params, 'mt_only_text', False):
+                enc = m('crossfwd', stream_='text', x=x_src, lengths=src_len, langs=lang_src, causal=False, refine_image=refine)
+                len_all = src_len
+            else:
+                enc = m('jointfwd', x=x_src, lengths=src_len, x_img=x1, lengths_img=len1, causal=False, langs=None,
+                        image_loc=img_loc, refine_image=refine)
+                len_all = len1 + src_len
+            _decode_and_score(m, stats, enc.transpose(0, 1), len_all, x2, len2, langs, pred_mask, y)
+    name = '%s_%s-%s' % (data_set, lang1, lang2)
+    return stats.write(scores, name + '_IC_ppl', name + '_IC_acc')
+
+
+def run_all_evals(model, params, get_iterator, epoch):
+    """The scores ``Trainer.save_best_model`` / ``end_epoch`` consume, after every epoch: xevaluator.py:120-235 for the tasks
+    built here plus evaluator.py:250-252's ``evaluate_mlm`` over ``params.mlm_steps``, on the 'valid' split.
+    ``get_iterator(data_set, lang1, lang2)`` is the caller's (``XTrainer.get_iterator`` fits): ``lang2`` is None for the
+    monolingual sets (MLM stream, MASS sentences), the second language for pairs, and ``lang1`` again for the text-to-text
+    pairs of ``evaluate_ntg`` (both sides in one language).  Only the master rank evaluates: the others return
+    {'epoch': epoch}."""
+    scores = OrderedDict({'epoch': epoch})
+    g = lambda name, default: getattr(params, name, default)       # noqa: E731
+    if g('is_master', True) is False:
+        return scores
+    data_set = 'valid'
+    for lang1, lang2 in g('mlm_steps', []):
+        evaluate_mlm(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
+    mass = list(g('mass_steps', []))
+    for lang in mass:
+        evaluate_mass(model, params, get_iterator(data_set, lang, None), scores, data_set, lang)
+    pairs = list(g('mt_steps', [])) + [(l2, l3) for _, l2, l3 in g('bt_steps', [])] + [(a, b) for a in mass for b in mass if a != b]
+    for lang1, lang2 in sorted(set(pairs)):
+        evaluate_mt(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
+    if g('is_ntg', False):
+        for lang1, _ in g('text_steps', []):
+            evaluate_ntg(model, params, get_iterator(data_set, lang1, lang1), scores, data_set, lang1)
+    if g('is_generation', False):
+        fn = evaluate_mt_ic if g('is_mt', False) else evaluate_ic
+        for lang1, lang2 in sorted(set(g('cross_modal_steps', []))):
+            fn(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
+    rel = list(g('cross_rel_steps', []))
+    if g('is_understanding', False) and not g('is_slide', False):
+        for lang1, lang2 in sorted(set(rel)):
+            evaluate_understanding_tasks(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
+    # averages per task
+    mono = [l1 for l1, l2 in g('mlm_steps', []) if l2 is None]
+    if mono:
+        scores['%s_mlm_ppl' % data_set] = np.mean([scores['%s_%s_mlm_ppl' % (data_set, l)] for l in mono])
+        scores['%s_mlm_acc' % data_set] = np.mean([scores['%s_%s_mlm_acc' % (data_set, l)] for l in mono])
+    if mass:
+        scores['%s_mass_ppl' % data_set] = np.mean([scores['%s_%s-%s_mass_ppl' % (data_set, l, l)] for l in mass])
+        scores['%s_mass_acc' % data_set] = np.mean([scores['%s_%s-%s_mass_acc' % (data_set, l, l)] for l in mass])
+    if rel and g('is_understanding', False) and not g('is_slide', False):
+        # (the reference's own pairing, :226-234: t2i_flag publishes the i2t accuracies as I2T, i2t_flag the t2i ones as T2I)
+        if g('t2i_flag', False):
+            scores['%s_I2T_acc' % data_set] = np.mean([scores['%s_%s-%s_rel_i2t_acc' % (data_set, a, b)] for a, b in rel])
+        if g('i2t_flag', False):
+            scores['%s_T2I_acc' % data_set] = np.mean([scores['%s_%s-%s_rel_t2i_acc' % (data_set, a, b)] for a, b in rel])
     return scores

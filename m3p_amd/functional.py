@@ -1601,11 +1601,11 @@ class ItmLossFn(torch.autograd.Function):
         return d.view(shape).to(dtype), None, None, None, None
 
 
-def mlm_head(model, tensor, pred_mask, y, want_scores):
+def _mlm_rows(model, tensor, pred_mask, y):
     """Resolve ``tensor`` (T,B,d) — normally the view ``encoder_out[R:]`` — to rows of its
     underlying contiguous [rows, d] buffer, so the gather reads the activation in place.
     (The reference's host-side ``assert (y == pad).sum().item() == 0`` (:108) is a device
-    sync per step and is not reproduced.)"""
+    sync per step and is not reproduced.)  -> (tensor, base, int32 rows of the True entries of pred_mask, n)."""
     d = model.dim
     assert tensor.dim() == 3 and tensor.shape[-1] == d and tensor.dtype == BF16, \
         'predict() expects the bf16 encoder output (T, B, d)'
@@ -1628,6 +1628,64 @@ def mlm_head(model, tensor, pred_mask, y, want_scores):
         pm = pm != 0
     # rows of the True entries in (t, b) order: one compaction launch, no host sync (the count is y's length)
     row_idx = ops.mask_to_rows(pm.contiguous(), B, s0, s1, soff, d, n)
+    return tensor, base, row_idx, n
+
+
+def mlm_head(model, tensor, pred_mask, y, want_scores):
+    """predict() default branch on the rows ``_mlm_rows`` resolves."""
+    tensor, base, row_idx, n = _mlm_rows(model, tensor, pred_mask, y)
     scores_out = [] if want_scores else None
     loss = MLMHeadFn.apply(tensor, model, base, row_idx, y.to(tensor.device), scores_out, _sink_of(tensor, base))
     return loss, (scores_out[0] if want_scores else None)
+
+
+# Validation scoring runs the vocabulary projection on at most this many prediction rows at a time, so the bf16 logits it
+# materialises stay bounded whatever the batch: 4096 rows x V_pad = 250 112 columns x 2 bytes = 2.05 GB at the M3P vocabulary.
+EVAL_CHUNK_ROWS = 4096
+
+
+def _eval_chunks(n):
+    """Row ranges of the scoring chunks: as few as EVAL_CHUNK_ROWS allows, of equal size rounded up to whole 256-row
+    tiles (4864 rows -> 2560 + 2304, both on the full-tile projection, instead of 4096 + a ragged 768)."""
+    k = -(-n // EVAL_CHUNK_ROWS)
+    per = min(_round_up(-(-n // k), 256), EVAL_CHUNK_ROWS)
+    return [(r0, min(n, r0 + per)) for r0 in range(0, n, per)]
+
+
+def mlm_eval_head(model, tensor, pred_mask, y):
+    """What the reference's evaluators take from ``predict(..., get_scores=True)`` (xevaluator.py:433-438 and its siblings):
+    the summed cross-entropy of the predicted rows and the number of rows whose best-scoring word is the target, without
+    the training head's by-products.  Forward only: boolean-mask gather, tied vocabulary projection (plain bias epilogue; the
+    same full-tile / ragged choice as MLMHeadFn) into a bounded bf16 buffer, one read-only pass of ``ops.ce_eval`` per
+    chunk.  No gradient is written, no fp32 copy of the scores is made and nothing is read back to the host.
+    -> (loss_sum 0-d fp64, n_correct 0-d int64 (lowest-index argmax == y), n = len(y)), the first two on the device."""
+    if torch.is_grad_enabled() and model.training:
+        raise NotImplementedError('the scoring head is forward only: call it in eval mode or under torch.no_grad()')
+    with torch.no_grad():
+        tensor, base, row_idx, n = _mlm_rows(model, tensor, pred_mask, y)
+        dev = tensor.device
+        loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+        n_correct = torch.zeros((), dtype=torch.int64, device=dev)
+        if n == 0:
+            return loss_sum, n_correct, 0
+        ar = model.arena()
+        ar.refresh()
+        d, V = model.dim, model.n_words
+        y = y.to(dev).contiguous()
+        hsel = ops.gather_rows(base, row_idx, n, d)
+        chunks = _eval_chunks(n)
+        logits = torch.empty((chunks[0][1], ar.V_pad), dtype=BF16, device=dev)
+        o = ar.offsets['pred_layer.proj.bias'][0]
+        for r0, r1 in chunks:
+            m = r1 - r0
+            full_tiles = _VOCAB_FULL_TILES and m >= 1024 and m % 256 == 0
+            # (whole tiles: the eight-wave kernel over V_pad columns; it reads the bias up to V_pad like the matrix - the
+            #  arena bytes behind it - and ce_eval ignores what lands in columns [V, V_pad))
+            ops.gemm_nt(hsel[r0:r1], ar.w('embeddings.weight'), L.EPI_BIAS,
+                        bias=ar.master[o:o + ar.V_pad] if full_tiles else ar.p('pred_layer.proj.bias'),
+                        out=logits[:m], n=ar.V_pad if full_tiles else V)
+            yc = y[r0:r1]
+            row_loss, row_argmax = ops.ce_eval(logits[:m], V, yc)
+            loss_sum += row_loss.sum(dtype=torch.float64)
+            n_correct += (row_argmax == yc).sum()
+        return loss_sum, n_correct, n

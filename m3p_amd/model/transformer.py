@@ -393,6 +393,8 @@ class TransformerModel(nn.Module):
             return self.jointfwd(**kwargs)
         elif mode == 'predict':
             return self.predict(**kwargs)
+        elif mode == 'predict_stats':
+            return self.predict_stats(**kwargs)
         elif mode == 'crossfwd':
             return self.crossfwd(**kwargs)
         elif mode == 'transform':
@@ -523,6 +525,13 @@ class TransformerModel(nn.Module):
             return Fn.mrfr_dense_rows(self, tensor)
         loss, scores = Fn.mlm_head(self, tensor, pred_mask, y, bool(get_scores))
         return scores, loss
+
+    def predict_stats(self, tensor, pred_mask, y):
+        """Validation scoring of the default ``predict`` branch: (sum of the predicted rows' cross-entropy, number of rows
+        whose best-scoring word - lowest index on ties - is the target, len(y)); the first two are device scalars (fp64,
+        int64).  What the reference's evaluators compute from ``predict(..., get_scores=True)`` (xevaluator.py:433-438),
+        in one pass over the logits and with no host read.  Forward only."""
+        return Fn.mlm_eval_head(self, tensor, pred_mask, y)
 
     def generate(self, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, cross_modal=True):
         """transformer.py:1216-1317 (greedy / sampled decoding)."""

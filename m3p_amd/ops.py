@@ -658,6 +658,20 @@ def ce_from_block_stats(logits, V, target, stats, loss_scale, grad_scale):
     return (row_loss.sum() * loss_scale).reshape(1), row_loss, cs
 
 
+def ce_eval(logits, V, target):
+    """Validation scoring, one read-only pass over bf16 logits [n, ld >= V] (columns [V, ld) ignored): returns
+    (row_loss fp32 [n] = logsumexp - target logit, row_argmax int32 [n] = lowest column of the row's maximum)."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and target.dtype == torch.int64 and target.is_contiguous()
+    n, ld = logits.shape[0], logits.stride(0)
+    assert target.numel() == n and ld >= V
+    row_loss = torch.empty(n, dtype=torch.float32, device=logits.device)
+    row_argmax = torch.empty(n, dtype=torch.int32, device=logits.device)
+    L.check(L.load().m3p_ce_eval(logits.data_ptr(), ld, n, V, target.data_ptr(), row_loss.data_ptr(), row_argmax.data_ptr(),
+                                 L.stream()), 'm3p_ce_eval')
+    return row_loss, row_argmax
+
+
 def colsum(x, ncols, out, scale=None):
     rc = L.load().m3p_colsum_bf16(x.data_ptr(), x.stride(0), x.shape[0], ncols, out.data_ptr(), L.ptr(scale), L.stream())
     L.check(rc, 'm3p_colsum_bf16')
