@@ -64,7 +64,10 @@ enum {
   M3P_EPI_BIAS_LSE = 9       /* C = acc + bias (M3P_EPI_BIAS without alpha / column scale) and, for the cross-entropy over the
                                 N columns (PredLayer, transformer.py:104-117): out2 = float2 [N / 64][M], the (maximum, sum of
                                 exp(x - maximum)) of every row over each 64-column block, columns >= ld_out2 (= V, the valid
-                                vocabulary) left out; m3p_ce_lse_from_blocks folds them into the rows' log-sum-exp */
+                                vocabulary) left out; m3p_ce_lse_from_blocks folds them into the rows' log-sum-exp.
+                                With M3PEpilogue::row_ref set, the shifted-exponential form: C = bf16(exp(acc + bias - c_n)) with
+                                an exact 0 at the target column y_n and at the columns >= ld_out2, out2 = float [N / 64][M], the
+                                fp32 sum of the rounded values of every 64-column block (m3p_ce_shift_* below) */
 };
 
 typedef struct M3PEpilogue {
@@ -98,6 +101,10 @@ typedef struct M3PEpilogue {
    * tensor the dropout stream is indexed by - the keep decision of element (m, n) is that of element rng_rows[m] * N + n,
    * so a launch over gathered rows drops exactly what the launch over all rows drops there.  NULL = m itself. */
   const int32_t* rng_rows;
+  /* BIAS_LSE, shifted-exponential form: row_ref[m] = {float c_m, int32 y_m} (8 bytes per row, device, 8-byte aligned; written
+   * by m3p_ce_shift_target): the shift subtracted from row m's logits before the exponential and the column left out of
+   * it.  NULL = the plain form (logits and (maximum, sum) pairs). */
+  const void* row_ref;
 } M3PEpilogue;
 
 /* C[M,N] (bf16, row pitch ldc) = epilogue( A[M,K] (bf16, pitch lda) x W[N,K]^T (bf16, pitch ldw) ).
@@ -384,6 +391,38 @@ M3P_API size_t m3p_ce_colsum_workspace_bytes(int ld, int n_rows);
 M3P_API int m3p_ce_fwd_bwd_colsum(void* logits, int ld, int n_rows, int V, const int64_t* target, float* row_loss,
                                   float* row_lse, float grad_scale, float* colsum, void* workspace,
                                   size_t workspace_bytes, void* stream);
+
+/* Cross-entropy of the tied vocabulary projection WITHOUT a gradient pass over the logits (PredLayer, transformer.py:104-117, and
+ * its autograd).  Softmax is invariant under a per-row shift and its normaliser is a per-row scalar, so the projection stores
+ * e[n, v] = bf16(exp(x[n, v] - c_n)) once (M3P_EPI_BIAS_LSE with row_ref; exact 0 at v = y_n and v >= V) and 1 / sum(e) is applied
+ * to the small [n, d] operands of the two gradient products.  With t_n = h_n . E[y_n] + b[y_n] in fp32, c_n = t_n + 40 (the row
+ * maximum is at least t_n: the largest stored value of a row is at least e^-40, bf16's normal range reaches e^-87; the fp32 row sum
+ * overflows only past a loss of ~116 nats and then yields a NON-FINITE loss, never a finite wrong one), gs = grad_scale:
+ *   Sigma_n = sum_v e[n, v] + exp(-40),  loss_n = 40 + log Sigma_n,  s_n = gs / Sigma_n,  q_n = gs * expm1(-loss_n)
+ *   db = g * (sum_n s_n e[n, :]) ; db[y_n] += g q_n        dE = e^T x bf16(g s_n H[n, :]) ; dE[y_n, :] += g q_n H[n, :]
+ *   dH[n, :] = bf16(g * (s_n (e x E)[n, :] + q_n E[y_n, :]))         (g = the upstream gradient, a device scalar)
+ * Every entry point is one launch (m3p_ce_shift_colsum: the tile pass + its fold), reads g from device memory where it needs it
+ * and never synchronises with the host. */
+/* (a) row_t[n] = t_n, row_ref[n] = {t_n + 40, y_n}: one wave per row.  h bf16 [n_rows, d], emb bf16 [V, d], bias fp32 [V]; d % 4 == 0 */
+M3P_API int m3p_ce_shift_target(const void* h, const void* emb, const float* bias, const int64_t* target, float* row_t, void* row_ref,
+                                int n_rows, int d, void* stream);
+/* (b) folds the block sums (float [n_blocks][n_rows], n_rows % 64 == 0) into row_loss, row_s, row_q [n_rows]; scratch: float
+ * [32][n_rows] owned by the caller */
+M3P_API int m3p_ce_shift_rows(const void* stats, int n_blocks, int n_rows, float grad_scale, float* row_loss, float* row_s,
+                              float* row_q, void* scratch, void* stream);
+/* (c) colsum[v] (fp32 [ld], OVERWRITTEN) = sum_n row_s[n] * e[n, v]: one read-only pass over e (bf16 [n_rows, ld]); workspace as
+ * for m3p_ce_bwd_colsum (m3p_ce_colsum_workspace_bytes) */
+M3P_API int m3p_ce_shift_colsum(const void* e, int ld, int n_rows, const float* row_s, float* colsum, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* (d) out[n, :] = bf16(g[0] * row_s[n] * h[n, :]) - the second operand of the weight-gradient product.  d % 4 == 0 */
+M3P_API int m3p_ce_shift_scale_rows(const void* h, const float* row_s, const float* g, void* out, int n_rows, int d, void* stream);
+/* (e) the target's term: demb[y_n, :] (fp32 [V, d]) += g[0] * row_q[n] * h[n, :] and dbias[y_n] += g[0] * row_q[n], fp32 atomics (ids
+ * repeat), one wave per row.  Runs AFTER the (stored) weight gradient. */
+M3P_API int m3p_ce_shift_target_rows(const void* h, const int64_t* target, const float* row_q, const float* g, float* demb, float* dbias,
+                                     int n_rows, int d, void* stream);
+/* (f) dh[n, :] = bf16(g[0] * (row_s[n] * dh32[n, :] + row_q[n] * emb[y_n, :])); dh32 fp32 [n_rows, d] = e x E.  d % 4 == 0 */
+M3P_API int m3p_ce_shift_dh(const float* dh32, const void* emb, const int64_t* target, const float* row_s, const float* row_q,
+                            const float* g, void* dh, int n_rows, int d, void* stream);
 
 /* Validation scoring in one read-only pass over bf16 logits [n_rows, ld] (V valid columns): what the reference's evaluators take
  * from predict(..., get_scores=True) per batch - `loss.item() * len(y)` and `(word_scores.max(1)[1] == y).sum()`

@@ -745,6 +745,70 @@ __device__ __forceinline__ void epilogue_half_lse(bf16* __restrict__ C, int ldc,
   }
 }
 
+// The shifted-exponential form of that epilogue (M3P_EPI_BIAS_LSE with M3PEpilogue::row_ref set; inside the library an
+// instantiation of its own, like M3P_EPI_DROP_RES_ROWS).  The softmax normaliser is a per-row scalar: it factors out of both
+// gradient products and of the bias gradient, so what the cross-entropy's backward needs of the logits is
+//   e[n, v] = bf16(exp(x[n, v] - c_n))
+// for ANY per-row shift c_n known before the launch - row_ref[n] = {c_n, y_n}, c_n = the target's own logit + CE_SHIFT
+// (csrc/heads.hip) - and the 2.4-GB tensor is never rewritten.  e is an exact 0 at the target column y_n (its term is handled in
+// fp32 by the row kernels: a bf16 p_y - 1 is all rounding error on a confident row) and at the pad columns >= V (the weight
+// gradient's pad rows alias the bias gradient in the arena and rely on += 0).  stats[block][row] = the fp32 sum of the ROUNDED
+// values of the block: what summing the stored tensor gives.  No maximum pass, one shuffle pair, one float per (block, row).
+constexpr int M3P_EPI_BIAS_EXP = 11;
+struct CeRowRef { float c; int32_t y; };
+__device__ __forceinline__ void epilogue_half_exp(bf16* __restrict__ C, int ldc, float* __restrict__ stats, const CeRowRef* __restrict__ ref,
+                                                  int V, int mrow0, int nw, char* r1, const f32x4 (&rows0)[4], const f32x4 (&rows1)[4],
+                                                  const f32x4 (&biasv)[4], int lane, bool edge) {
+  constexpr float kLog2e = 1.4426950408889634f;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int srow = lane >> 3, sch = lane & 7;
+  const float2 rf[2] = {*reinterpret_cast<const float2*>(ref + mrow0 + fr), *reinterpret_cast<const float2*>(ref + mrow0 + 16 + fr)};
+#pragma unroll
+  for (int ii = 0; ii < 2; ++ii) {
+    const float cb = rf[ii].x * kLog2e;
+    const int tc = __builtin_bit_cast(int, rf[ii].y) - nw - fg * 4;      // the target's place among this lane's columns j * 16 + r
+    f32x4 x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 a = ((ii ? rows1[j] : rows0[j]) + biasv[j]) * kLog2e - cb;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) x[j][r] = __builtin_amdgcn_exp2f(a[r]);
+    }
+    if (edge) {        // (wave-uniform: only the last column tile holds columns >= V)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (nw + j * 16 + fg * 4 + r >= V) x[j][r] = 0.f;
+    }
+    if (__any((unsigned)(tc + fg * 4) < 64u)) {      // (wave-uniform: one of these 16 rows has its target in this 64-column block)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (j * 16 + r == tc) x[j][r] = 0.f;
+    }
+    f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bf16x4 xb = bf16x4{(bf16)x[j][0], (bf16)x[j][1], (bf16)x[j][2], (bf16)x[j][3]};
+      *reinterpret_cast<bf16x4*>(r1 + ep_off8<true>(ii * 16 + fr, (j * 16 + fg * 4) * 2)) = xb;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s4[r] += (float)xb[r];
+    }
+    float sm = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    sm += __shfl_xor(sm, 16, 64);
+    sm += __shfl_xor(sm, 32, 64);
+    if (fg == 0) stats[mrow0 + ii * 16 + fr] = sm;
+  }
+  bf16* Cp = C + (size_t)mrow0 * ldc + nw + sch * 8;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int row = it * 8 + srow;
+    st16p<true>(Cp + (size_t)row * ldc, flip_halves(*reinterpret_cast<const u32x4*>(r1 + ep_off<true>(row, sch * 16)), it & 1));
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The lin1 + GELU + byte epilogue (M3P_EPI_BIAS_GELUQ) from ONE table read per element (round 6).  h = gelu_erf(u) is staged
 // to row order like any output tile; gelu_erf'(u) leaves as one byte per element straight from the accumulator layout in
@@ -1412,19 +1476,29 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
         csum_nw = nw;
       }
       const bool fast = io_aligned && (m0 + BM <= M) && (n0 + BN <= N);
-      if constexpr (EPI == M3P_EPI_BIAS_LSE) {
+      if constexpr (EPI == M3P_EPI_BIAS_LSE || EPI == M3P_EPI_BIAS_EXP) {
         if (fast) {
           char* r1 = smem + 2 * STAGE + wid * 4096;
           f32x4 biasv[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) biasv[j] = *reinterpret_cast<const f32x4*>(ep.bias + nw + j * 16 + (lane >> 4) * 4);
           const int V = ep.ld_out2;
-          float2* st = reinterpret_cast<float2*>(ep.out2) + (size_t)(tn * 4 + wn) * M;
           const bool edge = (nw + 64 > V);
+          if constexpr (EPI == M3P_EPI_BIAS_EXP) {
+            float* st = reinterpret_cast<float*>(ep.out2) + (size_t)(tn * 4 + wn) * M;
+            const CeRowRef* ref = reinterpret_cast<const CeRowRef*>(ep.row_ref);
 #pragma unroll
-          for (int hf = 0; hf < 4; ++hf) {
-            epilogue_half_lse(C, ldc, st, V, mw + 32 * hf, nw, r1, acc[2 * hf], acc[2 * hf + 1], biasv, lane, edge);
-            __builtin_amdgcn_sched_barrier(0);
+            for (int hf = 0; hf < 4; ++hf) {
+              epilogue_half_exp(C, ldc, st, ref, V, mw + 32 * hf, nw, r1, acc[2 * hf], acc[2 * hf + 1], biasv, lane, edge);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          } else {
+            float2* st = reinterpret_cast<float2*>(ep.out2) + (size_t)(tn * 4 + wn) * M;
+#pragma unroll
+            for (int hf = 0; hf < 4; ++hf) {
+              epilogue_half_lse(C, ldc, st, V, mw + 32 * hf, nw, r1, acc[2 * hf], acc[2 * hf + 1], biasv, lane, edge);
+              __builtin_amdgcn_sched_barrier(0);
+            }
           }
         }
       } else if constexpr (kGqLut) {
@@ -2856,9 +2930,11 @@ static int launch_nt_gq(const bf16* A, int lda, const bf16* W, int ldw, bf16* C,
   if (M < 1024 || (M % 256) || (N % 256) || N < 512 || (K % 64) || (lda % 8) || (ldw % 8) || (ldc % 8) || ((uintptr_t)C & 15))
     return M3P_EINVAL;
   if (EPI == M3P_EPI_MULQ && (!ep.aux || ((uintptr_t)ep.aux & 15))) return M3P_EINVAL;
-  if ((EPI == M3P_EPI_BIAS_GELUQ || EPI == M3P_EPI_BIAS_LSE) && (!ep.out2 || ((uintptr_t)ep.out2 & 15) || !ep.bias || ((uintptr_t)ep.bias & 15)))
+  constexpr bool kLse = (EPI == M3P_EPI_BIAS_LSE || EPI == M3P_EPI_BIAS_EXP);
+  if ((EPI == M3P_EPI_BIAS_GELUQ || kLse) && (!ep.out2 || ((uintptr_t)ep.out2 & 15) || !ep.bias || ((uintptr_t)ep.bias & 15)))
     return M3P_EINVAL;
-  if (EPI == M3P_EPI_BIAS_LSE && (ep.ld_out2 <= 0 || ep.ld_out2 > N)) return M3P_EINVAL;
+  if (kLse && (ep.ld_out2 <= 0 || ep.ld_out2 > N)) return M3P_EINVAL;
+  if (EPI == M3P_EPI_BIAS_EXP && (!ep.row_ref || ((uintptr_t)ep.row_ref & 7))) return M3P_EINVAL;
   const int tiles_m = M / 256, tiles_n = N / 256;
   const size_t lds = 2 * 512 * ROWB + ((EPI == M3P_EPI_BIAS_GELUQ) ? GQ_TAB_BYTES + 8 * 2048 + 8 * 1024 : 8 * (EPI != M3P_EPI_MULQ ? 4096 : 2048)) +
                      (EPI == M3P_EPI_MULQ ? 2048 + 8 * 1024 : 0);      // (MULQ: behind the staging rows 2 KB - the 8-bit copy's running maxima / the
@@ -3819,7 +3895,9 @@ int m3p_gemm_nt_bf16(const void* A, int lda, const void* W, int ldw, void* C, in
     case M3P_EPI_MUL: return launch_nt<M3P_EPI_MUL>(a, lda, w, ldw, c, ldc, M, N, K, ep, st);
     case M3P_EPI_MULQ: return launch_nt_gq<M3P_EPI_MULQ>(a, lda, w, ldw, c, ldc, M, N, K, ep, st);
     case M3P_EPI_BIAS_GELUQ: return launch_nt_gq<M3P_EPI_BIAS_GELUQ>(a, lda, w, ldw, c, ldc, M, N, K, ep, st);
-    case M3P_EPI_BIAS_LSE: return launch_nt_gq<M3P_EPI_BIAS_LSE>(a, lda, w, ldw, c, ldc, M, N, K, ep, st);
+    case M3P_EPI_BIAS_LSE:      // (row_ref set: the shifted-exponential form, an instantiation of its own)
+      if (ep.row_ref) return launch_nt_gq<M3P_EPI_BIAS_EXP>(a, lda, w, ldw, c, ldc, M, N, K, ep, st);
+      return launch_nt_gq<M3P_EPI_BIAS_LSE>(a, lda, w, ldw, c, ldc, M, N, K, ep, st);
     default: return M3P_EINVAL;
   }
 }

@@ -379,9 +379,240 @@ __global__ __launch_bounds__(256) void colsum_kernel(const bf16* __restrict__ x,
     if (4 * c4 + j < ncols) unsafeAtomicAdd(out + 4 * c4 + j, acc[j] * sc);
 }
 
+// ---- cross-entropy of the tied vocabulary projection without a gradient pass over the logits (include/m3p_hip.h,
+// m3p_ce_shift_*).  The projection's epilogue stores e[n, v] = bf16(exp(x[n, v] - c_n)), an exact 0 at the target column and at
+// the pad columns, and the fp32 sums of the rounded values per (row, 64-column block); the softmax normaliser 1 / Sigma_n goes
+// onto the [n, d] operands of the two gradient products, the target's term (p_y - 1) is kept in fp32 beside them.
+//
+// The shift c_n = t_n + CE_SHIFT, t_n = the target's own logit:
+//   * the row maximum is at least t_n, so the largest stored value of a row is at least e^-40; bf16's normal range reaches down to
+//     e^-87, i.e. the stored values keep full bf16 precision 47 nats below the row maximum;
+//   * entries that flush to zero have less than e^-47 of the target's probability: over 250 002 columns less than 1e-15 of the
+//     mass, below fp32 resolution of the sum;
+//   * the fp32 row sum overflows only if x_max - t_n > 88.7 - ln V + 40 ~ 116, a row whose loss exceeds 116 nats.  That row comes
+//     out NON-FINITE (Sigma = inf -> loss = inf), never finite and wrong: the trainer's non-finite check stops the run.
+// The target column must be kept out of e for accuracy: on a confident row a bf16-rounded p_y minus 1 carries an absolute error
+// of 2^-9, more than the gradient itself once 1 - p_y < 1e-3.
+constexpr float CE_SHIFT = 40.f;
+struct CeRowRef { float c; int32_t y; };      // (what the projection's epilogue loads per row: csrc/gemm.hip)
+
+// (a) one wave per row: t_n = h_n . E[y_n] + b[y_n], fp32 accumulation over the bf16 operands the GEMM reads
+__global__ __launch_bounds__(256) void ce_shift_target_kernel(const bf16* __restrict__ h, const bf16* __restrict__ emb, const float* __restrict__ bias,
+                                                              const int64_t* __restrict__ target, float* __restrict__ row_t,
+                                                              CeRowRef* __restrict__ row_ref, int n_rows, int d) {
+  const int lane = threadIdx.x & 63;
+  const int row = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  if (row >= n_rows) return;
+  const int64_t y = target[row];
+  const bf16* hr = h + (size_t)row * d;
+  const bf16* er = emb + (size_t)y * d;
+  float acc = 0.f;
+  for (int c = lane * 4; c < d; c += 256) {
+    const f32x4 a = Vec4<bf16>::load(hr + c), b = Vec4<bf16>::load(er + c);
+    acc += (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    const float t = acc + bias[y];
+    row_t[row] = t;
+    row_ref[row] = CeRowRef{t + CE_SHIFT, (int32_t)y};
+  }
+}
+
+// (b) the block sums -> Sigma_n, loss, s_n, q_n: the two stages of ce_lse_partial / final_kernel on plain sums
+__global__ __launch_bounds__(256) void ce_shift_partial_kernel(const float* __restrict__ stats, int n_blocks, int n_rows, float* __restrict__ part) {
+  __shared__ float sh[4][64];
+  const int r = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int row = blockIdx.x * 64 + r;
+  const int per = (n_blocks + CE_LSE_SPLIT - 1) / CE_LSE_SPLIT;
+  const int b0 = blockIdx.y * per, b1 = min(n_blocks, b0 + per);
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  int b = b0 + q;
+  for (; b + 12 < b1; b += 16) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] += stats[(size_t)(b + 4 * k) * n_rows + row];
+  }
+  for (; b < b1; b += 4) s[0] += stats[(size_t)b * n_rows + row];
+  sh[q][r] = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  if (q == 0) part[(size_t)blockIdx.y * n_rows + row] = (sh[0][r] + sh[1][r]) + (sh[2][r] + sh[3][r]);
+}
+// With r = sum * e^SHIFT (= the other columns' mass relative to the target's): Sigma = e^-SHIFT (1 + r), loss = SHIFT + log Sigma =
+// log1p(r), p_y - 1 = expm1(-loss) = -r / (1 + r).  The right-hand forms are taken while r is small - a confident row, where
+// SHIFT + log Sigma would cancel to the fp32 spacing at 40 - the left-hand ones beyond (r overflows long before Sigma does).
+__global__ __launch_bounds__(256) void ce_shift_final_kernel(const float* __restrict__ part, int n_rows, float gs, float* __restrict__ row_loss,
+                                                             float* __restrict__ row_s, float* __restrict__ row_q) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  float sum = 0.f;
+  for (int k = 0; k < CE_LSE_SPLIT; ++k) sum += part[(size_t)k * n_rows + row];
+  const float e0 = expf(-CE_SHIFT);
+  const float sigma = sum + e0;
+  float loss, q;
+  if (sum < e0) {
+    const float r = sum * expf(CE_SHIFT);
+    loss = log1pf(r);
+    q = -gs * r / (1.f + r);
+  } else {
+    loss = CE_SHIFT + logf(sigma);
+    q = gs * expm1f(-loss);
+  }
+  row_loss[row] = loss;
+  row_s[row] = gs / sigma;
+  row_q[row] = q;
+}
+
+// (c) part[row group][v] = sum over the group's rows of s_n e[n, v]: ce_grad_tile_kernel's tile (64 rows x 2048 columns, four
+// rows' 16-byte non-temporal loads in flight per thread) without its stores - one read-only pass over e
+__global__ __launch_bounds__(256) void ce_shift_colsum_tile_kernel(const bf16* __restrict__ e, int ld, int n_rows, const float* __restrict__ row_s,
+                                                                   float* __restrict__ part) {
+  const int col0 = blockIdx.x * CE_CB + threadIdx.x * 8;
+  if (col0 >= ld) return;
+  const int r0 = blockIdx.y * CE_RB, r1 = min(n_rows, r0 + CE_RB);
+  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  constexpr int U = 4;
+  for (int rb = r0; rb < r1; rb += U) {
+    bf16x8 v[U];
+    float w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r = min(rb + u, r1 - 1);
+      v[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(e + (size_t)r * ld + col0));
+      w[u] = (rb + u < r1) ? row_s[r] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) cs[j] = __builtin_fmaf(w[u], (float)v[u][j], cs[j]);
+  }
+  float* out = part + (size_t)blockIdx.y * ld + col0;
+  *reinterpret_cast<f32x4*>(out) = f32x4{cs[0], cs[1], cs[2], cs[3]};
+  *reinterpret_cast<f32x4*>(out + 4) = f32x4{cs[4], cs[5], cs[6], cs[7]};
+}
+
+// (d) out[n, :] = bf16(g s_n h[n, :])
+__global__ __launch_bounds__(256) void ce_shift_scale_rows_kernel(const bf16* __restrict__ h, const float* __restrict__ row_s, const float* __restrict__ g,
+                                                                  bf16* __restrict__ out, int n, int d) {
+  const int nchunk = d >> 2;
+  const size_t total = (size_t)n * nchunk;
+  const float gv = *g;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / nchunk);
+    Vec4<bf16>::store(out + 4 * i, Vec4<bf16>::load(h + 4 * i) * (gv * row_s[r]));
+  }
+}
+
+// (e) the target's term: demb[y_n, :] += g q_n h[n, :], dbias[y_n] += g q_n.  One wave per row, one atomic instruction = 64
+// consecutive floats (full 128-byte lines), the form of scatter_add_token_rows_kernel; ids repeat
+__global__ __launch_bounds__(256) void ce_shift_target_rows_kernel(const bf16* __restrict__ h, const int64_t* __restrict__ target,
+                                                                   const float* __restrict__ row_q, const float* __restrict__ g,
+                                                                   float* __restrict__ demb, float* __restrict__ dbias, int n, int d) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), nwave = (int)((gridDim.x * blockDim.x) >> 6);
+  const float gv = *g;
+  for (int r = wave; r < n; r += nwave) {
+    const int64_t id = target[r];
+    const float c = gv * row_q[r];
+    const bf16* src = h + (size_t)r * d;
+    float* out = demb + (size_t)id * d;
+    for (int k = lane; k < d; k += 64) {
+      const float v = c * (float)src[k];
+      if (v != 0.f) unsafeAtomicAdd(out + k, v);
+    }
+    if (lane == 0) unsafeAtomicAdd(dbias + id, c);
+  }
+}
+
+// (f) dh[n, :] = bf16(g (s_n dh32[n, :] + q_n E[y_n, :]))
+__global__ __launch_bounds__(256) void ce_shift_dh_kernel(const float* __restrict__ dh32, const bf16* __restrict__ emb, const int64_t* __restrict__ target,
+                                                          const float* __restrict__ row_s, const float* __restrict__ row_q,
+                                                          const float* __restrict__ g, bf16* __restrict__ dh, int n, int d) {
+  const int nchunk = d >> 2;
+  const size_t total = (size_t)n * nchunk;
+  const float gv = *g;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / nchunk), c = (int)(i - (size_t)r * nchunk);
+    const f32x4 a = Vec4<float>::load(dh32 + 4 * i);
+    const f32x4 b = Vec4<bf16>::load(emb + (size_t)target[r] * d + 4 * c);
+    Vec4<bf16>::store(dh + 4 * i, (a * row_s[r] + b * row_q[r]) * gv);
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int m3p_ce_shift_target(const void* h, const void* emb, const float* bias, const int64_t* target, float* row_t, void* row_ref,
+                        int n_rows, int d, void* stream) {
+  if (n_rows <= 0 || d <= 0 || (d % 4) != 0 || !h || !emb || !bias || !target || !row_t || !row_ref || ((uintptr_t)h & 7) ||
+      ((uintptr_t)emb & 7) || ((uintptr_t)row_ref & 7))
+    return M3P_EINVAL;
+  hipLaunchKernelGGL(ce_shift_target_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16*)h, (const bf16*)emb,
+                     bias, target, row_t, (CeRowRef*)row_ref, n_rows, d);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_ce_shift_rows(const void* stats, int n_blocks, int n_rows, float grad_scale, float* row_loss, float* row_s, float* row_q,
+                      void* scratch, void* stream) {
+  if (n_blocks <= 0 || n_rows <= 0 || (n_rows % 64) != 0 || !stats || !row_loss || !row_s || !row_q || !scratch)
+    return M3P_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ce_shift_partial_kernel, dim3(n_rows / 64, CE_LSE_SPLIT), dim3(256), 0, st, (const float*)stats, n_blocks, n_rows,
+                     (float*)scratch);
+  hipLaunchKernelGGL(ce_shift_final_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, st, (const float*)scratch, n_rows, grad_scale,
+                     row_loss, row_s, row_q);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_ce_shift_colsum(const void* e, int ld, int n_rows, const float* row_s, float* colsum, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  if (n_rows <= 0 || ld <= 0 || (ld % 8) != 0 || !e || !row_s || !colsum || !workspace || ((uintptr_t)e & 15) ||
+      ((uintptr_t)colsum & 15) || ((uintptr_t)workspace & 15))
+    return M3P_EINVAL;
+  if (workspace_bytes < m3p_ce_colsum_workspace_bytes(ld, n_rows)) return M3P_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int groups = (n_rows + CE_RB - 1) / CE_RB;
+  hipLaunchKernelGGL(ce_shift_colsum_tile_kernel, dim3((ld + CE_CB - 1) / CE_CB, groups), dim3(256), 0, st, (const bf16*)e, ld, n_rows,
+                     row_s, (float*)workspace);
+  if (hipMemsetAsync(colsum, 0, (size_t)ld * sizeof(float), st) != hipSuccess) return M3P_EINVAL;
+  hipLaunchKernelGGL(ce_colsum_reduce_kernel, dim3((ld / 4 + 255) / 256, groups >= 16 ? 8 : 1), dim3(256), 0, st,
+                     (const float*)workspace, ld, groups, colsum);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+static int ce_shift_blocks(size_t total) { return (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048); }
+
+int m3p_ce_shift_scale_rows(const void* h, const float* row_s, const float* g, void* out, int n_rows, int d, void* stream) {
+  if (n_rows <= 0 || d <= 0 || (d % 4) != 0 || !h || !row_s || !g || !out || ((uintptr_t)h & 7) || ((uintptr_t)out & 7)) return M3P_EINVAL;
+  hipLaunchKernelGGL(ce_shift_scale_rows_kernel, dim3(ce_shift_blocks((size_t)n_rows * (d / 4))), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16*)h, row_s, g, (bf16*)out, n_rows, d);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_ce_shift_target_rows(const void* h, const int64_t* target, const float* row_q, const float* g, float* demb, float* dbias,
+                             int n_rows, int d, void* stream) {
+  if (n_rows <= 0 || d <= 0 || !h || !target || !row_q || !g || !demb || !dbias) return M3P_EINVAL;
+  const int blocks = (n_rows + 3) / 4 < 4096 ? (n_rows + 3) / 4 : 4096;
+  hipLaunchKernelGGL(ce_shift_target_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)h, target, row_q, g, demb,
+                     dbias, n_rows, d);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_ce_shift_dh(const float* dh32, const void* emb, const int64_t* target, const float* row_s, const float* row_q, const float* g,
+                    void* dh, int n_rows, int d, void* stream) {
+  if (n_rows <= 0 || d <= 0 || (d % 4) != 0 || !dh32 || !emb || !target || !row_s || !row_q || !g || !dh || ((uintptr_t)dh32 & 15) ||
+      ((uintptr_t)emb & 7) || ((uintptr_t)dh & 7))
+    return M3P_EINVAL;
+  hipLaunchKernelGGL(ce_shift_dh_kernel, dim3(ce_shift_blocks((size_t)n_rows * (d / 4))), dim3(256), 0, (hipStream_t)stream, dh32,
+                     (const bf16*)emb, target, row_s, row_q, g, (bf16*)dh, n_rows, d);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
 
 size_t m3p_ce_colsum_workspace_bytes(int ld, int n_rows) {
   return (size_t)((n_rows + CE_RB - 1) / CE_RB) * (size_t)ld * sizeof(float);

@@ -1265,7 +1265,9 @@ class DecoderFn(torch.autograd.Function):
 class MLMHeadFn(torch.autograd.Function):
     """predict() default branch: boolean-mask gather (transformer.py:1208), tied vocabulary
     projection (:111, :728-729) and mean cross-entropy (:112).  The bf16 logits are turned
-    into their own gradient in place by the CE kernel, so backward is two GEMMs."""
+    into their own gradient in place by the CE kernel, so backward is two GEMMs - or, on the benchmarked
+    whole-tile path with no scores wanted, never stored at all: the projection writes exp(logit - shift)
+    and the normaliser is applied to the two GEMMs' small operands."""
 
     @staticmethod
     def forward(ctx, tensor, model, base, row_idx, y, scores_out, sink=None):
@@ -1279,8 +1281,18 @@ class MLMHeadFn(torch.autograd.Function):
         full_tiles = _VOCAB_FULL_TILES and n >= 1024 and n % 256 == 0
         n_cols = ar.V_pad if full_tiles else V   # whole tiles: the eight-wave kernel
         fused_lse = _CE_FUSED_LSE and full_tiles
+        # no caller wants the scores: the projection stores exp(logit - shift) instead of the logits and the cross-entropy's
+        # gradient pass over them (2.4 GB read and written) disappears - the softmax normaliser goes onto the [n, d] operands of
+        # backward's two products instead (a caller that wants scores needs real logits)
+        shifted = fused_lse and scores_out is None
         stats = None
-        if fused_lse:
+        if shifted:
+            o = ar.offsets['pred_layer.proj.bias'][0]
+            _, row_ref = ops.ce_shift_target(hsel, ar.w('embeddings.weight'), ar.p('pred_layer.proj.bias'), y)
+            stats = torch.empty((ar.V_pad // 64, n), dtype=torch.float32, device=hsel.device)
+            ops.gemm_nt(hsel, ar.w('embeddings.weight'), L.EPI_BIAS_LSE, bias=ar.master[o:o + ar.V_pad], out=logits, n=n_cols,
+                        out2=stats, scale_cols=V, row_ref=row_ref)
+        elif fused_lse:
             # the projection's epilogue also leaves (max, sum exp) of every row per 64-column block: the cross-entropy's
             # log-sum-exp becomes a reduction over V / 64 pairs instead of a pass over the 2.4 GB of logits
             # (the bias vector is read up to V_pad like the matrix: the arena bytes behind it)
@@ -1293,7 +1305,11 @@ class MLMHeadFn(torch.autograd.Function):
         if scores_out is not None:
             scores_out.append(logits[:, :V].float())
         dbias = None
-        if fused_lse:
+        rows = None
+        if shifted:
+            loss_sum, _, row_s, row_q, dbias = ops.ce_shift_from_block_sums(logits, stats, 1.0 / n, 1.0 / n)
+            rows = (row_s, row_q, y)
+        elif fused_lse:
             loss_sum, _, dbias = ops.ce_from_block_stats(logits, V, y, stats, 1.0 / n, 1.0 / n)
         elif _VOCAB_FULL_TILES and n >= 1024:
             # the pass that writes the gradient also sums its columns (the output-bias gradient up to the upstream scale):
@@ -1302,7 +1318,7 @@ class MLMHeadFn(torch.autograd.Function):
         else:
             loss_sum, _ = ops.ce_fwd_bwd(logits, V, y, 1.0 / n, 1.0 / n)
         ctx.model = model
-        ctx.saved = (hsel, logits, row_idx, tuple(tensor.shape), tuple(tensor.stride()), tensor.storage_offset(), base, dbias)
+        ctx.saved = (hsel, logits, row_idx, tuple(tensor.shape), tuple(tensor.stride()), tensor.storage_offset(), base, dbias, rows)
         return loss_sum[0].clone()
 
     @staticmethod
@@ -1318,11 +1334,13 @@ class MLMHeadFn(torch.autograd.Function):
         ar.touch('embeddings.weight', 'pred_layer.proj.bias')
         ar.vocab_stored = False
         d, V = model.dim, model.n_words
-        hsel, dlogits, row_idx, shape, stride, soff, base, dbias = ctx.saved
+        hsel, dlogits, row_idx, shape, stride, soff, base, dbias, rows = ctx.saved
         ctx.saved = None
         n = hsel.shape[0]
         g = gloss.reshape(1).float()
-        hs = ops.scale_bf16_dev(hsel, g)
+        # (shifted-exponential path: `dlogits` holds e = exp(logit - shift) with zeros at the target and pad columns, the rows'
+        #  normaliser rides on the second operand and the targets' fp32 terms are added behind the product)
+        hs = ops.scale_bf16_dev(hsel, g) if rows is None else ops.ce_shift_scale_rows(hsel, rows[0], g)
         if _VOCAB_FULL_TILES and n >= 4096 and n % 64 == 0:
             # whole 256-row tiles of the vocabulary: the four-wave weight-gradient kernel.  The pad columns of dlogits are
             # exact zeros (the CE kernel wrote them), so rows V .. V_pad - 1 of "the matrix" - the head of the bias
@@ -1346,11 +1364,17 @@ class MLMHeadFn(torch.autograd.Function):
             ops.axpy_dev(ar.g('pred_layer.proj.bias'), dbias[:V], g)
         else:
             ops.colsum(dlogits, V, ar.g('pred_layer.proj.bias'), scale=g)
+        if rows is not None:
+            # a later accumulate into ranges the weight gradient has already stored (its pad rows cover the head of the bias gradient)
+            ops.ce_shift_target_rows(hsel, rows[2], rows[1], g, ar.g('embeddings.weight'), ar.g('pred_layer.proj.bias'))
         dH32 = torch.zeros((n, d), dtype=torch.float32, device=dlogits.device)
         # E [V, d] read in place (no transposed copy); whole 256-row tiles of predictions run on the four-wave kernel, which
         # reads all V_pad rows of "the matrix" - the bf16 arena behind E, finite numbers against dlogits' exact-zero pad columns
         ops.gemm_nn(dlogits, ar.w('embeddings.weight'), dH32, k_rows_readable=ar.V_pad if _VOCAB_DGRAD_W4 else None)
-        dH = ops.scale_bf16_dev(dH32, g)
+        if rows is None:
+            dH = ops.scale_bf16_dev(dH32, g)
+        else:
+            dH = ops.ce_shift_dh(dH32, ar.w('embeddings.weight'), rows[2], rows[0], rows[1], g)
         # gradient wrt `tensor` (a strided view of the encoder output): the rows go to the pass's gradient sink, or - for a
         # tensor that is not an encoder pass's output - onto a zeroed twin of the underlying row buffer
         dtensor = _scatter_rows_grad(dH, row_idx, base, shape, stride, soff, ctx.sink)

@@ -32,6 +32,7 @@ class Epilogue(C.Structure):
         ('descale_a', C.c_void_p), ('descale_b', C.c_void_p),
         ('out8', C.c_void_p), ('scale8', C.c_void_p), ('amax8', C.c_void_p), ('ld_out8', C.c_int32), ('out8_bf8', C.c_int32),
         ('rng_rows', C.c_void_p),
+        ('row_ref', C.c_void_p),
     ]
 
 
@@ -75,6 +76,12 @@ SIGNATURES = {
     'm3p_ce_fwd_bwd_colsum': (_i, [_p, _i, _i, _i, _p, _p, _p, _f, _p, _p, C.c_size_t, _p]),
     'm3p_ce_lse_from_blocks': (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
     'm3p_ce_bwd_colsum': (_i, [_p, _i, _i, _i, _p, _p, _f, _p, _p, C.c_size_t, _p]),
+    'm3p_ce_shift_target': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    'm3p_ce_shift_rows': (_i, [_p, _i, _i, _f, _p, _p, _p, _p, _p]),
+    'm3p_ce_shift_colsum': (_i, [_p, _i, _i, _p, _p, _p, C.c_size_t, _p]),
+    'm3p_ce_shift_scale_rows': (_i, [_p, _p, _p, _p, _i, _i, _p]),
+    'm3p_ce_shift_target_rows': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    'm3p_ce_shift_dh': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     'm3p_ce_eval': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     'm3p_colsum_bf16': (_i, [_p, _i, _i, _i, _p, _p, _p]),
     'm3p_sumsq_f32': (_i, [_p, C.c_longlong, _p, _p]),

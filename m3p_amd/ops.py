@@ -46,13 +46,15 @@ def _chk_bf16(*ts):
 
 def gemm_nt(a, w, epilogue=L.EPI_NONE, bias=None, aux=None, out=None, out2=None, colsum=None,
             scale_cols=0, scale=1.0, alpha=1.0, seed=0, p_drop=0.0, n=None, out8=None, scale8=None, amax8=None, out8_bf8=False,
-            rng_rows=None):
+            rng_rows=None, row_ref=None):
     """C[M,N] = epi(a[M,K] @ w[N,K]^T).  a, w bf16 (row pitch = stride(0)); returns C (bf16).
     ``n`` restricts the number of output columns (rows of w) used.
     rng_rows (EPI_BIAS_DROP_RES on gathered rows): int32 [M], the number of each row in the full tensor the dropout stream
     is indexed by - the launch then drops exactly the elements the launch over all rows drops in those rows.
     out8 (EPI_BIAS_GELUQ / EPI_MULQ): uint8 [M, N] that receives the 8-bit copy of C - sat(C * scale8) in e4m3, or e5m2 with
-    out8_bf8 - for the fp8 product that consumes C; amax8 (fp32 [1], zeroed by the caller) is raised to max |C|."""
+    out8_bf8 - for the fp8 product that consumes C; amax8 (fp32 [1], zeroed by the caller) is raised to max |C|.
+    row_ref (EPI_BIAS_LSE): the rows' {shift, target} pairs of ``ce_shift_target`` - the shifted-exponential form of the
+    epilogue: C = bf16(exp(a w^T + bias - shift)), 0 at the target and pad columns, out2 = float32 [N / 64, M] block sums."""
     M, K = a.shape
     N = w.shape[0] if n is None else n
     if epilogue == L.EPI_MULQ:     # aux = the byte codes of gelu_fwd_gq for this [M, N], in the GEMM's fragment order
@@ -60,8 +62,10 @@ def gemm_nt(a, w, epilogue=L.EPI_NONE, bias=None, aux=None, out=None, out2=None,
         assert aux is not None and aux.dtype == torch.uint8 and aux.is_contiguous() and aux.numel() == M * N
     elif epilogue == L.EPI_BIAS_LSE:        # out2 = float32 [N / 64, M, 2] block statistics; scale_cols = V (valid columns)
         _chk_bf16(a, w, out)
-        assert out2 is not None and out2.dtype == torch.float32 and out2.is_contiguous() and out2.numel() == (N // 64) * M * 2
+        assert out2 is not None and out2.dtype == torch.float32 and out2.is_contiguous()
+        assert out2.numel() == (N // 64) * M * (2 if row_ref is None else 1)
         assert bias is not None and 0 < scale_cols <= N
+        assert row_ref is None or (row_ref.dtype == torch.int32 and row_ref.is_cuda and row_ref.is_contiguous() and row_ref.numel() == 2 * M)
     elif epilogue == L.EPI_BIAS_GELUQ:      # out2 = where those codes go (uint8 [M * N]); C = gelu(a w^T + bias)
         _chk_bf16(a, w, out)
         assert out2 is not None and out2.dtype == torch.uint8 and out2.is_contiguous() and out2.numel() == M * N and bias is not None
@@ -91,6 +95,9 @@ def gemm_nt(a, w, epilogue=L.EPI_NONE, bias=None, aux=None, out=None, out2=None,
         assert epilogue == L.EPI_BIAS_DROP_RES and rng_rows.dtype == torch.int32 and rng_rows.is_cuda \
             and rng_rows.is_contiguous() and rng_rows.numel() == M
         ep.rng_rows = rng_rows.data_ptr()
+    if row_ref is not None:
+        assert epilogue == L.EPI_BIAS_LSE
+        ep.row_ref = row_ref.data_ptr()
     if out8 is not None:
         assert epilogue in (L.EPI_BIAS_GELUQ, L.EPI_MULQ) and out8.dtype == torch.uint8 and out8.shape == (M, N) and out8.stride(1) == 1
         ep.out8, ep.ld_out8, ep.out8_bf8 = out8.data_ptr(), out8.stride(0), 1 if out8_bf8 else 0
@@ -656,6 +663,76 @@ def ce_from_block_stats(logits, V, target, stats, loss_scale, grad_scale):
     L.check(L.load().m3p_ce_bwd_colsum(logits.data_ptr(), ld, n, V, target.data_ptr(), row_lse.data_ptr(), grad_scale, cs.data_ptr(),
                                        ws.data_ptr(), ws.numel(), L.stream()), 'm3p_ce_bwd_colsum')
     return (row_loss.sum() * loss_scale).reshape(1), row_loss, cs
+
+
+def ce_shift_target(h, emb, bias, target):
+    """The target's own logit of every row, t = h . emb[target] + bias[target] (fp32 accumulation over the bf16 operands), and the
+    rows' {t + 40, target} pairs the shifted-exponential projection reads (``gemm_nt(..., EPI_BIAS_LSE, row_ref=...)``).
+    Returns (row_t fp32 [n], row_ref int32 [n, 2]: the shift's fp32 bits and the target)."""
+    _chk_bf16(h, emb)
+    n, d = h.shape
+    assert h.is_contiguous() and emb.stride(0) == d and emb.stride(1) == 1 and bias.dtype == torch.float32 and bias.is_contiguous()
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == n
+    row_t = torch.empty(n, dtype=torch.float32, device=h.device)
+    row_ref = torch.empty((n, 2), dtype=torch.int32, device=h.device)
+    L.check(L.load().m3p_ce_shift_target(h.data_ptr(), emb.data_ptr(), bias.data_ptr(), target.data_ptr(), row_t.data_ptr(),
+                                         row_ref.data_ptr(), n, d, L.stream()), 'm3p_ce_shift_target')
+    return row_t, row_ref
+
+
+def ce_shift_from_block_sums(e, stats, loss_scale, grad_scale):
+    """The cross-entropy from what the shifted-exponential projection left (e bf16 [n, ld], stats fp32 [N / 64, n] block sums):
+    returns (loss_sum [1], row_loss [n], row_s [n] = grad_scale / Sigma, row_q [n] = grad_scale * (p_target - 1),
+    colsum fp32 [ld] = sum_n row_s[n] e[n, :] - the output-bias gradient but for the targets' terms).  e is only read."""
+    n, ld = e.shape[0], e.stride(0)
+    dev = e.device
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape[1] == n
+    row_loss = torch.empty(n, dtype=torch.float32, device=dev)
+    row_s = torch.empty(n, dtype=torch.float32, device=dev)
+    row_q = torch.empty(n, dtype=torch.float32, device=dev)
+    scratch = torch.empty((32, n), dtype=torch.float32, device=dev)
+    L.check(L.load().m3p_ce_shift_rows(stats.data_ptr(), stats.shape[0], n, grad_scale, row_loss.data_ptr(), row_s.data_ptr(),
+                                       row_q.data_ptr(), scratch.data_ptr(), L.stream()), 'm3p_ce_shift_rows')
+    cs = torch.empty(ld, dtype=torch.float32, device=dev)
+    need = L.load().m3p_ce_colsum_workspace_bytes(ld, n)
+    ws = _CE_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _CE_WS[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(L.load().m3p_ce_shift_colsum(e.data_ptr(), ld, n, row_s.data_ptr(), cs.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+            'm3p_ce_shift_colsum')
+    return (row_loss.sum() * loss_scale).reshape(1), row_loss, row_s, row_q, cs
+
+
+def ce_shift_scale_rows(h, row_s, g):
+    """bf16(g[0] * row_s[n] * h[n, :]): the weight-gradient product's second operand with the softmax normaliser on it."""
+    _chk_bf16(h)
+    assert h.is_contiguous() and row_s.dtype == g.dtype == torch.float32 and row_s.numel() == h.shape[0] and g.numel() == 1
+    out = torch.empty_like(h)
+    L.check(L.load().m3p_ce_shift_scale_rows(h.data_ptr(), row_s.data_ptr(), g.data_ptr(), out.data_ptr(), h.shape[0], h.shape[1],
+                                             L.stream()), 'm3p_ce_shift_scale_rows')
+    return out
+
+
+def ce_shift_target_rows(h, target, row_q, g, demb, dbias):
+    """demb[target[n], :] += g[0] * row_q[n] * h[n, :] and dbias[target[n]] += g[0] * row_q[n] (fp32 atomics; ids repeat)."""
+    _chk_bf16(h)
+    n, d = h.shape
+    assert h.is_contiguous() and target.dtype == torch.int64 and target.numel() == n and row_q.dtype == g.dtype == torch.float32
+    assert demb.dtype == dbias.dtype == torch.float32 and demb.shape[1] == d and demb.stride(0) == d and dbias.is_contiguous()
+    L.check(L.load().m3p_ce_shift_target_rows(h.data_ptr(), target.data_ptr(), row_q.data_ptr(), g.data_ptr(), demb.data_ptr(),
+                                              dbias.data_ptr(), n, d, L.stream()), 'm3p_ce_shift_target_rows')
+
+
+def ce_shift_dh(dh32, emb, target, row_s, row_q, g):
+    """bf16(g[0] * (row_s[n] * dh32[n, :] + row_q[n] * emb[target[n], :])) for dh32 = e x E (fp32 [n, d])."""
+    _chk_bf16(emb)
+    n, d = dh32.shape
+    assert dh32.dtype == torch.float32 and dh32.is_contiguous() and emb.stride(0) == d and emb.stride(1) == 1
+    assert target.dtype == torch.int64 and target.numel() == n and row_s.dtype == row_q.dtype == g.dtype == torch.float32
+    out = torch.empty((n, d), dtype=BF16, device=dh32.device)
+    L.check(L.load().m3p_ce_shift_dh(dh32.data_ptr(), emb.data_ptr(), target.data_ptr(), row_s.data_ptr(), row_q.data_ptr(),
+                                     g.data_ptr(), out.data_ptr(), n, d, L.stream()), 'm3p_ce_shift_dh')
+    return out
 
 
 def ce_eval(logits, V, target):
