@@ -272,6 +272,22 @@ M3P_API int m3p_attn_rows_bwd(const void* q, int ld_q, const void* kv, long long
                               int dh, int Lk, int causal, int pos0, float qscale, uint32_t seed, uint32_t thresh24,
                               float inv_keep, void* stream);
 
+/* Causal SELF-attention of a decoder-only training pass (the causal language-model objective, xtrainer.py:694-732) on
+ * tiled MFMA kernels: exactly m3p_attn_rows_fwd / _bwd(causal = 1, klen = NULL, pos0 = 0, Lk = T) - query t sees keys 0 .. t
+ * by position only, fp32 softmax, the same dropout stream index ((b*H + h)*T + t)*T + key - without atomics.
+ * qkv bf16 [B*T, ld_qkv] is the fused projection (d = H*dh): q at column h*dh (biased and scaled by 1/sqrt(dh)), k at
+ * d + h*dh, v at 2*d + h*dh.  ctx bf16 [B*T, d], lse fp32 [B, H, T] (natural log).
+ * dh in {32, 64}, 1 <= T <= 512, B*H*T*T < 2^32, ld % 8 == 0 and 16-byte aligned pointers; any other shape returns
+ * M3P_ENOTIMPL (the caller then takes the rows kernels). */
+M3P_API int m3p_attn_causal_fwd(const void* qkv, int ld_qkv, void* ctx, float* lse, int B, int T, int H, int dh,
+                                uint32_t seed, uint32_t thresh24, float inv_keep, void* stream);
+/* Backward: dqkv bf16 [B*T, ld_dqkv] laid out dq | dk | dv like qkv; dq is the gradient of the UNSCALED projection
+ * (x qscale, like m3p_attn_rows_bwd).  Every element of the B*T rows' 3*d columns is written: no fp32 buffer, nothing for
+ * the caller to zero.  (While the call runs, the first four bytes of each (row, head) dq slot hold an intermediate.) */
+M3P_API int m3p_attn_causal_bwd(const void* qkv, int ld_qkv, const void* dctx, const float* lse, void* dqkv, int ld_dqkv,
+                                int B, int T, int H, int dh, float qscale, uint32_t seed, uint32_t thresh24,
+                                float inv_keep, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Input assembly of jointfwd (transformer.py:901-943) and its backward
  * ---------------------------------------------------------------------------------- */

@@ -21,8 +21,11 @@ Valid-set perplexity and accuracy of the language-model objectives (``evaluate_m
 (``eval_mask_out`` :89-118, ``eval_mask_sent`` :541-602).  Per batch the reference reads ``loss.item() * len(y)`` and
 ``(word_scores.max(1)[1] == y).sum().item()`` back to the host; here ``predict_stats`` leaves both on the device, they are
 summed there, and a data set costs ONE host read.  Ties of the maximum count for the lowest word id (the reference leaves them
-open).  Not built: ``evaluate_clm``, the ``eval_bleu`` branches (hypothesis files, BLEU scripts), ``evaluate_slide`` and the
-test-set captioning generators.
+open).  ``evaluate_clm`` (:329-387) scores next-word prediction on the monolingual stream or on joined pairs, without a masking
+RNG; by default through the causal pass that ``Trainer.clm_step`` trains (the call the reference left commented out, :373),
+``causal=False`` reproduces the reference's live line (:371-372), in which every position sees its own target.
+Not built: the ``eval_bleu`` branches (hypothesis files, BLEU scripts), ``evaluate_slide`` and the test-set captioning
+generators.
 """
 from collections import OrderedDict
 
@@ -324,6 +327,40 @@ def evaluate_mlm(model, params, iterator, scores, data_set, lang1, lang2):
 
 
 @torch.no_grad()
+def evaluate_clm(model, params, iterator, scores, data_set, lang1, lang2, causal=True):
+    """xevaluator.py:329-387: next-word perplexity and accuracy on the monolingual stream (``lang2 is None``, batches
+    (x, lengths)) or on pairs (batches ((x1, len1), (x2, len2)) joined with reset positions); word t + 1 is scored from
+    position t, nothing from a sentence's last word (:362-364).  No word is masked, so there is no RNG.
+    ``causal=True`` (the default here) runs ``crossfwd(stream_='text', causal=True)``, the pass ``Trainer.clm_step`` trains
+    and the call the reference left commented out (:373, as ``fwd``).  ``causal=False`` is the reference's live line
+    (:371-372): the bidirectional text stream, in which position t attends word t + 1 - the number the reference prints, not
+    a language-model perplexity.  Like the reference, a data set without a word divides by zero."""
+    assert data_set in ('valid', 'test')
+    assert lang1 in params.langs and (lang2 is None or lang2 in params.langs)
+    lang1_id = params.lang2id[lang1]
+    lang2_id = params.lang2id[lang2] if lang2 is not None else None
+    stats = _LMStats()
+    with _eval_mode(model) as m:
+        for batch in iterator:
+            if lang2 is None:
+                x, lengths = batch
+                positions = None
+                langs = x.clone().fill_(lang1_id) if params.n_langs > 1 else None
+            else:
+                (sent1, len1), (sent2, len2) = batch
+                x, lengths, positions, langs = concat_batches(sent1, len1, lang1_id, sent2, len2, lang2_id, params.pad_index,
+                                                              params.eos_index, reset_positions=True)
+            pred_mask, y = _next_word_targets(x, lengths)
+            x, lengths, positions, langs, pred_mask, y = to_cuda(x, lengths, positions, langs, pred_mask, y)
+            tensor = m('crossfwd', stream_='text', x=x, lengths=lengths, positions=positions, langs=langs, causal=bool(causal))
+            stats.add(*m('predict_stats', tensor=tensor, pred_mask=pred_mask, y=y))
+    if stats.n == 0:
+        raise ZeroDivisionError('evaluate_clm: no word to score in %s (%s, %s)' % (data_set, lang1, lang2))
+    name = '%s_%s' % (data_set, lang1) if lang2 is None else '%s_%s-%s' % (data_set, lang1, lang2)
+    return stats.write(scores, name + '_clm_ppl', name + '_clm_acc')
+
+
+@torch.no_grad()
 def evaluate_mass(model, params, iterator, scores, data_set, lang1, lang2=None):
     """xevaluator.py:493-539: the hidden span of ``eval_mask_sent`` decoded over the masked sentence; the decoder may not
     look at the source's <mask> positions (``enc_mask``) and reads its inputs at their original positions."""
@@ -430,7 +467,8 @@ def evaluate_mt_ic(model, params, iterator, scores, data_set, lang1, lang2):
 
 def run_all_evals(model, params, get_iterator, epoch):
     """The scores ``Trainer.save_best_model`` / ``end_epoch`` consume, after every epoch: xevaluator.py:120-235 for the tasks
-    built here plus evaluator.py:250-252's ``evaluate_mlm`` over ``params.mlm_steps``, on the 'valid' split.
+    built here (``evaluate_clm`` over ``params.clm_steps`` first, as there) plus evaluator.py:250-252's ``evaluate_mlm`` over
+    ``params.mlm_steps``, on the 'valid' split.
     ``get_iterator(data_set, lang1, lang2)`` is the caller's (``XTrainer.get_iterator`` fits): ``lang2`` is None for the
     monolingual sets (MLM stream, MASS sentences), the second language for pairs, and ``lang1`` again for the text-to-text
     pairs of ``evaluate_ntg`` (both sides in one language).  Only the master rank evaluates: the others return
@@ -440,6 +478,8 @@ def run_all_evals(model, params, get_iterator, epoch):
     if g('is_master', True) is False:
         return scores
     data_set = 'valid'
+    for lang1, lang2 in g('clm_steps', []):
+        evaluate_clm(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
     for lang1, lang2 in g('mlm_steps', []):
         evaluate_mlm(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
     mass = list(g('mass_steps', []))
@@ -460,6 +500,10 @@ def run_all_evals(model, params, get_iterator, epoch):
         for lang1, lang2 in sorted(set(rel)):
             evaluate_understanding_tasks(model, params, get_iterator(data_set, lang1, lang2), scores, data_set, lang1, lang2)
     # averages per task
+    clm_mono = [l1 for l1, l2 in g('clm_steps', []) if l2 is None]
+    if clm_mono:
+        scores['%s_clm_ppl' % data_set] = np.mean([scores['%s_%s_clm_ppl' % (data_set, l)] for l in clm_mono])
+        scores['%s_clm_acc' % data_set] = np.mean([scores['%s_%s_clm_acc' % (data_set, l)] for l in clm_mono])
     mono = [l1 for l1, l2 in g('mlm_steps', []) if l2 is None]
     if mono:
         scores['%s_mlm_ppl' % data_set] = np.mean([scores['%s_%s_mlm_ppl' % (data_set, l)] for l in mono])

@@ -1051,13 +1051,21 @@ class ImageStreamFn(torch.autograd.Function):
 
 N_DEC_ARGS = 12     # positional arguments of DecoderFn.forward
 
+# Self-attention of a DecoderFn pass WITHOUT a source encoding (the causal language-model step: every lane of a stream batch is
+# bptt long) runs on the tiled MFMA kernels of csrc/attn_causal.hip from this sequence length on, where their launcher takes
+# the shape; below it, and in every pass that attends a source encoding, on the rows kernels.  32 is the smallest measured T
+# (tools/attn_causal_bench.py, profiles/attn_causal_vs_rows.txt): the tiled pair already wins there, 9.9x, in all three alternations.
+CAUSAL_TILED_MIN_T = 32
+
 
 class DecoderFn(torch.autograd.Function):
     """crossfwd(stream_='text', causal=True, src_enc=..., src_len=...) with gradients: the teacher-forced pass of the
     translation / auto-encoding steps (transformer.py:1005-1102; caller xtrainer.py:1383-1441).  Text embedding assembly as
     in the non-causal stream, then per layer causal self-attention -> LN1 -> attention over the source encoding -> LN1.5
     -> FFN -> LN2.  Target sequences are short, so both attentions run on the rows kernels (csrc/decode.hip: a wave per
-    (sequence, head, query)); every projection, LayerNorm and the embedding assembly are the encoder's kernels.  The
+    (sequence, head, query)); every projection, LayerNorm and the embedding assembly are the encoder's kernels.  Without a
+    source encoding (the causal language-model step, whose stream batches are bptt long in every lane) the self-attention
+    runs on the tiled MFMA kernels of csrc/attn_causal.hip from CAUSAL_TILED_MIN_T on.  The
     gradient wrt src_enc is returned to autograd (it flows on into the encoder pass that produced it); parameter
     gradients go to the arena."""
 
@@ -1105,12 +1113,19 @@ class DecoderFn(torch.autograd.Function):
             src16 = src_enc.detach().to(device=dev, dtype=BF16).contiguous().view(B * S, d)
             src_klen = src_len.to(device=dev, dtype=torch.int32).clamp(max=S).contiguous()
         qscale = 1.0 / math.sqrt(dh)
+        tiled = not has_src and T >= CAUSAL_TILED_MIN_T
         saved = []
         for i in range(nL):
             a, f, e = 'attentions.%d.' % i, 'ffns.%d.' % i, 'encoder_attn.%d.' % i
             qkv = ops.gemm_nt(h, ar.qkv_w16(i), L.EPI_BIAS, bias=ar.qkv_bias(i), scale_cols=d, scale=qscale)
-            ctxt, lse = ops.attn_rows_fwd(qkv, qkv.view(B, T, 3 * d)[:, :, d:], None, B, T, H, dh, T, causal=True,
-                                          seed=dseed(0, i), p_drop=p_attn)
+            # (the first layer decides for the pass: the launcher's answer depends on the shape alone)
+            res = ops.attn_causal_fwd(qkv, B, T, H, dh, seed=dseed(0, i), p_drop=p_attn) if tiled else None
+            if res is None:
+                assert i == 0 or not tiled
+                tiled = False
+                res = ops.attn_rows_fwd(qkv, qkv.view(B, T, 3 * d)[:, :, d:], None, B, T, H, dh, T, causal=True,
+                                        seed=dseed(0, i), p_drop=p_attn)
+            ctxt, lse = res
             pre1 = ops.gemm_nt(ctxt, ar.w(a + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(a + 'out_lin.bias'), aux=h,
                                seed=dseed(1, i), p_drop=p_drop)
             x1, mean1, rstd1 = ops.layernorm_fwd(pre1, ar.p('layer_norm1.%d.weight' % i), ar.p('layer_norm1.%d.bias' % i))
@@ -1135,6 +1150,7 @@ class DecoderFn(torch.autograd.Function):
         ctx.model = model
         ctx.dims = (B, T, S, d, H, dh, nL)
         ctx.drop = (p_drop, p_attn, seed_step)
+        ctx.self_attn_tiled = tiled      # backward takes the kernels the forward took
         ctx.saved = (x, totlen, rowmask, emb_saved, saved, src16, src_klen, langs, positions)
         ctx.text_meta = (text_embed.dtype, text_embed.device, text_embed.requires_grad) if text_embed is not None else None
         ctx.src_meta = (src_enc.dtype, src_enc.requires_grad) if has_src else None
@@ -1205,10 +1221,15 @@ class DecoderFn(torch.autograd.Function):
                 dAO = dpre1
             ops.gemm_wgrad(dAO, ctxt, ar.g(a + 'out_lin.weight'))
             dctx = ops.gemm_nt(dAO, ar.wt[('out', i)], L.EPI_NONE)
-            dqkv = torch.empty_like(qkv)
-            _, dkv = ops.attn_rows_bwd(qkv, qkv.view(B, T, 3 * d)[:, :, d:], None, dctx, lse, B, T, H, dh, T, qscale, causal=True,
-                                       seed=dseed(0, i), p_drop=p_attn, dq_out=dqkv)
-            dqkv.view(B, T, 3 * d)[:, :, d:] = dkv
+            if ctx.self_attn_tiled:
+                dqkv = ops.attn_causal_bwd(qkv, dctx, lse, B, T, H, dh, qscale, seed=dseed(0, i), p_drop=p_attn)
+                if dqkv is None:
+                    raise L.M3PError('m3p_attn_causal_bwd declined (M3P_ENOTIMPL) a shape m3p_attn_causal_fwd took')
+            else:
+                dqkv = torch.empty_like(qkv)
+                _, dkv = ops.attn_rows_bwd(qkv, qkv.view(B, T, 3 * d)[:, :, d:], None, dctx, lse, B, T, H, dh, T, qscale,
+                                           causal=True, seed=dseed(0, i), p_drop=p_attn, dq_out=dqkv)
+                dqkv.view(B, T, 3 * d)[:, :, d:] = dkv
             ops.colsum(dqkv, 3 * d, ar.qkv_bias(i, grad=True))
             ops.gemm_wgrad(dqkv, h_in, ar.qkv_wgrad(i))
             dh_ = ops.gemm_nt(dqkv, ar.wt[('qkv', i)], L.EPI_RES, aux=dpre1)

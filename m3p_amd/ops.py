@@ -374,6 +374,48 @@ def attn_rows_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, causal=False
     return dq, dkv
 
 
+def attn_causal_fwd(qkv, B, T, H, dh, seed=0, p_drop=0.0, out=None):
+    """Causal self-attention of a decoder-only training pass on the tiled MFMA kernels (csrc/attn_causal.hip): qkv bf16
+    [B*T, >= 3*H*dh] (q scaled | k | v) -> (ctx bf16 [B*T, H*dh], lse fp32 [B, H, T]), the results of
+    attn_rows_fwd(causal=True, klen=None, Lk=T) under the same seed.  Returns None when the kernels do not take the shape
+    (M3P_ENOTIMPL: dh not in {32, 64}, T > 512, ...) - the caller then runs the rows kernels.  out = (ctx, lse) to write into."""
+    _chk_bf16(qkv)
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[0] == B * T and qkv.shape[1] >= 3 * H * dh
+    if out is not None:
+        ctx, lse = out
+        assert ctx.dtype == BF16 and ctx.is_contiguous() and ctx.shape == (B * T, H * dh)
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, T)
+    else:
+        ctx = torch.empty((B * T, H * dh), dtype=BF16, device=qkv.device)
+        lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
+    rc = L.load().m3p_attn_causal_fwd(qkv.data_ptr(), qkv.stride(0), ctx.data_ptr(), lse.data_ptr(), B, T, H, dh, seed,
+                                      L.thresh24(p_drop), 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+    if rc == -2:            # (M3P_ENOTIMPL)
+        return None
+    L.check(rc, 'm3p_attn_causal_fwd')
+    return ctx, lse
+
+
+def attn_causal_bwd(qkv, dctx, lse, B, T, H, dh, qscale, seed=0, p_drop=0.0, out=None):
+    """-> dqkv bf16 [B*T, 3*H*dh] (dq of the unscaled projection | dk | dv; every element written, no atomics), or written
+    into ``out`` (row pitch out.stride(0)); None when the kernels do not take the shape."""
+    _chk_bf16(qkv, dctx)
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[0] == B * T and dctx.is_contiguous()
+    assert dctx.shape == (B * T, H * dh) and lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, T)
+    if out is not None:
+        dqkv = out
+        assert dqkv.dtype == BF16 and dqkv.stride(1) == 1 and dqkv.shape == (B * T, 3 * H * dh)
+    else:
+        dqkv = torch.empty((B * T, 3 * H * dh), dtype=BF16, device=qkv.device)
+    rc = L.load().m3p_attn_causal_bwd(qkv.data_ptr(), qkv.stride(0), dctx.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),
+                                      dqkv.stride(0), B, T, H, dh, qscale, seed, L.thresh24(p_drop),
+                                      1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+    if rc == -2:            # (M3P_ENOTIMPL)
+        return None
+    L.check(rc, 'm3p_attn_causal_bwd')
+    return dqkv
+
+
 def cast_bf16(x):
     """fp32 -> bf16 through the HIP cast kernel (bf16 input is returned unchanged)."""
     if x.dtype == BF16:

@@ -57,7 +57,8 @@ def _stat_names(params):
     """Loss statistics of the steps this build runs (xtrainer.py:101-130 lists them for every task)."""
     g = lambda k: getattr(params, k, [])   # noqa: E731
     names = ['MLM-%s' % l for l in g('langs')] + ['MT-%s-%s' % (l1, l2) for l1, l2 in (g('mt_steps') or [])] + \
-        ['AE-%s' % l for l in (g('ae_steps') or [])]
+        ['AE-%s' % l for l in (g('ae_steps') or [])] + \
+        [('CLM-%s' % l1) if l2 is None else ('CLM-%s-%s' % (l1, l2)) for l1, l2 in (g('clm_steps') or [])]
     for key, steps in (('CMLM', g('cross_mlm_steps')), ('MRM', g('cross_mrm_steps')), ('MRFR', g('cross_mrfr_steps')),
                        ('t2i', g('cross_rel_steps')), ('i2t', g('cross_rel_steps'))):
         names += ['%s-%s' % (key, l1) for l1, _ in steps]
@@ -283,6 +284,44 @@ class Trainer(object):
         tensor = model('crossfwd', stream_='text', x=x, lengths=lengths, positions=positions, langs=langs, causal=False)
         _, loss = model('predict', tensor=tensor, pred_mask=pred_mask, y=y, get_scores=False)
         self._stat(stat or 'MLM-%s' % lang, loss)
+        self.optimize(lambda_coeff * loss)
+        self.n_sentences += self.params.batch_size
+        self.stats['processed_s'] += lengths.size(0)
+        self._pending_w.append(n_words)
+        return loss
+
+    def clm_step(self, lang1, lang2, lambda_coeff):
+        """Next-word prediction on a text batch, the causal language-model objective (xtrainer.py:694-732): the monolingual
+        stream (``lang2 is None``: every lane bptt long) or a pair joined with reset positions; word t + 1 is predicted from
+        position t, nothing from a sentence's last word or its padding, and nothing from the first ``context_size`` rows."""
+        assert lambda_coeff >= 0
+        if lambda_coeff == 0:
+            return
+        params = self.params
+        x, lengths, positions, langs, _ = self.generate_batch(lang1, lang2, 'causal')
+        x, lengths, positions, langs, _ = self.round_batch(x, lengths, positions, langs)
+        alen = torch.arange(int(lengths.max()), dtype=torch.long, device=lengths.device)
+        pred_mask = alen[:, None] < lengths[None] - 1
+        if getattr(params, 'context_size', 0) > 0:           # do not predict without context
+            pred_mask[:params.context_size] = 0
+        y = x[1:].masked_select(pred_mask[:-1])
+        return self.clm_step_on_batch(x, lengths, pred_mask, y, lang1, lambda_coeff, langs=langs, positions=positions,
+                                      stat=None if lang2 is None else 'CLM-%s-%s' % (lang1, lang2))
+
+    def clm_step_on_batch(self, x, lengths, pred_mask, y, lang='en', lambda_coeff=1, langs=None, positions=None, stat=None):
+        """Loss path of clm_step (:717-732).  The reference calls the XLM-era ``model('fwd', ..., causal=True)``; this build
+        keeps ``fwd`` outside its surface and runs ``crossfwd(stream_='text', causal=True)``: the same decoder-only pass plus
+        the language embedding of a multilingual model (transformer.py:1059-1060; ``fwd`` :824-829 adds none) - what the
+        reference's own evaluate_clm feeds, so training and scoring agree.  The two are identical for n_langs == 1.
+        (The reference does not hand ``positions`` to ``fwd``; a pair batch here restarts them like its evaluator does.)"""
+        model = self.model
+        model.train()
+        self._dp_plan(True, expect=('mlm',))
+        n_words = pred_mask.sum()
+        x, y, pred_mask, lengths = to_cuda(x, y, pred_mask, lengths)
+        tensor = model('crossfwd', stream_='text', x=x, lengths=lengths, positions=positions, langs=langs, causal=True)
+        _, loss = model('predict', tensor=tensor, pred_mask=pred_mask, y=y, get_scores=False)
+        self._stat(stat or 'CLM-%s' % lang, loss)
         self.optimize(lambda_coeff * loss)
         self.n_sentences += self.params.batch_size
         self.stats['processed_s'] += lengths.size(0)
