@@ -288,6 +288,27 @@ M3P_API int m3p_attn_causal_bwd(const void* qkv, int ld_qkv, const void* dctx, c
                                 int B, int T, int H, int dh, float qscale, uint32_t seed, uint32_t thresh24,
                                 float inv_keep, void* stream);
 
+/* Attention over a SOURCE ENCODING in a teacher-forced decoder pass (the encoder-attention sub-layer of the seq2seq steps)
+ * on tiled MFMA kernels: exactly m3p_attn_rows_fwd / _bwd(causal = 0, pos0 = 0) - the same layouts (q bf16 [B*Tq, ld_q],
+ * biased and scaled; key j of sequence b, head h at kv + b*kv_bstride + j*ld_kv + h*dh, its value H*dh elements further;
+ * klen int32 [B] or NULL), fp32 softmax over the first nk = min(klen[b], Lk) keys, the same dropout stream index
+ * ((b*H + h)*Tq + t)*Lk + key - without atomics.  Key / value rows at or past nk are never used and may hold anything
+ * (NaN included).  ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq] (natural log); klen[b] == 0 gives ctx = 0 and lse = 0.
+ * dh in {32, 64}, 1 <= Tq <= 512, 1 <= Lk <= 1024, B*H*Tq*Lk < 2^32, strides multiples of 8 and 16-byte aligned pointers;
+ * any other shape returns M3P_ENOTIMPL (the caller then takes the rows kernels). */
+M3P_API int m3p_attn_cross_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen,
+                               void* ctx, float* lse, int B, int Tq, int H, int dh, int Lk, uint32_t seed, uint32_t thresh24,
+                               float inv_keep, void* stream);
+/* Backward: dq bf16 [B*Tq, ld_dq] = gradient of the UNSCALED query projection (x qscale, like m3p_attn_rows_bwd); dkv BF16
+ * [B, Lk, ld_dkv] (keys | values per position, ld_dkv >= 2*H*dh): every one of the Lk rows' 2*H*dh columns is written
+ * exactly once - fp32 accumulators rounded once, exact zeros for keys >= nk - so the caller zeroes nothing and casts
+ * nothing.  klen[b] == 0 gives dq = 0 and dkv = 0.  (While the call runs, the first four bytes of each (row, head) dq slot
+ * hold an intermediate.) */
+M3P_API int m3p_attn_cross_bwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen,
+                               const void* dctx, const float* lse, void* dq, int ld_dq, void* dkv, int ld_dkv, int B, int Tq,
+                               int H, int dh, int Lk, float qscale, uint32_t seed, uint32_t thresh24, float inv_keep,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Input assembly of jointfwd (transformer.py:901-943) and its backward
  * ---------------------------------------------------------------------------------- */

@@ -4,6 +4,10 @@
 // output (cross-attention).  Decoding is HBM / latency work - one new token per sequence and step, klen <= a few hundred
 // keys of 128 bytes - so there are no MFMAs here: one wave per (sequence, head, query row), coalesced 16-byte loads, fp32
 // softmax (the reference's is fp32 too, :202), bf16 context out.
+// The training forms below (m3p_attn_rows_fwd / _bwd) are the complete fallback of the teacher-forced passes: where the
+// dispatch rules of functional.py select them and their launchers take the shape, the self-attention of such a pass runs on
+// attn_causal.hip and its attention over the source encoding on attn_cross.hip (tiled MFMA kernels, no atomics); these
+// serve the shapes below the rules' thresholds or outside the tiled launchers' range.
 #include "common.hpp"
 
 namespace {

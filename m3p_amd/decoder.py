@@ -5,7 +5,10 @@ it, ``generate`` (greedy / sampled) and ``generate_beam`` - transformer.py:970-1
 
 One decoding step is latency / HBM work: one new token per sequence, every weight read once.  The projections run on the
 bf16 GEMM of the training path (fused bias, 1/sqrt(dh), residual and GELU epilogues), attention on
-``m3p_attn_query_fwd`` (csrc/decode.hip: one wave per (sequence, head, query) over the cached keys / values).  The cache
+``m3p_attn_query_fwd`` (csrc/decode.hip: one wave per (sequence, head, query) over the cached keys / values).  A call
+WITHOUT a cache - the teacher-forced scoring pass of the evaluations, every target position at once - takes the tiled MFMA
+forwards of the training pass instead (csrc/attn_causal.hip for the self-attention, csrc/attn_cross.hip over the source
+encoding) where the dispatch rules of ``functional`` pick them and the launchers take the shape.  The cache
 holds, per layer, ONE token-major bf16 tensor [bs, capacity, 2 d] (keys | values) for the self-attention and one
 [bs, S_src, 2 d] for the encoder attention (projected once, at the first step); the reference keeps (k, v) head-major
 tuples under the module ids and concatenates per step.  ``cache['slen']`` has the reference's meaning.
@@ -19,6 +22,7 @@ import math
 
 import torch
 
+from . import functional as Fn
 from . import lib as L
 from . import ops
 
@@ -112,16 +116,29 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
         cw = model.decoder_cold_weights()
         src_klen = src_len.to(dev).to(torch.int32).clamp(max=S).contiguous()
         src16 = None
+    # without a cache every position is scored at once: the attentions of the training pass, by its rules, without dropout
+    tiled = cache is None and slen >= Fn.CAUSAL_TILED_MIN_T
+    xtiled = cache is None and src_enc is not None and Fn.cross_attn_tiled(slen, S)
     for i in range(model.n_layers):
         a, f = 'attentions.%d.' % i, 'ffns.%d.' % i
         wqkv, bqkv = ar.qkv_w16(i), ar.qkv_bias(i)
-        q = ops.gemm_nt(h16, wqkv[:d], L.EPI_BIAS, bias=bqkv[:d], scale_cols=d, scale=qscale)
-        kv = ops.gemm_nt(h16, wqkv[d:], L.EPI_BIAS, bias=bqkv[d:]).view(bs, n_new, 2 * d)
-        if cache is not None:
-            store = _self_cache(cache, i, bs, slen, d, dev)
-            store[:, pos0:slen] = kv
-            kv = store
-        ctx = ops.attn_query_fwd(q, kv, None, bs, n_new, H, dh, slen, causal=True, pos0=pos0)
+        ctx = None
+        if tiled:
+            qkv = ops.gemm_nt(h16, wqkv, L.EPI_BIAS, bias=bqkv, scale_cols=d, scale=qscale)
+            res = ops.attn_causal_fwd(qkv, bs, slen, H, dh)
+            if res is None:                 # (the first layer decides for the pass: the launcher's answer depends on the shape alone)
+                assert i == 0
+                tiled = False
+            else:
+                ctx = res[0]
+        if ctx is None:
+            q = ops.gemm_nt(h16, wqkv[:d], L.EPI_BIAS, bias=bqkv[:d], scale_cols=d, scale=qscale)
+            kv = ops.gemm_nt(h16, wqkv[d:], L.EPI_BIAS, bias=bqkv[d:]).view(bs, n_new, 2 * d)
+            if cache is not None:
+                store = _self_cache(cache, i, bs, slen, d, dev)
+                store[:, pos0:slen] = kv
+                kv = store
+            ctx = ops.attn_query_fwd(q, kv, None, bs, n_new, H, dh, slen, causal=True, pos0=pos0)
         pre = ops.gemm_nt(ctx, ar.w(a + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(a + 'out_lin.bias'), aux=h16)
         h16, _, _ = ops.layernorm_fwd(pre, ar.p('layer_norm1.%d.weight' % i), ar.p('layer_norm1.%d.bias' % i))
         if cw is not None:
@@ -133,7 +150,13 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
                 kvc = ops.gemm_nt(src16, cw.kv[i], L.EPI_BIAS, bias=cw.bkv[i]).view(bs, S, 2 * d)
                 if cache is not None:
                     cache[('cross', i)] = kvc
-            ctx2 = ops.attn_query_fwd(q2, kvc, src_klen, bs, n_new, H, dh, S)
+            res2 = ops.attn_cross_fwd(q2, kvc, src_klen, bs, n_new, H, dh, S) if xtiled else None
+            if res2 is None:
+                assert i == 0 or not xtiled
+                xtiled = False
+                ctx2 = ops.attn_query_fwd(q2, kvc, src_klen, bs, n_new, H, dh, S)
+            else:
+                ctx2 = res2[0]
             pre = ops.gemm_nt(ctx2, cw.out[i], L.EPI_BIAS_DROP_RES, bias=cw.bo[i], aux=h16)
             ln15 = model.get_submodule('layer_norm15.%d' % i)
             h16, _, _ = ops.layernorm_fwd(pre, ln15.weight.detach(), ln15.bias.detach())

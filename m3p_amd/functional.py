@@ -1051,21 +1051,36 @@ class ImageStreamFn(torch.autograd.Function):
 
 N_DEC_ARGS = 12     # positional arguments of DecoderFn.forward
 
-# Self-attention of a DecoderFn pass WITHOUT a source encoding (the causal language-model step: every lane of a stream batch is
-# bptt long) runs on the tiled MFMA kernels of csrc/attn_causal.hip from this sequence length on, where their launcher takes
-# the shape; below it, and in every pass that attends a source encoding, on the rows kernels.  32 is the smallest measured T
-# (tools/attn_causal_bench.py, profiles/attn_causal_vs_rows.txt): the tiled pair already wins there, 9.9x, in all three alternations.
+# Self-attention of a DecoderFn pass (the causal language-model step, whose stream batches are bptt long in every lane, and the
+# teacher-forced pass of the seq2seq steps alike: klen = None, a position-only mask) runs on the tiled MFMA kernels of
+# csrc/attn_causal.hip from this sequence length on, where their launcher takes the shape; below it on the rows kernels.
+# 32 is the smallest measured T (tools/attn_causal_bench.py, profiles/attn_causal_vs_rows.txt): the tiled pair already wins
+# there, 9.9x, in all three alternations - and at the seq2seq shapes (tools/attn_cross_bench.py,
+# profiles/attn_cross_vs_rows.txt), so a source encoding does not change the rule.
 CAUSAL_TILED_MIN_T = 32
+
+# Attention over the source encoding in the same pass runs on the tiled MFMA kernels of csrc/attn_cross.hip where this rule
+# says so and their launcher takes the shape, otherwise on the rows kernels.  The constants are the smallest measured target
+# and source lengths (tools/attn_cross_bench.py, profiles/attn_cross_vs_rows.txt): the tiled pair wins all three
+# alternations at every measured (Tq, S) from there on; nothing below was measured, and below it the rows kernels stay.
+CROSS_TILED_MIN_TQ = 8
+CROSS_TILED_MIN_S = 36
+
+
+def cross_attn_tiled(Tq, S):
+    """The dispatch rule of the encoder-attention sub-layer: True = tiled kernels (csrc/attn_cross.hip)."""
+    return Tq >= CROSS_TILED_MIN_TQ and S >= CROSS_TILED_MIN_S
 
 
 class DecoderFn(torch.autograd.Function):
     """crossfwd(stream_='text', causal=True, src_enc=..., src_len=...) with gradients: the teacher-forced pass of the
     translation / auto-encoding steps (transformer.py:1005-1102; caller xtrainer.py:1383-1441).  Text embedding assembly as
     in the non-causal stream, then per layer causal self-attention -> LN1 -> attention over the source encoding -> LN1.5
-    -> FFN -> LN2.  Target sequences are short, so both attentions run on the rows kernels (csrc/decode.hip: a wave per
-    (sequence, head, query)); every projection, LayerNorm and the embedding assembly are the encoder's kernels.  Without a
-    source encoding (the causal language-model step, whose stream batches are bptt long in every lane) the self-attention
-    runs on the tiled MFMA kernels of csrc/attn_causal.hip from CAUSAL_TILED_MIN_T on.  The
+    -> FFN -> LN2.  Both attentions run on tiled MFMA kernels without atomics where a measured rule says so and the launcher
+    takes the shape - the self-attention on csrc/attn_causal.hip from CAUSAL_TILED_MIN_T on (with or without a source
+    encoding), the attention over the source encoding on csrc/attn_cross.hip where cross_attn_tiled(T, S) - and otherwise on
+    the rows kernels (csrc/decode.hip: a wave per (sequence, head, query)); every projection, LayerNorm and the embedding
+    assembly are the encoder's kernels.  The
     gradient wrt src_enc is returned to autograd (it flows on into the encoder pass that produced it); parameter
     gradients go to the arena."""
 
@@ -1110,10 +1125,15 @@ class DecoderFn(torch.autograd.Function):
         if has_src:
             assert model.cross_attention_hot, 'the encoder-attention sub-layer is not in the training arena (params.mt_steps)'
             S = src_enc.shape[1]
-            src16 = src_enc.detach().to(device=dev, dtype=BF16).contiguous().view(B * S, d)
             src_klen = src_len.to(device=dev, dtype=torch.int32).clamp(max=S).contiguous()
+            # rows past the source length as zeros: no attention kernel reads them, but they may hold anything (NaN included)
+            # and the key / value weight gradient multiplies them with the zero rows of dkv
+            src16 = src_enc.detach().to(device=dev, dtype=BF16)
+            src16 = torch.where((torch.arange(S, device=dev)[None, :] < src_klen[:, None])[:, :, None], src16,
+                                torch.zeros((), dtype=BF16, device=dev)).contiguous().view(B * S, d)
         qscale = 1.0 / math.sqrt(dh)
-        tiled = not has_src and T >= CAUSAL_TILED_MIN_T
+        tiled = T >= CAUSAL_TILED_MIN_T
+        xtiled = has_src and cross_attn_tiled(T, S)
         saved = []
         for i in range(nL):
             a, f, e = 'attentions.%d.' % i, 'ffns.%d.' % i, 'encoder_attn.%d.' % i
@@ -1134,7 +1154,12 @@ class DecoderFn(torch.autograd.Function):
             if has_src:
                 q2 = ops.gemm_nt(x1, ar.xattn(i, 'q'), L.EPI_BIAS, bias=ar.xattn(i, 'bq'), scale_cols=d, scale=qscale)
                 kvc = ops.gemm_nt(src16, ar.xattn(i, 'kv'), L.EPI_BIAS, bias=ar.xattn(i, 'bkv')).view(B, S, 2 * d)
-                ctx2, lse2 = ops.attn_rows_fwd(q2, kvc, src_klen, B, T, H, dh, S, seed=dseed(2, i), p_drop=p_attn)
+                res2 = ops.attn_cross_fwd(q2, kvc, src_klen, B, T, H, dh, S, seed=dseed(2, i), p_drop=p_attn) if xtiled else None
+                if res2 is None:
+                    assert i == 0 or not xtiled
+                    xtiled = False
+                    res2 = ops.attn_rows_fwd(q2, kvc, src_klen, B, T, H, dh, S, seed=dseed(2, i), p_drop=p_attn)
+                ctx2, lse2 = res2
                 pre15 = ops.gemm_nt(ctx2, ar.w(e + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(e + 'out_lin.bias'),
                                     aux=x1, seed=dseed(3, i), p_drop=p_drop)
                 xf, mean15, rstd15 = ops.layernorm_fwd(pre15, ar.p('layer_norm15.%d.weight' % i), ar.p('layer_norm15.%d.bias' % i))
@@ -1151,6 +1176,7 @@ class DecoderFn(torch.autograd.Function):
         ctx.dims = (B, T, S, d, H, dh, nL)
         ctx.drop = (p_drop, p_attn, seed_step)
         ctx.self_attn_tiled = tiled      # backward takes the kernels the forward took
+        ctx.cross_attn_tiled = xtiled
         ctx.saved = (x, totlen, rowmask, emb_saved, saved, src16, src_klen, langs, positions)
         ctx.text_meta = (text_embed.dtype, text_embed.device, text_embed.requires_grad) if text_embed is not None else None
         ctx.src_meta = (src_enc.dtype, src_enc.requires_grad) if has_src else None
@@ -1204,8 +1230,17 @@ class DecoderFn(torch.autograd.Function):
                     dAO2 = dpre15
                 ops.gemm_wgrad(dAO2, ctx2, ar.g(e + 'out_lin.weight'))
                 dctx2 = ops.gemm_nt(dAO2, ar.wt[('xout', i)], L.EPI_NONE)
-                dq2, dkvc = ops.attn_rows_bwd(q2, kvc, src_klen, dctx2, lse2, B, T, H, dh, S, qscale, seed=dseed(2, i), p_drop=p_attn)
-                dkvc = dkvc.to(BF16).view(B * S, 2 * d)
+                if ctx.cross_attn_tiled:
+                    # (bf16 straight from the kernel, keys past the source length as exact zeros: nothing to zero or cast)
+                    res2 = ops.attn_cross_bwd(q2, kvc, src_klen, dctx2, lse2, B, T, H, dh, S, qscale, seed=dseed(2, i), p_drop=p_attn)
+                    if res2 is None:
+                        raise L.M3PError('m3p_attn_cross_bwd declined (M3P_ENOTIMPL) a shape m3p_attn_cross_fwd took')
+                    dq2, dkvc = res2
+                    dkvc = dkvc.view(B * S, 2 * d)
+                else:
+                    dq2, dkvc = ops.attn_rows_bwd(q2, kvc, src_klen, dctx2, lse2, B, T, H, dh, S, qscale, seed=dseed(2, i),
+                                                  p_drop=p_attn)
+                    dkvc = dkvc.to(BF16).view(B * S, 2 * d)
                 ops.gemm_wgrad(dq2, x1, ar.xattn(i, 'q', grad=True))
                 ops.colsum(dq2, d, ar.xattn(i, 'bq', grad=True))
                 ops.gemm_wgrad(dkvc, src16, ar.xattn(i, 'kv', grad=True))

@@ -416,6 +416,57 @@ def attn_causal_bwd(qkv, dctx, lse, B, T, H, dh, qscale, seed=0, p_drop=0.0, out
     return dqkv
 
 
+def attn_cross_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=0, p_drop=0.0, out=None):
+    """Attention over a source encoding in a teacher-forced decoder pass on the tiled MFMA kernels (csrc/attn_cross.hip):
+    operands as attn_rows_fwd(causal=False) -> (ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq]), its results under the same
+    seed; key / value rows at or past klen[b] may hold anything.  Returns None when the kernels do not take the shape
+    (M3P_ENOTIMPL: dh not in {32, 64}, Tq > 512, Lk > 1024, ...) - the caller then runs the rows kernels.
+    out = (ctx, lse) to write into."""
+    _chk_bf16(q, kv)
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[0] == B * Tq
+    assert kv.dim() == 3 and kv.stride(2) == 1 and kv.shape[0] == B and kv.shape[1] >= Lk
+    if out is not None:
+        ctx, lse = out
+        assert ctx.dtype == BF16 and ctx.is_contiguous() and ctx.shape == (B * Tq, H * dh)
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, Tq)
+    else:
+        ctx = torch.empty((B * Tq, H * dh), dtype=BF16, device=q.device)
+        lse = torch.empty((B, H, Tq), dtype=torch.float32, device=q.device)
+    rc = L.load().m3p_attn_cross_fwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
+                                     ctx.data_ptr(), lse.data_ptr(), B, Tq, H, dh, Lk, seed, L.thresh24(p_drop),
+                                     1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+    if rc == -2:            # (M3P_ENOTIMPL)
+        return None
+    L.check(rc, 'm3p_attn_cross_fwd')
+    return ctx, lse
+
+
+def attn_cross_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, seed=0, p_drop=0.0, out=None):
+    """-> (dq bf16 [B*Tq, H*dh] of the unscaled projection, dkv BF16 [B, Lk, 2*H*dh]: every row written once, exact zeros
+    for keys >= klen[b], no atomics - nothing to zero or cast), or written into out = (dq, dkv) (row pitches
+    dq.stride(0), dkv.stride(1)); None when the kernels do not take the shape."""
+    _chk_bf16(q, kv, dctx)
+    d = H * dh
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[0] == B * Tq and dctx.is_contiguous() and dctx.shape == (B * Tq, d)
+    assert kv.dim() == 3 and kv.stride(2) == 1 and kv.shape[0] == B and kv.shape[1] >= Lk
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, Tq)
+    if out is not None:
+        dq, dkv = out
+        assert dq.dtype == BF16 and dq.stride(1) == 1 and dq.shape == (B * Tq, d)
+        assert dkv.dtype == BF16 and dkv.shape == (B, Lk, 2 * d) and dkv.stride(2) == 1 and dkv.stride(0) == Lk * dkv.stride(1)
+    else:
+        dq = torch.empty((B * Tq, d), dtype=BF16, device=q.device)
+        dkv = torch.empty((B, Lk, 2 * d), dtype=BF16, device=q.device)
+    rc = L.load().m3p_attn_cross_bwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
+                                     dctx.data_ptr(), lse.data_ptr(), dq.data_ptr(), dq.stride(0), dkv.data_ptr(),
+                                     dkv.stride(1), B, Tq, H, dh, Lk, qscale, seed, L.thresh24(p_drop),
+                                     1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+    if rc == -2:            # (M3P_ENOTIMPL)
+        return None
+    L.check(rc, 'm3p_attn_cross_bwd')
+    return dq, dkv
+
+
 def cast_bf16(x):
     """fp32 -> bf16 through the HIP cast kernel (bf16 input is returned unchanged)."""
     if x.dtype == BF16:
