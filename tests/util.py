@@ -260,6 +260,96 @@ def assert_accum_bound(got, ref64, abssum64, n_terms, extra=0.0, what=''):
     return worst
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The row kernels behind the shifted-exponential MLM head (csrc/heads.hip: ce_shift_*).
+# ---------------------------------------------------------------------------------------------------------------------
+CE_SHIFT = 40.0                 # heads.hip CE_SHIFT: the rows' shift above the target's own logit
+CE_LSE_SPLIT = 32               # heads.hip CE_LSE_SPLIT: the splits of a row's blocks, one partial sum each
+
+
+def shift_rowsum_adds(n_blocks):
+    """The most fp32 additions any one block sum passes through on its way into a row's sum (ce_shift_partial_kernel, then
+    ce_shift_final_kernel).  All addends are positive, so the sum's relative error is at most that many unit roundoffs -
+    linear in the count, as in sumsq_bound.  Counted in the kernels' order:
+      t   a split holds per = ceil(n_blocks / 32) blocks and its four waves take every fourth, so a thread adds at most
+          t = ceil(per / 4) of them one after the other (the unrolled loop spreads them over four accumulators and only the
+          tail is sequential: t is the upper bound of both);
+      2   the thread's four accumulators, (s0 + s1) + (s2 + s3);
+      2   the four waves of the block, (w0 + w1) + (w2 + w3);
+      32  the partial sums of the 32 splits, added one after the other."""
+    per = -(-int(n_blocks) // CE_LSE_SPLIT)
+    t = -(-per // 4)
+    return t + 2 + 2 + CE_LSE_SPLIT
+
+
+def shift_rows_ref64(stats, gs):
+    """fp64 (row sum, loss, s, q) of ce_shift_from_block_sums from the fp32 block sums [n_blocks, n] and the fp32 value of the
+    gradient scale: r = sum e^40 is the other columns' mass relative to the target's; loss = log1p(r), s = gs / (sum + e^-40),
+    q = gs expm1(-loss) = gs (p_target - 1)."""
+    gs = _f32(gs)
+    total = stats.double().sum(0)
+    loss = torch.log1p(total * math.exp(CE_SHIFT))
+    return total, loss, gs / (total + math.exp(-CE_SHIFT)), gs * torch.expm1(-loss)
+
+
+def shift_rows_bound(row_loss, row_s, row_q, stats, gs):
+    """Every row's loss, s and q against shift_rows_ref64, in units of its bound.  With rho = shift_rowsum_adds(n_blocks) u,
+    the relative error of the row sum: the loss moves by at most rho (d log1p(r) = dr / (1 + r) <= dr / r), plus the fp32
+    evaluation of 40 + log(sum + e^-40), relative to its operands: F32_OUT (40 + loss), absolute.  s and q are held relative
+    to themselves: rho plus F32_OUT 40 (q = gs expm1(-loss) follows the loss' absolute error, at most F32_OUT 40 where the
+    second branch begins, at loss = log 2, where d q / q = d loss / (e^loss - 1) = d loss).  NaN counts as infinite.
+    Returns {'loss' | 's' | 'q': (worst, row)}."""
+    _, loss, s, q = shift_rows_ref64(stats, gs)
+    rho = shift_rowsum_adds(stats.shape[0]) * U32
+    out = {}
+    for k, got, ref, bound in (('loss', row_loss, loss, rho + F32_OUT * (CE_SHIFT + loss)),
+                               ('s', row_s, s, s.abs() * (rho + F32_OUT * CE_SHIFT)),
+                               ('q', row_q, q, q.abs() * (rho + F32_OUT * CE_SHIFT))):
+        r = torch.nan_to_num((got.to(ref.device, torch.float64) - ref).abs() / (bound + _TINY), nan=math.inf)
+        w, i = r.max(0)
+        out[k] = (float(w), int(i))
+    return out
+
+
+def assert_shift_rows_bound(row_loss, row_s, row_q, stats, gs, what=''):
+    worst = shift_rows_bound(row_loss, row_s, row_q, stats, gs)
+    for k, (w, i) in worst.items():
+        assert w <= 1.0, '%s: %s of row %d is off by %.3g x its bound (%d blocks)' % (what, k, i, w, stats.shape[0])
+    return {k: w for k, (w, _) in worst.items()}
+
+
+def scale_rows_bound(got, h, row_s, g):
+    """ce_shift_scale_rows: bf16(g s_n h[n, :]) against fp64 - one bf16 rounding of the result plus the fp32 products, F32_OUT
+    relative to |g s h|."""
+    ref = float(g) * row_s.double()[:, None] * h.double()
+    return gemm_bound(got, ref, torch.zeros_like(ref), 0, BF16_OUT, F32_OUT * ref.abs())
+
+
+def shift_dh_bound(got, dh32, emb_rows, row_s, row_q, g):
+    """ce_shift_dh: bf16(g (s_n dh32[n, :] + q_n E[y_n, :])) against fp64 (emb_rows = E[y], [n, d]) - one bf16 rounding of the
+    result plus the fp32 evaluation, relative to the two terms that may cancel: F32_OUT |g| (|s dh32| + |q E[y]|)."""
+    a, b = row_s.double()[:, None] * dh32.double(), row_q.double()[:, None] * emb_rows.double()
+    ref = float(g) * (a + b)
+    return gemm_bound(got, ref, torch.zeros_like(ref), 0, BF16_OUT, F32_OUT * abs(float(g)) * (a.abs() + b.abs()))
+
+
+def target_rows_bound(demb, dbias, demb0, dbias0, h, y, row_q, g):
+    """ce_shift_target_rows: demb[y_n, :] += g q_n h[n, :] and dbias[y_n] += g q_n onto what the two held before (demb0,
+    dbias0), fp32 atomics in any order.  accum_bound with as many terms per word as rows name it; the products g q h are
+    rounded in fp32 before they are added: extra = F32_OUT sum |g q h|.  Returns ((worst, at) of demb, (worst, at) of dbias)."""
+    V = demb0.shape[0]
+    c = float(g) * row_q.double()
+    terms = c[:, None] * h.double()
+    cnt = torch.bincount(y, minlength=V).double()
+    ref = demb0.double().index_add(0, y, terms)
+    at = torch.zeros_like(ref).index_add(0, y, terms.abs())
+    we = accum_bound(demb, ref, demb0.double().abs() + at, cnt[:, None], F32_OUT * at)
+    refb = dbias0.double().index_add(0, y, c)
+    ab = torch.zeros_like(refb).index_add(0, y, c.abs())
+    wb = accum_bound(dbias, refb, dbias0.double().abs() + ab, cnt, F32_OUT * ab)
+    return we, wb
+
+
 def assert_bits_equal(got, ref, what=''):
     """Bit-for-bit equality of two tensors of one dtype and shape (signed zeros and NaN payloads included), naming the first
     element that differs."""
