@@ -258,6 +258,35 @@ M3P_API int m3p_attn_query_fwd(const void* q, int ld_q, const void* kv, long lon
                                const int32_t* klen, void* ctx, int B, int Tq, int H, int dh, int Lk, int causal,
                                int pos0, void* stream);
 
+/* m3p_attn_query_fwd over key / value rows that stay where they were written (beam search without re-ordering the caches):
+ * key j of query sequence b - and its value - is read from kv row owner[b*owner_bstride + j*owner_kstride] instead of row b
+ * (kv + row*kv_bstride + j*ld_kv + h*dh).  owner_kstride = 1: one row per (sequence, key) - the self-attention cache, where
+ * position j of a hypothesis lives in the row of the beam that wrote it; owner_kstride = 0: one row per sequence - an
+ * encoder-attention cache kept once per sentence.  klen stays indexed by b.  The arithmetic and its order are
+ * m3p_attn_query_fwd's: the result equals that call on the gathered copy bit for bit.  Entries of owner outside the kv
+ * tensor are the caller's error (they are not checked). */
+M3P_API int m3p_attn_query_owner_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv,
+                                     const int32_t* klen, void* ctx, int B, int Tq, int H, int dh, int Lk, int causal,
+                                     int pos0, const int32_t* owner, int owner_bstride, int owner_kstride, void* stream);
+
+/* Word selection of the decoding loops from the bf16 logits of the vocabulary projection (csrc/select.hip).
+ * logits bf16 [n, ld], n = bs*beam rows (the beams of a sentence are consecutive rows), ld >= V, ld % 8 == 0, 16-byte
+ * aligned; columns V .. ld-1 may hold anything.  beam_scores fp32 [n] or NULL (zeros).
+ *   lse[r]                       fp32 log-sum-exp of row r over its V columns
+ *   score of entry (r, w)        fl32(fl32(float(logits[r, w]) - lse[r]) + beam_scores[r])
+ *   scores [bs, k], flat_idx [bs, k] (= beam*V + w)   per sentence the first k of its beam*V entries under the total
+ *                                order: score descending, then beam ascending, then logit descending, then word ascending.
+ * Two launches, no atomics, every logit read once; bit-reproducible.  workspace: m3p_vocab_select_workspace_bytes(n, V, k)
+ * bytes, 16-byte aligned, contents irrelevant.  k <= m3p_vocab_select_max_k() (16), beam <= 64, k <= beam*V; larger k or
+ * beam returns M3P_ENOTIMPL.  m3p_vocab_select_plan answers what the launcher would (M3P_OK / M3P_ENOTIMPL / M3P_EINVAL)
+ * for a shape, without launching. */
+M3P_API int m3p_vocab_select_max_k(void);
+M3P_API int m3p_vocab_select_plan(int n, int V, int ld, int beam, int k);
+M3P_API size_t m3p_vocab_select_workspace_bytes(int n, int V, int k);
+M3P_API int m3p_vocab_select(const void* logits, int ld, int n, int V, const float* beam_scores, int beam, int k,
+                             void* workspace, size_t workspace_bytes, float* scores, long long* flat_idx, float* lse,
+                             void* stream);
+
 /* The same attention for the TRAINING of the causal / cross-attention sub-layers (teacher forcing: Tq = the whole target
  * sequence, pos0 = 0): dropout on the probabilities (stream (seed, thresh24) indexed ((b*H + h)*Tq + t)*Lk + key) and the
  * log-sum-exp lse fp32 [B, H, Tq] kept for backward.  B*H*Tq*Lk < 2^32. */

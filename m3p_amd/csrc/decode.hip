@@ -31,13 +31,19 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 // ctx  bf16 [B*Tq, H*DH]
 // lse  fp32 [B, H, Tq] (nullable): log-sum-exp of the scores, kept for the backward of the training path
 // thresh24 != 0: dropout on the probabilities (transformer.py:203), stream (seed) indexed ((b*H + h)*Tq + t)*Lk + key
-template <int DH>
+// OWNER: key j of sequence b (and its value) is read from kv row owner[b*owner_bstride + j*owner_kstride] instead of row b -
+// caches that stay in place under beam search (decoder.py).  Only addresses change: the arithmetic and its order are the
+// same, so the result equals the plain kernel's on the gathered copy bit for bit.  The rows are fetched once, by the lanes
+// that score the keys, and kept in LDS for the context loop.
+template <int DH, bool OWNER>
 __global__ __launch_bounds__(256) void attn_query_fwd_kernel(const bf16* __restrict__ q, int ld_q, const bf16* __restrict__ kv,
                                                             long long kv_bstride, int ld_kv, const int32_t* __restrict__ klen,
                                                             bf16* __restrict__ ctx, float* __restrict__ lse, int B, int Tq, int H,
                                                             int Lk, int causal, int pos0, uint32_t seed, uint32_t thresh24,
-                                                            float inv_keep) {
+                                                            float inv_keep, const int32_t* __restrict__ owner, int owner_bstride,
+                                                            int owner_kstride) {
   __shared__ float sc[4][QA_MAX_KEYS];
+  __shared__ int32_t own[OWNER ? 4 : 1][OWNER ? QA_MAX_KEYS : 1];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   long long item = (long long)blockIdx.x * 4 + wv;                // (b, t, h), h fastest
   const bool live = item < (long long)B * Tq * H;                 // (idle waves of the last block walk item 0 without storing)
@@ -59,11 +65,17 @@ __global__ __launch_bounds__(256) void attn_query_fwd_kernel(const bf16* __restr
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[c * 8 + e] = (float)v[e];
   }
-  const bf16* kb = kv + (size_t)b * kv_bstride + h * DH;
+  const bf16* kb = kv + (OWNER ? (size_t)0 : (size_t)b * kv_bstride) + h * DH;
+  const int32_t* ob = OWNER ? owner + (size_t)b * owner_bstride : nullptr;
   // scores: lane l takes keys l, l + 64, ...
   float mx = -INFINITY;
   for (int j = lane; j < nk; j += 64) {
     const bf16* kp = kb + (size_t)j * ld_kv;
+    if constexpr (OWNER) {
+      const int32_t o = ob[(size_t)j * owner_kstride];
+      own[wv][j] = o;
+      kp += (size_t)o * kv_bstride;
+    }
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < DH / 8; ++c) {
@@ -90,13 +102,14 @@ __global__ __launch_bounds__(256) void attn_query_fwd_kernel(const bf16* __restr
   float acc = 0.f;
   if (lane < DH) {
     const bf16* vb = kb + d + lane;
+    auto val = [&](int jj) { return (float)vb[(size_t)jj * ld_kv + (OWNER ? (size_t)own[wv][jj] * kv_bstride : (size_t)0)]; };
     int j = 0;
     for (; j + 4 <= nk; j += 4) {
-      const float v0 = (float)vb[(size_t)j * ld_kv], v1 = (float)vb[(size_t)(j + 1) * ld_kv];
-      const float v2 = (float)vb[(size_t)(j + 2) * ld_kv], v3 = (float)vb[(size_t)(j + 3) * ld_kv];
+      const float v0 = val(j), v1 = val(j + 1);
+      const float v2 = val(j + 2), v3 = val(j + 3);
       acc += sc[wv][j] * v0 + sc[wv][j + 1] * v1 + sc[wv][j + 2] * v2 + sc[wv][j + 3] * v3;
     }
-    for (; j < nk; ++j) acc += sc[wv][j] * (float)vb[(size_t)j * ld_kv];
+    for (; j < nk; ++j) acc += sc[wv][j] * val(j);
     if (live) out[lane] = (bf16)(nk > 0 ? acc / sum : 0.f);
   }
 }
@@ -179,28 +192,48 @@ __global__ __launch_bounds__(256) void attn_rows_bwd_kernel(const bf16* __restri
 
 extern "C" {
 
-int m3p_attn_rows_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen, void* ctx,
-                      float* lse, int B, int Tq, int H, int dh, int Lk, int causal, int pos0, uint32_t seed, uint32_t thresh24,
-                      float inv_keep, void* stream) {
+// the shared launcher: owner == nullptr is the plain kernel
+static int attn_rows_launch(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen, void* ctx,
+                            float* lse, int B, int Tq, int H, int dh, int Lk, int causal, int pos0, uint32_t seed, uint32_t thresh24,
+                            float inv_keep, const int32_t* owner, int owner_bstride, int owner_kstride, void* stream) {
   if (B <= 0 || Tq <= 0 || H <= 0 || Lk <= 0 || Lk > QA_MAX_KEYS || (dh != 32 && dh != 64)) return M3P_EINVAL;
   if ((ld_q % 8) != 0 || (ld_kv % 8) != 0 || (kv_bstride % 8) != 0 || ((uintptr_t)q & 15) || ((uintptr_t)kv & 15)) return M3P_EINVAL;
   if (ld_kv < 2 * H * dh || ld_q < H * dh) return M3P_EINVAL;
   if ((unsigned long long)B * H * Tq * Lk >= (1ull << 32)) return M3P_EINVAL;       // 32-bit dropout stream index
   const long long items = (long long)B * Tq * H;
   const dim3 grid((unsigned)((items + 3) / 4)), block(256);
-  if (dh == 64)
-    hipLaunchKernelGGL(attn_query_fwd_kernel<64>, grid, block, 0, (hipStream_t)stream, (const bf16*)q, ld_q, (const bf16*)kv,
-                       kv_bstride, ld_kv, klen, (bf16*)ctx, lse, B, Tq, H, Lk, causal, pos0, seed, thresh24, inv_keep);
-  else
-    hipLaunchKernelGGL(attn_query_fwd_kernel<32>, grid, block, 0, (hipStream_t)stream, (const bf16*)q, ld_q, (const bf16*)kv,
-                       kv_bstride, ld_kv, klen, (bf16*)ctx, lse, B, Tq, H, Lk, causal, pos0, seed, thresh24, inv_keep);
+#define M3P_QA_LAUNCH(DH_, OWN_)                                                                                                  \
+  hipLaunchKernelGGL((attn_query_fwd_kernel<DH_, OWN_>), grid, block, 0, (hipStream_t)stream, (const bf16*)q, ld_q, (const bf16*)kv, \
+                     kv_bstride, ld_kv, klen, (bf16*)ctx, lse, B, Tq, H, Lk, causal, pos0, seed, thresh24, inv_keep, owner,         \
+                     owner_bstride, owner_kstride)
+  if (owner) {
+    if (dh == 64) M3P_QA_LAUNCH(64, true); else M3P_QA_LAUNCH(32, true);
+  } else {
+    if (dh == 64) M3P_QA_LAUNCH(64, false); else M3P_QA_LAUNCH(32, false);
+  }
+#undef M3P_QA_LAUNCH
   M3P_CHECK_LAUNCH();
   return M3P_OK;
+}
+
+int m3p_attn_rows_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen, void* ctx,
+                      float* lse, int B, int Tq, int H, int dh, int Lk, int causal, int pos0, uint32_t seed, uint32_t thresh24,
+                      float inv_keep, void* stream) {
+  return attn_rows_launch(q, ld_q, kv, kv_bstride, ld_kv, klen, ctx, lse, B, Tq, H, dh, Lk, causal, pos0, seed, thresh24, inv_keep,
+                          nullptr, 0, 0, stream);
 }
 
 int m3p_attn_query_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen, void* ctx,
                        int B, int Tq, int H, int dh, int Lk, int causal, int pos0, void* stream) {
   return m3p_attn_rows_fwd(q, ld_q, kv, kv_bstride, ld_kv, klen, ctx, nullptr, B, Tq, H, dh, Lk, causal, pos0, 0, 0, 1.f, stream);
+}
+
+int m3p_attn_query_owner_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen,
+                             void* ctx, int B, int Tq, int H, int dh, int Lk, int causal, int pos0, const int32_t* owner,
+                             int owner_bstride, int owner_kstride, void* stream) {
+  if (!owner || owner_bstride < 0 || owner_kstride < 0) return M3P_EINVAL;
+  return attn_rows_launch(q, ld_q, kv, kv_bstride, ld_kv, klen, ctx, nullptr, B, Tq, H, dh, Lk, causal, pos0, 0, 0, 1.f, owner,
+                          owner_bstride, owner_kstride, stream);
 }
 
 int m3p_attn_rows_bwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen,

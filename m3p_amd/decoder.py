@@ -13,6 +13,13 @@ holds, per layer, ONE token-major bf16 tensor [bs, capacity, 2 d] (keys | values
 [bs, S_src, 2 d] for the encoder attention (projected once, at the first step); the reference keeps (k, v) head-major
 tuples under the module ids and concatenates per step.  ``cache['slen']`` has the reference's meaning.
 
+The next word comes from ``ops.vocab_select`` (csrc/select.hip) on a CUDA model: the rows' log-sum-exp and, per sentence,
+the best entries of its beam * V scores straight from the bf16 logits - no fp32 copy, no log_softmax tensor, no topk.  Under
+beam search the caches then stay in place: ``cache['owner']`` (int32 [rows, capacity]) names, per hypothesis and position,
+the row whose slot holds that position's keys / values (``advance_owner`` after every step; ``m3p_attn_query_owner_fwd``
+reads through it), and with ``cache['beam']`` the source's keys / values are kept once per sentence, not once per beam.
+``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, sampling and wider beams run the torch code below unchanged.
+
 This module is forward only; the teacher-forced training pass of the same stream is ``functional.DecoderFn``
 (``TransformerModel.crossfwd`` picks it in training mode), and calling ``decoder_forward`` itself with autograd enabled on
 a model in training mode raises.
@@ -27,6 +34,11 @@ from . import lib as L
 from . import ops
 
 BF16 = torch.bfloat16
+
+# Dispatch of the word selection, like functional.CAUSAL_TILED_MIN_T: a CUDA model takes ops.vocab_select for a step that
+# asks for k <= VOCAB_SELECT_MAX_K entries per sentence (greedy: 1, beam search: 2 * beam_size) where the launcher takes
+# the shape (VS_MAX_K = 16 of csrc/select.hip); 0 sends every call to the torch path.
+VOCAB_SELECT_MAX_K = 16
 
 
 class _ColdWeights:
@@ -91,6 +103,10 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
     ar = model.arena()
     ar.refresh()
     pos0 = int(cache['slen']) if cache is not None else 0
+    # caches that stay in place under beam search (generate_beam): the row that holds each (hypothesis, position), and how
+    # many consecutive rows share one source sentence
+    owner = cache.get('owner') if cache is not None else None
+    beam = int(cache.get('beam', 1)) if cache is not None else 1
     n_new = slen - pos0
     assert n_new >= 1
     x = x.to(dev)
@@ -111,11 +127,17 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
     qscale = 1.0 / math.sqrt(dh)
     cw = None
     if src_enc is not None:
-        assert src_enc.size(0) == bs and src_enc.size(2) == d
+        assert src_enc.size(0) * beam == bs and src_enc.size(2) == d
         S = src_enc.size(1)
         cw = model.decoder_cold_weights()
         src_klen = src_len.to(dev).to(torch.int32).clamp(max=S).contiguous()
+        assert src_klen.size(0) == bs
         src16 = None
+        xowner = None
+        if beam > 1:
+            xowner = cache.get('cross_owner')
+            if xowner is None:
+                cache['cross_owner'] = xowner = (torch.arange(bs, device=dev) // beam).to(torch.int32)
     # without a cache every position is scored at once: the attentions of the training pass, by its rules, without dropout
     tiled = cache is None and slen >= Fn.CAUSAL_TILED_MIN_T
     xtiled = cache is None and src_enc is not None and Fn.cross_attn_tiled(slen, S)
@@ -138,7 +160,8 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
                 store = _self_cache(cache, i, bs, slen, d, dev)
                 store[:, pos0:slen] = kv
                 kv = store
-            ctx = ops.attn_query_fwd(q, kv, None, bs, n_new, H, dh, slen, causal=True, pos0=pos0)
+            assert owner is None or (owner.shape[0] == bs and owner.shape[1] >= slen)
+            ctx = ops.attn_query_fwd(q, kv, None, bs, n_new, H, dh, slen, causal=True, pos0=pos0, owner=owner)
         pre = ops.gemm_nt(ctx, ar.w(a + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(a + 'out_lin.bias'), aux=h16)
         h16, _, _ = ops.layernorm_fwd(pre, ar.p('layer_norm1.%d.weight' % i), ar.p('layer_norm1.%d.bias' % i))
         if cw is not None:
@@ -146,15 +169,23 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
             kvc = cache.get(('cross', i)) if cache is not None else None
             if kvc is None:
                 if src16 is None:
-                    src16 = src_enc.detach().to(device=dev, dtype=BF16).contiguous().view(bs * S, d)
-                kvc = ops.gemm_nt(src16, cw.kv[i], L.EPI_BIAS, bias=cw.bkv[i]).view(bs, S, 2 * d)
+                    src16 = src_enc.detach().to(device=dev, dtype=BF16).contiguous()
+                    if beam > 1:
+                        # The GEMM picks its kernel by the row count, and two kernels add the products in different orders:
+                        # projected on bs / beam * S rows, a few keys / values come out one bf16 ulp off those of the
+                        # expanded source.  So this one projection (the first step only) runs on the row count of the
+                        # torch path; every sentence's rows are `beam` identical copies, of which the cache keeps one.
+                        src16 = src16.unsqueeze(1).expand(bs // beam, beam, S, d).contiguous()
+                    src16 = src16.view(-1, d)
+                kvc = ops.gemm_nt(src16, cw.kv[i], L.EPI_BIAS, bias=cw.bkv[i])
+                kvc = kvc.view(bs // beam, beam, S, 2 * d)[:, 0].contiguous() if beam > 1 else kvc.view(bs, S, 2 * d)
                 if cache is not None:
                     cache[('cross', i)] = kvc
             res2 = ops.attn_cross_fwd(q2, kvc, src_klen, bs, n_new, H, dh, S) if xtiled else None
             if res2 is None:
                 assert i == 0 or not xtiled
                 xtiled = False
-                ctx2 = ops.attn_query_fwd(q2, kvc, src_klen, bs, n_new, H, dh, S)
+                ctx2 = ops.attn_query_fwd(q2, kvc, src_klen, bs, n_new, H, dh, S, owner=xowner)
             else:
                 ctx2 = res2[0]
             pre = ops.gemm_nt(ctx2, cw.out[i], L.EPI_BIAS_DROP_RES, bias=cw.bo[i], aux=h16)
@@ -169,15 +200,41 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
     return h16.view(bs, n_new, d).transpose(0, 1)
 
 
-def word_scores(model, tensor):
-    """PredLayer.get_scores (transformer.py:120-124): (n, d) -> (n, n_words) fp32 on the tied vocabulary matrix."""
+def word_logits16(model, tensor):
+    """The logits of PredLayer.get_scores as the vocabulary GEMM leaves them: (n, d) -> (bf16 [n, V_pad], V); columns V ..
+    V_pad - 1 are not written."""
     ar = model.arena()
     ar.refresh()
     V = model.n_words
     x16 = tensor.detach().to(BF16).reshape(-1, model.dim).contiguous()
     logits = torch.empty((x16.shape[0], ar.V_pad), dtype=BF16, device=x16.device)
     ops.gemm_nt(x16, ar.w('embeddings.weight'), L.EPI_BIAS, bias=ar.p('pred_layer.proj.bias'), out=logits, n=V)
+    return logits, V
+
+
+def word_scores(model, tensor):
+    """PredLayer.get_scores (transformer.py:120-124): (n, d) -> (n, n_words) fp32 on the tied vocabulary matrix."""
+    logits, V = word_logits16(model, tensor)
     return logits[:, :V].float()
+
+
+def advance_owner(owner, beam_idx, next_pos):
+    """The owner table after a beam step.  owner int32 [n, cap]: owner[r, p] = the cache row whose slot p holds position p
+    of the hypothesis now in row r.  Row r continues the hypothesis of row beam_idx[r], so it inherits that row's map; the
+    position the next step writes, next_pos, goes into every row's own slot.  A slot (row, position) is written once - by
+    the step that decodes that position - and never again, so the slots a surviving hypothesis points to stay intact
+    however the beams are re-ordered afterwards."""
+    n = owner.shape[0]
+    new = owner.index_select(0, beam_idx)
+    new[:, next_pos] = torch.arange(n, dtype=owner.dtype, device=owner.device)
+    return new
+
+
+def _select(logits, V, beam_scores, beam, k):
+    res = ops.vocab_select(logits, V, beam_scores, beam, k)
+    if res is None:
+        raise L.M3PError('m3p_vocab_select declined (M3P_ENOTIMPL) a shape m3p_vocab_select_plan took')
+    return res
 
 
 def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None):
@@ -197,14 +254,19 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     gen_len = torch.ones(bs, dtype=torch.long, device=dev)
     unfinished = torch.ones(bs, dtype=torch.long, device=dev)
     cache = {'slen': 0, 'max_len': max_len}
+    # (a launcher that would answer M3P_ENOTIMPL - it is asked once, the answer depends on the shape alone - leaves the torch path)
+    select = (sample_temperature is None and dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
+              and ops.vocab_select_takes(bs, model.n_words, model.arena().V_pad, 1, 1))
     while cur_len < max_len:
         tensor = decoder_forward(model, generated[:cur_len], gen_len, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
         assert tensor.size() == (1, bs, model.dim)
-        scores = word_scores(model, tensor[-1])
-        if sample_temperature is None:
-            next_words = torch.topk(scores, 1)[1].squeeze(1)
+        if select:                     # the first maximum of each row, from the bf16 logits
+            next_words = _select(*word_logits16(model, tensor[-1]), None, 1, 1)[1].squeeze(1)
+        elif sample_temperature is None:
+            next_words = torch.topk(word_scores(model, tensor[-1]), 1)[1].squeeze(1)
         else:
+            scores = word_scores(model, tensor[-1])
             next_words = torch.multinomial(torch.softmax(scores / sample_temperature, dim=1), 1).squeeze(1)
         generated[cur_len] = next_words * unfinished + model.pad_index * (1 - unfinished)
         gen_len.add_(unfinished)
@@ -261,16 +323,23 @@ class BeamHypotheses(object):
 
 
 def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200):
-    """transformer.py:1319-1515: beam search; the beam is folded into the batch dimension (bs * beam_size rows), the key /
-    value caches are re-ordered by the surviving beams' source rows after every step.
+    """transformer.py:1319-1515: beam search; the beam is folded into the batch dimension (bs * beam_size rows).  On the torch
+    path the key / value caches are re-ordered by the surviving beams' source rows after every step; on the select path
+    (module docstring) they stay in place behind cache['owner'] and the source is kept once per sentence.
     -> (decoded (max tgt_len, bs) int64, tgt_len (bs))."""
     assert src_enc.size(0) == src_len.size(0) and beam_size >= 1
     bs = len(src_len)
     n_words = model.n_words
     dev = model.embeddings.weight.device
     src_len = src_len.to(dev)
-    src_enc = src_enc.to(dev).unsqueeze(1).expand((bs, beam_size) + src_enc.shape[1:]).contiguous().view(
-        (bs * beam_size,) + src_enc.shape[1:])
+    n = bs * beam_size
+    select = (dev.type == 'cuda' and 2 * beam_size <= VOCAB_SELECT_MAX_K
+              and ops.vocab_select_takes(n, n_words, model.arena().V_pad, beam_size, 2 * beam_size))
+    if select:
+        src_enc = src_enc.to(dev)
+    else:
+        src_enc = src_enc.to(dev).unsqueeze(1).expand((bs, beam_size) + src_enc.shape[1:]).contiguous().view(
+            (bs * beam_size,) + src_enc.shape[1:])
     src_len = src_len.unsqueeze(1).expand(bs, beam_size).contiguous().view(-1)
     generated = torch.full((max_len, bs * beam_size), model.pad_index, dtype=torch.long, device=dev)
     generated[0].fill_(model.eos_index)
@@ -283,15 +352,21 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     beam_scores = beam_scores.view(-1)
     cur_len = 1
     cache = {'slen': 0, 'max_len': max_len}
+    if select:
+        cache['beam'] = beam_size
+        cache['owner'] = torch.arange(n, dtype=torch.int32, device=dev)[:, None].expand(n, max_len).contiguous()
     done = [False] * bs
     while cur_len < max_len:
         lengths = torch.full((bs * beam_size,), cur_len, dtype=torch.long, device=dev)
         tensor = decoder_forward(model, generated[:cur_len], lengths, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
         assert tensor.size() == (1, bs * beam_size, model.dim)
-        scores = torch.log_softmax(word_scores(model, tensor[-1]), dim=-1)
-        _scores = (scores + beam_scores[:, None]).view(bs, beam_size * n_words)
-        next_scores, next_words = torch.topk(_scores, 2 * beam_size, dim=1, largest=True, sorted=True)
+        if select:
+            next_scores, next_words, _ = _select(*word_logits16(model, tensor[-1]), beam_scores, beam_size, 2 * beam_size)
+        else:
+            scores = torch.log_softmax(word_scores(model, tensor[-1]), dim=-1)
+            _scores = (scores + beam_scores[:, None]).view(bs, beam_size * n_words)
+            next_scores, next_words = torch.topk(_scores, 2 * beam_size, dim=1, largest=True, sorted=True)
         next_scores_h, next_words_h = next_scores.tolist(), next_words.tolist()       # one host copy per step
         next_batch_beam = []
         for sent in range(bs):
@@ -318,9 +393,12 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
         beam_idx = torch.tensor([v[2] for v in next_batch_beam], dtype=torch.long, device=dev)
         generated = generated[:, beam_idx]
         generated[cur_len] = beam_words
-        for k in list(cache.keys()):
-            if isinstance(k, tuple):                       # key / value tensors follow their beams
-                cache[k] = cache[k].index_select(0, beam_idx)
+        if select:                                         # key / value tensors stay; the map to them follows the beams
+            cache['owner'] = advance_owner(cache['owner'], beam_idx, cur_len)
+        else:
+            for k in list(cache.keys()):
+                if isinstance(k, tuple):                   # key / value tensors follow their beams
+                    cache[k] = cache[k].index_select(0, beam_idx)
         cur_len += 1
         if all(done):
             break

@@ -58,6 +58,11 @@ SIGNATURES = {
     'm3p_attn_fwd': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _u32, _u32, _f, _p]),
     'm3p_attn_bwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _u32, _u32, _f, _p]),
     'm3p_attn_query_fwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    'm3p_attn_query_owner_fwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p]),
+    'm3p_vocab_select_max_k': (_i, []),
+    'm3p_vocab_select_plan': (_i, [_i, _i, _i, _i, _i]),
+    'm3p_vocab_select_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
+    'm3p_vocab_select': (_i, [_p, _i, _i, _i, _p, _i, _i, _p, C.c_size_t, _p, _p, _p, _p]),
     'm3p_attn_rows_fwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _u32, _u32, _f, _p]),
     'm3p_attn_rows_bwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _f, _u32, _u32, _f, _p]),
     'm3p_attn_causal_fwd': (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _u32, _u32, _f, _p]),

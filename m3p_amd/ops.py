@@ -334,16 +334,77 @@ def attn_bwd(qkv, keylen, ctx, dctx, lse, B, S, H, dh, dbias_qkv=None, seed=0, p
     return dqkv
 
 
-def attn_query_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, pos0=0):
+def attn_query_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, pos0=0, owner=None):
     """Decoder-inference attention: q bf16 [B*Tq, >= H*dh] (scaled), kv bf16 [B, >= Lk, >= 2*H*dh] (keys | values per
-    cached position), klen int32 [B] or None -> ctx bf16 [B*Tq, H*dh]  (csrc/decode.hip)."""
+    cached position), klen int32 [B] or None -> ctx bf16 [B*Tq, H*dh]  (csrc/decode.hip).
+    owner: int32 tensor, [B, >= Lk] (a kv row per (sequence, key): key j of sequence b is read from kv[owner[b, j], j]) or
+    [B] (a kv row per sequence); kv then holds any number of rows and every entry of owner must name one of them."""
     _chk_bf16(q, kv)
-    assert q.stride(1) == 1 and kv.dim() == 3 and kv.stride(2) == 1 and kv.shape[0] == B and kv.shape[1] >= Lk
+    assert q.stride(1) == 1 and kv.dim() == 3 and kv.stride(2) == 1 and kv.shape[1] >= Lk
     ctx = torch.empty((B * Tq, H * dh), dtype=BF16, device=q.device)
-    rc = L.load().m3p_attn_query_fwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
-                                     ctx.data_ptr(), B, Tq, H, dh, Lk, 1 if causal else 0, pos0, L.stream())
-    L.check(rc, 'm3p_attn_query_fwd')
+    if owner is None:
+        assert kv.shape[0] == B
+        rc = L.load().m3p_attn_query_fwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
+                                         ctx.data_ptr(), B, Tq, H, dh, Lk, 1 if causal else 0, pos0, L.stream())
+        L.check(rc, 'm3p_attn_query_fwd')
+        return ctx
+    assert owner.dtype == torch.int32 and owner.is_cuda and owner.shape[0] == B and owner.dim() in (1, 2)
+    assert owner.dim() == 1 or (owner.shape[1] >= Lk and owner.stride(1) == 1)
+    if _DEBUG_CHECKS:
+        used = owner if owner.dim() == 1 else owner[:, :Lk]
+        assert int(used.min()) >= 0 and int(used.max()) < kv.shape[0], 'owner names a row outside the key / value tensor'
+    rc = L.load().m3p_attn_query_owner_fwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
+                                           ctx.data_ptr(), B, Tq, H, dh, Lk, 1 if causal else 0, pos0, owner.data_ptr(),
+                                           owner.stride(0), 1 if owner.dim() == 2 else 0, L.stream())
+    L.check(rc, 'm3p_attn_query_owner_fwd')
     return ctx
+
+
+_ENOTIMPL = -2          # M3P_ENOTIMPL of include/m3p_hip.h
+
+
+def vocab_select_max_k():
+    """VS_MAX_K of csrc/select.hip: the most entries per sentence m3p_vocab_select returns."""
+    return int(L.load().m3p_vocab_select_max_k())
+
+
+def vocab_select_takes(n, V, ld, beam, k):
+    """Does the launcher of vocab_select take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
+    rc = L.load().m3p_vocab_select_plan(n, V, ld, beam, k)
+    if rc == _ENOTIMPL:
+        return False
+    L.check(rc, 'm3p_vocab_select_plan')
+    return True
+
+
+def vocab_select(logits, V, beam_scores, beam, k):
+    """Word selection of a decoding step (csrc/select.hip): logits bf16 [n, ld >= V] (n = bs * beam rows, columns past V
+    hold anything), beam_scores fp32 [n] or None (zeros) -> (scores fp32 [bs, k], flat_idx int64 [bs, k], lse fp32 [n]):
+    lse = the rows' log-sum-exp over V columns, the score of (row r, word w) = (float(logits[r, w]) - lse[r]) + beam_scores[r]
+    in fp32, and per sentence the first k of its beam * V entries by score descending, beam ascending, logit descending, word
+    ascending, flat_idx = beam * V + word.  None when the launcher does not take the shape (M3P_ENOTIMPL: k > 16, beam > 64)."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    n = logits.shape[0]
+    assert n % beam == 0 and logits.shape[1] >= V
+    if beam_scores is not None:
+        assert beam_scores.dtype == torch.float32 and beam_scores.is_cuda and beam_scores.is_contiguous() and beam_scores.numel() == n
+    lib = L.load()
+    rc = lib.m3p_vocab_select_plan(n, V, logits.stride(0), beam, k)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_vocab_select_plan')
+    bs = n // beam
+    dev = logits.device
+    ws_bytes = lib.m3p_vocab_select_workspace_bytes(n, V, k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    scores = torch.empty((bs, k), dtype=torch.float32, device=dev)
+    flat_idx = torch.empty((bs, k), dtype=torch.int64, device=dev)
+    lse = torch.empty((n,), dtype=torch.float32, device=dev)
+    rc = lib.m3p_vocab_select(logits.data_ptr(), logits.stride(0), n, V, L.ptr(beam_scores), beam, k, ws.data_ptr(), ws_bytes,
+                              scores.data_ptr(), flat_idx.data_ptr(), lse.data_ptr(), L.stream())
+    L.check(rc, 'm3p_vocab_select')
+    return scores, flat_idx, lse
 
 
 def attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, seed=0, p_drop=0.0):

@@ -1,37 +1,217 @@
 #!/usr/bin/env python3
-"""Decode-step timing of the causal decoder (m3p_amd/decoder.py) at the M3P-base size: 12 layers / 768 wide / 12 heads,
-V = 250 002, a source of 36 regions + 100 tokens; greedy and beam search.   python tools/decode_bench.py [bs] [beam]"""
-import os, sys, time
+"""A/B of the decoding step inside ONE process: the torch path of m3p_amd/decoder.py (fp32 copy of the logits, log_softmax,
+topk over beam * V columns, index_select of every layer's caches, the source expanded per beam: decoder.VOCAB_SELECT_MAX_K = 0)
+against the select path (csrc/select.hip on the bf16 logits, caches in place behind cache['owner'], the source once per
+sentence), on the cfg2 decoder geometry - 12 layers / 768 wide / 12 heads, V = 250 002, S = 164 source rows - with seeded
+weights, the <EOS> bias pushed far down so that no sentence ends early, early_stopping = False, max_len = 64:
+    generate_beam  32 sentences x beam 4
+    generate_beam  64 sentences x beam 5
+    generate       128 sentences, greedy
+Every run is warmed up on both paths, then timed in three alternating pairs with device events around a window that ends in
+a synchronise; ms per decoding step = window / (max_len - 1).  The outputs of the two paths on the timed inputs are compared
+(tokens and lengths) and every sentence that differs is reported.  It fails without a GPU.
+    timeout -k 10 900 python tools/decode_bench.py > profiles/decode_select_vs_torch.txt
+Kernel shares come from a run of its own under the profiler, select path only (the timings above are taken with it off):
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/decode_bench.py --trace beam4
+    python tools/decode_bench.py --stats <dir>/.../*_kernel_stats.csv beam4 >> profiles/decode_select_vs_torch.txt
+which gives the selection kernels' achieved bytes/s (bytes = n * V * 2 per step, counted here) against the HBM peak, and the
+share of the summed KERNEL time (not of the step's wall time: host gaps between launches are not in it) that goes to
+kernels other than the project's own, with the largest of those listed.  The round-2 form of this tool (one shape from the
+command line, host clock; it wrote profiles/r02_decode_bench.txt) is the file as of the commit named in that profile."""
+import csv
+import os
+import sys
+
 import torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from m3p_amd import synth
-from m3p_amd.model.transformer import TransformerModel
 
-bs = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-beam = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-P = synth.model_params(768, 12, 12, 250002, n_dec_layers=12, n_langs=2, id2lang={0: 'en', 1: 'zh'}, lang2id={'en': 0, 'zh': 1})
-torch.manual_seed(0)
-m = TransformerModel(P, is_encoder=False, with_output=True, is_crossModal=True).cuda().eval()
-with torch.no_grad():
-    m.pred_layer.proj.bias[synth.EOS] = -1e4          # nobody stops early: every run decodes max_len - 1 steps
-S, max_len = 136, 33
-src = torch.randn(bs, S, 768, device='cuda')
-src_len = torch.full((bs,), S, dtype=torch.long, device='cuda')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from m3p_amd import decoder, synth   # noqa: E402
+
+D, HEADS, LAYERS, V, S, MAX_LEN = 768, 12, 12, 250002, 164, 64
+RUNS = {'beam4': ('generate_beam', 32, 4), 'beam5': ('generate_beam', 64, 5), 'greedy': ('generate', 128, 1)}
+PAIRS = 3
+HBM_PEAK = 8.0e12               # bytes/s of an MI355X (HBM3E)
 
 
-def timed(fn, reps=3):
-    fn()
+def model():
+    from m3p_amd.model.transformer import TransformerModel
+    P = synth.model_params(D, HEADS, LAYERS, V, n_dec_layers=LAYERS, n_langs=2, id2lang={0: 'en', 1: 'zh'}, lang2id={'en': 0, 'zh': 1})
+    torch.manual_seed(0)
+    m = TransformerModel(P, is_encoder=False, with_output=True, is_crossModal=True).cuda().eval()
+    with torch.no_grad():
+        m.pred_layer.proj.bias[synth.EOS] = -1e4          # nobody stops early: every run decodes max_len - 1 steps
+    return m
+
+
+def inputs(bs):
+    g = torch.Generator(device='cuda').manual_seed(bs)
+    src = torch.randn(bs, S, D, device='cuda', generator=g)
+    src_len = torch.randint(S // 2, S + 1, (bs,), device='cuda', generator=g)
+    src_len[0] = S
+    return src, src_len
+
+
+def call(m, kind, src, src_len, beam):
+    with torch.no_grad():
+        if kind == 'generate':
+            return m.generate(src, src_len, 1, max_len=MAX_LEN)
+        return m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=MAX_LEN)
+
+
+def timed(fn):
     torch.cuda.synchronize()
-    t = time.perf_counter()
-    for _ in range(reps):
-        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
     torch.cuda.synchronize()
-    return (time.perf_counter() - t) / reps
+    return e0.elapsed_time(e1) / (MAX_LEN - 1), out
 
 
-with torch.no_grad():
-    dt = timed(lambda: m.generate(src, src_len, 1, max_len=max_len))
-    print('greedy  bs=%d: %.2f ms per step, %.0f tokens/s' % (bs, dt / (max_len - 1) * 1e3, bs * (max_len - 1) / dt))
-    dt = timed(lambda: m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=max_len))
-    print('beam %d  bs=%d (%d rows): %.2f ms per step, %.0f sentences x tokens/s'
-          % (beam, bs, bs * beam, dt / (max_len - 1) * 1e3, bs * (max_len - 1) / dt))
+def with_rule(rule, fn):
+    saved = decoder.VOCAB_SELECT_MAX_K
+    decoder.VOCAB_SELECT_MAX_K = rule
+    try:
+        return fn()
+    finally:
+        decoder.VOCAB_SELECT_MAX_K = saved
+
+
+def differing(a, b):
+    """Sentences whose tokens or lengths differ between two (tokens (len, bs), lengths (bs)) results."""
+    (ta, la), (tb, lb) = a, b
+    out = []
+    for s in range(la.shape[0]):
+        n = int(la[s])
+        if int(lb[s]) != n or not torch.equal(ta[:n, s], tb[:n, s]):
+            out.append(s)
+    return out
+
+
+def selection_gaps(m, src, src_len, beam):
+    """Where do the two selections part?  One generate_beam on the select path; at every step the torch selection
+    (log_softmax of the fp32 logits + beam_scores, topk) is taken from the SAME logits.  The hidden states of the two paths
+    are bit-identical up to a sentence's first differing selection, so that step is where its outputs part.  -> per sentence
+    that ever differs: (sentence, step, |torch score of torch's entry - torch score of the kernel's entry|) at the first
+    differing rank of its first differing step."""
+    real, step, first = decoder._select, [0], {}
+
+    def both(logits, V_, beam_scores, beam_, k):
+        res = real(logits, V_, beam_scores, beam_, k)
+        t = (torch.log_softmax(logits[:, :V_].float(), dim=-1) + beam_scores[:, None]).view(-1, beam_ * V_)
+        _, ti = torch.topk(t, k, dim=1, largest=True, sorted=True)
+        for s in (ti != res[1]).any(1).nonzero().view(-1).tolist():
+            if s not in first:
+                j = int((ti[s] != res[1][s]).nonzero()[0])
+                first[s] = (step[0], abs(float(t[s, ti[s, j]]) - float(t[s, res[1][s, j]])))
+        step[0] += 1
+        return res
+    decoder._select = both
+    try:
+        call(m, 'generate_beam', src, src_len, beam)
+    finally:
+        decoder._select = real
+    return sorted((s, st, g) for s, (st, g) in first.items())
+
+
+def bench(m):
+    print('decoding step, %d layers, d = %d, V = %d, S = %d, max_len = %d; ms per decoding step, %d alternating pairs; '
+          'ratio = torch / select' % (LAYERS, D, V, S, MAX_LEN, PAIRS))
+    rule = decoder.VOCAB_SELECT_MAX_K
+    for name, (kind, bs, beam) in RUNS.items():
+        src, src_len = inputs(bs)
+        one = lambda: call(m, kind, src, src_len, beam)   # noqa: E731
+        with_rule(0, one)                                  # warm-up of every shape on both paths
+        with_rule(rule, one)
+        old, new = [], []
+        for _ in range(PAIRS):
+            t, out_old = timed(lambda: with_rule(0, one))
+            old.append(t)
+            t, out_new = timed(lambda: with_rule(rule, one))
+            new.append(t)
+        ratios = [a / b for a, b in zip(old, new)]
+        rows = bs * beam
+        print('%-6s %-13s bs %3d beam %d (%3d rows)  torch ms %s  select ms %s  ratio %s  select %s' % (
+            name, kind, bs, beam, rows, ' '.join('%7.3f' % v for v in old), ' '.join('%7.3f' % v for v in new),
+            ' '.join('%5.2f' % v for v in ratios), 'wins all three' if min(ratios) > 1 else 'does NOT win all three'))
+        assert out_old[0].shape[0] == MAX_LEN and out_new[0].shape[0] == MAX_LEN, 'a sentence ended early'
+        diff = differing(out_old, out_new)
+        print('       outputs on the timed inputs: %d of %d sentences differ between the paths%s' % (
+            len(diff), bs, (' ' + str(diff)) if diff else ''))
+        print('       bytes of logits per step (n * V * 2): %.1f MB' % (rows * V * 2 / 1e6))
+        if kind == 'generate_beam':
+            gaps = selection_gaps(m, src, src_len, beam)
+            print('       selections on the same logits (kernel against log_softmax + topk): %d of %d sentences see a different '
+                  'list at some step; score gap at the first difference: max %.3g%s' % (
+                      len(gaps), bs, max([g for _, _, g in gaps] or [0.0]),
+                      ''.join('\n         sentence %d step %d gap %.3g' % e for e in gaps)))
+
+
+def trace(m, name):
+    kind, bs, beam = RUNS[name]
+    src, src_len = inputs(bs)
+    call(m, kind, src, src_len, beam)
+    torch.cuda.synchronize()
+    t, _ = timed(lambda: call(m, kind, src, src_len, beam))
+    print('%s under the profiler: %.3f ms per step (slower than the timed runs: tracing)' % (name, t))
+
+
+def own_kernel(kname):
+    """Is this a kernel of libm3p_hip.so?  They all live in a top-level anonymous namespace: the demangled name starts with
+    '(anonymous namespace)::' (behind an optional 'void '), the mangled one with '_ZN12_GLOBAL__N_1'.  Most torch kernels
+    carry an anonymous namespace too, but inside at::native:: or in a template argument - never in front."""
+    k = kname.strip()
+    if k.startswith('void '):
+        k = k[5:]
+    if k.startswith('_ZN12_GLOBAL__N_1'):
+        return True
+    pre = '(anonymous namespace)::'
+    if not k.startswith(pre):
+        return False
+    own_name = k[len(pre):].split('<')[0].split('(')[0]       # the kernel's own name, in front of template and call arguments
+    return '::' not in own_name
+
+
+def stats(path, name):
+    """Kernel shares of a `--trace NAME` run from rocprofv3's kernel stats (Name, Calls, TotalDurationNs, ...): shares of
+    the summed KERNEL time, not of the step's wall time (host gaps between launches are in neither term)."""
+    kind, bs, beam = RUNS[name]
+    rows = bs * beam
+    total = own = 0.0
+    sel, others = {}, []
+    for r in csv.DictReader(open(path)):
+        ns, calls, kname = float(r['TotalDurationNs']), int(r['Calls']), r['Name']
+        total += ns
+        if own_kernel(kname):
+            own += ns
+        else:
+            others.append((ns, calls, kname))
+        for key in ('vs_chunk_kernel', 'vs_merge_kernel'):
+            if key in kname:
+                sel[key] = (ns / calls, calls)
+    print('\nkernel shares, %s (%d rows), select path, from a profiled run of its own (warm-up + one timed run)' % (name, rows))
+    for key, (avg, calls) in sorted(sel.items()):
+        print('  %-16s %5d calls  %8.1f us per call' % (key, calls, avg / 1e3))
+    if len(sel) == 2:
+        both = sum(v[0] for v in sel.values())
+        bps = rows * V * 2 / (both * 1e-9)
+        print('  selection (both kernels): %.1f us per step for %.1f MB of logits = %.2f TB/s, %.0f %% of the %.1f TB/s HBM peak' % (
+            both / 1e3, rows * V * 2 / 1e6, bps / 1e12, 100 * bps / HBM_PEAK, HBM_PEAK / 1e12))
+    print('  kernel time outside the project\'s kernels: %.1f %% of %.1f ms of kernel time (host gaps between launches are not '
+          'kernel time and are in neither figure)' % (100 * (total - own) / total, total / 1e6))
+    print('  the largest kernels counted as NOT the project\'s (check the classification by eye):')
+    for ns, calls, kname in sorted(others, reverse=True)[:8]:
+        print('    %6.2f %%  %6d calls  %s' % (100 * ns / total, calls, kname[:150]))
+
+
+if __name__ == '__main__':
+    if len(sys.argv) >= 4 and sys.argv[1] == '--stats':
+        stats(sys.argv[2], sys.argv[3])
+        sys.exit(0)
+    assert torch.cuda.is_available(), 'decode_bench.py measures on a GPU'
+    if len(sys.argv) >= 3 and sys.argv[1] == '--trace':
+        trace(model(), sys.argv[2])
+    else:
+        print(torch.cuda.get_device_name(0))
+        bench(model())
