@@ -6,7 +6,7 @@
 // softmax (the reference's is fp32 too, :202), bf16 context out.
 // The training forms below (m3p_attn_rows_fwd / _bwd) are the complete fallback of the teacher-forced passes: where the
 // dispatch rules of functional.py select them and their launchers take the shape, the self-attention of such a pass runs on
-// attn_causal.hip and its attention over the source encoding on attn_cross.hip (tiled MFMA kernels, no atomics); these
+// attn_tiled.hip and its attention over the source encoding on the same file's source-mask kernels (tiled MFMA, no atomics); these
 // serve the shapes below the rules' thresholds or outside the tiled launchers' range.
 #include "common.hpp"
 

@@ -7,8 +7,8 @@ One decoding step is latency / HBM work: one new token per sequence, every weigh
 bf16 GEMM of the training path (fused bias, 1/sqrt(dh), residual and GELU epilogues), attention on
 ``m3p_attn_query_fwd`` (csrc/decode.hip: one wave per (sequence, head, query) over the cached keys / values).  A call
 WITHOUT a cache - the teacher-forced scoring pass of the evaluations, every target position at once - takes the tiled MFMA
-forwards of the training pass instead (csrc/attn_causal.hip for the self-attention, csrc/attn_cross.hip over the source
-encoding) where the dispatch rules of ``functional`` pick them and the launchers take the shape.  The cache
+forwards of the training pass instead (csrc/attn_tiled.hip: its causal kernels for the self-attention, its source-mask
+kernels over the source encoding) where the dispatch rules of ``functional`` pick them and the launchers take the shape.  The cache
 holds, per layer, ONE token-major bf16 tensor [bs, capacity, 2 d] (keys | values) for the self-attention and one
 [bs, S_src, 2 d] for the encoder attention (projected once, at the first step); the reference keeps (k, v) head-major
 tuples under the module ids and concatenates per step.  ``cache['slen']`` has the reference's meaning.

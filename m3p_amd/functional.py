@@ -1053,13 +1053,13 @@ N_DEC_ARGS = 12     # positional arguments of DecoderFn.forward
 
 # Self-attention of a DecoderFn pass (the causal language-model step, whose stream batches are bptt long in every lane, and the
 # teacher-forced pass of the seq2seq steps alike: klen = None, a position-only mask) runs on the tiled MFMA kernels of
-# csrc/attn_causal.hip from this sequence length on, where their launcher takes the shape; below it on the rows kernels.
+# csrc/attn_tiled.hip from this sequence length on, where their launcher takes the shape; below it on the rows kernels.
 # 32 is the smallest measured T (tools/attn_causal_bench.py, profiles/attn_causal_vs_rows.txt): the tiled pair already wins
 # there, 9.9x, in all three alternations - and at the seq2seq shapes (tools/attn_cross_bench.py,
 # profiles/attn_cross_vs_rows.txt), so a source encoding does not change the rule.
 CAUSAL_TILED_MIN_T = 32
 
-# Attention over the source encoding in the same pass runs on the tiled MFMA kernels of csrc/attn_cross.hip where this rule
+# Attention over the source encoding in the same pass runs on the source-mask kernels of csrc/attn_tiled.hip where this rule
 # says so and their launcher takes the shape, otherwise on the rows kernels.  The constants are the smallest measured target
 # and source lengths (tools/attn_cross_bench.py, profiles/attn_cross_vs_rows.txt): the tiled pair wins all three
 # alternations at every measured (Tq, S) from there on; nothing below was measured, and below it the rows kernels stay.
@@ -1068,7 +1068,7 @@ CROSS_TILED_MIN_S = 36
 
 
 def cross_attn_tiled(Tq, S):
-    """The dispatch rule of the encoder-attention sub-layer: True = tiled kernels (csrc/attn_cross.hip)."""
+    """The dispatch rule of the encoder-attention sub-layer: True = tiled kernels (csrc/attn_tiled.hip)."""
     return Tq >= CROSS_TILED_MIN_TQ and S >= CROSS_TILED_MIN_S
 
 
@@ -1077,8 +1077,8 @@ class DecoderFn(torch.autograd.Function):
     translation / auto-encoding steps (transformer.py:1005-1102; caller xtrainer.py:1383-1441).  Text embedding assembly as
     in the non-causal stream, then per layer causal self-attention -> LN1 -> attention over the source encoding -> LN1.5
     -> FFN -> LN2.  Both attentions run on tiled MFMA kernels without atomics where a measured rule says so and the launcher
-    takes the shape - the self-attention on csrc/attn_causal.hip from CAUSAL_TILED_MIN_T on (with or without a source
-    encoding), the attention over the source encoding on csrc/attn_cross.hip where cross_attn_tiled(T, S) - and otherwise on
+    takes the shape - the self-attention on the causal kernels of csrc/attn_tiled.hip from CAUSAL_TILED_MIN_T on (with or without a source
+    encoding), the attention over the source encoding on its source-mask kernels where cross_attn_tiled(T, S) - and otherwise on
     the rows kernels (csrc/decode.hip: a wave per (sequence, head, query)); every projection, LayerNorm and the embedding
     assembly are the encoder's kernels.  The
     gradient wrt src_enc is returned to autograd (it flows on into the encoder pass that produced it); parameter

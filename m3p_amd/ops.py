@@ -435,22 +435,27 @@ def attn_rows_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, causal=False
     return dq, dkv
 
 
+def _attn_tiled_fwd_out(out, B, T, H, dh, device):
+    """(ctx bf16 [B*T, H*dh], lse fp32 [B, H, T]) of a tiled forward: ``out`` checked, or fresh."""
+    if out is None:
+        return (torch.empty((B * T, H * dh), dtype=BF16, device=device), torch.empty((B, H, T), dtype=torch.float32, device=device))
+    ctx, lse = out
+    assert ctx.dtype == BF16 and ctx.is_contiguous() and ctx.shape == (B * T, H * dh)
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, T)
+    return ctx, lse
+
+
 def attn_causal_fwd(qkv, B, T, H, dh, seed=0, p_drop=0.0, out=None):
-    """Causal self-attention of a decoder-only training pass on the tiled MFMA kernels (csrc/attn_causal.hip): qkv bf16
+    """Causal self-attention of a decoder-only training pass on the tiled MFMA kernels (csrc/attn_tiled.hip): qkv bf16
     [B*T, >= 3*H*dh] (q scaled | k | v) -> (ctx bf16 [B*T, H*dh], lse fp32 [B, H, T]), the results of
     attn_rows_fwd(causal=True, klen=None, Lk=T) under the same seed.  Returns None when the kernels do not take the shape
     (M3P_ENOTIMPL: dh not in {32, 64}, T > 512, ...) - the caller then runs the rows kernels.  out = (ctx, lse) to write into."""
     _chk_bf16(qkv)
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[0] == B * T and qkv.shape[1] >= 3 * H * dh
-    if out is not None:
-        ctx, lse = out
-        assert ctx.dtype == BF16 and ctx.is_contiguous() and ctx.shape == (B * T, H * dh)
-        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, T)
-    else:
-        ctx = torch.empty((B * T, H * dh), dtype=BF16, device=qkv.device)
-        lse = torch.empty((B, H, T), dtype=torch.float32, device=qkv.device)
-    rc = L.load().m3p_attn_causal_fwd(qkv.data_ptr(), qkv.stride(0), ctx.data_ptr(), lse.data_ptr(), B, T, H, dh, seed,
-                                      L.thresh24(p_drop), 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+    ctx, lse = _attn_tiled_fwd_out(out, B, T, H, dh, qkv.device)
+    th, ik = _drop_args(p_drop)
+    rc = L.load().m3p_attn_causal_fwd(qkv.data_ptr(), qkv.stride(0), ctx.data_ptr(), lse.data_ptr(), B, T, H, dh, seed, th, ik,
+                                      L.stream())
     if rc == -2:            # (M3P_ENOTIMPL)
         return None
     L.check(rc, 'm3p_attn_causal_fwd')
@@ -468,9 +473,9 @@ def attn_causal_bwd(qkv, dctx, lse, B, T, H, dh, qscale, seed=0, p_drop=0.0, out
         assert dqkv.dtype == BF16 and dqkv.stride(1) == 1 and dqkv.shape == (B * T, 3 * H * dh)
     else:
         dqkv = torch.empty((B * T, 3 * H * dh), dtype=BF16, device=qkv.device)
+    th, ik = _drop_args(p_drop)
     rc = L.load().m3p_attn_causal_bwd(qkv.data_ptr(), qkv.stride(0), dctx.data_ptr(), lse.data_ptr(), dqkv.data_ptr(),
-                                      dqkv.stride(0), B, T, H, dh, qscale, seed, L.thresh24(p_drop),
-                                      1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+                                      dqkv.stride(0), B, T, H, dh, qscale, seed, th, ik, L.stream())
     if rc == -2:            # (M3P_ENOTIMPL)
         return None
     L.check(rc, 'm3p_attn_causal_bwd')
@@ -478,7 +483,7 @@ def attn_causal_bwd(qkv, dctx, lse, B, T, H, dh, qscale, seed=0, p_drop=0.0, out
 
 
 def attn_cross_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=0, p_drop=0.0, out=None):
-    """Attention over a source encoding in a teacher-forced decoder pass on the tiled MFMA kernels (csrc/attn_cross.hip):
+    """Attention over a source encoding in a teacher-forced decoder pass on the tiled MFMA kernels (csrc/attn_tiled.hip):
     operands as attn_rows_fwd(causal=False) -> (ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq]), its results under the same
     seed; key / value rows at or past klen[b] may hold anything.  Returns None when the kernels do not take the shape
     (M3P_ENOTIMPL: dh not in {32, 64}, Tq > 512, Lk > 1024, ...) - the caller then runs the rows kernels.
@@ -486,16 +491,10 @@ def attn_cross_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=0, p_drop=0.0, out=None):
     _chk_bf16(q, kv)
     assert q.dim() == 2 and q.stride(1) == 1 and q.shape[0] == B * Tq
     assert kv.dim() == 3 and kv.stride(2) == 1 and kv.shape[0] == B and kv.shape[1] >= Lk
-    if out is not None:
-        ctx, lse = out
-        assert ctx.dtype == BF16 and ctx.is_contiguous() and ctx.shape == (B * Tq, H * dh)
-        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, H, Tq)
-    else:
-        ctx = torch.empty((B * Tq, H * dh), dtype=BF16, device=q.device)
-        lse = torch.empty((B, H, Tq), dtype=torch.float32, device=q.device)
+    ctx, lse = _attn_tiled_fwd_out(out, B, Tq, H, dh, q.device)
+    th, ik = _drop_args(p_drop)
     rc = L.load().m3p_attn_cross_fwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
-                                     ctx.data_ptr(), lse.data_ptr(), B, Tq, H, dh, Lk, seed, L.thresh24(p_drop),
-                                     1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+                                     ctx.data_ptr(), lse.data_ptr(), B, Tq, H, dh, Lk, seed, th, ik, L.stream())
     if rc == -2:            # (M3P_ENOTIMPL)
         return None
     L.check(rc, 'm3p_attn_cross_fwd')
@@ -518,10 +517,10 @@ def attn_cross_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, seed=0, p_d
     else:
         dq = torch.empty((B * Tq, d), dtype=BF16, device=q.device)
         dkv = torch.empty((B, Lk, 2 * d), dtype=BF16, device=q.device)
+    th, ik = _drop_args(p_drop)
     rc = L.load().m3p_attn_cross_bwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), L.ptr(klen),
                                      dctx.data_ptr(), lse.data_ptr(), dq.data_ptr(), dq.stride(0), dkv.data_ptr(),
-                                     dkv.stride(1), B, Tq, H, dh, Lk, qscale, seed, L.thresh24(p_drop),
-                                     1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0, L.stream())
+                                     dkv.stride(1), B, Tq, H, dh, Lk, qscale, seed, th, ik, L.stream())
     if rc == -2:            # (M3P_ENOTIMPL)
         return None
     L.check(rc, 'm3p_attn_cross_bwd')

@@ -1,32 +1,22 @@
-"""Tiled causal self-attention of the causal language-model pass (csrc/attn_causal.hip: m3p_attn_causal_fwd / _bwd) against
+"""Tiled causal self-attention of the causal language-model pass (csrc/attn_tiled.hip: m3p_attn_causal_fwd / _bwd) against
 fp64 torch autograd on the same bf16 operands, with the position-only causal mask and the dropout keep mask of the RNG twin
 (the stream index of the rows kernels, so the two implementations are interchangeable under one seed).
 
 Shapes are the smallest that reach each path of the kernels (blocks of 64 queries / keys, 16 per wave): one key, less than
 a tile, exactly one block, one row over, a ragged third block, the workload's T = 256, one short of the cap and the cap.
 Outputs live inside larger poisoned buffers: an unwritten element reads NaN, and the guard rows around them must keep their
-bits.  The CPU part reads the compiler's resource summary of every instantiation."""
-import os
-import re
-import subprocess
-
+bits.  (The compiler's resource summary of every instantiation is read in test_attn_tiled.py.)"""
 import numpy as np
 import pytest
 import torch
 
 from tests.util import (ATTN_CTX_RTOL, ATTN_DS_FLOOR, ATTN_DS_RTOL, GLOBAL_ATTN_CTX, GLOBAL_ATTN_GRAD, ROW_FLOOR,
-                        assert_bits_equal, assert_block_bound, poisoned_outputs, rel_l2)
+                        assert_bits_equal, assert_block_bound, assert_guards, guarded, heads, poisoned_outputs, rel_l2)
 
 BF16 = torch.bfloat16
 SEED = 4242
-GUARD = 3                       # guard rows before and after every output
 SHAPES = [(2, 1, 2, 32, 0.0), (3, 17, 4, 32, 0.1), (2, 64, 2, 64, 0.1), (2, 65, 12, 64, 0.1), (1, 130, 4, 64, 0.0),
           (2, 256, 12, 64, 0.1), (1, 511, 2, 64, 0.1), (1, 512, 2, 32, 0.1)]
-
-
-def _heads(x, B, T, H, dh):
-    """[B*T, H*dh] -> [B, H, T, dh]: one block per (sequence, head, row)."""
-    return x.reshape(B, T, H, dh).transpose(1, 2)
 
 
 def _inputs(B, T, H, dh):
@@ -42,7 +32,7 @@ def _reference(qkv, dctx, B, T, H, dh, p):
     """fp64 autograd -> ctx, lse, dq (of the unscaled projection), dk, dv as [B, H, T, dh] / [B, H, T]."""
     from m3p_amd import rng
     d = H * dh
-    qf, kf, vf = (_heads(qkv[:, i * d:(i + 1) * d].double(), B, T, H, dh).clone().requires_grad_(True) for i in range(3))
+    qf, kf, vf = (heads(qkv[:, i * d:(i + 1) * d].double(), B, T, H, dh).clone().requires_grad_(True) for i in range(3))
     s = qf @ kf.transpose(2, 3)
     j = torch.arange(T, device='cuda')
     s = s.masked_fill(~(j[None, :] <= j[:, None])[None, None], float('-inf'))
@@ -50,31 +40,17 @@ def _reference(qkv, dctx, B, T, H, dh, p):
     if p > 0:
         pr = pr * torch.from_numpy(rng.keep_mask(B * H * T * T, SEED, p, (B, H, T, T))).cuda() / (1 - p)
     ctx = pr @ vf
-    ctx.backward(_heads(dctx.double(), B, T, H, dh))
+    ctx.backward(heads(dctx.double(), B, T, H, dh))
     return ctx.detach(), torch.logsumexp(s, -1).detach(), qf.grad / np.sqrt(dh), kf.grad, vf.grad
-
-
-def _guarded(rows, cols, dtype):
-    """A poisoned (0xFF bytes) buffer of GUARD + rows + GUARD rows -> (whole buffer, the view handed to the kernel)."""
-    buf = torch.empty((rows + 2 * GUARD, cols), dtype=dtype, device='cuda')
-    buf.untyped_storage().fill_(0xFF)
-    return buf, buf[GUARD:GUARD + rows]
-
-
-def _assert_guards(buf, what):
-    poison = torch.empty_like(buf)
-    poison.untyped_storage().fill_(0xFF)
-    assert_bits_equal(buf[:GUARD], poison[:GUARD], what + ': guard rows before the output')
-    assert_bits_equal(buf[-GUARD:], poison[-GUARD:], what + ': guard rows behind the output')
 
 
 def _tiled(qkv, dctx, B, T, H, dh, p):
     """The tiled kernels into guarded buffers -> ctx, lse, dqkv."""
     from m3p_amd import ops
     d = H * dh
-    cbuf, ctx = _guarded(B * T, d, BF16)
-    lbuf, lse = _guarded(B * H, T, torch.float32)
-    gbuf, dqkv = _guarded(B * T, 3 * d, BF16)
+    cbuf, ctx = guarded(B * T, d, BF16)
+    lbuf, lse = guarded(B * H, T, torch.float32)
+    gbuf, dqkv = guarded(B * T, 3 * d, BF16)
     with poisoned_outputs():
         out = ops.attn_causal_fwd(qkv, B, T, H, dh, seed=SEED, p_drop=p, out=(ctx, lse.view(B, H, T)))
         assert out is not None and out[0] is ctx
@@ -82,17 +58,17 @@ def _tiled(qkv, dctx, B, T, H, dh, p):
         assert got is dqkv
     torch.cuda.synchronize()
     for buf, name in ((cbuf, 'ctx'), (lbuf, 'lse'), (gbuf, 'dqkv')):
-        _assert_guards(buf, name)
+        assert_guards(buf, name)
     return ctx, lse.view(B, H, T), dqkv
 
 
 def _check(ctx, lse, dqkv, ref, B, T, H, dh, what):
     d = H * dh
     r_ctx, r_lse, r_dq, r_dk, r_dv = ref
-    dq, dk, dv = (_heads(dqkv[:, i * d:(i + 1) * d], B, T, H, dh) for i in range(3))
+    dq, dk, dv = (heads(dqkv[:, i * d:(i + 1) * d], B, T, H, dh) for i in range(3))
     for t, name in ((ctx, 'ctx'), (lse, 'lse'), (dq, 'dq'), (dk, 'dk'), (dv, 'dv')):
         assert bool(torch.isfinite(t.float()).all()), '%s: %s holds an element that is not finite (never written?)' % (what, name)
-    ctx_h = _heads(ctx, B, T, H, dh)
+    ctx_h = heads(ctx, B, T, H, dh)
     figures = dict(ctx=rel_l2(ctx_h, r_ctx), lse=rel_l2(lse, r_lse), dq=rel_l2(dq, r_dq), dk=rel_l2(dk, r_dk), dv=rel_l2(dv, r_dv))
     print(what, ' '.join('%s %.3g' % kv for kv in figures.items()))
     assert figures['ctx'] < GLOBAL_ATTN_CTX, (what, figures)
@@ -132,9 +108,49 @@ def test_rows_and_tiled_kernels_share_one_dropout_stream():
                                    dq_out=r_dqkv)
     r_dqkv.view(B, T, 3 * d)[:, :, d:] = dkv
     _check(r_ctx, r_lse, r_dqkv, ref, B, T, H, dh, 'rows kernels against the reference')
-    rows = (_heads(r_ctx.double(), B, T, H, dh), r_lse.double()) + tuple(
-        _heads(r_dqkv[:, i * d:(i + 1) * d].double(), B, T, H, dh) for i in range(3))
+    rows = (heads(r_ctx.double(), B, T, H, dh), r_lse.double()) + tuple(
+        heads(r_dqkv[:, i * d:(i + 1) * d].double(), B, T, H, dh) for i in range(3))
     _check(ctx, lse, dqkv, rows, B, T, H, dh, 'tiled against rows kernels')
+
+
+@pytest.mark.gpu
+def test_strided_qkv_and_dqkv_give_the_packed_results_bit_for_bit():
+    """qkv as the first 3d columns of a NaN-filled [B*T, 3d + 16] buffer, dqkv out into the same kind of slice: the pitch is
+    not the packed one.  Two query blocks, the second ragged: the smallest shape where a diagonal and an off-diagonal tile
+    run."""
+    from m3p_amd import ops
+    B, T, H, dh, p = 2, 65, 4, 64, 0.1
+    d = H * dh
+    qkv, dctx = _inputs(B, T, H, dh)
+    packed = _tiled(qkv, dctx, B, T, H, dh, p)
+    wide = torch.full((B * T, 3 * d + 16), float('nan'), dtype=BF16, device='cuda')
+    wide[:, :3 * d] = qkv
+    qkv_s = wide[:, :3 * d]
+    gbuf, gwide = guarded(B * T, 3 * d + 16, BF16)
+    dqkv_s = gwide[:, :3 * d]
+    assert qkv_s.stride(0) == 3 * d + 16 and dqkv_s.stride(0) == 3 * d + 16
+    with poisoned_outputs():
+        ctx, lse = ops.attn_causal_fwd(qkv_s, B, T, H, dh, seed=SEED, p_drop=p)
+        got = ops.attn_causal_bwd(qkv_s, dctx, lse, B, T, H, dh, 1.0 / np.sqrt(dh), seed=SEED, p_drop=p, out=dqkv_s)
+        assert got is dqkv_s
+    torch.cuda.synchronize()
+    assert_guards(gbuf, 'strided dqkv')
+    poison = torch.empty_like(gwide)
+    poison.untyped_storage().fill_(0xFF)
+    assert_bits_equal(gwide[:, 3 * d:], poison[:, 3 * d:], 'strided dqkv: columns behind the slice')
+    for a, b, name in zip((ctx, lse, dqkv_s), packed, ('ctx', 'lse', 'dqkv')):
+        assert_bits_equal(a, b, 'strided qkv / dqkv: ' + name)
+
+
+@pytest.mark.gpu
+def test_two_launches_give_the_same_bits():
+    """(The D value parked in the dq slot must not leak from one launch into the next.)"""
+    B, T, H, dh, p = 1, 130, 4, 64, 0.1
+    qkv, dctx = _inputs(B, T, H, dh)
+    first = _tiled(qkv, dctx, B, T, H, dh, p)
+    second = _tiled(qkv, dctx, B, T, H, dh, p)
+    for a, b, name in zip(first, second, ('ctx', 'lse', 'dqkv')):
+        assert_bits_equal(a, b, 'second launch: ' + name)
 
 
 @pytest.mark.gpu
@@ -145,32 +161,3 @@ def test_shapes_outside_the_tiled_kernels_are_declined(B, T, H, dh):
     lse = torch.zeros((B, H, T), dtype=torch.float32, device='cuda')
     assert ops.attn_causal_fwd(qkv, B, T, H, dh, seed=SEED, p_drop=0.1) is None
     assert ops.attn_causal_bwd(qkv, dctx, lse, B, T, H, dh, 1.0 / np.sqrt(dh), seed=SEED, p_drop=0.1) is None
-
-
-# --------------------------------------------------------------------------------------------------------- CPU: resources
-# DESIGN.md section 4 states these; a change of the kernels that moves them has to move the table too.
-OCCUPANCY = {('fwd', 64): 4, ('fwd', 32): 5, ('bwd_q', 64, 0): 4, ('bwd_q', 64, 1): 3, ('bwd_q', 32, 0): 5, ('bwd_q', 32, 1): 4,
-             ('bwd_kv', 64): 2, ('bwd_kv', 32): 4}
-
-
-HIPCC = '/opt/rocm/bin/hipcc'
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_attn_causal_kernels_use_no_scratch_and_keep_their_occupancy(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(root, 'm3p_amd', 'csrc', 'attn_causal.hip')
-    out = str(tmp_path / 'attn_causal.s')
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast', '-S',
-                    '--cuda-device-only', src, '-o', out], check=True, capture_output=True)
-    text = open(out).read()
-    seen = {}
-    for m in re.finditer(r'^(_Z\w*attn_causal_(fwd|bwd_q|bwd_kv)_kernelILi(\d+)E(?:Lb([01])E)?\w*):.*?^; Kernel info:(.*?)^; COMPUTE_PGM_RSRC2',
-                         text, re.S | re.M):
-        kind, dh, dq, info = m.group(2), int(m.group(3)), m.group(4), m.group(5)
-        key = (kind, dh) if dq is None else (kind, dh, int(dq))
-        seen[key] = (int(re.search(r'ScratchSize: (\d+)', info).group(1)), int(re.search(r'Occupancy: (\d+)', info).group(1)))
-    assert set(seen) == set(OCCUPANCY), sorted(seen)
-    for key, (scratch, occ) in seen.items():
-        assert scratch == 0, (key, scratch)
-        assert occ == OCCUPANCY[key], (key, occ, OCCUPANCY[key])

@@ -1,36 +1,27 @@
-"""Tiled attention over a source encoding (csrc/attn_cross.hip: m3p_attn_cross_fwd / _bwd) against fp64 torch autograd on
+"""Tiled attention over a source encoding (csrc/attn_tiled.hip: m3p_attn_cross_fwd / _bwd) against fp64 torch autograd on
 the same bf16 operands, with per-sequence key counts and the dropout keep mask of the RNG twin under the stream index of
 the rows kernels (so the two implementations are interchangeable under one seed).
 
 Shapes are the smallest that reach each path of the kernels (blocks of 64 queries / keys, 16 per wave).  Key / value rows
 at or past klen[b] hold NaN before the launch: nothing of them may reach an output, and their dk / dv rows are exact
 zeros.  Outputs live inside larger poisoned buffers: an unwritten element reads NaN, and the guard rows around them must
-keep their bits.  The CPU part reads the compiler's resource summary of every instantiation."""
-import os
-import re
-import subprocess
-
+keep their bits.  (The compiler's resource summary of every instantiation is read in test_attn_tiled.py.)"""
 import numpy as np
 import pytest
 import torch
 
 from tests.util import (ATTN_CTX_RTOL, ATTN_DS_FLOOR, ATTN_DS_RTOL, GLOBAL_ATTN_CTX, GLOBAL_ATTN_GRAD, ROW_FLOOR,
-                        assert_bits_equal, assert_block_bound, assert_exact_zero, poisoned_outputs, rel_l2)
+                        assert_bits_equal, assert_block_bound, assert_exact_zero, assert_guards, guarded, heads, poisoned_outputs,
+                        rel_l2)
 
 BF16 = torch.bfloat16
 SEED = 4242
-GUARD = 3                       # guard rows before and after every output
 # (B, Tq, H, dh, Lk, p): one query and one key; under a tile on both sides; exactly one block each; one row over and one key
 # short; caption-shaped with a ragged third key tile; three query blocks over short keys; 100 regions; the translation shape;
 # both caps
 SHAPES = [(2, 1, 2, 32, 1, 0.0), (3, 17, 4, 32, 9, 0.1), (2, 64, 2, 64, 64, 0.1), (2, 65, 12, 64, 63, 0.1),
           (2, 5, 4, 64, 130, 0.0), (1, 130, 4, 64, 37, 0.1), (2, 40, 12, 64, 100, 0.1), (1, 256, 2, 64, 256, 0.1),
           (1, 512, 2, 32, 1024, 0.1)]
-
-
-def _heads(x, B, T, H, dh):
-    """[B*T, H*dh] -> [B, H, T, dh]: one block per (sequence, head, row)."""
-    return x.reshape(B, T, H, dh).transpose(1, 2)
 
 
 def _klen(B, Lk, g):
@@ -69,42 +60,28 @@ def _reference(q, kv, klen, dctx, B, Tq, H, dh, Lk, p):
     d = H * dh
     past = torch.arange(Lk, device='cuda')[None, :] >= klen[:, None]
     kvc = kv.double().masked_fill(past[:, :, None], 0.0)
-    qf = _heads(q.double(), B, Tq, H, dh).clone().requires_grad_(True)
-    kf = _heads(kvc[:, :, :d], B, Lk, H, dh).clone().requires_grad_(True)
-    vf = _heads(kvc[:, :, d:], B, Lk, H, dh).clone().requires_grad_(True)
+    qf = heads(q.double(), B, Tq, H, dh).clone().requires_grad_(True)
+    kf = heads(kvc[:, :, :d], B, Lk, H, dh).clone().requires_grad_(True)
+    vf = heads(kvc[:, :, d:], B, Lk, H, dh).clone().requires_grad_(True)
     s = (qf @ kf.transpose(2, 3)).masked_fill(past[:, None, None, :], float('-inf'))
     empty = (klen == 0)[:, None, None, None]
     pr = torch.softmax(s.masked_fill(empty, 0.0), -1).masked_fill(empty | past[:, None, None, :], 0.0)
     if p > 0:
         pr = pr * torch.from_numpy(rng.keep_mask(B * H * Tq * Lk, SEED, p, (B, H, Tq, Lk))).cuda() / (1 - p)
     ctx = pr @ vf
-    ctx.backward(_heads(dctx.double(), B, Tq, H, dh))
+    ctx.backward(heads(dctx.double(), B, Tq, H, dh))
     lse = torch.logsumexp(s.masked_fill(empty, 0.0), -1).masked_fill(empty[..., 0], 0.0)
     return ctx.detach(), lse.detach(), qf.grad / np.sqrt(dh), kf.grad, vf.grad
-
-
-def _guarded(rows, cols, dtype):
-    """A poisoned (0xFF bytes) buffer of GUARD + rows + GUARD rows -> (whole buffer, the view handed to the kernel)."""
-    buf = torch.empty((rows + 2 * GUARD, cols), dtype=dtype, device='cuda')
-    buf.untyped_storage().fill_(0xFF)
-    return buf, buf[GUARD:GUARD + rows]
-
-
-def _assert_guards(buf, what):
-    poison = torch.empty_like(buf)
-    poison.untyped_storage().fill_(0xFF)
-    assert_bits_equal(buf[:GUARD], poison[:GUARD], what + ': guard rows before the output')
-    assert_bits_equal(buf[-GUARD:], poison[-GUARD:], what + ': guard rows behind the output')
 
 
 def _tiled(q, kv, klen, dctx, B, Tq, H, dh, Lk, p):
     """The tiled kernels into guarded buffers -> ctx, lse, dq, dkv."""
     from m3p_amd import ops
     d = H * dh
-    cbuf, ctx = _guarded(B * Tq, d, BF16)
-    lbuf, lse = _guarded(B * H, Tq, torch.float32)
-    qbuf, dq = _guarded(B * Tq, d, BF16)
-    kbuf, dkv = _guarded(B * Lk, 2 * d, BF16)
+    cbuf, ctx = guarded(B * Tq, d, BF16)
+    lbuf, lse = guarded(B * H, Tq, torch.float32)
+    qbuf, dq = guarded(B * Tq, d, BF16)
+    kbuf, dkv = guarded(B * Lk, 2 * d, BF16)
     with poisoned_outputs():
         out = ops.attn_cross_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=SEED, p_drop=p, out=(ctx, lse.view(B, H, Tq)))
         assert out is not None and out[0] is ctx
@@ -113,7 +90,7 @@ def _tiled(q, kv, klen, dctx, B, Tq, H, dh, Lk, p):
         assert got is not None and got[0] is dq
     torch.cuda.synchronize()
     for buf, name in ((cbuf, 'ctx'), (lbuf, 'lse'), (qbuf, 'dq'), (kbuf, 'dkv')):
-        _assert_guards(buf, name)
+        assert_guards(buf, name)
     return ctx, lse.view(B, H, Tq), dq, dkv.view(B, Lk, 2 * d)
 
 
@@ -126,8 +103,8 @@ def _check(ctx, lse, dq, dkv, ref, klen, B, Tq, H, dh, Lk, what, seqs=None):
         past = torch.arange(Lk, device='cuda')[None, :] >= klen[:, None]
         assert_exact_zero(dkv[past], what + ' dk, dv of keys past the sequence')
     sel = slice(None) if seqs is None else seqs
-    got = (_heads(ctx, B, Tq, H, dh), lse, _heads(dq, B, Tq, H, dh), _heads(dkv[:, :, :d].reshape(B * Lk, d), B, Lk, H, dh),
-           _heads(dkv[:, :, d:].reshape(B * Lk, d), B, Lk, H, dh))
+    got = (heads(ctx, B, Tq, H, dh), lse, heads(dq, B, Tq, H, dh), heads(dkv[:, :, :d].reshape(B * Lk, d), B, Lk, H, dh),
+           heads(dkv[:, :, d:].reshape(B * Lk, d), B, Lk, H, dh))
     g_ctx, g_lse, g_dq, g_dk, g_dv = (t[sel] for t in got)
     r_ctx, r_lse, r_dq, r_dk, r_dv = (t[sel] for t in ref)
     figures = dict(ctx=rel_l2(g_ctx, r_ctx), lse=rel_l2(g_lse, r_lse), dq=rel_l2(g_dq, r_dq), dk=rel_l2(g_dk, r_dk),
@@ -199,9 +176,9 @@ def test_rows_and_tiled_cross_kernels_share_one_dropout_stream():
         r_ctx, r_lse = ops.attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=SEED, p_drop=p)
         r_dq, r_dkv = ops.attn_rows_bwd(q, kv, klen, dctx, r_lse, B, Tq, H, dh, Lk, 1.0 / np.sqrt(dh), seed=SEED, p_drop=p)
     _check(r_ctx, r_lse, r_dq, r_dkv, ref, klen, B, Tq, H, dh, Lk, 'rows kernels against the reference')
-    rows = (_heads(r_ctx.double(), B, Tq, H, dh), r_lse.double(), _heads(r_dq.double(), B, Tq, H, dh),
-            _heads(r_dkv[:, :, :d].double().reshape(B * Lk, d), B, Lk, H, dh),
-            _heads(r_dkv[:, :, d:].double().reshape(B * Lk, d), B, Lk, H, dh))
+    rows = (heads(r_ctx.double(), B, Tq, H, dh), r_lse.double(), heads(r_dq.double(), B, Tq, H, dh),
+            heads(r_dkv[:, :, :d].double().reshape(B * Lk, d), B, Lk, H, dh),
+            heads(r_dkv[:, :, d:].double().reshape(B * Lk, d), B, Lk, H, dh))
     _check(ctx, lse, dq, dkv, rows, klen, B, Tq, H, dh, Lk, 'tiled against rows kernels')
 
 
@@ -223,32 +200,3 @@ def test_shapes_outside_the_tiled_cross_kernels_are_declined(B, Tq, H, dh, Lk):
     lse = torch.zeros((B, H, Tq), dtype=torch.float32, device='cuda')
     assert ops.attn_cross_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=SEED, p_drop=0.1) is None
     assert ops.attn_cross_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, 1.0 / np.sqrt(dh), seed=SEED, p_drop=0.1) is None
-
-
-# --------------------------------------------------------------------------------------------------------- CPU: resources
-# DESIGN.md section 4 states these; a change of the kernels that moves them has to move the table too.
-OCCUPANCY = {('fwd', 64): 4, ('fwd', 32): 5, ('bwd_q', 64, 0): 3, ('bwd_q', 64, 1): 2, ('bwd_q', 32, 0): 5, ('bwd_q', 32, 1): 4,
-             ('bwd_kv', 64): 2, ('bwd_kv', 32): 4}
-
-
-HIPCC = '/opt/rocm/bin/hipcc'
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_attn_cross_kernels_use_no_scratch_and_keep_their_occupancy(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(root, 'm3p_amd', 'csrc', 'attn_cross.hip')
-    out = str(tmp_path / 'attn_cross.s')
-    subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast', '-S',
-                    '--cuda-device-only', src, '-o', out], check=True, capture_output=True)
-    text = open(out).read()
-    seen = {}
-    for m in re.finditer(r'^(_Z\w*attn_cross_(fwd|bwd_q|bwd_kv)_kernelILi(\d+)E(?:Lb([01])E)?\w*):.*?^; Kernel info:(.*?)^; COMPUTE_PGM_RSRC2',
-                         text, re.S | re.M):
-        kind, dh, dq, info = m.group(2), int(m.group(3)), m.group(4), m.group(5)
-        key = (kind, dh) if dq is None else (kind, dh, int(dq))
-        seen[key] = (int(re.search(r'ScratchSize: (\d+)', info).group(1)), int(re.search(r'Occupancy: (\d+)', info).group(1)))
-    assert set(seen) == set(OCCUPANCY), sorted(seen)
-    for key, (scratch, occ) in seen.items():
-        assert scratch == 0, (key, scratch)
-        assert occ == OCCUPANCY[key], (key, occ, OCCUPANCY[key])

@@ -1,6 +1,6 @@
 """The teacher-forced decoder pass of the seq2seq steps on the tiled attention kernels: functional.DecoderFn and the
-cache-less scoring pass of decoder.decoder_forward dispatch the attention over the source encoding to csrc/attn_cross.hip
-by functional.cross_attn_tiled (and the self-attention to csrc/attn_causal.hip from CAUSAL_TILED_MIN_T on), and fall back to
+cache-less scoring pass of decoder.decoder_forward dispatch the attention over the source encoding to csrc/attn_tiled.hip
+by functional.cross_attn_tiled (and the self-attention to its causal kernels from CAUSAL_TILED_MIN_T on), and fall back to
 the rows kernels of csrc/decode.hip.
 
 GPU: the translation and captioning steps against the reference's goldens with the rules forced either way; a case large

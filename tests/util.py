@@ -376,6 +376,28 @@ def assert_exact_zero(t, where):
             where, n, first, float(t[first]))
 
 
+def heads(x, B, T, H, dh):
+    """[B*T, H*dh] -> [B, H, T, dh]: one block per (sequence, head, row)."""
+    return x.reshape(B, T, H, dh).transpose(1, 2)
+
+
+GUARD = 3                       # guard rows before and after every output of guarded()
+
+
+def guarded(rows, cols, dtype):
+    """A poisoned (0xFF bytes) buffer of GUARD + rows + GUARD rows -> (whole buffer, the view handed to the kernel)."""
+    buf = torch.empty((rows + 2 * GUARD, cols), dtype=dtype, device='cuda')
+    buf.untyped_storage().fill_(0xFF)
+    return buf, buf[GUARD:GUARD + rows]
+
+
+def assert_guards(buf, what):
+    poison = torch.empty_like(buf)
+    poison.untyped_storage().fill_(0xFF)
+    assert_bits_equal(buf[:GUARD], poison[:GUARD], what + ': guard rows before the output')
+    assert_bits_equal(buf[-GUARD:], poison[-GUARD:], what + ': guard rows behind the output')
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Poisoned outputs.  Inside poisoned_outputs() the floating-point buffers that the launchers of m3p_amd/ops.py allocate
 # with torch.empty / torch.empty_like come back filled with 0xFF bytes - NaN in bf16 and fp32 - so an element a kernel

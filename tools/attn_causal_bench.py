@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the causal self-attention of a decoder-only pass inside ONE process: the rows kernels (csrc/decode.hip, a wave per
-query, dk / dv through fp32 atomics) against the tiled MFMA kernels (csrc/attn_causal.hip), forward + backward as
+query, dk / dv through fp32 atomics) against the tiled MFMA kernels (csrc/attn_tiled.hip, causal mask), forward + backward as
 functional.DecoderFn runs each branch (the rows branch with its zeroed fp32 dkv buffer and the copy into dqkv), p = 0.1,
 H = 12, dh = 64, three alternating pairs per shape, device events.  Then one clm_step of the 12-layer / 768-d / V = 250 002
 model at B = 32, T = 256 with functional.CAUSAL_TILED_MIN_T forced to 0 (tiled) and to 10^9 (rows).

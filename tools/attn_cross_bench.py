@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """A/B of the attention over a source encoding in a teacher-forced decoder pass inside ONE process: the rows kernels
-(csrc/decode.hip, a wave per query, dk / dv through fp32 atomics) against the tiled MFMA kernels (csrc/attn_cross.hip),
+(csrc/decode.hip, a wave per query, dk / dv through fp32 atomics) against the tiled MFMA kernels (csrc/attn_tiled.hip, source mask),
 forward + backward as functional.DecoderFn runs each branch (the rows branch with its zeroed fp32 dkv buffer and the cast to
 bf16), p = 0.1, H = 12, dh = 64, ragged key counts uniform on [S / 2, S], three alternating pairs per shape, device events.
-Then the self-attention pair (rows against csrc/attn_causal.hip) at the seq2seq shapes, and one mt_step / ic_step of the
+Then the self-attention pair (rows against the causal kernels of csrc/attn_tiled.hip) at the seq2seq shapes, and one mt_step / ic_step of the
 12-layer / 768-d / V = 250 002 model with the dispatch constants of functional.py forced to 10^9 (rows: the code path before
 the tiled kernels) and to 0 (tiled).  The constants the grid supports - the simplest rule Tq >= a and S >= b under which every
 selected shape won all three alternations - are printed at the end; tests/test_seq2seq_tiled.py compares functional.py's
@@ -82,7 +82,7 @@ def cross_grid():
 def self_pairs():
     d = H * DH
     qscale = 1.0 / np.sqrt(DH)
-    print('\ncausal self-attention of the same pass, forward + backward, rows against csrc/attn_causal.hip')
+    print('\ncausal self-attention of the same pass, forward + backward, rows against the causal kernels of csrc/attn_tiled.hip')
     ok = True
     for B, T in SELF_SHAPES:
         g = torch.Generator(device='cuda').manual_seed(7)
