@@ -287,6 +287,33 @@ M3P_API int m3p_vocab_select(const void* logits, int ld, int n, int V, const flo
                              void* workspace, size_t workspace_bytes, float* scores, long long* flat_idx, float* lse,
                              void* stream);
 
+/* Seeded temperature / top-k sampling of the next word from the same logits (csrc/select.hip), by Gumbel-max: one pass, no
+ * prefix sums, and every random number is a pure function of (seed, row, word), so a draw can be replayed and checked
+ * (NumPy twin: m3p_amd/rng.py sample_uniform / sample_keys / sample_words).  For row r and word w < V:
+ *   m = m3p_hash32(r*V + w, seed) >> 8      (24 bits; the hash of csrc/common.hpp)
+ *   u = (m + 0.5) * 2^-24                   in (0, 1)
+ *   E = -log(u)
+ *   key(r, w) = float(logits[r, w]) * inv_t - log(E)
+ * words[r] = the argmax of key(r, .) over the allowed set, ties to the lowest word: a sample of softmax(float(logits[r, :V]) *
+ * inv_t) restricted to that set and renormalised.  The one deviation is the 24-bit grid of u: log(E) spans [-17.33, 2.85],
+ * so a word whose probability is below about 2^-24 of the most likely word's is never drawn.
+ *   allowed set   top_k = 0: all V words; 1 <= top_k <= m3p_vocab_select_max_k() (16): the row's first top_k entries under
+ *                 (logit descending, word ascending); larger top_k returns M3P_ENOTIMPL, top_k > V M3P_EINVAL.
+ *   words   int64 [n]
+ *   logprob fp32 [n]   x_w*inv_t - lse_T, lse_T = log-sum-exp of float(logits[r, w])*inv_t over the allowed set
+ *   key     fp32 [n]   the winning key; may be NULL
+ * logits as for m3p_vocab_select (bf16 [n, ld], ld >= V, ld % 8 == 0, 16-byte aligned); columns V .. ld-1 may hold anything
+ * (NaN, inf) and are never chosen; a -inf logit below V has probability 0 and is never chosen while the row holds a finite
+ * one.  Preconditions: n*V < 2^32 (the hash counter; M3P_ENOTIMPL otherwise), inv_t > 0 and finite (M3P_EINVAL otherwise),
+ * every row holds at least one finite logit and no NaN in its V columns (not checked).  The row index of the counter is the
+ * row of THIS call: the draw of a row depends on its position in the batch.  Two launches, no atomics, sums in a fixed
+ * order: the same inputs give the same bits.  workspace: m3p_vocab_sample_workspace_bytes(n, V, top_k) bytes, 16-byte
+ * aligned, contents irrelevant.  m3p_vocab_sample_plan answers what the launcher would for a shape, without launching. */
+M3P_API int m3p_vocab_sample_plan(int n, int V, int ld, int top_k);
+M3P_API size_t m3p_vocab_sample_workspace_bytes(int n, int V, int top_k);
+M3P_API int m3p_vocab_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, uint32_t seed, void* workspace,
+                             size_t workspace_bytes, long long* words, float* logprob, float* key, void* stream);
+
 /* The same attention for the TRAINING of the causal / cross-attention sub-layers (teacher forcing: Tq = the whole target
  * sequence, pos0 = 0): dropout on the probabilities (stream (seed, thresh24) indexed ((b*H + h)*Tq + t)*Lk + key) and the
  * log-sum-exp lse fp32 [B, H, Tq] kept for backward.  B*H*Tq*Lk < 2^32. */

@@ -13,7 +13,38 @@
 //   phase 2  (vs_merge_kernel, a workgroup per sentence): lse of the sentence's rows from the chunks' (max, sum), then k
 //            rounds of a block-wide maximum over the beam * chunks * k candidates under T.
 // No atomics; sums are added in a fixed order, so results are reproducible bit for bit.
+//
+// Seeded sampling (decoder.py: generate(sample_seed=...); m3p_vocab_sample) draws the next word of every row from
+// softmax(float(logit) * inv_t) over an allowed set by Gumbel-max - an exponential race: one pass, no prefix sums, and the
+// random number of (row r, word w) is a pure function of (seed, r * V + w), so the NumPy twin (m3p_amd/rng.py: sample_*)
+// regenerates the very numbers a launch used:
+//   m = m3p_hash32(r * V + w, seed) >> 8        24 bits
+//   u = (m + 0.5) * 2^-24                       in (0, 1), never 0 or 1
+//   E = -log(u)                                 a unit exponential
+//   key(r, w) = float(logit[r, w]) * inv_t - log(E)
+// The sampled word is the argmax of key over the allowed set, ties to the lowest word: P(w wins) = softmax(x * inv_t)[w]
+// exactly, but for the 24-bit grid of u - log(E) spans [-17.33, 2.85], so a word whose probability is below about 2^-24 of
+// the most likely one's is never drawn.  Allowed set: top_k = 0 every word below V; 1 <= top_k <= VS_MAX_K the row's first
+// top_k entries under (logit descending, word ascending) - phase 1 of the selection above, run as it is.  Outputs per row:
+// the word, logprob = x_w * inv_t - lse_T (lse_T = log-sum-exp of x * inv_t over the allowed set) and the winning key.
+// Columns at or past V are never chosen whatever they hold; a -inf logit has key -inf and loses to every finite one.
+//   all words  phase 1 (vsmp_chunk_kernel, a workgroup per (row, chunk), the loads of vs_chunk_kernel): per element the
+//              hash and a key, the winner by one unsigned maximum of the 64-bit (sortable key << 32 | ~column) - every
+//              element gets a cheap approximate key, the few that can still win the accurate one (see the kernel) -; the
+//              chunk's winner and its (max, sum exp) of x * inv_t;  phase 2 (vsmp_merge_kernel, a wave per row): the row's winner, lse_T
+//              from the chunks' (max, sum), logprob from the winner's own logit.
+//   top_k      vs_chunk_kernel with k = top_k, then vsmp_topk_kernel (a wave per row): top_k rounds of a wave-wide maximum
+//              over the chunks' candidates, lane j keeps entry j; keys, lse_T and the argmax over those lanes.
+// Noise accuracy: E comes from the accurate logf / log1pf (never __logf: near u = 1 the native log's ABSOLUTE error is as
+// large as E itself).  u and 1 - u are both exact in fp32 in their own half: m < 2^23 takes logf(u), m >= 2^23 takes
+// log1pf(-(1 - u)) with 1 - u = (2^24 - m - 0.5) * 2^-24.  The key is ONE fma (x * inv_t is not rounded on its own).
+// __expf in the chunk sums of phase 1, by the argument above restated for y = x * inv_t: what __expf adds to expf is the
+// rounding of (y - max) * log2 e, which moves a term by |y - max| * 6e-8 relative at most; terms that matter to the sum lie
+// within ln V + a few of the row's maximum WHATEVER inv_t is (a term d below the maximum weighs e^-d), so the sum moves by
+// < 1e-6 relative, below the rounding of lse_T itself.  The scale inv_t enters only through the size of lse_T: its fp32
+// rounding is |lse_T| * 6e-8, which is why the tests hold logprob to 1e-5 * max(1, max|x| * inv_t / 16).
 #include "common.hpp"
+#include <math.h>
 
 namespace {
 
@@ -198,6 +229,227 @@ int vs_plan(int n, int V, int ld, int beam, int k) {
   return M3P_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------
+// seeded sampling
+// ------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long y = (unsigned long long)__shfl_xor((long long)v, o, 64);
+    v = y > v ? y : v;
+  }
+  return v;
+}
+
+// log(E) of element idx = row * V + word, E = -log(u), u = (m + 0.5) 2^-24: in [-17.33, 2.85]
+__device__ __forceinline__ float vsmp_log_e(uint32_t idx, uint32_t seed) {
+  const uint32_t m = m3p_hash32(idx, seed) >> 8;
+  // 2 m + 1 < 2^24 in the lower half and 2^25 - 2 m - 1 < 2^24 in the upper half: both conversions and the scaling are exact
+  const float E = m >= (1u << 23) ? -log1pf(-((float)((1u << 25) - 2u * m - 1u) * 0x1p-25f))
+                                  : -logf((float)(2u * m + 1u) * 0x1p-25f);
+  return logf(E);
+}
+__device__ __forceinline__ unsigned long long vsmp_key64(float key, uint32_t word) {
+  return (unsigned long long)vs_sortable32(key) << 32 | (unsigned long long)(~word);
+}
+
+// A cheap stand-in for vsmp_log_e, within 0.01 of it: native log2 (v_log_f32), and in the upper half
+// log E = log(1 - u) + log(E / (1 - u)) with the series  log(-log(1 - v) / v) = v/2 + 5 v^2/24 + v^3/8 + ...  cut after the
+// cube: every further term is positive and at v <= 1/2 they add up to 0.0089; the native log's own error is below 1e-5 here.
+__device__ __forceinline__ float vsmp_log_e_approx(uint32_t idx, uint32_t seed) {
+  const uint32_t m = m3p_hash32(idx, seed) >> 8;
+  const bool up = m >= (1u << 23);
+  const float a = (float)(up ? (1u << 25) - 2u * m - 1u : 2u * m + 1u) * 0x1p-25f;     // 1 - u or u, exact
+  const float l = __log2f(a) * 0.69314718f;                                             // log(1 - u) or log(u) < 0
+  return up ? l + a * (0.5f + a * (5.f / 24.f + a * 0.125f)) : __log2f(-l) * 0.69314718f;
+}
+constexpr float VSMP_BAND = 0.04f;        // twice a bound (0.02) on |approximate key - key|, the roundings of the keys aside
+
+// logits bf16 [n, ld]; block (row, chunk) -> wkey[block] = (sortable key << 32 | ~word) of the chunk's winner,
+// pstat[block * 2 + {0, 1}] = {max, sum exp(y - max)} of y = x * inv_t over the chunk's columns below V.
+// Three accurate logarithms per element would make this kernel VALU bound (measured: 152 us at 128 x 250 002 against 25 us
+// of vs_chunk_kernel), and all but one or two of a thread's 16 keys cannot win.  So every element gets an APPROXIMATE key
+// first (vsmp_log_e_approx: two native logarithms), within d = 0.02 + |key| 2^-21 of the accurate one; the thread's accurate
+// maximum then lies among the elements whose approximate key is within 2 d of the approximate maximum (if e* holds the
+// accurate maximum and e^ the approximate one:  approx(e*) >= key(e*) - d >= key(e^) - d >= approx(e^) - 2 d), and only
+// those are evaluated with vsmp_log_e - the approximate maximum itself by every lane, the others (a few per cent of the
+// lanes hold one) in a loop that re-reads their logit.  The winner and its key are those of evaluating every element.
+__global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks, float inv_t,
+                                                        uint32_t seed, unsigned long long* __restrict__ wkey,
+                                                        float* __restrict__ pstat) {
+  __shared__ unsigned long long redk[4];
+  __shared__ float redm[4];
+  __shared__ float reds[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+  const uint32_t col0 = (uint32_t)chunk * VS_CHUNK;
+  const uint32_t idx0 = (uint32_t)row * (uint32_t)V + col0;        // (the launcher holds n * V below 2^32)
+  float y[16], ka[16];                     // x * inv_t (-inf: no column) and the approximate key (NaN: no column)
+  float mx = -INFINITY, amax = -INFINITY;
+  int lbest = -1;                          // column in the chunk of the approximate maximum (-1: the thread holds no column)
+  float xbest = 0.f;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
+    const int left = V - (int)(col0 + lc0);                // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float yy = -INFINITY, k = __builtin_nanf("");
+      if (e < left) {                                      // columns at or past V hold anything: never looked at
+        const float x = __uint_as_float((uint32_t)v[e] << 16);
+        yy = __fmul_rn(x, inv_t);
+        k = __fmaf_rn(x, inv_t, -vsmp_log_e_approx(idx0 + (uint32_t)(lc0 + e), seed));
+        mx = fmaxf(mx, yy);
+        if (lbest < 0 || k > amax) {                       // (the first column, then strictly better ones)
+          amax = k;
+          lbest = lc0 + e;
+          xbest = x;
+        }
+      }
+      y[half * 8 + e] = yy;
+      ka[half * 8 + e] = k;
+    }
+  }
+  unsigned long long best = 0ull;          // 0: no entry (a key's upper word is 0 for one NaN pattern only)
+  if (lbest >= 0) best = vsmp_key64(__fmaf_rn(xbest, inv_t, -vsmp_log_e(idx0 + (uint32_t)lbest, seed)), col0 + (uint32_t)lbest);
+  // the other columns that may still hold the accurate maximum (amax = -inf: the threshold is -inf, every column of the thread)
+  const float thr = amax - (VSMP_BAND + fabsf(amax) * 0x1p-20f);
+  uint32_t pending = 0u;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int lc = (e >> 3) * (VS_CHUNK / 2) + tid * 8 + (e & 7);
+    if (ka[e] >= thr && lc != lbest) pending |= 1u << e;
+  }
+  while (pending) {
+    const int e = __builtin_ctz(pending);
+    pending &= pending - 1u;
+    const int lc = (e >> 3) * (VS_CHUNK / 2) + tid * 8 + (e & 7);      // (a column below V: ka is NaN elsewhere)
+    const float x = __uint_as_float((uint32_t)base[lc] << 16);
+    const unsigned long long k64 = vsmp_key64(__fmaf_rn(x, inv_t, -vsmp_log_e(idx0 + (uint32_t)lc, seed)), col0 + (uint32_t)lc);
+    best = k64 > best ? k64 : best;
+  }
+  best = wave_max_u64(best);
+  mx = wave_max(mx);
+  if (lane == 0) {
+    redk[wv] = best;
+    redm[wv] = mx;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    best = redk[q] > best ? redk[q] : best;
+    mx = fmaxf(mx, redm[q]);
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e)
+    if (y[e] > -INFINITY) s += __expf(y[e] - mx);          // (a finite y: the maximum is finite too)
+  s = wave_sum(s);
+  if (lane == 0) reds[wv] = s;
+  __syncthreads();
+  if (tid == 0) {
+    wkey[blockIdx.x] = best;
+    pstat[(size_t)blockIdx.x * 2] = mx;
+    pstat[(size_t)blockIdx.x * 2 + 1] = (reds[0] + reds[1]) + (reds[2] + reds[3]);
+  }
+}
+
+// a wave per row: the row's winner among its chunks' winners, lse_T from the chunks' (max, sum)
+__global__ __launch_bounds__(256) void vsmp_merge_kernel(const bf16* __restrict__ logits, int ld, int n, int V, int nchunks, float inv_t,
+                                                        const unsigned long long* __restrict__ wkey,
+                                                        const float* __restrict__ pstat, long long* __restrict__ words,
+                                                        float* __restrict__ logprob, float* __restrict__ key_out) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
+  const unsigned long long* wk = wkey + (size_t)row * nchunks;
+  const float* ps = pstat + (size_t)row * nchunks * 2;
+  unsigned long long best = 0ull;
+  float m = -INFINITY;
+  for (int c = lane; c < nchunks; c += 64) {
+    best = wk[c] > best ? wk[c] : best;
+    m = fmaxf(m, ps[2 * c]);
+  }
+  best = wave_max_u64(best);
+  m = wave_max(m);
+  float s = 0.f;
+  for (int c = lane; c < nchunks; c += 64) {
+    const float pm = ps[2 * c];
+    if (pm > -INFINITY) s += ps[2 * c + 1] * expf(pm - m);
+  }
+  s = wave_sum(s);
+  if (lane == 0) {
+    const uint32_t word = min(~(uint32_t)best, (uint32_t)(V - 1));      // (a chunk's winner is a column below V; the clamp guards the read)
+    const float x = __uint_as_float((uint32_t)reinterpret_cast<const unsigned short*>(logits)[(size_t)row * ld + word] << 16);
+    words[row] = (long long)word;
+    logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(s)));
+    if (key_out) key_out[row] = vs_value32((uint32_t)(best >> 32));
+  }
+}
+
+// a wave per row over the candidates vs_chunk_kernel left with k = top_k: lane j ends up with the row's j-th entry under
+// (logit descending, word ascending); keys, lse_T and the argmax over those lanes
+__global__ __launch_bounds__(256) void vsmp_topk_kernel(const uint32_t* __restrict__ cand, int n, int V, int nchunks, int k, float inv_t,
+                                                       uint32_t seed, long long* __restrict__ words, float* __restrict__ logprob,
+                                                       float* __restrict__ key_out) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
+  const int total = nchunks * k;
+  const uint32_t* cs = cand + (size_t)row * total;
+  unsigned long long bound = ~0ull;        // entries strictly below it are still to be had by this lane
+  unsigned long long best;
+  auto scan = [&]() {
+    best = 0ull;
+    for (int i = lane; i < total; i += 64) {
+      const uint32_t c32 = cs[i];
+      if (c32 == 0u) continue;
+      const uint32_t word = (uint32_t)(i / k) * VS_CHUNK + (0xFFFFu - (c32 & 0xFFFFu));
+      const unsigned long long x = (unsigned long long)(c32 >> 16) << 32 | (unsigned long long)(~word);
+      if (x < bound && x > best) best = x;
+    }
+  };
+  scan();
+  unsigned long long mine = 0ull;
+  for (int j = 0; j < k; ++j) {
+    const unsigned long long w = wave_max_u64(best);
+    if (lane == j) mine = w;
+    if (best == w && w != 0ull) {          // the word is part of the entry: one lane
+      bound = w;
+      scan();
+    }
+  }
+  const uint32_t word = ~(uint32_t)mine;
+  const float x = vs_value16((uint32_t)(mine >> 32));
+  float yy = -INFINITY;
+  unsigned long long k64 = 0ull;
+  if (mine != 0ull) {                      // (lanes 0 .. top_k - 1: the launcher asks for top_k <= V)
+    yy = __fmul_rn(x, inv_t);
+    k64 = vsmp_key64(__fmaf_rn(x, inv_t, -vsmp_log_e((uint32_t)row * (uint32_t)V + word, seed)), word);
+  }
+  const float m = wave_max(yy);
+  const float s = wave_sum(yy > -INFINITY ? expf(yy - m) : 0.f);
+  const unsigned long long win = wave_max_u64(k64);
+  if (k64 == win && win != 0ull) {
+    words[row] = (long long)word;
+    logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(s)));
+    if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
+  }
+}
+
+int vsmp_plan(int n, int V, int ld, int top_k) {
+  if (n <= 0 || V <= 0 || top_k < 0 || ld < V || (ld % 8) != 0 || top_k > V) return M3P_EINVAL;
+  if (top_k > VS_MAX_K) return M3P_ENOTIMPL;
+  if ((long long)n * V >= (1ll << 32)) return M3P_ENOTIMPL;                          // the hash counter r * V + w is 32 bits
+  const long long nchunks = ((long long)V + VS_CHUNK - 1) / VS_CHUNK;
+  if ((long long)n * nchunks * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block and candidate indices
+  return M3P_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -226,6 +478,46 @@ int m3p_vocab_select(const void* logits, int ld, int n, int V, const float* beam
   M3P_CHECK_LAUNCH();
   hipLaunchKernelGGL(vs_merge_kernel, dim3((unsigned)(n / beam)), dim3(256), 0, (hipStream_t)stream, (const float*)pstat,
                      (const uint32_t*)cand, beam_scores, scores, flat_idx, lse, V, nchunks, beam, k);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_vocab_sample_plan(int n, int V, int ld, int top_k) { return vsmp_plan(n, V, ld, top_k); }
+
+size_t m3p_vocab_sample_workspace_bytes(int n, int V, int top_k) {
+  if (n <= 0 || V <= 0 || top_k < 0) return 0;
+  if (top_k > 0) return m3p_vocab_select_workspace_bytes(n, V, top_k);
+  const size_t blocks = (size_t)n * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
+  return blocks * (sizeof(unsigned long long) + 2 * sizeof(float));
+}
+
+int m3p_vocab_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, uint32_t seed, void* workspace,
+                     size_t workspace_bytes, long long* words, float* logprob, float* key, void* stream) {
+  const int rc = vsmp_plan(n, V, ld, top_k);
+  if (rc != M3P_OK) return rc;
+  if (!(inv_t > 0.f) || isinf(inv_t)) return M3P_EINVAL;
+  if (!logits || !workspace || !words || !logprob || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
+  if (workspace_bytes < m3p_vocab_sample_workspace_bytes(n, V, top_k)) return M3P_EINVAL;
+  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
+  const unsigned rows4 = (unsigned)((n + 3) / 4);
+  if (top_k == 0) {
+    unsigned long long* wkey = (unsigned long long*)workspace;
+    float* pstat = (float*)(wkey + (size_t)n * nchunks);
+    hipLaunchKernelGGL(vsmp_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld,
+                       V, nchunks, inv_t, seed, wkey, pstat);
+    M3P_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vsmp_merge_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, n, V, nchunks,
+                       inv_t, (const unsigned long long*)wkey, (const float*)pstat, words, logprob, key);
+    M3P_CHECK_LAUNCH();
+    return M3P_OK;
+  }
+  float* pstat = (float*)workspace;                       // (the chunks' unscaled (max, sum): written, not read here)
+  uint32_t* cand = (uint32_t*)(pstat + (size_t)n * nchunks * 2);
+  hipLaunchKernelGGL(vs_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, V,
+                     nchunks, top_k, pstat, cand);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsmp_topk_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)cand, n, V, nchunks, top_k,
+                     inv_t, seed, words, logprob, key);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }

@@ -18,7 +18,9 @@ the best entries of its beam * V scores straight from the bf16 logits - no fp32 
 beam search the caches then stay in place: ``cache['owner']`` (int32 [rows, capacity]) names, per hypothesis and position,
 the row whose slot holds that position's keys / values (``advance_owner`` after every step; ``m3p_attn_query_owner_fwd``
 reads through it), and with ``cache['beam']`` the source's keys / values are kept once per sentence, not once per beam.
-``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, sampling and wider beams run the torch code below unchanged.
+``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, unseeded sampling and wider beams run the torch code below unchanged.
+``generate(sample_seed=...)`` draws the next word by the seeded Gumbel-max contract of ``ops.vocab_sample`` (csrc/select.hip;
+NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation and the sampled words' log-probabilities.
 
 This module is forward only; the teacher-forced training pass of the same stream is ``functional.DecoderFn``
 (``TransformerModel.crossfwd`` picks it in training mode), and calling ``decoder_forward`` itself with autograd enabled on
@@ -32,6 +34,7 @@ import torch
 from . import functional as Fn
 from . import lib as L
 from . import ops
+from . import rng
 
 BF16 = torch.bfloat16
 
@@ -39,6 +42,10 @@ BF16 = torch.bfloat16
 # asks for k <= VOCAB_SELECT_MAX_K entries per sentence (greedy: 1, beam search: 2 * beam_size) where the launcher takes
 # the shape (VS_MAX_K = 16 of csrc/select.hip); 0 sends every call to the torch path.
 VOCAB_SELECT_MAX_K = 16
+
+# Stream-key site of the seeded sampling draws (rng.stream_seed(sample_seed, position, SAMPLE_SITE)): outside the dropout
+# sites of the encoder (< 2^20), the refiner (functional._REF_SITE0 = 2^20 + ...) and the causal stream (_DEC_SITE0 = 2^21 + ...).
+SAMPLE_SITE = 1 << 22
 
 
 class _ColdWeights:
@@ -237,9 +244,37 @@ def _select(logits, V, beam_scores, beam, k):
     return res
 
 
-def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None):
+def _sample_twin(scores, inv_t, seed, top_k):
+    """The seeded draw on fp32 scores [bs, V] through the NumPy twin of m3p_vocab_sample (a CPU model, a shape the launcher
+    declines, VOCAB_SELECT_MAX_K == 0) -> (words int64 [bs], logprob fp32 [bs]) on the scores' device."""
+    words, logprob, _ = rng.sample_words(scores.detach().cpu().numpy(), inv_t, seed, top_k)
+    return (torch.from_numpy(words).to(scores.device), torch.from_numpy(logprob.astype('float32')).to(scores.device))
+
+
+def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, sample_seed=None, sample_top_k=None,
+             return_logprobs=False):
     """transformer.py:1216-1317: greedy (or temperature-sampled) decoding with the key / value cache.
-    -> (generated (cur_len, bs) int64, gen_len (bs))."""
+    -> (generated (cur_len, bs) int64, gen_len (bs)).
+
+    Without ``sample_seed`` this is the reference's loop: greedy, or ``torch.multinomial`` on torch's global generator when
+    ``sample_temperature`` is given.  With ``sample_seed`` the words are drawn by the seeded Gumbel-max contract of
+    include/m3p_hip.h (m3p_vocab_sample): ``sample_temperature`` defaults to 1.0, ``sample_top_k`` (None or 0: every word)
+    restricts the draw to the row's top_k words, and the step that decodes position ``cur_len`` uses the stream key
+    ``rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)``.  A CUDA model whose shape the launcher takes runs
+    ``ops.vocab_sample`` on the bf16 logits; everything else (a CPU model, top_k > 16, VOCAB_SELECT_MAX_K == 0) runs the NumPy
+    twin on ``word_scores`` - the same seed is the same random stream on both routes.  Torch's CPU and CUDA generators are
+    not touched, so a seeded run can be replayed exactly.  The counter of the random stream is (row of the batch, word): a
+    sentence's draw depends on its position in the batch.  ``return_logprobs`` (seeded runs only) adds a third value, fp32
+    (cur_len, bs): the log-probability, under the tempered and truncated distribution, of each sampled word; 0 at position
+    0, at pad positions and where <EOS> was forced at ``max_len``."""
+    seeded = sample_seed is not None
+    if sample_top_k is not None and not seeded:
+        raise ValueError('sample_top_k needs sample_seed: the torch sampling path has no top-k mode')
+    if return_logprobs and not seeded:
+        raise ValueError('return_logprobs needs sample_seed')
+    top_k = int(sample_top_k or 0)
+    if top_k < 0:
+        raise ValueError('sample_top_k must be >= 0, got %r' % (sample_top_k,))
     bs = len(src_len)
     assert src_enc.size(0) == bs
     dev = model.embeddings.weight.device
@@ -255,13 +290,32 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     unfinished = torch.ones(bs, dtype=torch.long, device=dev)
     cache = {'slen': 0, 'max_len': max_len}
     # (a launcher that would answer M3P_ENOTIMPL - it is asked once, the answer depends on the shape alone - leaves the torch path)
-    select = (sample_temperature is None and dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
+    select = (sample_temperature is None and not seeded and dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
               and ops.vocab_select_takes(bs, model.n_words, model.arena().V_pad, 1, 1))
+    if seeded:
+        temperature = 1.0 if sample_temperature is None else float(sample_temperature)
+        inv_t = rng.inv_temperature(temperature)
+        top_k = min(top_k, model.n_words)
+        sample_dev = (dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
+                      and ops.vocab_sample_takes(bs, model.n_words, model.arena().V_pad, top_k))
+        logprobs = torch.zeros((max_len, bs), dtype=torch.float32, device=dev) if return_logprobs else None
     while cur_len < max_len:
         tensor = decoder_forward(model, generated[:cur_len], gen_len, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
         assert tensor.size() == (1, bs, model.dim)
-        if select:                     # the first maximum of each row, from the bf16 logits
+        if seeded:
+            step_seed = rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)
+            if sample_dev:
+                logits, V = word_logits16(model, tensor[-1])
+                res = ops.vocab_sample(logits, V, temperature, step_seed, top_k)
+                if res is None:
+                    raise L.M3PError('m3p_vocab_sample declined (M3P_ENOTIMPL) a shape m3p_vocab_sample_plan took')
+                next_words, step_logprob = res[0], res[1]
+            else:
+                next_words, step_logprob = _sample_twin(word_scores(model, tensor[-1]), inv_t, step_seed, top_k)
+            if return_logprobs:
+                logprobs[cur_len] = step_logprob.masked_fill(unfinished == 0, 0.0)
+        elif select:                   # the first maximum of each row, from the bf16 logits
             next_words = _select(*word_logits16(model, tensor[-1]), None, 1, 1)[1].squeeze(1)
         elif sample_temperature is None:
             next_words = torch.topk(word_scores(model, tensor[-1]), 1)[1].squeeze(1)
@@ -276,7 +330,11 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
             break
     if cur_len == max_len:
         generated[-1].masked_fill_(unfinished.bool(), model.eos_index)
+        if return_logprobs:
+            logprobs[-1].masked_fill_(unfinished.bool(), 0.0)        # (a forced <EOS> was not drawn)
     assert int((generated == model.eos_index).sum()) == 2 * bs
+    if return_logprobs:
+        return generated[:cur_len], gen_len, logprobs[:cur_len]
     return generated[:cur_len], gen_len
 
 

@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import lib as L
+from . import rng
 
 BF16 = torch.bfloat16
 _DEBUG_CHECKS = os.environ.get('M3P_DEBUG_CHECKS') == '1'      # host-synchronising consistency checks (tests, debugging)
@@ -405,6 +406,43 @@ def vocab_select(logits, V, beam_scores, beam, k):
                               scores.data_ptr(), flat_idx.data_ptr(), lse.data_ptr(), L.stream())
     L.check(rc, 'm3p_vocab_select')
     return scores, flat_idx, lse
+
+
+def vocab_sample_takes(n, V, ld, top_k):
+    """Does the launcher of vocab_sample take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
+    rc = L.load().m3p_vocab_sample_plan(n, V, ld, top_k)
+    if rc == _ENOTIMPL:
+        return False
+    L.check(rc, 'm3p_vocab_sample_plan')
+    return True
+
+
+def vocab_sample(logits, V, temperature, seed, top_k=0):
+    """Seeded sampling of a decoding step (csrc/select.hip; the contract is in include/m3p_hip.h, the NumPy twin in
+    m3p_amd/rng.py): logits bf16 [n, ld >= V] (columns past V hold anything) -> (words int64 [n], logprob fp32 [n], key fp32 [n]):
+    per row the argmax over the allowed set of  float(logit) * inv_t - log(-log(u)),  u from m3p_hash32(row * V + word, seed),
+    inv_t = rng.inv_temperature(temperature); top_k = 0 allows every word, 1 .. 16 the row's top_k under (logit descending, word
+    ascending); logprob = x_w * inv_t - log-sum-exp over the allowed set; key = the winning key.  None when the launcher does
+    not take the shape (M3P_ENOTIMPL: top_k > 16, n * V >= 2^32)."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
+    n = logits.shape[0]
+    lib = L.load()
+    rc = lib.m3p_vocab_sample_plan(n, V, logits.stride(0), top_k)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_vocab_sample_plan')
+    dev = logits.device
+    ws_bytes = lib.m3p_vocab_sample_workspace_bytes(n, V, top_k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    words = torch.empty((n,), dtype=torch.int64, device=dev)
+    logprob = torch.empty((n,), dtype=torch.float32, device=dev)
+    key = torch.empty((n,), dtype=torch.float32, device=dev)
+    rc = lib.m3p_vocab_sample(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k,
+                              int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, words.data_ptr(), logprob.data_ptr(), key.data_ptr(),
+                              L.stream())
+    L.check(rc, 'm3p_vocab_sample')
+    return words, logprob, key
 
 
 def attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, seed=0, p_drop=0.0):

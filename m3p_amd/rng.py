@@ -1,7 +1,9 @@
 """NumPy twin of the counter-based dropout RNG in csrc/common.hpp (m3p_hash32 /
 m3p_keep): the keep mask of every dropout site is a pure function of
 (stream seed, linear element index), so tests can hand the oracle the exact mask a
-kernel used and compare outputs / gradients element-wise with dropout switched on."""
+kernel used and compare outputs / gradients element-wise with dropout switched on.  The same hash drives the seeded sampling
+of the decoding loop (csrc/select.hip: m3p_vocab_sample); its twin - the uniforms, the keys and the whole draw in fp64 - is
+at the end of this file."""
 import numpy as np
 
 
@@ -36,3 +38,63 @@ def stream_seed(base_seed, step, site):
     x = (x * 0xD6E8FEB86659FD93) & (2 ** 64 - 1)
     x ^= x >> 32
     return int(x & 0xFFFFFFFF)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Seeded sampling (csrc/select.hip: m3p_vocab_sample; decoder.generate(sample_seed=...)): the NumPy twin of the contract in
+# include/m3p_hip.h, in fp64.  For row r and word w < V:  m = hash32(r * V + w, seed) >> 8,  u = (m + 0.5) 2^-24,
+# E = -log(u),  key(r, w) = x[r, w] * inv_t - log(E);  the sampled word is the argmax of key over the allowed set, ties to the
+# lowest word.  That is a draw from softmax(x * inv_t) on the allowed set but for the 24-bit grid of u: log(E) spans
+# [-17.33, 2.85], so a word whose probability is below about 2^-24 of the most likely word's is never drawn.
+# ---------------------------------------------------------------------------------------------------------------------
+def inv_temperature(temperature):
+    """1 / T as the fp32 number the kernel is handed (both routes of the decoder use this one value)."""
+    t = float(temperature)
+    if not t > 0.0:
+        raise ValueError('the sampling temperature must be positive, got %r' % (temperature,))
+    return float(np.float32(1.0 / t))
+
+
+def sample_uniform(n, V, seed):
+    """The exact u of every (row, word), fp64 [n, V] (every u is a 25-bit number: exact in fp64)."""
+    assert int(n) * int(V) < 2 ** 32, 'the counter r * V + w is 32 bits'
+    m = hash32(np.arange(int(n) * int(V), dtype=np.uint64), seed) >> np.uint32(8)
+    return ((m.astype(np.float64) + 0.5) * 2.0 ** -24).reshape(int(n), int(V))
+
+
+def sample_keys(x32, inv_t, seed):
+    """The fp64 keys of fp32 logits x32 [n, V] (bf16 values on the device route); inv_t at its fp32 value."""
+    x = np.asarray(x32, dtype=np.float32).astype(np.float64)
+    assert x.ndim == 2
+    u = sample_uniform(x.shape[0], x.shape[1], seed)
+    return x * float(np.float32(inv_t)) - np.log(-np.log(u))
+
+
+def sample_allowed(x32, top_k):
+    """Boolean [n, V]: top_k = 0 every word, else the row's first top_k words under (logit descending, word ascending)."""
+    x = np.asarray(x32, dtype=np.float32)
+    n, V = x.shape
+    top_k = int(top_k)
+    assert 0 <= top_k <= V
+    if top_k == 0:
+        return np.ones((n, V), dtype=bool)
+    order = np.argsort(-x, axis=1, kind='stable')[:, :top_k]         # stable: equal logits stay in word order
+    allowed = np.zeros((n, V), dtype=bool)
+    np.put_along_axis(allowed, order, True, axis=1)
+    return allowed
+
+
+def sample_words(x32, inv_t, seed, top_k=0):
+    """The whole contract: (words int64 [n], logprob fp64 [n], key fp64 [n]) - the argmax of the keys over the allowed set
+    (the lowest word among equal keys), logprob = x_w * inv_t - log-sum-exp of x * inv_t over the allowed set, and the
+    winning key."""
+    x = np.asarray(x32, dtype=np.float32)
+    allowed = sample_allowed(x, top_k)
+    keys = np.where(allowed, sample_keys(x, inv_t, seed), -np.inf)
+    words = np.argmax(keys, axis=1)                                  # (the first maximum: the lowest word)
+    rows = np.arange(x.shape[0])
+    assert allowed[rows, words].all(), 'a row without a finite logit in its allowed set'
+    y = np.where(allowed, x.astype(np.float64) * float(np.float32(inv_t)), -np.inf)
+    mx = y.max(axis=1)
+    lse = mx + np.log(np.exp(y - mx[:, None]).sum(axis=1))
+    return words.astype(np.int64), y[rows, words] - lse, keys[rows, words]

@@ -17,7 +17,15 @@ Kernel shares come from a run of its own under the profiler, select path only (t
 which gives the selection kernels' achieved bytes/s (bytes = n * V * 2 per step, counted here) against the HBM peak, and the
 share of the summed KERNEL time (not of the step's wall time: host gaps between launches are not in it) that goes to
 kernels other than the project's own, with the largest of those listed.  The round-2 form of this tool (one shape from the
-command line, host clock; it wrote profiles/r02_decode_bench.txt) is the file as of the commit named in that profile."""
+command line, host clock; it wrote profiles/r02_decode_bench.txt) is the file as of the commit named in that profile.
+
+`--sample` measures the sampled step instead: generate(sample_temperature=1.0) on 128 sentences through torch (fp32 copy of
+the logits, divide, softmax, torch.multinomial on torch's generator) against generate(sample_temperature=1.0, sample_seed=...)
+(csrc/select.hip: m3p_vocab_sample on the bf16 logits), same geometry, warm-up and pairs.  The two draw different words (two
+random streams), so outputs are not compared; the device route stands on reproducibility, the number gates nothing.
+    timeout -k 10 600 python tools/decode_bench.py --sample > profiles/decode_sample_vs_torch.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/decode_bench.py --trace sample
+    python tools/decode_bench.py --stats <dir>/.../*_kernel_stats.csv sample >> profiles/decode_sample_vs_torch.txt"""
 import csv
 import os
 import sys
@@ -30,6 +38,8 @@ from m3p_amd import decoder, synth   # noqa: E402
 
 D, HEADS, LAYERS, V, S, MAX_LEN = 768, 12, 12, 250002, 164, 64
 RUNS = {'beam4': ('generate_beam', 32, 4), 'beam5': ('generate_beam', 64, 5), 'greedy': ('generate', 128, 1)}
+SAMPLE = ('sample', 128, 1)       # the --sample run: T = 1.0, seeded device route against torch.multinomial
+SAMPLE_SEED = 17
 PAIRS = 3
 HBM_PEAK = 8.0e12               # bytes/s of an MI355X (HBM3E)
 
@@ -56,6 +66,10 @@ def call(m, kind, src, src_len, beam):
     with torch.no_grad():
         if kind == 'generate':
             return m.generate(src, src_len, 1, max_len=MAX_LEN)
+        if kind == 'sample':
+            return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED)
+        if kind == 'sample_torch':
+            return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0)
         return m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=MAX_LEN)
 
 
@@ -148,8 +162,32 @@ def bench(m):
                       ''.join('\n         sentence %d step %d gap %.3g' % e for e in gaps)))
 
 
+def bench_sample(m):
+    kind, bs, beam = SAMPLE
+    print('sampled decoding step (T = 1.0), %d layers, d = %d, V = %d, S = %d, max_len = %d, %d sentences; ms per decoding step, '
+          '%d alternating pairs; ratio = torch / seeded' % (LAYERS, D, V, S, MAX_LEN, bs, PAIRS))
+    src, src_len = inputs(bs)
+    torch.manual_seed(0)
+    call(m, 'sample_torch', src, src_len, beam)              # warm-up of both routes
+    call(m, 'sample', src, src_len, beam)
+    old, new = [], []
+    for _ in range(PAIRS):
+        t, out_old = timed(lambda: call(m, 'sample_torch', src, src_len, beam))
+        old.append(t)
+        t, out_new = timed(lambda: call(m, 'sample', src, src_len, beam))
+        new.append(t)
+    ratios = [a / b for a, b in zip(old, new)]
+    assert out_old[0].shape[0] == MAX_LEN and out_new[0].shape[0] == MAX_LEN, 'a sentence ended early'
+    print('sample generate       bs %3d          (%3d rows)  torch ms %s  seeded ms %s  ratio %s  the seeded route %s' % (
+        bs, bs, ' '.join('%7.3f' % v for v in old), ' '.join('%7.3f' % v for v in new), ' '.join('%5.2f' % v for v in ratios),
+        'is faster in all three pairs' if min(ratios) > 1 else 'is SLOWER than torch in at least one pair'))
+    again = call(m, 'sample', src, src_len, beam)
+    print('       a further seeded run gives the same tokens: %s' % torch.equal(again[0], out_new[0]))
+    print('       bytes of logits per step (n * V * 2): %.1f MB' % (bs * V * 2 / 1e6))
+
+
 def trace(m, name):
-    kind, bs, beam = RUNS[name]
+    kind, bs, beam = SAMPLE if name == 'sample' else RUNS[name]
     src, src_len = inputs(bs)
     call(m, kind, src, src_len, beam)
     torch.cuda.synchronize()
@@ -176,7 +214,7 @@ def own_kernel(kname):
 def stats(path, name):
     """Kernel shares of a `--trace NAME` run from rocprofv3's kernel stats (Name, Calls, TotalDurationNs, ...): shares of
     the summed KERNEL time, not of the step's wall time (host gaps between launches are in neither term)."""
-    kind, bs, beam = RUNS[name]
+    kind, bs, beam = SAMPLE if name == 'sample' else RUNS[name]
     rows = bs * beam
     total = own = 0.0
     sel, others = {}, []
@@ -187,10 +225,11 @@ def stats(path, name):
             own += ns
         else:
             others.append((ns, calls, kname))
-        for key in ('vs_chunk_kernel', 'vs_merge_kernel'):
+        for key in ('vs_chunk_kernel', 'vs_merge_kernel', 'vsmp_chunk_kernel', 'vsmp_merge_kernel', 'vsmp_topk_kernel'):
             if key in kname:
                 sel[key] = (ns / calls, calls)
-    print('\nkernel shares, %s (%d rows), select path, from a profiled run of its own (warm-up + one timed run)' % (name, rows))
+    print('\nkernel shares, %s (%d rows), %s, from a profiled run of its own (warm-up + one timed run)' % (
+        name, rows, 'seeded sampling' if name == 'sample' else 'select path'))
     for key, (avg, calls) in sorted(sel.items()):
         print('  %-16s %5d calls  %8.1f us per call' % (key, calls, avg / 1e3))
     if len(sel) == 2:
@@ -212,6 +251,9 @@ if __name__ == '__main__':
     assert torch.cuda.is_available(), 'decode_bench.py measures on a GPU'
     if len(sys.argv) >= 3 and sys.argv[1] == '--trace':
         trace(model(), sys.argv[2])
+    elif len(sys.argv) >= 2 and sys.argv[1] == '--sample':
+        print(torch.cuda.get_device_name(0))
+        bench_sample(model())
     else:
         print(torch.cuda.get_device_name(0))
         bench(model())
