@@ -7,7 +7,8 @@
 // Kernels, in the order the launchers prefer them:
 //   gemm_nt_w4_kernel / gemm_wgrad_w4_kernel   four waves, 256x256 tile, 128x128 per wave with the
 //       256 accumulators pinned in AGPRs, 64-deep K-tiles in two 64-KB LDS stages; full-tile shapes.
-//       Their bodies (the MFMA / memory-instruction schedule) are generated: tools/gen/gen_w4.py.
+//       They live in gemm_nt_w4.hpp / gemm_wgrad_w4.hpp, included below; the two halves of their K-tiles (the MFMA /
+//       memory-instruction schedule) are generated: tools/gen/gen_w4.py -> gen/*.inc.
 //   gemm_nt_ring_kernel / gemm_wgrad_ring_kernel   eight waves, 256x128 tile, 64x64 per wave,
 //       three-stage 48-KB ring; ragged shapes, the dGELU epilogue, the vocabulary matrices.
 //   gemm_nt_streamk_kernel   contraction-split NT with fp32 atomics (vocabulary data gradient).
@@ -34,6 +35,38 @@ namespace {
 
 constexpr int BK = 64;            // contraction elements per LDS stage
 constexpr int ROWB = BK * 2;      // bytes per LDS row of a K-contiguous tile (128)
+
+// Inline-asm LDS reads, counted waits and the barrier of the hand-scheduled K loops.  The reads are ones the compiler does
+// not see as loads: their destinations hold data only after OUR wait.  A wait or barrier is fenced with sched_barrier on
+// both sides so that nothing is scheduled across it.  (tests/test_kernel_isa.py checks what the compiler makes of them.)
+#define M3P_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
+#define M3P_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
+#define M3P_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define M3P_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define M3P_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+
+// Place of this workgroup in a persistent grid of nwg workgroups (a multiple of 8, one per CU): consecutive slots sit on one
+// XCD (workgroup b runs on XCD b & 7), so that what neighbouring slots share stays in that XCD's private L2.
+__device__ __forceinline__ int xcd_slot(int nwg) {
+  const int per_xcd = nwg >> 3;
+  return (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+}
+// The tile walk of the persistent NT kernels: workgroup `slot` takes tiles slot, slot + nwg, ...  Tile id -> (tm, tn) is
+// n-fastest - neighbours share the A row-panel - or, from `from` n-tiles on, where a full row of n-tiles no longer fits the L2
+// beside the A panels, in strips of about `width` n-tiles walked m-major: the run of tiles an XCD holds in one round is then
+// a block of a few A row-panels x `width` W panels.  (from / width are each kernel's own measurement: see there.)
+// strip_width gives the strips' actual width, split_tile the place of tile t.
+__device__ __forceinline__ int strip_width(int tiles_n, int from, int width) {
+  const int n_strips = (tiles_n >= from) ? (tiles_n + width - 1) / width : 1;
+  return (tiles_n + n_strips - 1) / n_strips;
+}
+__device__ __forceinline__ void split_tile(int t, int tiles_m, int tiles_n, int strip_w, int& tm, int& tn) {
+  const int strip = t / (tiles_m * strip_w);
+  const int rem = t - strip * tiles_m * strip_w;
+  const int bn = min(strip_w, tiles_n - strip * strip_w);
+  tm = rem / bn;
+  tn = strip * strip_w + (rem - tm * bn);
+}
 
 // ---------------------------------------------------------------------------------
 // NT kernel
@@ -943,23 +976,14 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
   // tile id -> (tm, tn): n-fastest shares the A row-panel between neighbours (weights small
   // enough for L2/MALL); strips pay off once a full row of n-tiles no longer fits beside the A panels (measured:
   // 24 n-tiles 805 -> 914 TF with 8-wide strips; 18 n-tiles lose ~5 %, so those stay n-fastest)
-  const int n_strips = (tiles_n >= 24) ? (tiles_n + 7) / 8 : 1;
-  const int strip_w = (tiles_n + n_strips - 1) / n_strips;
+  const int strip_w = strip_width(tiles_n, 24, 8);
   // (default order: strips of ~8 n-tiles walked m-major, so the 32 consecutive tiles an XCD
   //  holds in one round form a ~4 x 8 block: 4 A row-panels + 8 W panels are live per XCD
   //  instead of 1.3 + 24 -> fewer unique bytes per step in the 4-MB L2.  m-fastest order for a huge W used to win; with the
   //  strips the vocabulary projection went 2.20 -> 2.05 ms, 9.3 -> ~2 GB of reads)
-  auto split_tile = [&](int t, int& tm, int& tn) {
-    const int strip = t / (tiles_m * strip_w);
-    const int rem = t - strip * tiles_m * strip_w;
-    const int bn = min(strip_w, tiles_n - strip * strip_w);
-    tm = rem / bn;
-    tn = strip * strip_w + (rem - tm * bn);
-  };
   const int nwg = gridDim.x;
   // persistent schedule: sequence index q -> tile id
-  const int per_xcd = nwg >> 3;                       // workgroups per XCD (grid is a multiple of 8)
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   auto tile_of = [&](int q) { return q * nwg + slot; };
   const int my_tiles = (ntiles > slot) ? (ntiles - slot + nwg - 1) / nwg : 0;
   if (my_tiles == 0) return;
@@ -977,7 +1001,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
   auto set_load_tile = [&](int q) {
     const int t = tile_of(q);
     int tm, tn;
-    split_tile(t, tm, tn);
+    split_tile(t, tiles_m, tiles_n, strip_w, tm, tn);
 #pragma unroll
     for (int i = 0; i < 4; ++i) a_src[i] = A + (size_t)min(tm * BM + (wid + i * NWAVES) * 8 + sr, M - 1) * lda + sc * 8;
 #pragma unroll
@@ -1016,13 +1040,11 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
     a_addr[ks] = lds0 + (wm * 64 + fr) * ROWB + ch;
     b_addr[ks] = lds0 + A_BYTES + (wn * 64 + fr) * ROWB + ch;
   }
-#define M3P_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
   auto read_set = [&](uint32_t aa, uint32_t ba, bf16x8 (&af)[4], bf16x8 (&wf)[4]) {
     M3P_DSR(wf[0], ba, 0); M3P_DSR(af[0], aa, 0);
     M3P_DSR(wf[1], ba, 2048); M3P_DSR(wf[2], ba, 4096); M3P_DSR(wf[3], ba, 6144);
     M3P_DSR(af[1], aa, 2048); M3P_DSR(af[2], aa, 4096); M3P_DSR(af[3], aa, 6144);
   };
-#define M3P_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -1055,7 +1077,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
 
   bf16x8 af0[4], wf0[4], af1[4], wf1[4];
   read_set(a_addr[0], b_addr[0], af0, wf0);
-  M3P_LGKM0();
+  M3P_WAIT_LGKM(0);
   int cur = 0;      // stage of the current K-tile
   int c_q = 0, c_kt = 0;
   const bool io_aligned = ((ldc & 7) == 0) && (((uintptr_t)C & 15) == 0) &&
@@ -1089,7 +1111,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
     mfma_batch(af0, wf0);
     // k-step-1 fragments are in; every LDS read of this K-tile is complete; the next K-tile
     // has landed for this wave (the 6 LDS-DMAs just issued stay in flight) -> publish
-    M3P_LGKM0();
+    M3P_WAIT_LGKM(0);
     if (more2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -1098,7 +1120,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
     read_set(a_addr[0] + nxt * STAGE, b_addr[0] + nxt * STAGE, af0, wf0);   // stale after the last K-tile: unused
     __builtin_amdgcn_sched_barrier(0);
     mfma_batch(af1, wf1);
-    M3P_LGKM0();
+    M3P_WAIT_LGKM(0);
 
     if (++c_kt == nk) {
       // ---- epilogue of output tile c_q; stage `cur` is free (all waves passed the barrier above)
@@ -1106,7 +1128,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
       const int t = tile_of(c_q);
       ++c_q;
       int tm, tn;
-      split_tile(t, tm, tn);
+      split_tile(t, tiles_m, tiles_n, strip_w, tm, tn);
       const int m0 = tm * BM, n0 = tn * BN;
       const int mw = m0 + wm * 64, nw = n0 + wn * 64;
       // column sums (bias gradient of the dGELU / MUL epilogues) stay in registers across this workgroup's tiles
@@ -1152,7 +1174,7 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
       if (step + 1 < total) {
         // the staging region is the slot the next iteration's loads go into: nobody may issue
         // them before every wave has finished its LDS round trip
-        M3P_LGKM0();
+        M3P_WAIT_LGKM(0);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
@@ -1160,8 +1182,6 @@ void gemm_nt_ring_kernel(const bf16* __restrict__ A, int lda, const bf16* __rest
     cur = nxt;
   }
   if ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) && ep.colsum && csum_nw >= 0) flush_csum();
-#undef M3P_DSR
-#undef M3P_LGKM0
 }
 
 
@@ -1199,8 +1219,8 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   const int ntiles = tiles_m * tiles_n;
   // (round 6: nine n-tiles - the QKV projection - in three strips of three instead of one row of nine: 131.4 -> 124.1 us on
   //  one box, 132 -> 131 on two others - never slower; profiles/r06_qkv_strips.txt)
-  const int n_strips = (tiles_n >= 9) ? (tiles_n + 3) / 4 : 1;
-  const int strip_w = (tiles_n + n_strips - 1) / n_strips;
+  const int strip_w = strip_width(tiles_n, 9, 4);
+  // (its own copy of split_tile: with the shared one the byte / statistics instantiations come out scheduled differently)
   auto split_tile = [&](int t, int& tm, int& tn) {
     const int strip = t / (tiles_m * strip_w);
     const int rem = t - strip * tiles_m * strip_w;
@@ -1211,7 +1231,7 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   const int nwg = gridDim.x;
   const int per_xcd = nwg >> 3;
   const int xcd = blockIdx.x & 7;
-  const int slot = xcd * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   if (slot >= ntiles) return;
   // Tile schedule.  Static: workgroup `slot` takes tiles slot, slot + nwg, ...  Dynamic (tile_ctr != NULL, data parallelism):
   // the first tile is the static one, every further tile is popped from its XCD's queue - the same tiles in the same order
@@ -1309,20 +1329,18 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     a_addr[ks] = lds0 + (wm * 128 + fr) * ROWB + ch;
     b_addr[ks] = lds0 + A_BYTES + (wn * 64 + fr) * ROWB + ch;
   }
-#define W8_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
   // fragments are fetched a QUARTER K-tile (16 MFMAs) ahead: four W fragments per k-step, four A fragments per half
   // (64 fragment registers instead of the 96 of a whole k-step ahead - with 128 accumulators that is the difference
   // between fitting the 256 registers two waves per SIMD leave and spilling inside the K loop)
   auto read_w = [&](uint32_t ba, bf16x8 (&wf)[4]) {
-    W8_DSR(wf[0], ba, 0); W8_DSR(wf[1], ba, 2048); W8_DSR(wf[2], ba, 4096); W8_DSR(wf[3], ba, 6144);
+    M3P_DSR(wf[0], ba, 0); M3P_DSR(wf[1], ba, 2048); M3P_DSR(wf[2], ba, 4096); M3P_DSR(wf[3], ba, 6144);
   };
   auto read_a_lo = [&](uint32_t aa, bf16x8 (&af)[4]) {
-    W8_DSR(af[0], aa, 0); W8_DSR(af[1], aa, 2048); W8_DSR(af[2], aa, 4096); W8_DSR(af[3], aa, 6144);
+    M3P_DSR(af[0], aa, 0); M3P_DSR(af[1], aa, 2048); M3P_DSR(af[2], aa, 4096); M3P_DSR(af[3], aa, 6144);
   };
   auto read_a_hi = [&](uint32_t aa, bf16x8 (&af)[4]) {
-    W8_DSR(af[0], aa, 8192); W8_DSR(af[1], aa, 10240); W8_DSR(af[2], aa, 12288); W8_DSR(af[3], aa, 14336);
+    M3P_DSR(af[0], aa, 8192); M3P_DSR(af[1], aa, 10240); M3P_DSR(af[2], aa, 12288); M3P_DSR(af[3], aa, 14336);
   };
-#define W8_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -1373,7 +1391,7 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   bf16x8 fa0[4], fa1[4], fw0[4], fw1[4];
   read_w(b_addr[0], fw0);
   read_a_lo(a_addr[0], fa0);
-  W8_LGKM0();
+  M3P_WAIT_LGKM(0);
   int c_kt = 0, c_q = 0;
   const bool io_aligned = ((ldc & 7) == 0) && (((uintptr_t)C & 15) == 0) &&
                           (!(EPI == M3P_EPI_BIAS_GELU) || (((ep.ld_out2 & 7) == 0) && (((uintptr_t)ep.out2 & 15) == 0))) &&
@@ -1411,7 +1429,7 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     read_a_hi(a_addr[0] + so, fa1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(H0{}, fa0, fw0);
-    W8_LGKM0();
+    M3P_WAIT_LGKM(0);
     // quarter 1: k-step 0, rows 64-127 | fetch k-step 1: W and rows 0-63
     if (pend) { issue_load(nxt, 6); issue_load(nxt, 7); }
     read_w(b_addr[1] + so, fw1);
@@ -1419,13 +1437,13 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(H1{}, fa1, fw0);
     if (pend) { load_done(); spread_pending = false; }
-    W8_LGKM0();
+    M3P_WAIT_LGKM(0);
     // quarter 2: k-step 1, rows 0-63 | fetch k-step 1, rows 64-127 (the last LDS read of this K-tile)
     read_a_hi(a_addr[1] + so, fa1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(H0{}, fa0, fw1);
     // every LDS read of this K-tile is complete and K-tile +1, requested one K-tile ago, has landed for this wave
-    W8_LGKM0();
+    M3P_WAIT_LGKM(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1459,7 +1477,7 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     }
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(H1{}, fa1, fw1);
-    W8_LGKM0();
+    M3P_WAIT_LGKM(0);
 
     if (++c_kt == nk) {
       // ---- epilogue of output tile c_q through the vacated stage `cur`
@@ -1641,7 +1659,7 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
       if (W8_H1) {
         read_w(b_addr[0] + nxt * STAGE, fw0);
         read_a_lo(a_addr[0] + nxt * STAGE, fa0);
-        W8_LGKM0();
+        M3P_WAIT_LGKM(0);
       }
     }
     if (dyn) {
@@ -1671,8 +1689,6 @@ void gemm_nt_w8_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   }
 #undef W8_H1
 #undef W8_MORE2
-#undef W8_DSR
-#undef W8_LGKM0
 }
 
 // ---------------------------------------------------------------------------------
@@ -1700,18 +1716,9 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = tiles_m * tiles_n;
-  const int n_strips = (tiles_n >= 12) ? (tiles_n + 3) / 4 : 1;
-  const int strip_w = (tiles_n + n_strips - 1) / n_strips;
-  auto split_tile = [&](int t, int& tm, int& tn) {
-    const int strip = t / (tiles_m * strip_w);
-    const int rem = t - strip * tiles_m * strip_w;
-    const int bn = min(strip_w, tiles_n - strip * strip_w);
-    tm = rem / bn;
-    tn = strip * strip_w + (rem - tm * bn);
-  };
+  const int strip_w = strip_width(tiles_n, 12, 4);
   const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   auto tile_of = [&](int q) { return q * nwg + slot; };
   const int my_tiles = (ntiles > slot) ? (ntiles - slot + nwg - 1) / nwg : 0;
   if (my_tiles == 0) return;
@@ -1735,7 +1742,7 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
   int l_q = 0, l_kt = 0;
   auto set_load_tile = [&](int q) {
     int tm, tn;
-    split_tile(tile_of(q), tm, tn);
+    split_tile(tile_of(q), tiles_m, tiles_n, strip_w, tm, tn);
     a_src = A + (size_t)(tm * BM + wid * 8 + sr) * lda + sc * 16;
     w_src = W + (size_t)(tn * BN + wid * 8 + sr) * ldw + sc * 16;
   };
@@ -1784,7 +1791,6 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
     af[0] = frag(a0, a1);
     af[1] = frag(a0 + 2048, a1 + 2048);
   };
-#define F8_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -1822,7 +1828,7 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
   Frag fa0[2], fa1[2], fw[4];
   read_w(0, fw);
   read_a(Q0{}, 0, fa0);
-  F8_LGKM0();
+  M3P_WAIT_LGKM(0);
   int c_q = 0;
   const bool io_aligned = ((ldc & 7) == 0) && (((uintptr_t)C & 15) == 0) &&
                           (!ep.bias || (((uintptr_t)ep.bias & 15) == 0)) &&
@@ -1859,16 +1865,16 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
     read_a(Q1{}, so, fa1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(Q0{}, fa0, fw);
-    F8_LGKM0();
+    M3P_WAIT_LGKM(0);
     if (pend) { issue_load(nxt, 6); issue_load(nxt, 7); load_done(); spread_pending = false; }
     read_a(Q2{}, so, fa0);
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(Q1{}, fa1, fw);
-    F8_LGKM0();
+    M3P_WAIT_LGKM(0);
     read_a(Q3{}, so, fa1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_q(Q2{}, fa0, fw);
-    F8_LGKM0();
+    M3P_WAIT_LGKM(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1892,7 +1898,7 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
       }
     }
     __builtin_amdgcn_s_setprio(0);
-    F8_LGKM0();
+    M3P_WAIT_LGKM(0);
     ++step;
   };
   for (int tq = 0; tq < my_tiles; ++tq) {
@@ -1905,7 +1911,7 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
       const int t = tile_of(c_q);
       ++c_q;
       int tm, tn;
-      split_tile(t, tm, tn);
+      split_tile(t, tiles_m, tiles_n, strip_w, tm, tn);
       const int m0 = tm * BM, n0 = tn * BN;
       const int mw = m0 + wm * 128, nw = n0 + wn * 64;
       if ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) && ep.colsum && csum_nw != nw) {
@@ -1973,12 +1979,11 @@ void gemm_nt_w8f8_kernel(const uint8_t* __restrict__ A, int lda, const uint8_t* 
       if (more1) {
         read_w(nxt * STAGE, fw);
         read_a(Q0{}, nxt * STAGE, fa0);
-        F8_LGKM0();
+        M3P_WAIT_LGKM(0);
       }
     }
   }
   if ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) && ep.colsum && csum_nw >= 0) flush_csum();
-#undef F8_LGKM0
 }
 
 
@@ -2020,8 +2025,7 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
   const int nk = K / BK;
   const long long total_all = (long long)ntile * nk;
   const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   const long long share = (total_all + nwg - 1) / nwg;
   const long long g0l = share * slot;
   if (g0l >= total_all) return;
@@ -2093,23 +2097,20 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
     const int qx = wn * 8 + 2 * c + ((fr & 3) >> 1);
     x_addr[c] = lds0 + A_BYTES + t_row * 256 + ((qx ^ t_sw) << 4) + ((fr & 1) << 3);
   }
-#define M3P_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define M3P_TRH(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
   // ks = 0 / 1 selects the 32-deep k-step; so = byte offset of the stage
   auto read_set = [&](int ks, uint32_t so, bf16x8 (&af)[4], bf16x8 (&wf)[4], s16x4 (&wh)[4][2]) {
     const uint32_t aa = a_addr[ks] + so, ba = b_addr[ks] + so;
     if (W_KN) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        if (ks == 0) { M3P_TRH(wh[c][0], x_addr[c] + so, 0); M3P_TRH(wh[c][1], x_addr[c] + so, 1024); }
-        else { M3P_TRH(wh[c][0], x_addr[c] + so, 8192); M3P_TRH(wh[c][1], x_addr[c] + so, 9216); }
+        if (ks == 0) { M3P_TR(wh[c][0], x_addr[c] + so, 0); M3P_TR(wh[c][1], x_addr[c] + so, 1024); }
+        else { M3P_TR(wh[c][0], x_addr[c] + so, 8192); M3P_TR(wh[c][1], x_addr[c] + so, 9216); }
       }
     } else {
       M3P_DSR(wf[0], ba, 0); M3P_DSR(wf[1], ba, 2048); M3P_DSR(wf[2], ba, 4096); M3P_DSR(wf[3], ba, 6144);
     }
     M3P_DSR(af[0], aa, 0); M3P_DSR(af[1], aa, 2048); M3P_DSR(af[2], aa, 4096); M3P_DSR(af[3], aa, 6144);
   };
-#define M3P_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
   f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -2139,7 +2140,7 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
   bf16x8 af0[4], wf0[4], af1[4], wf1[4];
   s16x4 wh0[4][2], wh1[4][2];
   read_set(0, 0, af0, wf0, wh0);
-  M3P_LGKM0();
+  M3P_WAIT_LGKM(0);
   WgCursor cc = locate(g0l);
   int cur = 0;
   for (int step = 0; step < total; ++step) {
@@ -2150,7 +2151,7 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
     read_set(1, cur * STAGE, af1, wf1, wh1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_batch(af0, wf0, wh0);
-    M3P_LGKM0();
+    M3P_WAIT_LGKM(0);
     if (more2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -2159,7 +2160,7 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
     read_set(0, nxt * STAGE, af0, wf0, wh0);
     __builtin_amdgcn_sched_barrier(0);
     mfma_batch(af1, wf1, wh1);
-    M3P_LGKM0();
+    M3P_WAIT_LGKM(0);
     if ((cc.mt + 1 == cc.len) || (step + 1 == total)) {
       const int tm = cc.t / tiles_n, tn = cc.t - tm * tiles_n;
 #pragma unroll
@@ -2179,478 +2180,9 @@ void gemm_nt_streamk_kernel(const bf16* __restrict__ A, int lda, const bf16* __r
     advance(cc);
     cur = nxt;
   }
-#undef M3P_DSR
-#undef M3P_TRH
-#undef M3P_LGKM0
 }
 
-// W4-BEGIN (generated by tools/gen/gen_w4.py from tools/gen/w4_template.hip - edit those)
-// ---------------------------------------------------------------------------------
-// NT kernel, "w4" version: 256x256 output tile, FOUR waves (one per SIMD), each wave owns a
-// 128x128 sub-tile = 8x8 MFMA tiles (256 accumulator registers of the 512 a lone wave has).
-// Why: with 64x64 per wave (ring kernel above) every 32-deep k-step makes a wave read
-// (64+64) rows x 64 B from LDS for 16 MFMAs; eight waves then pull 128 KB of LDS reads per
-// 64-deep K-tile = 1024 clocks at the LDS's 128 B/clk - exactly the 1030 clocks the MFMAs
-// of that K-tile need, before the 48 KB of LDS-DMA writes are even counted: the ring kernel
-// is LDS-bandwidth bound (measured 2057 clk per K-tile).  128x128 per wave halves LDS bytes
-// per FLOP, 256x256 halves L2 -> LDS bytes per FLOP (64 KB per 2048 MFMA clocks = 32 B/clk/CU).
-// K-tiles are 64 deep with full 128-B rows: the first version of this kernel staged 32-deep
-// tiles (64-B row segments) and stalled on L2 ingest - tools/probe_ingest.py measures
-// 33 B/clk/CU for LDS-DMA with 64-B segments against 64 B/clk/CU with 128-B segments.
-// Pipeline: two 64-KB stages, 128 MFMAs per K-tile with every fragment read and LDS-DMA in their shadow
-// (the schedule is at ktile below).  The 16 LDS-DMAs of a K-tile are spread out: issued back to back
-// they ask the texture path for its full 64 B/clk and the issuing waves (alone on their SIMDs,
-// nothing else to run) stall on the queue.  Memory instructions
-// themselves are free in the shadow of an MFMA (tools/probe_issue2.py: +1 clock per 8 MFMAs).
-// LDS destinations are selected by the immediate offset, which moves source and destination
-// together (tools/probe_dma_offset.py).
-// The epilogue runs from a private 4.5-KB staging area per wave; the loads of the next
-// output tile are already in flight under it.
-// ---------------------------------------------------------------------------------
-// EPIX = the epilogue, or M3P_EPI_DROP_RES_ROWS: BIAS_DROP_RES that reads M3PEpilogue::rng_rows.  The lookup is compiled
-// into that instantiation alone: a uniform branch on the pointer in front of each pipelined piece brought the compiler's
-// wait for all vector memory operations with it - the previous piece's stores included - and cost every launch WITHOUT a
-// map 7-10 us of 168 (profiles/last_layer_rows_ab.txt)
-template <int EPIX>
-__global__ __launch_bounds__(256)
-void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw,
-                       bf16* __restrict__ C, int ldc, int M, int N, int K, M3PEpilogue ep,
-                       int tiles_m, int tiles_n, int m_fast) {
-  constexpr bool kRows = (EPIX == M3P_EPI_DROP_RES_ROWS);
-  constexpr int EPI = kRows ? (int)M3P_EPI_BIAS_DROP_RES : EPIX;
-  constexpr int BM = 256, BN = 256, KT = 64;
-  constexpr int A_BYTES = BM * KT * 2, STAGE = (BM + BN) * KT * 2;     // 32 KB, 64 KB
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ntiles = tiles_m * tiles_n;
-  const int n_strips = (tiles_n >= 12) ? (tiles_n + 3) / 4 : 1;
-  const int strip_w = (tiles_n + n_strips - 1) / n_strips;
-  auto split_tile = [&](int t, int& tm, int& tn) {
-    if (m_fast) { tn = t / tiles_m; tm = t - tn * tiles_m; return; }
-    const int strip = t / (tiles_m * strip_w);
-    const int rem = t - strip * tiles_m * strip_w;
-    const int bn = min(strip_w, tiles_n - strip * strip_w);
-    tm = rem / bn;
-    tn = strip * strip_w + (rem - tm * bn);
-  };
-  const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  auto tile_of = [&](int q) { return q * nwg + slot; };
-  const int my_tiles = (ntiles > slot) ? (ntiles - slot + nwg - 1) / nwg : 0;
-  if (my_tiles == 0) return;
-  const int nk = K / KT;
-  const int total = my_tiles * nk;
-
-  // ---- load cursor.  One LDS-DMA instruction = 1 KB = 8 tile rows of 128 B; lane l fills slot
-  // (l & 7) of row (l >> 3), which must hold 16-B chunk slot ^ (row & 7).  Wave w stages rows
-  // [64w, 64w + 64) of each operand = one contiguous 8-KB slice per operand.
-  const int l_row = lane >> 3;
-  const int l_col = ((lane & 7) ^ l_row) * 8;
-  // (only full tiles come here - the launcher sends ragged shapes to the ring kernel - so the
-  //  eight row groups of a slice are a uniform stride apart)
-  // The transfer is buffer_load_dwordx4 ... lds: resource = this wave's slice of the operand tile, scalar offset = K-tile +
-  // piece, one 32-bit lane offset per operand for the whole kernel - no vector arithmetic per piece and no per-piece address
-  // registers.  (Sixteen 64-bit lane addresses live across the K-tile made the compiler park values in the AGPRs - which are
-  // this kernel's accumulators.)  The immediate of the buffer form is unsigned 12-bit: pieces 0-3 and 4-7 of an operand get
-  // an M0 each (slice, slice + 4 KB), immediates 0..3072.
-  const uint32_t a_lane = (uint32_t)(l_row * lda + l_col) * 2u, w_lane = (uint32_t)(l_row * ldw + l_col) * 2u;
-  __amdgpu_buffer_rsrc_t a_rsrc, w_rsrc;
-  int l_q = 0, l_kt = 0;
-  auto set_load_tile = [&](int q) {
-    int tm, tn;
-    split_tile(tile_of(q), tm, tn);
-    const bf16* a_tile = A + (size_t)(tm * BM + wid * 64) * lda;      // this wave's slice of the tile, K-tile 0
-    const bf16* w_tile = W + (size_t)(tn * BN + wid * 64) * ldw;
-    a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(a_tile)), 0, 0xffffffff, 0x00020000);
-    w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(w_tile)), 0, 0xffffffff, 0x00020000);
-  };
-#define W4_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 8 ? a_rsrc : w_rsrc, LDS_PTR(sl), 16, piece < 8 ? a_lane : w_lane, soff, IMM, 0)
-  auto issue_load = [&](int s, int piece) {
-    const int pc = piece & 7;
-    char* sl = smem + s * STAGE + (piece < 8 ? 0 : A_BYTES) + wid * 8192 + (pc >> 2) * 4096;
-    const uint32_t k_off = (uint32_t)l_kt * (KT * 2);
-    const uint32_t soff = __builtin_amdgcn_readfirstlane(k_off + (uint32_t)pc * (uint32_t)((piece < 8 ? lda : ldw) * 16) - (uint32_t)(pc & 3) * 1024u);
-    switch (pc & 3) {
-      case 0: W4_LDB(0); break;
-      case 1: W4_LDB(1024); break;
-      case 2: W4_LDB(2048); break;
-      default: W4_LDB(3072); break;
-    }
-  };
-  auto load_done = [&]() {
-    // (past the end of the stream the last tile's K-tiles are requested again into stages nobody reads)
-    if (++l_kt == nk) { l_kt = 0; ++l_q; if (l_q < my_tiles) set_load_tile(l_q); }
-  };
-
-  // ---- fragment addressing (as in the ring kernel: 128-B rows, chunk ^= row & 7)
-  const int wm = wid >> 1, wn = wid & 1;
-  const int fr = lane & 15, fg = lane >> 4;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  uint32_t a_addr[2], b_addr[2];      // per k-step; fragment i at + i * 2048
-  uint32_t a_addr1[2], b_addr1[2];    // the same in stage 1 (the K loop is unrolled by two: the stage is a compile-time fact)
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int ch = ((fg + 4 * ks) ^ (fr & 7)) * 16;
-    a_addr[ks] = lds0 + (wm * 128 + fr) * 128 + ch;
-    b_addr[ks] = lds0 + A_BYTES + (wn * 128 + fr) * 128 + ch;
-    a_addr1[ks] = a_addr[ks] + STAGE;
-    b_addr1[ks] = b_addr[ks] + STAGE;
-  }
-#define W4_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define W4_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-
-  // The 256 accumulator registers live in a[0:255] under OUR control: every MFMA and every
-  // accumulator read is inline asm with literal AGPR numbers (tile (i,j) = a[(8i+j)*4 .. +3]).
-  // Left to the register allocator (builtin MFMAs, or asm with "+a" operands) the compiler
-  // shuffled accumulators between AGPRs, VGPRs and scratch inside the K loop.  The compiler
-  // itself never allocates AGPRs in this kernel (checked in the ISA: no v_accvgpr_* outside
-  // ASMSTART/ASMEND); the empty asm below makes the kernel descriptor reserve all 256.
-  asm volatile("" ::: "a0", "a255");
-#define W4_ACC(I, J) "a[((" #I ")*8+(" #J "))*4:((" #I ")*8+(" #J "))*4+3]"
-#define W4_M(FA, FW, I, J) do { if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 " W4_ACC(I, J) ", %1, %0, 0" :: "v"(FA[I]), "v"(FW[J])); \
-                                else asm volatile("v_mfma_f32_16x16x32_bf16 " W4_ACC(I, J) ", %1, %0, " W4_ACC(I, J) :: "v"(FA[I]), "v"(FW[J])); } while (0)
-#define W4_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
-
-  bf16x8 fa0[8], fw0[8], fa1[8], fw1[8];
-#define W4_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
-  // One K-tile (tile j in stage s, tile j+1 landing in stage s^1) = 128 MFMAs with every memory instruction in their shadow.
-  // What decides the schedule is the time a global -> LDS transfer is given to land:
-  //   MFMA   1..15  k-step 1 of tile j: W fragments out of stage s        (k-step 0 is in registers since the previous K-tile)
-  //         17..43  ... and the A fragments
-  //         20      lgkmcnt + barrier: nobody reads W of stage s any more  -> W of tile j+2 starts arriving there (21..49)
-  //         50      lgkmcnt(0) + barrier: nor A                            -> A of tile j+2 (53..)
-  //        107      vmcnt(16) + barrier: tile j+1 (requested one K-tile ago) has landed for everyone
-  //        108..123 k-step 0 of tile j+1 into the registers k-step 0 of tile j vacated at MFMA 63
-  // so a transfer has between 1.2 and 1.7 K-tiles (2500-3500 clocks) to land where the earlier two-phase form gave the last
-  // five pieces of a K-tile 46 MFMAs (740 clocks, less than an HBM miss), and the three barriers sit where their condition
-  // has long been true.
-  auto ktile = [&](auto first_c, auto stage_c) {
-    constexpr bool FIRST0 = decltype(first_c)::value;   // first K-tile of an output tile: C operand = 0 in k-step 0
-    constexpr int s_cur = decltype(stage_c)::value;
-    const uint32_t ra1 = s_cur ? a_addr1[1] : a_addr[1], rb1 = s_cur ? b_addr1[1] : b_addr[1];
-    const uint32_t ra0n = s_cur ? a_addr[0] : a_addr1[0], rb0n = s_cur ? b_addr[0] : b_addr1[0];
-    __builtin_amdgcn_sched_barrier(0);
-    {
-      constexpr bool FIRST = FIRST0;
-    W4_M(fa0, fw0, 0, 0);
-      W4_M(fa0, fw0, 0, 1); W4_DSR(fw1[0], rb1, 0);
-      W4_M(fa0, fw0, 0, 2);
-      W4_M(fa0, fw0, 0, 3); W4_DSR(fw1[1], rb1, 2048);
-      W4_M(fa0, fw0, 0, 4);
-      W4_M(fa0, fw0, 0, 5); W4_DSR(fw1[2], rb1, 4096);
-      W4_M(fa0, fw0, 0, 6);
-      W4_M(fa0, fw0, 0, 7); W4_DSR(fw1[3], rb1, 6144);
-      W4_M(fa0, fw0, 1, 0);
-      W4_M(fa0, fw0, 1, 1); W4_DSR(fw1[4], rb1, 8192);
-      W4_M(fa0, fw0, 1, 2);
-      W4_M(fa0, fw0, 1, 3); W4_DSR(fw1[5], rb1, 10240);
-      W4_M(fa0, fw0, 1, 4);
-      W4_M(fa0, fw0, 1, 5); W4_DSR(fw1[6], rb1, 12288);
-      W4_M(fa0, fw0, 1, 6);
-      W4_M(fa0, fw0, 1, 7); W4_DSR(fw1[7], rb1, 14336);
-      W4_M(fa0, fw0, 2, 0);
-      W4_M(fa0, fw0, 2, 1); W4_DSR(fa1[0], ra1, 0);
-      W4_M(fa0, fw0, 2, 2);
-      W4_M(fa0, fw0, 2, 3); W4_DSR(fa1[1], ra1, 2048);
-      W4_M(fa0, fw0, 2, 4); W4_WAIT_LGKM(2); W4_BAR();
-      W4_M(fa0, fw0, 2, 5); W4_L(8);
-      W4_M(fa0, fw0, 2, 6);
-      W4_M(fa0, fw0, 2, 7); W4_DSR(fa1[2], ra1, 4096);
-      W4_M(fa0, fw0, 3, 0);
-      W4_M(fa0, fw0, 3, 1);
-      W4_M(fa0, fw0, 3, 2); W4_L(9);
-      W4_M(fa0, fw0, 3, 3); W4_DSR(fa1[3], ra1, 6144);
-      W4_M(fa0, fw0, 3, 4);
-      W4_M(fa0, fw0, 3, 5);
-      W4_M(fa0, fw0, 3, 6);
-      W4_M(fa0, fw0, 3, 7); W4_DSR(fa1[4], ra1, 8192); W4_L(10);
-      W4_M(fa0, fw0, 4, 0);
-      W4_M(fa0, fw0, 4, 1);
-      W4_M(fa0, fw0, 4, 2);
-      W4_M(fa0, fw0, 4, 3); W4_DSR(fa1[5], ra1, 10240);
-      W4_M(fa0, fw0, 4, 4); W4_L(11);
-      W4_M(fa0, fw0, 4, 5);
-      W4_M(fa0, fw0, 4, 6);
-      W4_M(fa0, fw0, 4, 7); W4_DSR(fa1[6], ra1, 12288);
-      W4_M(fa0, fw0, 5, 0);
-      W4_M(fa0, fw0, 5, 1); W4_L(12);
-      W4_M(fa0, fw0, 5, 2);
-      W4_M(fa0, fw0, 5, 3); W4_DSR(fa1[7], ra1, 14336);
-      W4_M(fa0, fw0, 5, 4);
-      W4_M(fa0, fw0, 5, 5);
-      W4_M(fa0, fw0, 5, 6); W4_L(13);
-      W4_M(fa0, fw0, 5, 7);
-      W4_M(fa0, fw0, 6, 0);
-      W4_M(fa0, fw0, 6, 1);
-      W4_M(fa0, fw0, 6, 2); W4_WAIT_LGKM(0); W4_BAR();
-      W4_M(fa0, fw0, 6, 3);
-      W4_M(fa0, fw0, 6, 4); W4_L(14);
-      W4_M(fa0, fw0, 6, 5);
-      W4_M(fa0, fw0, 6, 6);
-      W4_M(fa0, fw0, 6, 7);
-      W4_M(fa0, fw0, 7, 0);
-      W4_M(fa0, fw0, 7, 1); W4_L(15);
-      W4_M(fa0, fw0, 7, 2);
-      W4_M(fa0, fw0, 7, 3);
-      W4_M(fa0, fw0, 7, 4);
-      W4_M(fa0, fw0, 7, 5);
-      W4_M(fa0, fw0, 7, 6); W4_L(0);
-      W4_M(fa0, fw0, 7, 7);
-    }
-    {
-      constexpr bool FIRST = false;
-    W4_M(fa1, fw1, 0, 0);
-      W4_M(fa1, fw1, 0, 1);
-      W4_M(fa1, fw1, 0, 2);
-      W4_M(fa1, fw1, 0, 3); W4_L(1);
-      W4_M(fa1, fw1, 0, 4);
-      W4_M(fa1, fw1, 0, 5);
-      W4_M(fa1, fw1, 0, 6);
-      W4_M(fa1, fw1, 0, 7);
-      W4_M(fa1, fw1, 1, 0); W4_L(2);
-      W4_M(fa1, fw1, 1, 1);
-      W4_M(fa1, fw1, 1, 2);
-      W4_M(fa1, fw1, 1, 3);
-      W4_M(fa1, fw1, 1, 4);
-      W4_M(fa1, fw1, 1, 5); W4_L(3);
-      W4_M(fa1, fw1, 1, 6);
-      W4_M(fa1, fw1, 1, 7);
-      W4_M(fa1, fw1, 2, 0);
-      W4_M(fa1, fw1, 2, 1);
-      W4_M(fa1, fw1, 2, 2); W4_L(4);
-      W4_M(fa1, fw1, 2, 3);
-      W4_M(fa1, fw1, 2, 4);
-      W4_M(fa1, fw1, 2, 5);
-      W4_M(fa1, fw1, 2, 6);
-      W4_M(fa1, fw1, 2, 7); W4_L(5);
-      W4_M(fa1, fw1, 3, 0);
-      W4_M(fa1, fw1, 3, 1);
-      W4_M(fa1, fw1, 3, 2);
-      W4_M(fa1, fw1, 3, 3);
-      W4_M(fa1, fw1, 3, 4); W4_L(6);
-      W4_M(fa1, fw1, 3, 5);
-      W4_M(fa1, fw1, 3, 6);
-      W4_M(fa1, fw1, 3, 7);
-      W4_M(fa1, fw1, 4, 0);
-      W4_M(fa1, fw1, 4, 1); W4_L(7);
-      W4_M(fa1, fw1, 4, 2); W4_LD();
-      W4_M(fa1, fw1, 4, 3);
-      W4_M(fa1, fw1, 4, 4);
-      W4_M(fa1, fw1, 4, 5);
-      W4_M(fa1, fw1, 4, 6);
-      W4_M(fa1, fw1, 4, 7);
-      W4_M(fa1, fw1, 5, 0);
-      W4_M(fa1, fw1, 5, 1);
-      W4_M(fa1, fw1, 5, 2);
-      W4_M(fa1, fw1, 5, 3); W4_WAIT_VM(16); W4_BAR();
-      W4_M(fa1, fw1, 5, 4); W4_DSR(fw0[0], rb0n, 0);
-      W4_M(fa1, fw1, 5, 5); W4_DSR(fw0[1], rb0n, 2048);
-      W4_M(fa1, fw1, 5, 6); W4_DSR(fw0[2], rb0n, 4096);
-      W4_M(fa1, fw1, 5, 7); W4_DSR(fw0[3], rb0n, 6144);
-      W4_M(fa1, fw1, 6, 0); W4_DSR(fw0[4], rb0n, 8192);
-      W4_M(fa1, fw1, 6, 1); W4_DSR(fw0[5], rb0n, 10240);
-      W4_M(fa1, fw1, 6, 2); W4_DSR(fw0[6], rb0n, 12288);
-      W4_M(fa1, fw1, 6, 3); W4_DSR(fw0[7], rb0n, 14336);
-      W4_M(fa1, fw1, 6, 4); W4_DSR(fa0[0], ra0n, 0);
-      W4_M(fa1, fw1, 6, 5); W4_DSR(fa0[1], ra0n, 2048);
-      W4_M(fa1, fw1, 6, 6); W4_DSR(fa0[2], ra0n, 4096);
-      W4_M(fa1, fw1, 6, 7); W4_DSR(fa0[3], ra0n, 6144);
-      W4_M(fa1, fw1, 7, 0); W4_DSR(fa0[4], ra0n, 8192);
-      W4_M(fa1, fw1, 7, 1); W4_DSR(fa0[5], ra0n, 10240);
-      W4_M(fa1, fw1, 7, 2); W4_DSR(fa0[6], ra0n, 12288);
-      W4_M(fa1, fw1, 7, 3); W4_DSR(fa0[7], ra0n, 14336);
-      W4_M(fa1, fw1, 7, 4);
-      W4_M(fa1, fw1, 7, 5);
-      W4_M(fa1, fw1, 7, 6);
-      W4_M(fa1, fw1, 7, 7); W4_WAIT_LGKM(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  // ---- prologue: K-tiles 0 and 1 into stages 0 and 1
-  set_load_tile(0);
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-#pragma unroll
-    for (int pc = 0; pc < 16; ++pc) issue_load(t, pc);
-    load_done();
-  }
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  W4_DSR(fw0[0], b_addr[0], 0); W4_DSR(fw0[1], b_addr[0], 2048); W4_DSR(fw0[2], b_addr[0], 4096); W4_DSR(fw0[3], b_addr[0], 6144);
-  W4_DSR(fw0[4], b_addr[0], 8192); W4_DSR(fw0[5], b_addr[0], 10240); W4_DSR(fw0[6], b_addr[0], 12288); W4_DSR(fw0[7], b_addr[0], 14336);
-  W4_DSR(fa0[0], a_addr[0], 0); W4_DSR(fa0[1], a_addr[0], 2048); W4_DSR(fa0[2], a_addr[0], 4096); W4_DSR(fa0[3], a_addr[0], 6144);
-  W4_DSR(fa0[4], a_addr[0], 8192); W4_DSR(fa0[5], a_addr[0], 10240); W4_DSR(fa0[6], a_addr[0], 12288); W4_DSR(fa0[7], a_addr[0], 14336);
-  W4_LGKM0();
-
-  int c_q = 0, c_kt = 0;
-  const bool io_aligned = ((ldc & 7) == 0) && (((uintptr_t)C & 15) == 0) &&
-                          (!(EPI == M3P_EPI_BIAS_GELU) || (((ep.ld_out2 & 7) == 0) && (((uintptr_t)ep.out2 & 15) == 0))) &&
-                          (!ep.bias || (((uintptr_t)ep.bias & 15) == 0)) &&
-                          (!ep.aux || (((ep.ld_aux & 7) == 0) && (((uintptr_t)ep.aux & 15) == 0)));
-  char* r1 = smem + 2 * STAGE + wid * EP_HALF;
-  f32x4 bias_lo[4], bias_hi[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) bias_lo[j] = bias_hi[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto kstep = [&](auto stage_c, int step) {
-    if (c_kt == 0) {
-      // bias values of this output tile: fetched now, used after the last K-tile (a load inside
-      // the epilogue is a stall with nothing to hide behind)
-      int btm, btn;
-      split_tile(tile_of(c_q), btm, btn);
-      if (btn * BN + BN <= N && io_aligned) {
-        load_bias4<EPI>(ep, btn * BN + wn * 128, lane, bias_lo);
-        load_bias4<EPI>(ep, btn * BN + wn * 128 + 64, lane, bias_hi);
-      }
-      ktile(std::true_type{}, stage_c);
-    } else {
-      ktile(std::false_type{}, stage_c);
-    }
-    if (++c_kt == nk) {
-      // ---- epilogue of output tile c_q out of the wave-private staging area
-      c_kt = 0;
-      // the compiler's hazard recogniser does not see the asm MFMAs: the wait for the last
-      // accumulator write before v_accvgpr_read is ours
-      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-      int tm, tn;
-      split_tile(tile_of(c_q), tm, tn);
-      ++c_q;
-      const int m0 = tm * BM, n0 = tn * BN;
-      const int mw = m0 + wm * 128, nw = n0 + wn * 128;
-      const bool fast = io_aligned && (m0 + BM <= M) && (n0 + BN <= N);
-      f32x4 csum[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) csum[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#define W4_RD(II, JJ, I, J)                                                         \
-  asm volatile("v_accvgpr_read_b32 %0, a[((" #I ")*8+(" #J "))*4+0]\n\t"            \
-               "v_accvgpr_read_b32 %1, a[((" #I ")*8+(" #J "))*4+1]\n\t"            \
-               "v_accvgpr_read_b32 %2, a[((" #I ")*8+(" #J "))*4+2]\n\t"            \
-               "v_accvgpr_read_b32 %3, a[((" #I ")*8+(" #J "))*4+3]"                \
-               : "=v"(t0), "=v"(t1), "=v"(t2), "=v"(t3));                           \
-  rows[II][JJ] = f32x4{t0, t1, t2, t3}
-#define W4_SLICE(RG, CH)                                                                      \
-  W4_RD(0, 0, 2 * RG, 4 * CH); W4_RD(0, 1, 2 * RG, 4 * CH + 1); W4_RD(0, 2, 2 * RG, 4 * CH + 2); W4_RD(0, 3, 2 * RG, 4 * CH + 3); \
-  W4_RD(1, 0, 2 * RG + 1, 4 * CH); W4_RD(1, 1, 2 * RG + 1, 4 * CH + 1); W4_RD(1, 2, 2 * RG + 1, 4 * CH + 2); W4_RD(1, 3, 2 * RG + 1, 4 * CH + 3)
-      // The plain epilogues with LDS accesses the compiler does not see (see lds_w64 ...): with transfers for the next output
-      // tile in flight it puts s_waitcnt vmcnt(0) in front of every staging access it knows of, i.e. every piece waits for the
-      // previous piece's global stores (~1150 clocks a piece, 9.2 k per output tile, a fifth of a K = 768 launch -
-      // timeline in DESIGN.md).  One swizzled 4-KB buffer inside each wave's 4.5-KB staging area (146 KB of LDS in all: a
-      // collective's kernel can still share the CU).
-      constexpr bool kPipe = (EPI == M3P_EPI_NONE || EPI == M3P_EPI_BIAS || EPI == M3P_EPI_RES || EPI == M3P_EPI_BIAS_DROP_RES);
-      if (kPipe && fast) {
-        char* rb = smem + 2 * STAGE + wid * EP_HALF;      // (one swizzled 4-KB buffer inside the wave's 4.5-KB staging area)
-        u32x4 tq[4];
-        load_aux_rows_issue<EPI>(ep, mw, nw, lane, tq);
-#pragma nounroll
-        for (int p = 0; p < 8; ++p) {
-          const int ch = p >> 2, rg = p & 3;
-          f32x4 rows[2][4];
-          float t0, t1, t2, t3;
-          switch (p) {
-            case 0: W4_SLICE(0, 0); break;
-            case 1: W4_SLICE(1, 0); break;
-            case 2: W4_SLICE(2, 0); break;
-            case 3: W4_SLICE(3, 0); break;
-            case 4: W4_SLICE(0, 1); break;
-            case 5: W4_SLICE(1, 1); break;
-            case 6: W4_SLICE(2, 1); break;
-            default: W4_SLICE(3, 1); break;
-          }
-          char* rc = rb;     // (one buffer: a wave's LDS instructions complete in order, piece p + 1's writes queue behind piece p's reads)
-          bf16x4 aux_cur[2][4];
-          load_aux_rows_finish<EPI, true, true>(lane, rc, tq, aux_cur);
-          if (p + 1 < 8) load_aux_rows_issue<EPI>(ep, mw + 32 * ((p + 1) & 3), nw + 64 * ((p + 1) >> 2), lane, tq);
-          bf16x4 ukeep[2][4];
-          epilogue_half_write<EPI, true, true, !kRows>(ep, N, mw + 32 * rg, nw + 64 * ch, rc, rows, ch ? bias_hi : bias_lo, aux_cur, lane, csum, ukeep);
-          // (read back at once: straight-line code between the asm reads and their wait, so that no compiler-made copy of the
-          //  destination registers can slip in between; what the asm accesses buy is the absence of vmcnt(0) - the stores of
-          //  piece p are in flight under piece p + 1)
-          u32x4 R[4];
-          epilogue_rows_read<true>(rc, lane, R);
-          lgkm_wait_rows<true>(R, false);
-          epilogue_rows_store(C, ldc, mw + 32 * rg, nw + 64 * ch, lane, R);
-        }
-      } else
-#pragma nounroll
-      for (int p = 0; p < 8; ++p) {
-        const int ch = p >> 2, rg = p & 3;        // column half outer: the bias-gradient sums run over rows
-        // (fetching the residual / pre-activation tile of piece p+1 during piece p was measured
-        //  neutral for the dropout-residual epilogue and 3 % slower for the plain residual one)
-        bf16x4 aux_cur[2][4];
-        if (fast) {
-          // (dGELU / MUL here are never launched - launch_nt keeps it on the eight-wave kernel - and the 16 extra
-          //  transient registers of the row-wise fetch make the compiler spill into our AGPRs)
-          if (EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) load_aux<EPI>(ep, mw + 32 * rg, nw + 64 * ch, lane, aux_cur);
-          else load_aux_rows<EPI>(ep, mw + 32 * rg, nw + 64 * ch, lane, r1, aux_cur);
-        }
-        f32x4 rows[2][4];
-        float t0, t1, t2, t3;
-        switch (p) {
-          case 0: W4_SLICE(0, 0); break;
-          case 1: W4_SLICE(1, 0); break;
-          case 2: W4_SLICE(2, 0); break;
-          case 3: W4_SLICE(3, 0); break;
-          case 4: W4_SLICE(0, 1); break;
-          case 5: W4_SLICE(1, 1); break;
-          case 6: W4_SLICE(2, 1); break;
-          default: W4_SLICE(3, 1); break;
-        }
-        const int mrow0 = mw + 32 * rg, ncol0 = nw + 64 * ch;
-        if (fast) {
-          epilogue_half<EPI>(ep, C, ldc, N, mrow0, ncol0, r1, rows, ch ? bias_hi : bias_lo, aux_cur, lane, csum);
-        } else {
-#pragma unroll
-          for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              epilogue_store<EPI>(ep, C, ldc, M, N, mrow0 + ii * 16 + fr, ncol0 + jj * 16 + fg * 4, rows[ii][jj], csum[jj]);
-        }
-        if ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) && rg == 3) {
-          if (ep.colsum) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                float sfl = csum[j][r];
-                sfl += __shfl_xor(sfl, 1, 64); sfl += __shfl_xor(sfl, 2, 64);
-                sfl += __shfl_xor(sfl, 4, 64); sfl += __shfl_xor(sfl, 8, 64);
-                const int n = ncol0 + j * 16 + fg * 4 + r;
-                if (fr == 0 && n < N) unsafeAtomicAdd(ep.colsum + n, sfl);
-              }
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) csum[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-#undef W4_SLICE
-#undef W4_RD
-    }
-  };
-  for (int step = 0; step < total; step += 2) {
-    kstep(std::integral_constant<int, 0>{}, step);
-    if (step + 1 < total) kstep(std::integral_constant<int, 1>{}, step + 1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
-#undef W4_LDB
-#undef W4_ACC
-#undef W4_DSR
-#undef W4_LGKM0
-#undef W4_M
-#undef W4_L
-#undef W4_WAIT_LGKM
-#undef W4_WAIT_VM
-#undef W4_BAR
-#undef W4_LD
-}
-
-// W4-END
+#include "gemm_nt_w4.hpp"
 
 // ---------------------------------------------------------------------------------
 // NT kernel for a handful of rows (M <= 128: one decoding step of the causal decoder, heads on a batch of [CLS] rows):
@@ -2732,6 +2264,23 @@ static int num_cus() {
   const int hw = hw_cus();
   return (g_persistent_grid > 0 && g_persistent_grid < hw) ? g_persistent_grid : hw;
 }
+// ... for a launch over ntiles output tiles: fewer tiles than CUs -> one workgroup per tile, rounded up to whole XCD rounds
+static int persistent_grid(int ntiles) {
+  const int grid = num_cus();
+  return ntiles < grid ? (ntiles + 7) / 8 * 8 : grid;
+}
+// Raises a kernel's dynamic-LDS limit in front of its first launch; 0 or the HIP error.  The flag is per kernel symbol, so
+// `lds` must be a function of the kernel's template arguments alone (every launcher's is).
+template <auto Kern>
+int set_max_lds(size_t lds) {
+  static bool done = false;      // (set on success only: a failed call is tried again by the next launch, as before)
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  return M3P_OK;
+}
 
 // dynamic tile queues of the eight-wave kernel (m3p_set_tile_queue): a ring of 8-counter slots, one slot per launch
 // The ring belongs to ONE stream - the first one a queued launch arrives on after m3p_set_tile_queue (slots are cleared by a
@@ -2800,10 +2349,8 @@ static int nt_plan(int epi, int M, int N, int K, int* queue) {
   if (whole && g_variant != 2 && !w4_first) {
     // dynamic tile queue only where a workgroup takes several tiles (not for the multiply epilogues: with the queue's
     // bookkeeping on top of their aux pieces and column sums the instantiation spills ~100 bytes per lane)
-    int grid = num_cus();
     const int ntiles = (M / 256) * (N / 256);
-    if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
-    if (queue) *queue = (!mul_epi && armed && ntiles > grid && K >= 8 * BK) ? 1 : 0;
+    if (queue) *queue = (!mul_epi && armed && ntiles > persistent_grid(ntiles) && K >= 8 * BK) ? 1 : 0;
     return M3P_KERN_NT_W8;
   }
   if (M >= 1024 && (M % 256) == 0 && (N % 256) == 0 && (g_variant == 2 || (g_variant == 1 && deep)))
@@ -2829,16 +2376,9 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     const int tiles_m = M / 256, tiles_n = N / 256;
     const size_t lds = 2 * 512 * ROWB + (EPI == M3P_EPI_DGELU ? GELU_TAB_N * sizeof(float) : 0) +
                        ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) ? 8 * 2048 : 8 * 4096);
-    auto kern = gemm_nt_w8_kernel<EPI>;
-    static bool attr_set8 = false;
-    if (!attr_set8) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      attr_set8 = true;
-    }
-    int grid = num_cus();
-    const int ntiles = tiles_m * tiles_n;
-    if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
+    constexpr auto kern = gemm_nt_w8_kernel<EPI>;
+    if (int rc = set_max_lds<kern>(lds)) return rc;
+    const int grid = persistent_grid(tiles_m * tiles_n);
     // dynamic tile queue (ep.tile_ctr: eight zeroed counters, one per XCD) only where a workgroup takes several tiles
     // (not for the multiply epilogues: with the queue's bookkeeping on top of their aux pieces and column sums the instantiation
     //  spills ~100 bytes per lane - 0.31 against 0.28 ms on the dGELU product, more than the queue returns on 12 launches a step)
@@ -2850,13 +2390,8 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
       if (e != hipSuccess) return (int)e;
     }
     if constexpr (kQueueOk) if (ctr) {
-      auto kern_d = gemm_nt_w8_kernel<EPI, true>;
-      static bool attr_set8d = false;
-      if (!attr_set8d) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern_d, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set8d = true;
-      }
+      constexpr auto kern_d = gemm_nt_w8_kernel<EPI, true>;
+      if (int rc = set_max_lds<kern_d>(lds)) return rc;
       hipLaunchKernelGGL(kern_d, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, ctr);
       M3P_CHECK_LAUNCH();
       return M3P_OK;
@@ -2871,17 +2406,10 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     const size_t lds = 2 * (BM + BN) * 128 + 4 * EP_HALF;
     // (a BIAS_DROP_RES launch with a row map runs the instantiation that looks the map up; every other launch compiles it out)
     const bool rows = (EPI == M3P_EPI_BIAS_DROP_RES && ep.rng_rows != nullptr);
-    auto kern = rows ? gemm_nt_w4_kernel<(EPI == M3P_EPI_BIAS_DROP_RES ? M3P_EPI_DROP_RES_ROWS : EPI)> : gemm_nt_w4_kernel<EPI>;
-    static bool attr_set_both[2] = {false, false};
-    bool& attr_set = attr_set_both[rows ? 1 : 0];
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-    int grid = num_cus();
-    const int ntiles = tiles_m * tiles_n;
-    if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
+    constexpr auto kern_rows = gemm_nt_w4_kernel<(EPI == M3P_EPI_BIAS_DROP_RES ? M3P_EPI_DROP_RES_ROWS : EPI)>, kern_plain = gemm_nt_w4_kernel<EPI>;
+    if (int rc = rows ? set_max_lds<kern_rows>(lds) : set_max_lds<kern_plain>(lds)) return rc;
+    auto kern = rows ? kern_rows : kern_plain;
+    const int grid = persistent_grid(tiles_m * tiles_n);
     const long long wbytes = 2LL * N * K, abytes = 2LL * M * K;
     const int m_fast = (wbytes > (64LL << 20) && abytes < wbytes) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, m_fast);
@@ -2892,16 +2420,9 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
     constexpr int BM = 256, BN = 128;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     const size_t lds = 3 * (BM + BN) * ROWB + (EPI == M3P_EPI_DGELU ? GELU_TAB_N * sizeof(float) : 0);
-    auto kern = gemm_nt_ring_kernel<EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-    int grid = num_cus();                       // one persistent workgroup per CU
-    const int ntiles = tiles_m * tiles_n;
-    if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
+    constexpr auto kern = gemm_nt_ring_kernel<EPI>;
+    if (int rc = set_max_lds<kern>(lds)) return rc;
+    const int grid = persistent_grid(tiles_m * tiles_n);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n);
     M3P_CHECK_LAUNCH();
     return M3P_OK;
@@ -2909,13 +2430,8 @@ int launch_nt(const bf16* A, int lda, const bf16* W, int ldw, bf16* C, int ldc, 
   constexpr int BM = 128, BN = 128;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const size_t lds = 2 * (BM + BN) * ROWB;
-  auto kern = gemm_nt_kernel<BM, BN, EPI>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_nt_kernel<BM, BN, EPI>;
+  if (int rc = set_max_lds<kern>(lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(256), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep,
                      tiles_m, tiles_n);
   M3P_CHECK_LAUNCH();
@@ -2939,33 +2455,21 @@ static int launch_nt_gq(const bf16* A, int lda, const bf16* W, int ldw, bf16* C,
   const size_t lds = 2 * 512 * ROWB + ((EPI == M3P_EPI_BIAS_GELUQ) ? GQ_TAB_BYTES + 8 * 2048 + 8 * 1024 : 8 * (EPI != M3P_EPI_MULQ ? 4096 : 2048)) +
                      (EPI == M3P_EPI_MULQ ? 2048 + 8 * 1024 : 0);      // (MULQ: behind the staging rows 2 KB - the 8-bit copy's running maxima / the
                                                                        //  prefetch experiment - and the 8-bit copy's own staging rows, 1 KB per wave)
-  int grid = num_cus();
-  const int ntiles = tiles_m * tiles_n;
-  if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
+  const int grid = persistent_grid(tiles_m * tiles_n);
   if constexpr (EPI == M3P_EPI_BIAS_GELUQ || EPI == M3P_EPI_MULQ) {
     if (ep.out8) {      // the instantiation that also leaves the 8-bit copy (its own registers: the plain one must not pay for it)
       if (((uintptr_t)ep.out8 & 15) || (ep.ld_out8 & 15) || ep.ld_out8 < N || !ep.scale8 || !ep.amax8) return M3P_EINVAL;
       // the copy of an activation is e4m3, of a gradient e5m2 - what the fp8 product's operand slots take (include/m3p_hip.h)
       if ((EPI == M3P_EPI_MULQ) != (ep.out8_bf8 != 0)) return M3P_EINVAL;
-      auto kern8 = gemm_nt_w8_kernel<EPI, false, true>;
-      static bool attr_set8 = false;
-      if (!attr_set8) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set8 = true;
-      }
+      constexpr auto kern8 = gemm_nt_w8_kernel<EPI, false, true>;
+      if (int rc = set_max_lds<kern8>(lds)) return rc;
       hipLaunchKernelGGL(kern8, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, (int*)nullptr);
       M3P_CHECK_LAUNCH();
       return M3P_OK;
     }
   }
-  auto kern = gemm_nt_w8_kernel<EPI>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_nt_w8_kernel<EPI>;
+  if (int rc = set_max_lds<kern>(lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n, (int*)nullptr);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
@@ -3108,531 +2612,7 @@ void gemm_wgrad_kernel(const bf16* __restrict__ dY, int lddy, const bf16* __rest
     }
 }
 
-// WGW4-BEGIN (generated by tools/gen/gen_w4.py from tools/gen/wgrad_w4_template.hip - edit those)
-// ---------------------------------------------------------------------------------
-// Weight-gradient kernel, four-wave version of the stream-K ring kernel below/above:
-// dW[i,j] += alpha * sum_m dY[m,i] X[m,j] with 256(i) x 256(j) output tiles, 128x128 per wave
-// (accumulators pinned in AGPRs as in gemm_nt_w4_kernel), 64-row K-tiles of M in two 64-KB LDS
-// stages ([64 m][256 cols] bf16, 512-B rows for both operands), the same one-piece K-tile schedule
-// (wktile below).
-// Both operands are contraction-strided, so fragments come out of LDS through
-// ds_read_b64_tr_b16 with the 32-B-segment swizzle of the ring kernel.  Stream-K bookkeeping
-// (chunk == one workgroup's share, round-robin for many tiles) is the ring kernel's; a segment
-// ends with fp32 atomics straight from the AGPRs, the next one starts with C = 0.
-// Full tiles only (N % 256 == 0, K % 256 == 0, M % 64 == 0): everything else stays on the ring kernel.
-// ---------------------------------------------------------------------------------
-// YROWS (the vocabulary DATA gradient dH [n, d] += dlogits [n, V] x E [V, d], round 4): the first operand is given with the
-// contraction index CONTIGUOUS - dY_a[i * lddy + m], rows = output rows - i.e. as an NT GEMM's activation panel; its K-tile is
-// staged as 256 rows x 128 B (chunk ^= row & 7 on the source, like the NT kernels) and its fragments are plain ds_read_b128,
-// which deliver exactly what the two transposing reads deliver for a contraction-strided operand: eight consecutive
-// contraction elements of one output row per lane.  Everything else - the second operand's transposing reads, the MFMA
-// stream, the (tile, chunk) schedule, the workspace flush and the reduction - is the weight-gradient kernel's.
-template <bool YROWS>
-__global__ __launch_bounds__(256)
-void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16* __restrict__ X_a, int ldx_a,
-                          float* __restrict__ dW_a, int lddw_a, int M, int N, int K, float alpha,
-                          int tiles_i, int tiles_j_a, int WR_CHUNK, float* __restrict__ ws, int* __restrict__ ws_tile,
-                          int overwrite, WgradProblem pb) {
-  // Two products over the same M in one launch (pb.tiles != 0; one-segment-per-workgroup mode only): the tiles of product b
-  // follow those of product a in the tile numbering, every workgroup picks its product once, before the K loop.  36 tiles of
-  // out_lin + q/k/v then share one launch, one end-of-kernel flush and one reduction instead of 9 tiles x 28 chunks beside
-  // 27 x 9.
-  const bf16* dY = dY_a;
-  const bf16* X = X_a;
-  float* dW = dW_a;
-  int lddy = lddy_a, ldx = ldx_a, lddw = lddw_a, tiles_j = tiles_j_a;
-  int tile_id0 = 0;
-  constexpr int TI = 256, TJ = 256, KT = 64;
-  constexpr int ROWB = 512;                          // bytes per LDS row of either operand
-  constexpr int Y_BYTES = KT * ROWB, STAGE = 2 * Y_BYTES;      // 32 KB, 64 KB
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ntile_a = tiles_i * tiles_j_a;
-  const int ntile = ntile_a + pb.tiles_i * pb.tiles_j;
-  const int nmt = M / KT;
-  const long long total_all = (long long)ntile * nmt;
-  const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  // Schedule.  Few tiles / long M (every layer weight): each workgroup owns ONE (tile, M-chunk)
-  // segment: C = nwg / ntile chunks per tile, slot = chunk * ntile + tile, so the 32 workgroups of
-  // an XCD walk the same rows of M on neighbouring tiles and share them in L2, and every
-  // workgroup flushes exactly once.  (Dealing the ragged remainder out stream-K style left two
-  // workgroups with 18 tile flushes each: 340 us for a 150-us kernel.)  nwg - C * ntile
-  // workgroups stay idle (1.6 % for 36 tiles).  Many tiles (WR_CHUNK == 0): whole tiles round-robin.
-  const bool rr = (WR_CHUNK == 0);
-  // first-segment partials go to this workgroup's private slot of the workspace with plain stores
-  // (ws_tile[slot] = tile id, -1 = nothing there); wgrad_reduce_kernel folds the slots into dW.
-  if (ws && tid == 0) ws_tile[slot] = -1;
-  int total, seg_tile, seg_m0, seg_len;
-  if (rr) {
-    const int my_tiles = (ntile > slot) ? (ntile - slot + nwg - 1) / nwg : 0;
-    if (my_tiles == 0) return;
-    total = my_tiles * nmt;
-    seg_tile = slot; seg_m0 = 0; seg_len = nmt;
-  } else {
-    const int C = max(nwg / ntile, 1);
-    if (slot >= C * ntile) return;
-    const int c = slot / ntile;
-    seg_tile = slot - c * ntile;
-    if (seg_tile >= ntile_a) {
-      dY = pb.dY; X = pb.X; dW = pb.dW; lddy = pb.lddy; ldx = pb.ldx; lddw = pb.lddw; tiles_j = pb.tiles_j;
-      seg_tile -= ntile_a;
-      tile_id0 = ntile_a;
-    }
-    seg_m0 = (int)((long long)c * nmt / C);
-    seg_len = (int)((long long)(c + 1) * nmt / C) - seg_m0;
-    total = seg_len;
-    if (total <= 0) return;
-  }
-  (void)total_all;
-  auto locate = [&](int) {
-    WgCursor cu;
-    cu.c = 0; cu.t = seg_tile; cu.mt = 0; cu.len = seg_len;
-    return cu;
-  };
-  auto advance = [&](WgCursor& cu) {
-    if (++cu.mt == cu.len) { cu.mt = 0; cu.t += nwg; }     // (round-robin mode: next tile; otherwise the stream ends here)
-  };
-  const int g0 = 0;
-
-  // ---- staging.  One wave instruction = 2 rows x 512 B: lane -> (row l >> 5, 16-B slot l & 31).
-  // Wave w stages rows [16w, 16w + 16) of each operand = one contiguous 8-KB slice (M0 trick as
-  // in the NT kernel).  Segment swizzle of the ring kernel: slot ^= 2 * ((row & 3) | ((row >> 3) & 1) << 2).
-  WgCursor lc = locate(g0);
-  int l_issued = 0;
-  const int l_hi = lane >> 5, l_pos = lane & 31;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const bf16* y_base;
-  const bf16* x_base;
-  // The transfers are buffer_load_dwordx4 ... lds - resource = the K-tile's base, scalar offset = the piece's rows, a 32-bit
-  // lane offset (four per operand: the swizzle of a row depends on the piece's parity and half) - rather than
-  // global_load_lds_dwordx4 with a 64-bit lane address per piece.  In the NT kernel the buffer form costs the issuing wave
-  // ~16 clocks a piece where the global form costs ~37.  The buffer form's immediate is unsigned 12-bit: pieces 0-3 and 4-7
-  // of an operand get an M0 each.  (YROWS: piece p of wave w = rows 64 w + 8 p .. + 7 of the 256-row panel, 128 B each:
-  // lane -> (row l >> 3, slot l & 7).)
-  __amdgpu_buffer_rsrc_t y_rsrc, x_rsrc;
-  uint32_t y_voff[4], x_voff[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int f = ((2 * (k & 1) + l_hi) & 3) | ((k >> 1) << 2);        // pieces p with (p & 1, p >= 4) = (k & 1, k >> 1)
-    const int gc = l_pos ^ (f << 1);
-    y_voff[k] = (uint32_t)(l_hi * lddy + gc * 8) * 2u;
-    x_voff[k] = (uint32_t)(l_hi * ldx + gc * 8) * 2u;
-    if (YROWS) y_voff[k] = (uint32_t)((lane >> 3) * lddy + (((lane & 7) ^ (lane >> 3)) * 8)) * 2u;
-  }
-  auto set_rsrc = [&]() {
-    y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(y_base)), 0, 0xffffffff, 0x00020000);
-    x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(uniform_ptr(x_base)), 0, 0xffffffff, 0x00020000);
-  };
-  auto set_load_ktile = [&]() {
-    const int ti = lc.t / tiles_j, tj = lc.t - ti * tiles_j;
-    const size_t mbase = (size_t)(seg_m0 + lc.mt) * KT;
-    y_base = YROWS ? dY + (size_t)(ti * TI) * lddy + mbase : dY + mbase * lddy + ti * TI;
-    x_base = X + mbase * ldx + tj * TJ;
-    set_rsrc();
-  };
-  set_load_ktile();
-#define WG_LDB(IMM) __builtin_amdgcn_raw_ptr_buffer_load_lds(piece < 8 ? y_rsrc : x_rsrc, LDS_PTR(sl), 16, voff, soff, IMM, 0)
-  auto issue_load = [&](int s, int piece) {
-    const int pc = piece & 7, k = (pc & 1) + 2 * (pc >> 2);
-    char* sl = smem + s * STAGE + (piece < 8 ? 0 : Y_BYTES) + wid * 8192 + (pc >> 2) * 4096;
-    const uint32_t voff = piece < 8 ? y_voff[YROWS ? 0 : k] : x_voff[k];
-    const uint32_t rows = (piece < 8 && YROWS) ? (uint32_t)(wid * 64 + 8 * pc) : (uint32_t)(wid * 16 + 2 * pc);
-    const uint32_t soff = __builtin_amdgcn_readfirstlane(rows * (uint32_t)((piece < 8 ? lddy : ldx) * 2) - (uint32_t)(pc & 3) * 1024u);
-    switch (pc & 3) {
-      case 0: WG_LDB(0); break;
-      case 1: WG_LDB(1024); break;
-      case 2: WG_LDB(2048); break;
-      default: WG_LDB(3072); break;
-    }
-  };
-  const size_t y_step = YROWS ? (size_t)KT : (size_t)KT * lddy, x_step = (size_t)KT * ldx;
-  auto load_done = [&]() {
-    // past the end of this workgroup's stream the last K-tile is re-loaded into a stage nobody
-    // reads again (keeps the loop body and the vmcnt bookkeeping uniform).
-    // Within a tile the bases just move on by 64 rows: recomputing them (a division by tiles_j, two 64-bit products) was ~60
-    // scalar instructions per K-tile in front of the mid-step barrier, with the matrix pipe running dry behind them.
-    // (one segment per workgroup - every layer weight: branch-free, a select and two 64-bit adds)
-    if (!rr) {
-      const bool more = ++l_issued < total;
-      y_base += more ? y_step : 0;
-      x_base += more ? x_step : 0;
-      set_rsrc();
-    } else if (++l_issued < total) {
-      if (++lc.mt == lc.len) { lc.mt = 0; lc.t += nwg; set_load_ktile(); }
-      else { y_base += y_step; x_base += x_step; set_rsrc(); }
-    }
-  };
-
-  // ---- fragment addressing (tr16): lane (t = l & 15, g = l >> 4) reads row 8g + (t >> 2) (+4 for the
-  // second half, +32 for k-step 1), 8-byte piece (t & 3) of 16-column sub-tile c
-  const int wi = wid >> 1, wj = wid & 1;
-  const int ft = lane & 15, fg = lane >> 4;
-  const int frow = fg * 8 + (ft >> 2);
-  const int fsw = ((ft >> 2) | ((fg & 1) << 2)) << 1;
-  // (one address per fragment column AND stage: the stage offset, 64 KB, is beyond the instruction's 16-bit immediate, and a
-  //  v_add per read - 32 per K-tile - is not free for a wave alone on its SIMD: every vector instruction between two MFMAs of
-  //  the same wave delays the second one.  7.74 -> 7.45 ms over the step's weight gradients, tools/ab_wgrad.py.)
-  uint32_t y_addr[2][8], x_addr[2][8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int qy = wi * 16 + 2 * c + ((ft & 3) >> 1), qx = wj * 16 + 2 * c + ((ft & 3) >> 1);
-    y_addr[0][c] = lds0 + frow * ROWB + ((qy ^ fsw) << 4) + ((ft & 1) << 3);
-    x_addr[0][c] = lds0 + Y_BYTES + frow * ROWB + ((qx ^ fsw) << 4) + ((ft & 1) << 3);
-    y_addr[1][c] = y_addr[0][c] + STAGE;
-    x_addr[1][c] = x_addr[0][c] + STAGE;
-  }
-  // YROWS: fragment c of k-step ks = 16 bytes of row 128 wi + 16 c + ft at chunk (fg + 4 ks) ^ (row & 7)
-  uint32_t yk_addr[2][2][8];      // [k-step][stage][c]
-#pragma unroll
-  for (int c = 0; c < 8; ++c)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      yk_addr[ks][0][c] = lds0 + (wi * 128 + 16 * c + ft) * 128 + (((fg + 4 * ks) ^ (ft & 7)) << 4);
-      yk_addr[ks][1][c] = yk_addr[ks][0][c] + STAGE;
-    }
-  // one fragment = two tr16 reads (rows +0 / +4); OFF selects the k-step (0 / 16384).  The outputs are EARLY-CLOBBER: without
-  // the '&' the compiler may give the first read's destination the address register (it did, in 21 of the kernel's 80 pairs),
-  // and when the wave stalls between the two reads for longer than the LDS latency the first read's data IS the second
-  // read's address - one half-fragment of wrong (finite) data, about once in 300 launches when the operands were freshly
-  // allocated (slow first touches), never with warm ones (tools/wgrad_stress2.py; found by tests/test_gemm.py failing once
-  // in ~20 runs of the suite)
-#define WG_TR2(LO, HI, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %2 offset:" #OFF "\n\tds_read_b64_tr_b16 %1, %2 offset:" #OFF "+2048" \
-                                               : "=&v"(LO), "=&v"(HI) : "v"(ADDR))
-// the first operand's fragment c of k-step KS from stage S: two transposing reads, or (YROWS) one ds_read_b128
-#define WG_YRD(C, S, KS) do { if constexpr (YROWS) asm volatile("ds_read_b128 %0, %1" : "=v"(yq[C]) : "v"(yk_addr[KS][S][C])); \
-                              else if constexpr ((KS) == 0) WG_TR2(yl[C], yh[C], y_addr[S][C], 0);                           \
-                              else WG_TR2(yl[C], yh[C], y_addr[S][C], 16384); } while (0)
-#define WG_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-
-  asm volatile("" ::: "a0", "a255");     // reserve all 256 AGPRs (see gemm_nt_w4_kernel)
-  // acc tile (b, a) = a[((b)*8+(a))*4 .. +3] holds D[i = 16a + 4(l >> 4) + r][j = 16b + (l & 15)]
-#define WG_ACC(B, A) "a[((" #B ")*8+(" #A "))*4:((" #B ")*8+(" #A "))*4+3]"
-#define WG_M(YF, XF, B, A) do { if (FIRST) asm volatile("v_mfma_f32_16x16x32_bf16 " WG_ACC(B, A) ", %0, %1, 0" :: "v"(YF[A]), "v"(XF[B])); \
-                                else asm volatile("v_mfma_f32_16x16x32_bf16 " WG_ACC(B, A) ", %0, %1, " WG_ACC(B, A) :: "v"(YF[A]), "v"(XF[B])); } while (0)
-#define WG_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
-  auto frag = [](const s16x4& lo, const s16x4& hi) {
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
-
-  s16x4 yl[8], yh[8], xl[8], xh[8];     // raw halves of the fragments being fetched
-  bf16x8 yq[8];                         // (YROWS: the first operand's fragments arrive whole)
-  auto yfrag = [&](int c) { if constexpr (YROWS) return yq[c]; else return frag(yl[c], yh[c]); };
-  bf16x8 yf0[8], xf0[8], yf1[8], xf1[8];
-#define WG_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_SET1() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf1[c] = yfrag(c); xf1[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_SET0() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
-  // The K-tile in one piece, as in gemm_nt_w4_kernel (the stage is a compile-time fact: the K loop is unrolled by two) - the first operand's region of the stage is released by
-  // a barrier as soon as its k-step-1 fragments are in registers (MFMA 20), the second's at MFMA 50, the next K-tile is waited
-  // for at MFMA 107 (vmcnt(16): this K-tile's own sixteen transfers stay in flight): a transfer has 1.2-1.7 K-tiles to land
-  // where the two-phase form gives the last five of a K-tile 46 MFMAs and waits ~200-270 clocks per K-tile at its vmcnt(0).
-  auto wktile = [&](auto first_c, auto stage_c) {
-    constexpr bool FIRST0 = decltype(first_c)::value;
-    constexpr int s_cur = decltype(stage_c)::value;
-    __builtin_amdgcn_sched_barrier(0);
-    {
-      constexpr bool FIRST = FIRST0;
-    WG_M(yf0, xf0, 0, 0);
-      WG_M(yf0, xf0, 0, 1); WG_YRD(0, s_cur, 1);
-      WG_M(yf0, xf0, 0, 2);
-      WG_M(yf0, xf0, 0, 3); WG_YRD(1, s_cur, 1);
-      WG_M(yf0, xf0, 0, 4);
-      WG_M(yf0, xf0, 0, 5); WG_YRD(2, s_cur, 1);
-      WG_M(yf0, xf0, 0, 6);
-      WG_M(yf0, xf0, 0, 7); WG_YRD(3, s_cur, 1);
-      WG_M(yf0, xf0, 1, 0);
-      WG_M(yf0, xf0, 1, 1); WG_YRD(4, s_cur, 1);
-      WG_M(yf0, xf0, 1, 2);
-      WG_M(yf0, xf0, 1, 3); WG_YRD(5, s_cur, 1);
-      WG_M(yf0, xf0, 1, 4);
-      WG_M(yf0, xf0, 1, 5); WG_YRD(6, s_cur, 1);
-      WG_M(yf0, xf0, 1, 6);
-      WG_M(yf0, xf0, 1, 7); WG_YRD(7, s_cur, 1);
-      WG_M(yf0, xf0, 2, 0);
-      WG_M(yf0, xf0, 2, 1); WG_TR2(xl[0], xh[0], x_addr[s_cur][0], 16384);
-      WG_M(yf0, xf0, 2, 2);
-      WG_M(yf0, xf0, 2, 3); WG_TR2(xl[1], xh[1], x_addr[s_cur][1], 16384);
-      WG_M(yf0, xf0, 2, 4); WG_WAIT_LGKM(4); WG_BAR();
-      WG_M(yf0, xf0, 2, 5); WG_L(0);
-      WG_M(yf0, xf0, 2, 6);
-      WG_M(yf0, xf0, 2, 7); WG_TR2(xl[2], xh[2], x_addr[s_cur][2], 16384);
-      WG_M(yf0, xf0, 3, 0);
-      WG_M(yf0, xf0, 3, 1);
-      WG_M(yf0, xf0, 3, 2); WG_L(1);
-      WG_M(yf0, xf0, 3, 3); WG_TR2(xl[3], xh[3], x_addr[s_cur][3], 16384);
-      WG_M(yf0, xf0, 3, 4);
-      WG_M(yf0, xf0, 3, 5);
-      WG_M(yf0, xf0, 3, 6);
-      WG_M(yf0, xf0, 3, 7); WG_TR2(xl[4], xh[4], x_addr[s_cur][4], 16384); WG_L(2);
-      WG_M(yf0, xf0, 4, 0);
-      WG_M(yf0, xf0, 4, 1);
-      WG_M(yf0, xf0, 4, 2);
-      WG_M(yf0, xf0, 4, 3); WG_TR2(xl[5], xh[5], x_addr[s_cur][5], 16384);
-      WG_M(yf0, xf0, 4, 4); WG_L(3);
-      WG_M(yf0, xf0, 4, 5);
-      WG_M(yf0, xf0, 4, 6);
-      WG_M(yf0, xf0, 4, 7); WG_TR2(xl[6], xh[6], x_addr[s_cur][6], 16384);
-      WG_M(yf0, xf0, 5, 0);
-      WG_M(yf0, xf0, 5, 1); WG_L(4);
-      WG_M(yf0, xf0, 5, 2);
-      WG_M(yf0, xf0, 5, 3); WG_TR2(xl[7], xh[7], x_addr[s_cur][7], 16384);
-      WG_M(yf0, xf0, 5, 4);
-      WG_M(yf0, xf0, 5, 5);
-      WG_M(yf0, xf0, 5, 6); WG_L(5);
-      WG_M(yf0, xf0, 5, 7);
-      WG_M(yf0, xf0, 6, 0);
-      WG_M(yf0, xf0, 6, 1);
-      WG_M(yf0, xf0, 6, 2); WG_WAIT_LGKM(0); WG_SET1(); WG_BAR();
-      WG_M(yf0, xf0, 6, 3);
-      WG_M(yf0, xf0, 6, 4); WG_L(6);
-      WG_M(yf0, xf0, 6, 5);
-      WG_M(yf0, xf0, 6, 6);
-      WG_M(yf0, xf0, 6, 7);
-      WG_M(yf0, xf0, 7, 0);
-      WG_M(yf0, xf0, 7, 1); WG_L(7);
-      WG_M(yf0, xf0, 7, 2);
-      WG_M(yf0, xf0, 7, 3);
-      WG_M(yf0, xf0, 7, 4);
-      WG_M(yf0, xf0, 7, 5);
-      WG_M(yf0, xf0, 7, 6); WG_L(8);
-      WG_M(yf0, xf0, 7, 7);
-    }
-    {
-      constexpr bool FIRST = false;
-    WG_M(yf1, xf1, 0, 0);
-      WG_M(yf1, xf1, 0, 1);
-      WG_M(yf1, xf1, 0, 2);
-      WG_M(yf1, xf1, 0, 3); WG_L(9);
-      WG_M(yf1, xf1, 0, 4);
-      WG_M(yf1, xf1, 0, 5);
-      WG_M(yf1, xf1, 0, 6);
-      WG_M(yf1, xf1, 0, 7);
-      WG_M(yf1, xf1, 1, 0); WG_L(10);
-      WG_M(yf1, xf1, 1, 1);
-      WG_M(yf1, xf1, 1, 2);
-      WG_M(yf1, xf1, 1, 3);
-      WG_M(yf1, xf1, 1, 4);
-      WG_M(yf1, xf1, 1, 5); WG_L(11);
-      WG_M(yf1, xf1, 1, 6);
-      WG_M(yf1, xf1, 1, 7);
-      WG_M(yf1, xf1, 2, 0);
-      WG_M(yf1, xf1, 2, 1);
-      WG_M(yf1, xf1, 2, 2); WG_L(12);
-      WG_M(yf1, xf1, 2, 3);
-      WG_M(yf1, xf1, 2, 4);
-      WG_M(yf1, xf1, 2, 5);
-      WG_M(yf1, xf1, 2, 6);
-      WG_M(yf1, xf1, 2, 7); WG_L(13);
-      WG_M(yf1, xf1, 3, 0);
-      WG_M(yf1, xf1, 3, 1);
-      WG_M(yf1, xf1, 3, 2);
-      WG_M(yf1, xf1, 3, 3);
-      WG_M(yf1, xf1, 3, 4); WG_L(14);
-      WG_M(yf1, xf1, 3, 5);
-      WG_M(yf1, xf1, 3, 6);
-      WG_M(yf1, xf1, 3, 7);
-      WG_M(yf1, xf1, 4, 0);
-      WG_M(yf1, xf1, 4, 1); WG_L(15);
-      WG_M(yf1, xf1, 4, 2); WG_LD();
-      WG_M(yf1, xf1, 4, 3);
-      WG_M(yf1, xf1, 4, 4);
-      WG_M(yf1, xf1, 4, 5);
-      WG_M(yf1, xf1, 4, 6);
-      WG_M(yf1, xf1, 4, 7);
-      WG_M(yf1, xf1, 5, 0);
-      WG_M(yf1, xf1, 5, 1);
-      WG_M(yf1, xf1, 5, 2);
-      WG_M(yf1, xf1, 5, 3); WG_WAIT_VM(16); WG_BAR();
-      WG_M(yf1, xf1, 5, 4); WG_YRD(0, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 5, 5); WG_YRD(1, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 5, 6); WG_YRD(2, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 5, 7); WG_YRD(3, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 6, 0); WG_YRD(4, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 6, 1); WG_YRD(5, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 6, 2); WG_YRD(6, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 6, 3); WG_YRD(7, s_cur ^ 1, 0);
-      WG_M(yf1, xf1, 6, 4); WG_TR2(xl[0], xh[0], x_addr[s_cur ^ 1][0], 0);
-      WG_M(yf1, xf1, 6, 5); WG_TR2(xl[1], xh[1], x_addr[s_cur ^ 1][1], 0);
-      WG_M(yf1, xf1, 6, 6); WG_TR2(xl[2], xh[2], x_addr[s_cur ^ 1][2], 0);
-      WG_M(yf1, xf1, 6, 7); WG_TR2(xl[3], xh[3], x_addr[s_cur ^ 1][3], 0);
-      WG_M(yf1, xf1, 7, 0); WG_TR2(xl[4], xh[4], x_addr[s_cur ^ 1][4], 0);
-      WG_M(yf1, xf1, 7, 1); WG_TR2(xl[5], xh[5], x_addr[s_cur ^ 1][5], 0);
-      WG_M(yf1, xf1, 7, 2); WG_TR2(xl[6], xh[6], x_addr[s_cur ^ 1][6], 0);
-      WG_M(yf1, xf1, 7, 3); WG_TR2(xl[7], xh[7], x_addr[s_cur ^ 1][7], 0);
-      WG_M(yf1, xf1, 7, 4);
-      WG_M(yf1, xf1, 7, 5);
-      WG_M(yf1, xf1, 7, 6);
-      WG_M(yf1, xf1, 7, 7); WG_WAIT_LGKM(0); WG_SET0();
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  // ---- prologue: K-tiles 0 and 1 of the stream into stages 0 and 1
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-#pragma unroll
-    for (int pc = 0; pc < 16; ++pc) issue_load(t, pc);
-    load_done();
-  }
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    WG_YRD(c, 0, 0);
-    WG_TR2(xl[c], xh[c], x_addr[0][c], 0);
-  }
-  WG_LGKM0();
-#pragma unroll
-  for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); }
-
-  WgCursor cc = locate(g0);
-  bool first = true;
-  int n_seg = 0;
-  auto kstep = [&](auto stage_c, int step) {
-    if (first) wktile(std::true_type{}, stage_c);
-    else wktile(std::false_type{}, stage_c);
-    first = false;
-
-    const bool last_of_tile = (cc.mt + 1 == cc.len) || (step + 1 == total);
-    if (last_of_tile) {
-      // flush this (tile, chunk) segment with fp32 atomics; the next segment starts from C = 0
-      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // asm MFMAs: the accumulator-read hazard is ours
-      const int ti = cc.t / tiles_j, tj = cc.t - ti * tiles_j;
-      float* dbase = dW + (size_t)(ti * TI + wi * 128 + fg * 4) * lddw + tj * TJ + wj * 128 + ft;
-      const bool to_ws = (ws != nullptr) && !rr && n_seg == 0 && (step + 1 == total);
-      if (to_ws) {       // (only the last segment of a workgroup: no K-tile is in flight towards the stages any more)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-      // the workgroups that share this output tile (one per chunk of M) flush at about the same
-      // time: each starts at a different 16-column group so they do not queue on the same lines
-#pragma nounroll
-      for (int bb = 0; bb < 8; ++bb) {
-        const int b = to_ws ? bb : ((bb + slot) & 7);
-        float v[32];
-#define WG_RD8(B)                                                                                   \
-  _Pragma("unroll") for (int q = 0; q < 32; ++q) v[q] = 0.f;                                        \
-  asm volatile("v_accvgpr_read_b32 %0, a[(" #B ")*32+0]\n\tv_accvgpr_read_b32 %1, a[(" #B ")*32+1]\n\t"   \
-               "v_accvgpr_read_b32 %2, a[(" #B ")*32+2]\n\tv_accvgpr_read_b32 %3, a[(" #B ")*32+3]\n\t"   \
-               "v_accvgpr_read_b32 %4, a[(" #B ")*32+4]\n\tv_accvgpr_read_b32 %5, a[(" #B ")*32+5]\n\t"   \
-               "v_accvgpr_read_b32 %6, a[(" #B ")*32+6]\n\tv_accvgpr_read_b32 %7, a[(" #B ")*32+7]"       \
-               : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]), "=v"(v[4]), "=v"(v[5]), "=v"(v[6]), "=v"(v[7]));   \
-  asm volatile("v_accvgpr_read_b32 %0, a[(" #B ")*32+8]\n\tv_accvgpr_read_b32 %1, a[(" #B ")*32+9]\n\t"   \
-               "v_accvgpr_read_b32 %2, a[(" #B ")*32+10]\n\tv_accvgpr_read_b32 %3, a[(" #B ")*32+11]\n\t" \
-               "v_accvgpr_read_b32 %4, a[(" #B ")*32+12]\n\tv_accvgpr_read_b32 %5, a[(" #B ")*32+13]\n\t" \
-               "v_accvgpr_read_b32 %6, a[(" #B ")*32+14]\n\tv_accvgpr_read_b32 %7, a[(" #B ")*32+15]"     \
-               : "=v"(v[8]), "=v"(v[9]), "=v"(v[10]), "=v"(v[11]), "=v"(v[12]), "=v"(v[13]), "=v"(v[14]), "=v"(v[15])); \
-  asm volatile("v_accvgpr_read_b32 %0, a[(" #B ")*32+16]\n\tv_accvgpr_read_b32 %1, a[(" #B ")*32+17]\n\t" \
-               "v_accvgpr_read_b32 %2, a[(" #B ")*32+18]\n\tv_accvgpr_read_b32 %3, a[(" #B ")*32+19]\n\t" \
-               "v_accvgpr_read_b32 %4, a[(" #B ")*32+20]\n\tv_accvgpr_read_b32 %5, a[(" #B ")*32+21]\n\t" \
-               "v_accvgpr_read_b32 %6, a[(" #B ")*32+22]\n\tv_accvgpr_read_b32 %7, a[(" #B ")*32+23]"     \
-               : "=v"(v[16]), "=v"(v[17]), "=v"(v[18]), "=v"(v[19]), "=v"(v[20]), "=v"(v[21]), "=v"(v[22]), "=v"(v[23])); \
-  asm volatile("v_accvgpr_read_b32 %0, a[(" #B ")*32+24]\n\tv_accvgpr_read_b32 %1, a[(" #B ")*32+25]\n\t" \
-               "v_accvgpr_read_b32 %2, a[(" #B ")*32+26]\n\tv_accvgpr_read_b32 %3, a[(" #B ")*32+27]\n\t" \
-               "v_accvgpr_read_b32 %4, a[(" #B ")*32+28]\n\tv_accvgpr_read_b32 %5, a[(" #B ")*32+29]\n\t" \
-               "v_accvgpr_read_b32 %6, a[(" #B ")*32+30]\n\tv_accvgpr_read_b32 %7, a[(" #B ")*32+31]"     \
-               : "=v"(v[24]), "=v"(v[25]), "=v"(v[26]), "=v"(v[27]), "=v"(v[28]), "=v"(v[29]), "=v"(v[30]), "=v"(v[31]))
-        switch (b) {
-          case 0: { WG_RD8(0); } break;
-          case 1: { WG_RD8(1); } break;
-          case 2: { WG_RD8(2); } break;
-          case 3: { WG_RD8(3); } break;
-          case 4: { WG_RD8(4); } break;
-          case 5: { WG_RD8(5); } break;
-          case 6: { WG_RD8(6); } break;
-          default: { WG_RD8(7); } break;
-        }
-#undef WG_RD8
-        if (to_ws) {
-          // through this wave's LDS patch (the K loop is over: the stages are free) so that the
-          // workspace is written in full 128-B lines: lanes hold columns, lines run along rows.
-          // 4-byte stores in 64-B pieces left the kernel waiting ~150 us after its last wave.
-          float* lw = reinterpret_cast<float*>(smem) + wid * (128 * 36) + (fg * 4) * 36 + (b & 1) * 16 + ft;
-#pragma unroll
-          for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) lw[(a * 16 + r) * 36] = v[a * 4 + r];
-          if (b & 1) {
-            // patch = 128 rows x 32 columns (pitch 36 words); one instruction moves 8 rows x 128 B
-            const float* lr = reinterpret_cast<const float*>(smem) + wid * (128 * 36) + (lane >> 3) * 36 + (lane & 7) * 4;
-            float* wrow = ws + (size_t)slot * (TI * TJ + 272) + (size_t)(wi * 128 + (lane >> 3)) * TJ + wj * 128 + (b >> 1) * 32 + (lane & 7) * 4;
-#pragma unroll
-            for (int it = 0; it < 16; ++it)
-              *reinterpret_cast<f32x4*>(wrow + it * 8 * TJ) = *reinterpret_cast<const f32x4*>(lr + it * 8 * 36);
-          }
-        } else {
-          float* dcol = dbase + b * 16;
-#pragma unroll
-          for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              // overwrite (whole-tile round-robin mode on a gradient the caller knows to be zero: the vocabulary matrix's
-              // first product of a step): a plain store - the atomic is a read-modify-write of 768 MB that is not in any cache
-              if (overwrite) dcol[(size_t)(a * 16 + r) * lddw] = alpha * v[a * 4 + r];
-              else unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
-        }
-      }
-      if (to_ws && tid == 0) ws_tile[slot] = tile_id0 + cc.t;
-      ++n_seg;
-      first = true;
-    }
-    advance(cc);
-  };
-  for (int step = 0; step < total; step += 2) {
-    kstep(std::integral_constant<int, 0>{}, step);
-    if (step + 1 < total) kstep(std::integral_constant<int, 1>{}, step + 1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
-#undef WG_LDB
-#undef WG_TR2
-#undef WG_YRD
-#undef WG_LGKM0
-#undef WG_ACC
-#undef WG_M
-#undef WG_L
-}
-
-// dW[tile] += alpha * sum of the workspace slots that hold a partial of that tile.
-// grid = (16 row groups, ntile); block = 256 threads, each 4 rows x 4 consecutive columns.
-__global__ __launch_bounds__(256)
-void wgrad_reduce_kernel(const float* __restrict__ ws, const int* __restrict__ ws_tile, int nslots,
-                         float* __restrict__ dW, int lddw, int tiles_j, float alpha, int ntile_a, WgradProblem pb) {
-  const int t = blockIdx.y, rg = blockIdx.x;
-  int tl = t;
-  if (t >= ntile_a) { tl = t - ntile_a; dW = pb.dW; lddw = pb.lddw; tiles_j = pb.tiles_j; }      // (second product of a paired launch)
-  const int ti = tl / tiles_j, tj = tl - ti * tiles_j;
-  const int col = (threadIdx.x & 63) * 4, row0 = rg * 16 + (threadIdx.x >> 6) * 4;
-  f32x4 acc[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bool any = false;
-  // the producer of chunk c of tile t is workgroup slot c * ntile + t (see gemm_wgrad_w4_kernel)
-  const int ntile = gridDim.y;
-  for (int s = t; s < nslots; s += ntile) {
-    if (ws_tile[s] != t) continue;
-    any = true;
-    const float* p = ws + (size_t)s * (65536 + 272) + row0 * 256 + col;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] += *reinterpret_cast<const f32x4*>(p + r * 256);
-  }
-  if (!any) return;
-  float* d = dW + (size_t)(ti * 256 + row0) * lddw + tj * 256 + col;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    f32x4 v = *reinterpret_cast<f32x4*>(d + (size_t)r * lddw);
-    v += alpha * acc[r];
-    *reinterpret_cast<f32x4*>(d + (size_t)r * lddw) = v;
-  }
-}
-
-// WGW4-END
+#include "gemm_wgrad_w4.hpp"
 // ---------------------------------------------------------------------------------
 // Weight-gradient kernel, persistent stream-K ring version (production path when M % 64 == 0):
 // dW[i,j] += alpha * sum_m dY[m,i] X[m,j] with 256(i) x 128(j) output tiles.  The whole
@@ -3664,8 +2644,7 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
   const int nmt = M / BK;
   const long long total_all = (long long)ntile * nmt;
   const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   // Two schedules.  Few tiles / long M (every layer weight): stream-K with chunk == share, see
   // above.  Many tiles / short M (the tied vocabulary matrix: 5862 tiles, 76 K-tiles): tiles
   // are dealt round-robin (WR_CHUNK == 0), each done over all of M by one workgroup, so that
@@ -3749,7 +2728,6 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
     y_addr[c] = lds0 + frow * WR_YROW + ((qy ^ fsw) << 4) + ((ft & 1) << 3);
     x_addr[c] = lds0 + WR_YB + frow * WR_XROW + ((qx ^ fsw) << 4) + ((ft & 1) << 3);
   }
-#define M3P_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
   // k-step 0 / 1 of a stage: row offsets 0 / 32 rows; second half of a fragment: +4 rows
   auto read_set0 = [&](uint32_t so, s16x4 (&y)[4][2], s16x4 (&x)[4][2]) {
 #pragma unroll
@@ -3765,7 +2743,6 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
       M3P_TR(x[c][0], x_addr[c] + so, 8192); M3P_TR(x[c][1], x_addr[c] + so, 9216);
     }
   };
-#define M3P_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -3798,7 +2775,7 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
 
   s16x4 y0[4][2], x0[4][2], y1[4][2], x1[4][2];
   read_set0(0, y0, x0);
-  M3P_LGKM0();
+  M3P_WAIT_LGKM(0);
   WgCursor cc = locate(g0);
   int cur = 0;
   for (int step = 0; step < total; ++step) {
@@ -3809,7 +2786,7 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
     read_set1(cur * WR_STAGE, y1, x1);
     __builtin_amdgcn_sched_barrier(0);
     mfma_batch(y0, x0);
-    M3P_LGKM0();
+    M3P_WAIT_LGKM(0);
     if (more2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -3818,7 +2795,7 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
     read_set0(nxt * WR_STAGE, y0, x0);   // stale after the last K-tile: unused
     __builtin_amdgcn_sched_barrier(0);
     mfma_batch(y1, x1);
-    M3P_LGKM0();
+    M3P_WAIT_LGKM(0);
 
     const bool last_of_tile = (cc.mt + 1 == cc.len) || (step + 1 == total);
     if (last_of_tile) {
@@ -3840,8 +2817,6 @@ void gemm_wgrad_ring_kernel(const bf16* __restrict__ dY, int lddy, const bf16* _
     advance(cc);
     cur = nxt;
   }
-#undef M3P_TR
-#undef M3P_LGKM0
 }
 
 }  // namespace
@@ -3853,16 +2828,9 @@ int launch_nt_fp8(const uint8_t* A, int lda, const uint8_t* W, int ldw, bf16* C,
   const int tiles_m = M / 256, tiles_n = N / 256;
   const size_t lds = 2 * 512 * ROWB + (EPI == M3P_EPI_DGELU ? GELU_TAB_N * sizeof(float) : 0) +
                      ((EPI == M3P_EPI_DGELU || EPI == M3P_EPI_MUL) ? 8 * 2048 : 8 * 4096);
-  auto kern = gemm_nt_w8f8_kernel<EPI, A_BF8>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  int grid = num_cus();
-  const int ntiles = tiles_m * tiles_n;
-  if (ntiles < grid) grid = (ntiles + 7) / 8 * 8;
+  constexpr auto kern = gemm_nt_w8f8_kernel<EPI, A_BF8>;
+  if (int rc = set_max_lds<kern>(lds)) return rc;
+  const int grid = persistent_grid(tiles_m * tiles_n);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, lda, W, ldw, C, ldc, M, N, K, ep, tiles_m, tiles_n);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
@@ -3936,9 +2904,8 @@ static int launch_streamk(const void* A, int lda, const void* W, int ldw, float*
   if (w_kn && (k_valid <= 0 || k_valid > K)) return M3P_EINVAL;
   const int tiles_m_all = (M + 255) / 256, tiles_n = (N + 127) / 128;
   const size_t lds = 3 * (256 + 128) * ROWB;
+  if (int rc = w_kn ? set_max_lds<gemm_nt_streamk_kernel<true>>(lds) : set_max_lds<gemm_nt_streamk_kernel<false>>(lds)) return rc;
   auto kern = w_kn ? gemm_nt_streamk_kernel<true> : gemm_nt_streamk_kernel<false>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
   const int grid = num_cus();
   const int nk = K / BK;
   // More tiles than workgroups: one launch would hand every workgroup 1.x whole tiles, so the workgroups
@@ -4006,12 +2973,7 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
   if (pb_in) pb = *pb_in;
   const int ntile = ti * tj + pb.tiles_i * pb.tiles_j;
   const size_t lds = 2 * 65536;
-  static bool attr_set_w = false;
-  if (!attr_set_w) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_wgrad_w4_kernel<YROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set_w = true;
-  }
+  if (int rc = set_max_lds<gemm_wgrad_w4_kernel<YROWS>>(lds)) return rc;
   const int grid = num_cus();
   const int nmt = M / 64;
   long long share = ((long long)ntile * nmt + grid - 1) / grid;
@@ -4124,12 +3086,7 @@ int m3p_gemm_wgrad_bf16(const void* dY, int lddy, const void* X, int ldx, float*
   if (plan == M3P_KERN_WGRAD_RING) {
     const int ti = (N + WR_I - 1) / WR_I, tj = (K + WR_J - 1) / WR_J;
     const size_t lds = 3 * WR_STAGE;
-    static bool attr_set_r = false;
-    if (!attr_set_r) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_wgrad_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      attr_set_r = true;
-    }
+    if (int rc = set_max_lds<gemm_wgrad_ring_kernel>(lds)) return rc;
     const int grid = num_cus();
     const int nmt = M / BK;
     long long share = ((long long)ti * tj * nmt + grid - 1) / grid;
@@ -4150,12 +3107,7 @@ int m3p_gemm_wgrad_bf16(const void* dY, int lddy, const void* X, int ldx, float*
   int m_chunk = ((M + split - 1) / split + BK - 1) / BK * BK;
   split = (M + m_chunk - 1) / m_chunk;
   const size_t lds = 4 * WG_TILE_BYTES;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (int rc = set_max_lds<gemm_wgrad_kernel>(lds)) return rc;
   hipLaunchKernelGGL(gemm_wgrad_kernel, dim3(ntile * split), dim3(256), lds, (hipStream_t)stream,
                      (const bf16*)dY, lddy, (const bf16*)X, ldx, dW, lddw, M, N, K, alpha, tiles_i, tiles_j, m_chunk);
   M3P_CHECK_LAUNCH();

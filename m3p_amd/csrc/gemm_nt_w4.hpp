@@ -1,3 +1,4 @@
+// (part of gemm.hip, included there; the two halves of the K-tile are generated: tools/gen/gen_w4.py -> gen/nt_w4_ktile_{a,b}.inc)
 // ---------------------------------------------------------------------------------
 // NT kernel, "w4" version: 256x256 output tile, FOUR waves (one per SIMD), each wave owns a
 // 128x128 sub-tile = 8x8 MFMA tiles (256 accumulator registers of the 512 a lone wave has).
@@ -38,19 +39,13 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = tiles_m * tiles_n;
-  const int n_strips = (tiles_n >= 12) ? (tiles_n + 3) / 4 : 1;
-  const int strip_w = (tiles_n + n_strips - 1) / n_strips;
+  const int strip_w = strip_width(tiles_n, 12, 4);
   auto split_tile = [&](int t, int& tm, int& tn) {
-    if (m_fast) { tn = t / tiles_m; tm = t - tn * tiles_m; return; }
-    const int strip = t / (tiles_m * strip_w);
-    const int rem = t - strip * tiles_m * strip_w;
-    const int bn = min(strip_w, tiles_n - strip * strip_w);
-    tm = rem / bn;
-    tn = strip * strip_w + (rem - tm * bn);
+    if (m_fast) { tn = t / tiles_m; tm = t - tn * tiles_m; return; }      // (this kernel's own order for a huge W)
+    ::split_tile(t, tiles_m, tiles_n, strip_w, tm, tn);
   };
   const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   auto tile_of = [&](int q) { return q * nwg + slot; };
   const int my_tiles = (ntiles > slot) ? (ntiles - slot + nwg - 1) / nwg : 0;
   if (my_tiles == 0) return;
@@ -112,8 +107,6 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     a_addr1[ks] = a_addr[ks] + STAGE;
     b_addr1[ks] = b_addr[ks] + STAGE;
   }
-#define W4_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define W4_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   // The 256 accumulator registers live in a[0:255] under OUR control: every MFMA and every
   // accumulator read is inline asm with literal AGPR numbers (tile (i,j) = a[(8i+j)*4 .. +3]).
@@ -128,9 +121,6 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
 #define W4_L(PIECE) do { issue_load(s_cur, PIECE); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   bf16x8 fa0[8], fw0[8], fa1[8], fw1[8];
-#define W4_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define W4_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define W4_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
   // One K-tile (tile j in stage s, tile j+1 landing in stage s^1) = 128 MFMAs with every memory instruction in their shadow.
   // What decides the schedule is the time a global -> LDS transfer is given to land:
@@ -151,11 +141,11 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
     __builtin_amdgcn_sched_barrier(0);
     {
       constexpr bool FIRST = FIRST0;
-@KT_A@
+#include "gen/nt_w4_ktile_a.inc"
     }
     {
       constexpr bool FIRST = false;
-@KT_B@
+#include "gen/nt_w4_ktile_b.inc"
     }
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -171,11 +161,11 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  W4_DSR(fw0[0], b_addr[0], 0); W4_DSR(fw0[1], b_addr[0], 2048); W4_DSR(fw0[2], b_addr[0], 4096); W4_DSR(fw0[3], b_addr[0], 6144);
-  W4_DSR(fw0[4], b_addr[0], 8192); W4_DSR(fw0[5], b_addr[0], 10240); W4_DSR(fw0[6], b_addr[0], 12288); W4_DSR(fw0[7], b_addr[0], 14336);
-  W4_DSR(fa0[0], a_addr[0], 0); W4_DSR(fa0[1], a_addr[0], 2048); W4_DSR(fa0[2], a_addr[0], 4096); W4_DSR(fa0[3], a_addr[0], 6144);
-  W4_DSR(fa0[4], a_addr[0], 8192); W4_DSR(fa0[5], a_addr[0], 10240); W4_DSR(fa0[6], a_addr[0], 12288); W4_DSR(fa0[7], a_addr[0], 14336);
-  W4_LGKM0();
+  M3P_DSR(fw0[0], b_addr[0], 0); M3P_DSR(fw0[1], b_addr[0], 2048); M3P_DSR(fw0[2], b_addr[0], 4096); M3P_DSR(fw0[3], b_addr[0], 6144);
+  M3P_DSR(fw0[4], b_addr[0], 8192); M3P_DSR(fw0[5], b_addr[0], 10240); M3P_DSR(fw0[6], b_addr[0], 12288); M3P_DSR(fw0[7], b_addr[0], 14336);
+  M3P_DSR(fa0[0], a_addr[0], 0); M3P_DSR(fa0[1], a_addr[0], 2048); M3P_DSR(fa0[2], a_addr[0], 4096); M3P_DSR(fa0[3], a_addr[0], 6144);
+  M3P_DSR(fa0[4], a_addr[0], 8192); M3P_DSR(fa0[5], a_addr[0], 10240); M3P_DSR(fa0[6], a_addr[0], 12288); M3P_DSR(fa0[7], a_addr[0], 14336);
+  M3P_WAIT_LGKM(0);
 
   int c_q = 0, c_kt = 0;
   const bool io_aligned = ((ldc & 7) == 0) && (((uintptr_t)C & 15) == 0) &&
@@ -327,13 +317,8 @@ void gemm_nt_w4_kernel(const bf16* __restrict__ A, int lda, const bf16* __restri
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // junk loads of the tail must not outlive the LDS allocation
 #undef W4_LDB
 #undef W4_ACC
-#undef W4_DSR
-#undef W4_LGKM0
 #undef W4_M
 #undef W4_L
-#undef W4_WAIT_LGKM
-#undef W4_WAIT_VM
-#undef W4_BAR
 #undef W4_LD
 }
 

@@ -1,3 +1,4 @@
+// (part of gemm.hip, included there; the two halves of the K-tile are generated: tools/gen/gen_w4.py -> gen/wgrad_w4_ktile_{a,b}.inc)
 // ---------------------------------------------------------------------------------
 // Weight-gradient kernel, four-wave version of the stream-K ring kernel below/above:
 // dW[i,j] += alpha * sum_m dY[m,i] X[m,j] with 256(i) x 256(j) output tiles, 128x128 per wave
@@ -42,8 +43,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   const int nmt = M / KT;
   const long long total_all = (long long)ntile * nmt;
   const int nwg = gridDim.x;
-  const int per_xcd = nwg >> 3;
-  const int slot = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int slot = xcd_slot(nwg);
   // Schedule.  Few tiles / long M (every layer weight): each workgroup owns ONE (tile, M-chunk)
   // segment: C = nwg / ntile chunks per tile, slot = chunk * ntile + tile, so the 32 workgroups of
   // an XCD walk the same rows of M on neighbouring tiles and share them in L2, and every
@@ -194,7 +194,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #define WG_YRD(C, S, KS) do { if constexpr (YROWS) asm volatile("ds_read_b128 %0, %1" : "=v"(yq[C]) : "v"(yk_addr[KS][S][C])); \
                               else if constexpr ((KS) == 0) WG_TR2(yl[C], yh[C], y_addr[S][C], 0);                           \
                               else WG_TR2(yl[C], yh[C], y_addr[S][C], 16384); } while (0)
-#define WG_LGKM0() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
   asm volatile("" ::: "a0", "a255");     // reserve all 256 AGPRs (see gemm_nt_w4_kernel)
   // acc tile (b, a) = a[((b)*8+(a))*4 .. +3] holds D[i = 16a + 4(l >> 4) + r][j = 16b + (l & 15)]
@@ -210,9 +209,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   bf16x8 yq[8];                         // (YROWS: the first operand's fragments arrive whole)
   auto yfrag = [&](int c) { if constexpr (YROWS) return yq[c]; else return frag(yl[c], yh[c]); };
   bf16x8 yf0[8], xf0[8], yf1[8], xf1[8];
-#define WG_WAIT_LGKM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_WAIT_VM(N) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define WG_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_LD() do { load_done(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_SET1() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf1[c] = yfrag(c); xf1[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
 #define WG_SET0() do { _Pragma("unroll") for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); } __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -226,11 +222,11 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     __builtin_amdgcn_sched_barrier(0);
     {
       constexpr bool FIRST = FIRST0;
-@WKT_A@
+#include "gen/wgrad_w4_ktile_a.inc"
     }
     {
       constexpr bool FIRST = false;
-@WKT_B@
+#include "gen/wgrad_w4_ktile_b.inc"
     }
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -250,7 +246,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
     WG_YRD(c, 0, 0);
     WG_TR2(xl[c], xh[c], x_addr[0][c], 0);
   }
-  WG_LGKM0();
+  M3P_WAIT_LGKM(0);
 #pragma unroll
   for (int c = 0; c < 8; ++c) { yf0[c] = yfrag(c); xf0[c] = frag(xl[c], xh[c]); }
 
@@ -356,7 +352,6 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #undef WG_LDB
 #undef WG_TR2
 #undef WG_YRD
-#undef WG_LGKM0
 #undef WG_ACC
 #undef WG_M
 #undef WG_L

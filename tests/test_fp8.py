@@ -76,7 +76,7 @@ def test_gemm_nt_fp8_vs_fp32_product_of_the_same_operands(M, N, K, a_bf8):
     assert rel_l2(cs, c.float().sum(0)) < 1e-3
     # every epilogue element by element against the fp64 product of the dequantised 8-bit operands (exact in fp64), with the
     # worst-case accumulation term of the 8-bit MFMA (tests/util.py: gemm_bound, linear); the dGELU table is exact to fp32
-    # but below |u| = 2^-15, where its first entry serves: 2.4e-5 (csrc/gemm.hip:284)
+    # but below |u| = 2^-15, where its first entry serves: 2.4e-5 (csrc/gemm.hip: gelu_grad_table_fill)
     p64, ap64 = af.double() @ wf.double().t(), af.double().abs() @ wf.double().abs().t()
     b64, r64 = bias.double(), r.double()
     sc = torch.ones(N, dtype=torch.float64, device='cuda')

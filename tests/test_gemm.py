@@ -501,7 +501,7 @@ def test_gelu_byte_derivative_and_its_dgrad(M, N, K):
     # every element against fp64, in row chunks.  EPI_MULQ: the product times the decoded code (decoded with one fp32 fma,
     # and by gq_unpack in fp32: 2^-22 of the product covers both).  EPI_BIAS_GELUQ: h = max(x, 0) - |x| T(|x|) from a table
     # of the Gaussian tail T with 15 mantissa bits (the low byte holds the code: relative error 2^-15), indexed by |x|
-    # truncated to bf16 and evaluated at the middle of the bucket, and 4e-4 of h below |x| = 2^-11 (csrc/gemm.hip:745-755).
+    # truncated to bf16 and evaluated at the middle of the bucket, and 4e-4 of h below |x| = 2^-11 (csrc/gemm.hip: geluq_table_fill).
     # The bucket's half width is 2^-9 |x| in the middle of a binade but 2^-8 |x| at its bottom, so T is off by up to
     # phi(x) 2^-8 |x|.  The kernel's own accumulation error of x reaches h through gelu', at most 1.13.
     b64 = bias.double()

@@ -7,20 +7,33 @@ import os
 import re
 import shutil
 import subprocess
+import tempfile
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = '/opt/rocm/bin/hipcc'
+CSRC = os.path.join(ROOT, 'm3p_amd', 'csrc')
+_ISA = {}          # csrc file name -> its gfx950 assembly: every file is compiled at most once per session
+
+
+def isa(*srcs):
+    """Device assembly of the named csrc files, one after the other."""
+    for src in srcs:
+        if src not in _ISA:
+            with tempfile.TemporaryDirectory(prefix='m3p_isa_') as d:
+                out = os.path.join(d, src[:-4] + '.s')
+                cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
+                       '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(CSRC, src), '-o', out]
+                subprocess.run(cmd, check=True, capture_output=True, timeout=900)
+                with open(out) as f:
+                    _ISA[src] = f.read()
+    return '\n'.join(_ISA[src] for src in srcs)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_w4_gemm_accumulators_are_ours_in_every_epilogue(tmp_path):
-    out = tmp_path / 'gemm.s'
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
-           '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', 'gemm.hip'), '-o', str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    text = out.read_text().splitlines()
+def test_w4_gemm_accumulators_are_ours_in_every_epilogue():
+    text = isa('gemm.hip').splitlines()
     starts = [i for i, l in enumerate(text) if re.match(r'^_ZN\S*gemm_nt_w4_kernelILi\dEE\S*:', l)]
     assert len(starts) == 7, 'expected the seven epilogue instantiations of the production kernel'
     for st in starts:
@@ -49,16 +62,12 @@ def test_w4_gemm_accumulators_are_ours_in_every_epilogue(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_eight_wave_gemm_fits_two_waves_per_simd(tmp_path):
+def test_eight_wave_gemm_fits_two_waves_per_simd():
     """The eight-wave 256x256 NT kernel lives on 256 registers per wave (two waves per SIMD): 128 accumulators + a
     quarter K-tile of fragments.  A whole k-step of fragments ahead spilled inside the K loop - this pins the budget: no
     scratch at all in the plain / bias / residual instantiations, a few dwords at most (epilogue only) in the
     dGELU / multiply ones, occupancy 2 everywhere; the fp8 body may keep its small epilogue spill."""
-    out = tmp_path / 'gemm.s'
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
-           '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', 'gemm.hip'), '-o', str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=900)
-    body = out.read_text()
+    body = isa('gemm.hip')
     seen = 0
     queued = 0
     copies = 0
@@ -97,15 +106,11 @@ def test_eight_wave_gemm_fits_two_waves_per_simd(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_attention_kernels_keep_their_occupancy(tmp_path):
+def test_attention_kernels_keep_their_occupancy():
     """No production instantiation of the attention kernels spills to scratch, the M3P-sequence instantiations (S = 164: six
     32-row steps, eleven 16-row tiles) fit three waves per SIMD (three ~48-KB workgroups per CU) and the long-sequence
     ones (eight waves per workgroup) two."""
-    out = tmp_path / 'attention.s'
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
-           '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', 'attention.hip'), '-o', str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    body = out.read_text()
+    body = isa('attention.hip')
     seen = 0
     for m in re.finditer(r'^(_ZN\S*attn_(fwd|bwd)_kernelI(\S*?)EEv\S*):', body, re.M):
         k = body.index('; Kernel info:', body.index('.Lfunc_end', m.end()))
@@ -123,7 +128,7 @@ def test_attention_kernels_keep_their_occupancy(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_no_lds_read_may_overwrite_the_address_of_the_next_one(tmp_path):
+def test_no_lds_read_may_overwrite_the_address_of_the_next_one():
     """Two LDS reads from one inline-asm statement share their address register; if the first read's destination includes
     that register (outputs not marked early-clobber) the second read's address is the first read's DATA whenever the wave
     stalls between the two for longer than the LDS latency.  The weight-gradient kernel had 21 such pairs: one wrong
@@ -132,14 +137,10 @@ def test_no_lds_read_may_overwrite_the_address_of_the_next_one(tmp_path):
     the same address register must not write it."""
     pat = re.compile(r'\bds_read\w*\s+(v\[(\d+):(\d+)\]|v(\d+)),\s+v(\d+)\b')
     n_pairs = 0
-    for src in sorted(os.listdir(os.path.join(ROOT, 'm3p_amd', 'csrc'))):
+    for src in sorted(os.listdir(CSRC)):
         if not src.endswith('.hip'):
             continue
-        out = tmp_path / (src[:-4] + '.s')
-        cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
-               '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', src), '-o', str(out)]
-        subprocess.run(cmd, check=True, capture_output=True, timeout=900)
-        text = out.read_text().splitlines()
+        text = isa(src).splitlines()
         prev = None
         for i, l in enumerate(text):
             m = pat.search(l)
@@ -157,17 +158,13 @@ def test_no_lds_read_may_overwrite_the_address_of_the_next_one(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_nothing_touches_an_inline_lds_reads_destination_before_its_wait(tmp_path):
+def test_nothing_touches_an_inline_lds_reads_destination_before_its_wait():
     """The four-wave kernels read LDS through inline asm the compiler does not see as loads (fragment reads of the K loop,
     the epilogue's staging rows): the destination registers hold the data only after OUR s_waitcnt lgkmcnt.  To the compiler
     they are defined at once - given control flow between a read and its wait it copies them (phi moves) in front of the
     wait, which is how a pipelined form of the epilogue went wrong in round 4.  Checked on the ISA: between an inline
     ds_read and the next s_waitcnt lgkmcnt no compiler-generated instruction may name a register of its destination."""
-    out = tmp_path / 'gemm.s'
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
-           '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', 'gemm.hip'), '-o', str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    text = out.read_text().splitlines()
+    text = isa('gemm.hip').splitlines()
     rd = re.compile(r'^\s*ds_read\w*\s+v\[(\d+):(\d+)\]')
     reg = re.compile(r'\bv(?:\[(\d+):(\d+)\]|(\d+))')
     starts = [i for i, l in enumerate(text) if re.match(r'^_ZN\S*gemm_(?:nt|wgrad)_w4_kernel\S*:', l)]
@@ -211,23 +208,20 @@ def test_nothing_touches_an_inline_lds_reads_destination_before_its_wait(tmp_pat
 
 
 def test_generated_kernel_bodies_are_up_to_date():
-    """The two four-wave GEMM bodies in gemm.hip are generated (tools/gen/gen_w4.py: the MFMA / memory-instruction schedule is
-    a table there); the committed file must be what the generator makes of the committed templates."""
+    """The K-tile bodies of the two four-wave GEMM kernels (csrc/gen/*.inc, included by gemm_nt_w4.hpp / gemm_wgrad_w4.hpp) are
+    generated (tools/gen/gen_w4.py: the MFMA / memory-instruction schedule is a table there); the committed files must be
+    what the generator makes."""
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen', 'gen_w4.py'), '--check'], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr or r.stdout
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_persistent_attention_backward_fits_three_waves_per_simd(tmp_path):
+def test_persistent_attention_backward_fits_three_waves_per_simd():
     """attn_bwd_p_kernel runs one twelve-wave workgroup per CU: three waves per SIMD means at most 170 registers and no scratch;
     and its per-head bias sums are the halving butterfly of round 6 (bank-masked v_add_f32_dpp from inline asm - 48 of them per
     instantiation with dropout: two flushes of 16 + 8), not four full butterflies per value."""
-    out = tmp_path / 'attention.s'
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-ffp-contract=fast',
-           '-Wno-unused-result', '--cuda-device-only', '-S', os.path.join(ROOT, 'm3p_amd', 'csrc', 'attention.hip'), '-o', str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    body = out.read_text()
+    body = isa('attention.hip')
     found = 0
     for m in re.finditer(r'^(_ZN\S*attn_bwd_p_kernelILb[01]ELb[01]E\S*):', body, re.M):
         end = body.index('.Lfunc_end', m.end())

@@ -128,7 +128,7 @@ def assert_block_bound(got, ref, blocks, rtol, floor=ROW_FLOOR, what=''):
 
 # The GELU of csrc/common.hpp (gelu_parts), shared by the GEMM epilogues and the streaming GELU kernels.  The dGELU epilogue
 # looks gelu' up in a table of fp32 values that is exact to fp32 except below |u| = 2^-15, where the first entry serves:
-# 2.4e-5 (csrc/gemm.hip:284).  The GELU epilogue evaluates erf with |error| <= 1.5e-7 (csrc/common.hpp:83).
+# 2.4e-5 (csrc/gemm.hip: gelu_grad_table_fill).  The GELU epilogue evaluates erf with |error| <= 1.5e-7 (csrc/common.hpp:83).
 EPS_DGELU = 2.4e-5
 EPS_ERF = 1.5e-7
 

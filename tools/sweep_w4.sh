@@ -2,6 +2,7 @@
 # Schedule sweep of the two generated four-wave kernels (tools/gen/gen_w4.py knobs): every variant is generated and compiled in a
 # private copy of tools/gen + m3p_amd/csrc under /tmp/sweep_w4 and linked to m3p_amd/libm3p_hip_sw_<name>.so (git-ignored), for
 # tools/ab_gemm.py / tools/ab_wgrad.py on the GPU box.   usage: tools/sweep_w4.sh name "ENV=VAL ENV2=VAL" [name2 "..."] ...
+# (the generator writes the copy's m3p_amd/csrc/gen/*.inc, which gemm_nt_w4.hpp / gemm_wgrad_w4.hpp - parts of gemm.hip - include)
 set -u
 R=$(cd "$(dirname "$0")/.." && pwd)
 W=/tmp/sweep_w4; mkdir -p $W
