@@ -185,6 +185,28 @@ M3P_API int m3p_gemm_wgrad_store_bf16(const void* dY, int lddy, const void* X, i
 M3P_API int m3p_gemm_wgrad_pair_bf16(const void* dYa, int lddya, const void* Xa, int ldxa, float* dWa, int lddwa, int Na, int Ka,
                                      const void* dYb, int lddyb, const void* Xb, int ldxb, float* dWb, int lddwb, int Nb, int Kb,
                                      int M, float alpha, void* workspace, size_t workspace_bytes, void* stream);
+/* Up to M3P_WGRAD_GROUP_MAX weight gradients over the same M rows in ONE launch of the four-wave kernel, one workgroup per
+ * 256 x 256 output tile over the WHOLE of M: dW_k += alpha * dY_k^T X_k.  Where the pair above splits M over nwg / tiles
+ * chunks and folds the chunks' partial tiles through the workspace, a group that brings about one tile per CU (seven 36-tile
+ * products: the layer weight gradients of 2 1/3 encoder layers) has no partial tiles at all: every tile is a single running
+ * fp32 sum, added to dW once by its only writer - no workspace, no reduce kernel, no atomics, bit-reproducible.
+ * Accepted when every item is a whole-tile shape of the four-wave kernel (N % 256 == 0, K % 256 == 0, M % 64 == 0, M >= 4096,
+ * lddy / ldx % 8 == 0 and >= N / K, 16-byte aligned operands), lddw >= K, lddw % 4 == 0, dW 16-byte aligned, and the tiles of
+ * all items together are at most the persistent grid (the CU count, or what m3p_set_persistent_grid left of it).  Anything
+ * else returns M3P_ENOTIMPL (M3P_EINVAL for null pointers, non-positive sizes, n_items outside 1 .. M3P_WGRAD_GROUP_MAX) and
+ * writes nothing: the caller runs the products through the calls above.  The items' dW must not overlap. */
+#define M3P_WGRAD_GROUP_MAX 12
+typedef struct M3PWgradItem {
+  const void* dY; const void* X; float* dW;
+  int lddy, ldx, lddw, N, K;
+} M3PWgradItem;
+M3P_API int m3p_gemm_wgrad_group_bf16(const M3PWgradItem* items, int n_items, int M, float alpha, void* stream);
+/* The group's placement (host only, no device access): place[w], w < workgroups (a multiple of 8, at most 256), is what
+ * workgroup w of the launch computes - item << 16 | tile row << 8 | tile column, or 0xffffffff for none.  Workgroup w runs on
+ * XCD w % 8; tiles of one product share operand panels only through their XCD's L2, so a product's tiles are dealt to as few
+ * XCDs as possible: whole XCDs first, the remainders best-fit into what is left.  tiles_i / tiles_j: N / 256, K / 256 per
+ * item.  Returns M3P_ENOTIMPL when the tiles do not fit. */
+M3P_API int m3p_gemm_wgrad_group_place(const int* tiles_i, const int* tiles_j, int n_items, int workgroups, uint32_t* place);
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm (eps = 1e-12 in the reference: transformer.py:244,660,694,709)

@@ -1995,6 +1995,16 @@ struct WgradProblem {
   const bf16* dY; const bf16* X; float* dW;
   int lddy, ldx, lddw, tiles_i, tiles_j;
 };
+// the products and the placement of a grouped whole-tile launch, passed by kernel argument (1.5 KB): workgroup w computes tile
+// (place[w] >> 8 & 255, place[w] & 255) of item place[w] >> 16; 0xffffffff = nothing (wgrad_group_place)
+struct WgradGroup {
+  struct Item {
+    const bf16* dY; const bf16* X; float* dW;
+    int lddy, ldx, lddw, tiles_j;
+  } item[M3P_WGRAD_GROUP_MAX];
+  uint32_t place[256];
+};
+__device__ __forceinline__ const WgradGroup& wgrad_group_of(const WgradGroup& g) { return g; }      // (the kernel's trailing pack)
 
 // ---------------------------------------------------------------------------------
 // NT kernel, stream-K version with fp32 atomic output: Cf[M,N] += alpha * A[M,K] W[N,K]^T for
@@ -3006,6 +3016,9 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
 //
 //   shape                                                  kernel                                   why
 //   -----------------------------------------------------  ---------------------------------------  --------------------------------
+//   up to 12 whole-tile products over one M, together at   four-wave 256x256, ONE workgroup per      no partial tiles: 1339 TF over seven
+//     most one tile per CU (m3p_gemm_wgrad_group_bf16,       tile over all of M, placed by XCD;       36-tile units against 1109 through the
+//     not part of wgrad_plan: the caller groups)             dW += alpha * acc once, plain stores     launches below (tools/ab_wgrad_group.py)
 //   M % 64 == 0, M >= 4096, N % 256 == 0, K % 256 == 0,    four-wave 256x256, one (tile, M-chunk)   1063 / 858 / 983 TF on FFN1 / FFN2 /
 //     >= 9 output tiles, < 4 tiles per CU                    segment per workgroup; partial tiles     QKV against 845 / 751 / 808 on the
 //                                                            go to the caller's workspace and a       ring kernel; no atomics, summed in
@@ -3064,6 +3077,82 @@ int m3p_gemm_wgrad_pair_bf16(const void* dYa, int lddya, const void* Xa, int ldx
   if (lddya < Na || ldxa < Ka || lddyb < Nb || ldxb < Kb) return M3P_EINVAL;
   WgradProblem pb = {(const bf16*)dYb, (const bf16*)Xb, dWb, lddyb, ldxb, lddwb, Nb / 256, Kb / 256};
   return launch_wgrad_w4<>(dYa, lddya, Xa, ldxa, dWa, lddwa, M, Na, Ka, alpha, workspace, workspace_bytes, stream, &pb);
+}
+
+// Placement of a grouped launch: workgroup w sits on XCD w % 8, position w / 8 of its `workgroups / 8` CUs.  The tiles of one
+// product share their dY row panels and X column panels only through the XCD's L2, so every product first takes as many WHOLE
+// XCDs as it fills, then the remainders go, largest first, each to the XCD with the least room that still takes it whole
+// (split over the emptiest ones only when none does).  Seven 36-tile products on 256 CUs: 32 tiles of product k on XCD k,
+// the seven remainders of 4 on XCD 7.  A product's tiles are dealt in row-major order, so neighbours in an XCD share a dY panel.
+int m3p_gemm_wgrad_group_place(const int* tiles_i, const int* tiles_j, int n_items, int workgroups, uint32_t* place) {
+  if (!tiles_i || !tiles_j || !place || n_items < 1 || n_items > M3P_WGRAD_GROUP_MAX || workgroups < 8 || workgroups > 256 ||
+      (workgroups % 8) != 0)
+    return M3P_EINVAL;
+  const int per_xcd = workgroups / 8;
+  int total = 0;
+  for (int k = 0; k < n_items; ++k) {
+    if (tiles_i[k] < 1 || tiles_j[k] < 1 || tiles_i[k] > 256 || tiles_j[k] > 256) return M3P_EINVAL;
+    total += tiles_i[k] * tiles_j[k];
+    if (total > workgroups) return M3P_ENOTIMPL;
+  }
+  int used[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // tiles placed on each XCD
+  int next[M3P_WGRAD_GROUP_MAX];                // next tile of each item to place
+  for (int w = 0; w < workgroups; ++w) place[w] = 0xffffffffu;
+  auto put = [&](int k, int xcd, int n) {
+    for (int e = 0; e < n; ++e, ++next[k], ++used[xcd])
+      place[used[xcd] * 8 + xcd] = (uint32_t)k << 16 | (uint32_t)(next[k] / tiles_j[k]) << 8 | (uint32_t)(next[k] % tiles_j[k]);
+  };
+  int xcd = 0;
+  for (int k = 0; k < n_items; ++k) {
+    next[k] = 0;
+    for (int full = tiles_i[k] * tiles_j[k] / per_xcd; full > 0; --full) put(k, xcd++, per_xcd);
+  }
+  int order[M3P_WGRAD_GROUP_MAX];
+  for (int k = 0; k < n_items; ++k) order[k] = k;
+  auto left = [&](int k) { return tiles_i[k] * tiles_j[k] - next[k]; };
+  std::stable_sort(order, order + n_items, [&](int a, int b) { return left(a) > left(b); });
+  for (int o = 0; o < n_items; ++o) {
+    const int k = order[o];
+    while (left(k) > 0) {
+      int best = -1, emptiest = 0;
+      for (int x = 0; x < 8; ++x) {
+        const int room = per_xcd - used[x];
+        if (room >= left(k) && (best < 0 || room < per_xcd - used[best])) best = x;
+        if (room > per_xcd - used[emptiest]) emptiest = x;
+      }
+      if (best >= 0) put(k, best, left(k));
+      else put(k, emptiest, per_xcd - used[emptiest]);
+    }
+  }
+  return M3P_OK;
+}
+
+int m3p_gemm_wgrad_group_bf16(const M3PWgradItem* items, int n_items, int M, float alpha, void* stream) {
+  if (!items || n_items < 1 || n_items > M3P_WGRAD_GROUP_MAX || M <= 0) return M3P_EINVAL;
+  const int grid = num_cus();
+  if (grid > 256) return M3P_ENOTIMPL;
+  WgradGroup grp;
+  int ti[M3P_WGRAD_GROUP_MAX], tj[M3P_WGRAD_GROUP_MAX];
+  for (int k = 0; k < n_items; ++k) {
+    const M3PWgradItem& it = items[k];
+    if (!it.dY || !it.X || !it.dW || it.N <= 0 || it.K <= 0) return M3P_EINVAL;
+    if (!wgrad_w4_ok(M, it.N, it.K, it.lddy, it.ldx, it.dY, it.X) || it.lddy < it.N || it.ldx < it.K || it.lddw < it.K ||
+        (it.lddw % 4) != 0 || ((uintptr_t)it.dW & 15) || it.N / 256 > 256 || it.K / 256 > 256)
+      return M3P_ENOTIMPL;
+    ti[k] = it.N / 256;
+    tj[k] = it.K / 256;
+    grp.item[k] = {(const bf16*)it.dY, (const bf16*)it.X, it.dW, it.lddy, it.ldx, it.lddw, tj[k]};
+  }
+  for (int k = n_items; k < M3P_WGRAD_GROUP_MAX; ++k) grp.item[k] = {nullptr, nullptr, nullptr, 0, 0, 0, 0};
+  for (int w = grid; w < 256; ++w) grp.place[w] = 0xffffffffu;
+  if (int rc = m3p_gemm_wgrad_group_place(ti, tj, n_items, grid, grp.place)) return rc;
+  const size_t lds = 2 * 65536;
+  if (int rc = set_max_lds<gemm_wgrad_w4_kernel<false, WgradGroup>>(lds)) return rc;
+  hipLaunchKernelGGL((gemm_wgrad_w4_kernel<false, WgradGroup>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
+                     (const bf16*)nullptr, 0, (const bf16*)nullptr, 0, (float*)nullptr, 0, M, 0, 0, alpha, 0, 0, 1,
+                     (float*)nullptr, (int*)nullptr, 0, WgradProblem{}, grp);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
 }
 
 int m3p_gemm_wgrad_store_bf16(const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, int M, int N, int K,

@@ -17,12 +17,19 @@
 // which deliver exactly what the two transposing reads deliver for a contraction-strided operand: eight consecutive
 // contraction elements of one output row per lane.  Everything else - the second operand's transposing reads, the MFMA
 // stream, the (tile, chunk) schedule, the workspace flush and the reduction - is the weight-gradient kernel's.
-template <bool YROWS>
+// GROUP (m3p_gemm_wgrad_group_bf16): up to twelve products over the same M, ONE workgroup per output tile over the whole of
+// M.  The workgroup reads its (item, tile) from the launch's placement table before the K loop - the pair's product pick with
+// a table in place of one comparison - and ends with its tile's only flush: dW_tile += alpha * acc in whole 128-B lines,
+// through the LDS patches of the workspace flush.  No workspace, no tile-id words, no reduction.
+// It is this kernel with a WgradGroup appended to its arguments (GRP = one type; every other launch: none, and the same code as
+// before the parameter existed); the arguments in front of it are then unused.
+template <bool YROWS, typename... GRP>
 __global__ __launch_bounds__(256)
 void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16* __restrict__ X_a, int ldx_a,
                           float* __restrict__ dW_a, int lddw_a, int M, int N, int K, float alpha,
                           int tiles_i, int tiles_j_a, int WR_CHUNK, float* __restrict__ ws, int* __restrict__ ws_tile,
-                          int overwrite, WgradProblem pb) {
+                          int overwrite, WgradProblem pb, GRP... grp) {
+  constexpr bool GROUP = sizeof...(GRP) != 0;
   // Two products over the same M in one launch (pb.tiles != 0; one-segment-per-workgroup mode only): the tiles of product b
   // follow those of product a in the tile numbering, every workgroup picks its product once, before the K loop.  36 tiles of
   // out_lin + q/k/v then share one launch, one end-of-kernel flush and one reduction instead of 9 tiles x 28 chunks beside
@@ -50,12 +57,22 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   // workgroup flushes exactly once.  (Dealing the ragged remainder out stream-K style left two
   // workgroups with 18 tile flushes each: 340 us for a 150-us kernel.)  nwg - C * ntile
   // workgroups stay idle (1.6 % for 36 tiles).  Many tiles (WR_CHUNK == 0): whole tiles round-robin.
-  const bool rr = (WR_CHUNK == 0);
+  const bool rr = !GROUP && (WR_CHUNK == 0);
   // first-segment partials go to this workgroup's private slot of the workspace with plain stores
   // (ws_tile[slot] = tile id, -1 = nothing there); wgrad_reduce_kernel folds the slots into dW.
-  if (ws && tid == 0) ws_tile[slot] = -1;
+  if (!GROUP && ws && tid == 0) ws_tile[slot] = -1;
   int total, seg_tile, seg_m0, seg_len;
-  if (rr) {
+  if constexpr (GROUP) {
+    // the placement is by workgroup id, not by slot: the host dealt the tiles to the XCDs (workgroup w runs on XCD w & 7)
+    const WgradGroup& g = wgrad_group_of(grp...);
+    const uint32_t pl = g.place[blockIdx.x];
+    if (pl == 0xffffffffu) return;
+    const WgradGroup::Item& it = g.item[pl >> 16];
+    dY = it.dY; X = it.X; dW = it.dW; lddy = it.lddy; ldx = it.ldx; lddw = it.lddw; tiles_j = it.tiles_j;
+    seg_tile = (int)((pl >> 8) & 255u) * tiles_j + (int)(pl & 255u);
+    seg_m0 = 0; seg_len = nmt;
+    total = nmt;
+  } else if (rr) {
     const int my_tiles = (ntile > slot) ? (ntile - slot + nwg - 1) / nwg : 0;
     if (my_tiles == 0) return;
     total = my_tiles * nmt;
@@ -264,7 +281,8 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
       asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // asm MFMAs: the accumulator-read hazard is ours
       const int ti = cc.t / tiles_j, tj = cc.t - ti * tiles_j;
       float* dbase = dW + (size_t)(ti * TI + wi * 128 + fg * 4) * lddw + tj * TJ + wj * 128 + ft;
-      const bool to_ws = (ws != nullptr) && !rr && n_seg == 0 && (step + 1 == total);
+      // (GROUP: the workgroup's one segment is the whole tile - the same line-wise flush, onto dW itself)
+      const bool to_ws = GROUP || ((ws != nullptr) && !rr && n_seg == 0 && (step + 1 == total));
       if (to_ws) {       // (only the last segment of a workgroup: no K-tile is in flight towards the stages any more)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -321,10 +339,21 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
           if (b & 1) {
             // patch = 128 rows x 32 columns (pitch 36 words); one instruction moves 8 rows x 128 B
             const float* lr = reinterpret_cast<const float*>(smem) + wid * (128 * 36) + (lane >> 3) * 36 + (lane & 7) * 4;
+            if constexpr (GROUP) {
+              // this workgroup is the tile's only writer in the launch: a plain read-add-store of the same lines of dW
+              float* drow = dW + (size_t)(ti * TI + wi * 128 + (lane >> 3)) * lddw + tj * TJ + wj * 128 + (b >> 1) * 32 + (lane & 7) * 4;
+              f32x4 dv[16];
+#pragma unroll
+              for (int it = 0; it < 16; ++it) dv[it] = *reinterpret_cast<const f32x4*>(drow + (size_t)(it * 8) * lddw);
+#pragma unroll
+              for (int it = 0; it < 16; ++it)
+                *reinterpret_cast<f32x4*>(drow + (size_t)(it * 8) * lddw) = dv[it] + alpha * *reinterpret_cast<const f32x4*>(lr + it * 8 * 36);
+            } else {
             float* wrow = ws + (size_t)slot * (TI * TJ + 272) + (size_t)(wi * 128 + (lane >> 3)) * TJ + wj * 128 + (b >> 1) * 32 + (lane & 7) * 4;
 #pragma unroll
             for (int it = 0; it < 16; ++it)
               *reinterpret_cast<f32x4*>(wrow + it * 8 * TJ) = *reinterpret_cast<const f32x4*>(lr + it * 8 * 36);
+            }
           }
         } else {
           float* dcol = dbase + b * 16;
@@ -338,7 +367,7 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
               else unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
         }
       }
-      if (to_ws && tid == 0) ws_tile[slot] = tile_id0 + cc.t;
+      if (!GROUP && to_ws && tid == 0) ws_tile[slot] = tile_id0 + cc.t;
       ++n_seg;
       first = true;
     }

@@ -511,6 +511,53 @@ def first_rows_sink(model, tensor):
     return sink, base, rows
 
 
+WGRAD_QUEUE_TILES = None    # output tiles one grouped weight-gradient launch may hold; None = one per CU (tests lower it)
+
+
+class WgradQueue:
+    """The encoder layers' weight gradients, held back until ONE launch can give every CU a whole output tile
+    (ops.gemm_wgrad_group: no partial tiles, no reduction).  A unit is what the layer loop launches at one place - one product,
+    or the out_lin + q/k/v pair -, each product a (dy, x, dw) of whole 256 x 256 tiles; at d = 768 every unit has 36 tiles,
+    seven units fill 256 CUs.  The queue keeps the operands alive until their launch (ordinary references: the launch is
+    queued on the stream before they are dropped, like every other kernel's operands).  A list that is not nearly full is not
+    worth a grouped launch - T tiles keep T CUs busy for the whole of M -, so it goes through the per-product calls
+    (ops.gemm_wgrad / ops.gemm_wgrad_pair), and so does a unit the grouped launch cannot take."""
+    FILL = 7 / 8        # fewest tiles, as a share of the capacity, that a grouped launch is made for
+
+    def __init__(self, enabled=True):
+        self.capacity = 0 if not enabled else WGRAD_QUEUE_TILES if WGRAD_QUEUE_TILES is not None else L.num_cus()
+        self.units, self.tiles, self.items, self.M = [], 0, 0, None
+
+    @staticmethod
+    def _run(unit):
+        if len(unit) == 2:
+            ops.gemm_wgrad_pair(*unit[0], *unit[1])
+        else:
+            ops.gemm_wgrad(*unit[0])
+
+    def add(self, *unit):
+        """One unit of one or two (dy, x, dw): queued if a grouped launch can take it, launched at once if not."""
+        M = unit[0][0].shape[0]
+        tiles = sum((dy.shape[1] // 256) * (x.shape[1] // 256) for dy, x, _ in unit)
+        if self.capacity <= 0 or tiles > self.capacity or not all(ops.wgrad_group_takes(*p) for p in unit):
+            self._run(unit)
+            return
+        if self.units and (M != self.M or self.tiles + tiles > self.capacity or self.items + len(unit) > L.WGRAD_GROUP_MAX):
+            self.flush()
+        self.units.append(unit)
+        self.tiles, self.items, self.M = self.tiles + tiles, self.items + len(unit), M
+
+    def flush(self):
+        """Launch what is held: as one group if that fills the CUs (and the launcher takes it), else product by product."""
+        units, tiles = self.units, self.tiles
+        self.units, self.tiles, self.items, self.M = [], 0, 0, None
+        if not units:
+            return
+        if tiles < self.FILL * self.capacity or not ops.gemm_wgrad_group([p for u in units for p in u]):
+            for u in units:
+                self._run(u)
+
+
 N_ENC_ARGS = 17     # positional arguments of EncoderFn.forward (backward returns one None per argument)
 
 ROW_TILE = 256          # the compact row set is whole 256-row GEMM tiles (the byte-GELU epilogues take nothing else)
@@ -842,6 +889,10 @@ class EncoderFn(torch.autograd.Function):
             _, wt8, dws = st8.weights[(i, wsite)]
             return ops.gemm_nt_fp8(g8, wt8, epi, a_is_bf8=True, descale_a=dgs, descale_b=dws, **kw)
 
+        # The full-size layers' weight gradients wait in a queue until a launch is full (WgradQueue; about 1.5 GB of gradient
+        # activations of ~2 1/3 layers stay alive meanwhile at cfg2).  Data parallelism sends each layer's bucket as soon as
+        # the layer is done, and fp8 keeps its own launch order: both launch at once, exactly as before.
+        wq = WgradQueue(enabled=hook is None and model.ddp_hook is None and st8 is None)
         for i in reversed(range(nL)):
             a, f = 'attentions.%d.' % i, 'ffns.%d.' % i
             (h_in, qkv, ctxt, lse, pre1, mean1, rstd1, x1, u, hact, pre2, mean2, rstd2, ctx_c, mask_i) = saved_layers[i]
@@ -860,7 +911,10 @@ class EncoderFn(torch.autograd.Function):
                                            seed=seed('ffn', i), p_drop=p_drop, **rr)
             if dY2 is None:
                 dY2 = dpre2
-            ops.gemm_wgrad(dY2, hact, ar.g(f + 'lin2.weight'))
+            if compact:
+                ops.gemm_wgrad(dY2, hact, ar.g(f + 'lin2.weight'))
+            else:
+                wq.add((dY2, hact, ar.g(f + 'lin2.weight')))
             du8 = None
             if ctx.u_holds_grad == 'q':
                 o8 = {}
@@ -878,7 +932,10 @@ class EncoderFn(torch.autograd.Function):
                 dU = dgrad(dY2, i, 'dy2', 'w2', ar.wt[('lin2', i)], L.EPI_MUL if ctx.u_holds_grad else L.EPI_DGELU, aux=u,
                            colsum=ar.g(f + 'lin1.bias'))
             del hact, u, pre2
-            ops.gemm_wgrad(dU, x1, ar.g(f + 'lin1.weight'))
+            if compact:
+                ops.gemm_wgrad(dU, x1, ar.g(f + 'lin1.weight'))
+            else:
+                wq.add((dU, x1, ar.g(f + 'lin1.weight')))
             dx1 = dgrad(dU, i, 'du', 'w1', ar.wt[('lin1', i)], L.EPI_RES, aux=dpre2, pre8=du8)
             del dU, dpre2, dY2
             # LayerNorm1 and the attention-output dropout
@@ -902,12 +959,13 @@ class EncoderFn(torch.autograd.Function):
                 ops.gemm_wgrad(dqkv, h_in, ar.qkv_wgrad(i))
             else:
                 # out_lin's and q/k/v's weight gradients in one launch (9 + 27 output tiles fill the CUs like one FFN gradient)
-                ops.gemm_wgrad_pair(dqkv, h_in, ar.qkv_wgrad(i), dAO, ctxt, ar.g(a + 'out_lin.weight'))
+                wq.add((dqkv, h_in, ar.qkv_wgrad(i)), (dAO, ctxt, ar.g(a + 'out_lin.weight')))
             dh_ = dgrad(dqkv, i, 'dqkv', 'wqkv', ar.wt[('qkv', i)], L.EPI_RES, aux=dpre1)
             del dqkv, dctx, dAO, dpre1, dx1
-            ar.touch_layer(i)
+            ar.touch_layer(i)       # (host bookkeeping; a queued product is launched on this stream before backward returns)
             if hook is not None:
                 hook.layer_done(i, last)
+        wq.flush()
         if ctx.h0_mode is not None:       # no embedding assembly in this pass: the rows' gradient goes back to whoever made them
             if hook is not None:
                 hook.embed_done(last, ids=None, rows=None, n_max=ctx.tok_rows_max)

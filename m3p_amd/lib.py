@@ -36,6 +36,15 @@ class Epilogue(C.Structure):
     ]
 
 
+WGRAD_GROUP_MAX = 12
+
+
+class WgradItem(C.Structure):
+    """struct M3PWgradItem (include/m3p_hip.h)."""
+    _fields_ = [('dY', C.c_void_p), ('X', C.c_void_p), ('dW', C.c_void_p),
+                ('lddy', C.c_int32), ('ldx', C.c_int32), ('lddw', C.c_int32), ('N', C.c_int32), ('K', C.c_int32)]
+
+
 _p, _i, _f, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_uint32
 
 # name -> (restype, argtypes); mirrors include/m3p_hip.h one to one
@@ -52,6 +61,8 @@ SIGNATURES = {
     'm3p_gemm_wgrad_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
     'm3p_gemm_wgrad_store_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
     'm3p_gemm_wgrad_pair_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
+    'm3p_gemm_wgrad_group_bf16': (_i, [C.POINTER(WgradItem), _i, _i, _f, _p]),
+    'm3p_gemm_wgrad_group_place': (_i, [C.POINTER(_i), C.POINTER(_i), _i, _i, C.POINTER(_u32)]),
     'm3p_layernorm_fwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
     'm3p_layernorm_bwd': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _u32, _u32, _f, _p]),
     'm3p_layernorm_bwd_rows': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _u32, _u32, _f, _p, _p]),

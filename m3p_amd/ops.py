@@ -272,6 +272,52 @@ def gemm_wgrad_pair(dy_a, x_a, dw_a, dy_b, x_b, dw_b, alpha=1.0):
     _prof_end(e0, ('gemm_wgrad_pair', M, Na + Nb, Ka))
 
 
+def wgrad_group_takes(dy, x, dw):
+    """Whether dw += dy^T @ x can be an item of a grouped whole-tile launch (the conditions of m3p_gemm_wgrad_group_bf16 that
+    one product decides alone; the launcher checks them again, and the summed tile count)."""
+    M, N = dy.shape
+    K = x.shape[1]
+    return (M % 64 == 0 and M >= 4096 and N % 256 == 0 and K % 256 == 0 and dy.stride(1) == 1 and x.stride(1) == 1
+            and dw.stride(-1) == 1 and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dw.stride(0) % 4 == 0
+            and dw.stride(0) >= K and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and dw.data_ptr() % 16 == 0)
+
+
+def wgrad_group_place(tiles, workgroups):
+    """The grouped launch's placement for items of tiles = [(tiles_i, tiles_j), ...] on `workgroups` workgroups (host only):
+    a list with (item, tile row, tile column) or None per workgroup; workgroup w runs on XCD w % 8."""
+    n = len(tiles)
+    ti = (C.c_int * n)(*[t[0] for t in tiles])
+    tj = (C.c_int * n)(*[t[1] for t in tiles])
+    place = (C.c_uint32 * max(workgroups, 1))()
+    L.check(L.load().m3p_gemm_wgrad_group_place(ti, tj, n, workgroups, place), 'm3p_gemm_wgrad_group_place')
+    return [None if p == 0xffffffff else (p >> 16, (p >> 8) & 255, p & 255) for p in place]
+
+
+def gemm_wgrad_group(items, alpha=1.0):
+    """dw += alpha * dy^T @ x for every (dy, x, dw) of `items` (at most lib.WGRAD_GROUP_MAX, one shared M) in ONE launch with
+    one workgroup per 256 x 256 output tile over all of M: no partial tiles, no reduction.  Returns False - nothing launched,
+    nothing written - when the launcher declines (M3P_ENOTIMPL: a shape that is not whole tiles, more tiles than CUs): the
+    caller sends the products through gemm_wgrad / gemm_wgrad_pair."""
+    n = len(items)
+    assert 1 <= n <= L.WGRAD_GROUP_MAX
+    M = items[0][0].shape[0]
+    arr = (L.WgradItem * n)()
+    for k, (dy, x, dw) in enumerate(items):
+        _chk_bf16(dy, x)
+        assert dw.dtype == torch.float32 and dw.stride(-1) == 1 and dy.stride(1) == 1 and x.stride(1) == 1
+        assert dy.shape[0] == M and x.shape[0] == M and dw.shape[0] >= dy.shape[1] and dw.shape[1] >= x.shape[1]
+        arr[k] = L.WgradItem(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), dy.stride(0), x.stride(0), dw.stride(0),
+                             dy.shape[1], x.shape[1])
+    key = ('gemm_wgrad_group', M, sum(dy.shape[1] * x.shape[1] for dy, x, _ in items) // 256, 256)     # (2 M N K = the group's flops)
+    e0 = _prof_begin(key)
+    rc = L.load().m3p_gemm_wgrad_group_bf16(arr, n, M, alpha, L.stream())
+    if rc == -2:
+        return False
+    L.check(rc, 'm3p_gemm_wgrad_group_bf16')
+    _prof_end(e0, key)
+    return True
+
+
 def layernorm_fwd(x, gamma, beta, rowmask=None, eps=1e-12):
     _chk_bf16(x)
     rows, d = x.shape
