@@ -336,6 +336,31 @@ M3P_API size_t m3p_vocab_sample_workspace_bytes(int n, int V, int top_k);
 M3P_API int m3p_vocab_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, uint32_t seed, void* workspace,
                              size_t workspace_bytes, long long* words, float* logprob, float* key, void* stream);
 
+/* Nucleus (top-p) sampling: m3p_vocab_sample with a probability-mass cut on its allowed set (csrc/select.hip; NumPy twin:
+ * m3p_amd/rng.py nucleus_cut / sample_allowed / sample_words with top_p).  All masses are over the candidate set K of a row:
+ * top_k = 0 every word w < V; 1 <= top_k <= 16 the row's first top_k words under (logit descending, word ascending) - exactly
+ * the allowed set of m3p_vocab_sample.  With x_w = float(logits[r, w]), y_w = x_w*inv_t and m = max over K of y:
+ *   mass(v)    = #{w in K : x_w == v} * exp(v*inv_t - m)      for each distinct logit value v of the row
+ *   C(v)       = the sum of mass(v') over v' >= v;  C_above(v) the same over v' > v;  Z = C(-inf)
+ *   cut x*     = max{ v : C(v) >= top_p*Z }
+ *   allowed set A = { w in K : x_w >= x* }
+ * Words of equal logit are treated alike - the whole class at the cut is in: A has mass >= top_p, is the smallest union of
+ * whole classes that does, and always holds the row's maximum.  The draw, logprob and key are m3p_vocab_sample's with A as the
+ * allowed set: words[r] = the argmax over A of key(r, w) = x_w*inv_t - log(-log u), u from m3p_hash32(r*V + w, seed) (the
+ * counter does not change), ties to the lowest word; logprob = y_w - log-sum-exp of y over A.
+ *   cut     fp32 [n]   the bf16 value x*; may be NULL
+ * 0 < top_p (M3P_EINVAL otherwise, NaN included); top_p >= 1 is "off": the call is m3p_vocab_sample itself - its bits in
+ * words, logprob and key - and cut = -inf.  The device sums fixed-point integers (top_k = 0) or fp32 in a fixed order (top_k
+ * >= 1) where the definition is exact: a row whose cumulated mass lands on top_p*Z to within 4e-6 Z may cut one class earlier
+ * or later (the bound is derived in tests/test_vocab_nucleus.py).  Integer atomics only, no floating-point atomics: the same
+ * inputs give the same bits.  A -inf logit has mass 0 and never enters A before a finite one.  Limits, preconditions, logits
+ * and workspace as for m3p_vocab_sample, with m3p_vocab_nucleus_plan and m3p_vocab_nucleus_workspace_bytes(n, V, top_k). */
+M3P_API int m3p_vocab_nucleus_plan(int n, int V, int ld, int top_k);
+M3P_API size_t m3p_vocab_nucleus_workspace_bytes(int n, int V, int top_k);
+M3P_API int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed,
+                                     void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key,
+                                     float* cut, void* stream);
+
 /* The same attention for the TRAINING of the causal / cross-attention sub-layers (teacher forcing: Tq = the whole target
  * sequence, pos0 = 0): dropout on the probabilities (stream (seed, thresh24) indexed ((b*H + h)*Tq + t)*Lk + key) and the
  * log-sum-exp lse fp32 [B, H, Tq] kept for backward.  B*H*Tq*Lk < 2^32. */

@@ -43,6 +43,10 @@
 // within ln V + a few of the row's maximum WHATEVER inv_t is (a term d below the maximum weighs e^-d), so the sum moves by
 // < 1e-6 relative, below the rounding of lse_T itself.  The scale inv_t enters only through the size of lse_T: its fp32
 // rounding is |lse_T| * 6e-8, which is why the tests hold logprob to 1e-5 * max(1, max|x| * inv_t / 16).
+//
+// Nucleus (top-p) sampling (decoder.py: generate(sample_top_p=...); m3p_vocab_nucleus_sample) cuts that allowed set to the
+// words whose logit is at least x*, the largest logit value whose cumulated mass reaches top_p - see the block in front of
+// vnuc_coarse_kernel; with 1 <= top_k <= 16 the cut is a sum over the lanes of vsmp_topk_kernel<true>.
 #include "common.hpp"
 #include <math.h>
 
@@ -275,9 +279,11 @@ constexpr float VSMP_BAND = 0.04f;        // twice a bound (0.02) on |approximat
 // accurate maximum and e^ the approximate one:  approx(e*) >= key(e*) - d >= key(e^) - d >= approx(e^) - 2 d), and only
 // those are evaluated with vsmp_log_e - the approximate maximum itself by every lane, the others (a few per cent of the
 // lanes hold one) in a loop that re-reads their logit.  The winner and its key are those of evaluating every element.
+// CUT (nucleus sampling): columns whose sortable logit lies below cutkey[row] get no key, and no statistics are written.
+template <bool CUT>
 __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks, float inv_t,
                                                         uint32_t seed, unsigned long long* __restrict__ wkey,
-                                                        float* __restrict__ pstat) {
+                                                        float* __restrict__ pstat, const uint32_t* __restrict__ cutkey) {
   __shared__ unsigned long long redk[4];
   __shared__ float redm[4];
   __shared__ float reds[4];
@@ -288,6 +294,8 @@ __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict_
   const uint32_t idx0 = (uint32_t)row * (uint32_t)V + col0;        // (the launcher holds n * V below 2^32)
   float y[16], ka[16];                     // x * inv_t (-inf: no column) and the approximate key (NaN: no column)
   float mx = -INFINITY, amax = -INFINITY;
+  uint32_t ck = 0u;
+  if constexpr (CUT) ck = cutkey[row];
   int lbest = -1;                          // column in the chunk of the approximate maximum (-1: the thread holds no column)
   float xbest = 0.f;
 #pragma unroll
@@ -299,7 +307,9 @@ __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict_
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float yy = -INFINITY, k = __builtin_nanf("");
-      if (e < left) {                                      // columns at or past V hold anything: never looked at
+      bool take = e < left;                                // columns at or past V hold anything: never looked at
+      if constexpr (CUT) take = take && vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]) >= ck;
+      if (take) {
         const float x = __uint_as_float((uint32_t)v[e] << 16);
         yy = __fmul_rn(x, inv_t);
         k = __fmaf_rn(x, inv_t, -vsmp_log_e_approx(idx0 + (uint32_t)(lc0 + e), seed));
@@ -343,6 +353,10 @@ __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict_
   for (int q = 0; q < 4; ++q) {
     best = redk[q] > best ? redk[q] : best;
     mx = fmaxf(mx, redm[q]);
+  }
+  if constexpr (CUT) {                     // (the allowed set's log-sum-exp comes from vnuc_cut_kernel)
+    if (tid == 0) wkey[blockIdx.x] = best;
+    return;
   }
   float s = 0.f;
 #pragma unroll
@@ -392,10 +406,14 @@ __global__ __launch_bounds__(256) void vsmp_merge_kernel(const bf16* __restrict_
 }
 
 // a wave per row over the candidates vs_chunk_kernel left with k = top_k: lane j ends up with the row's j-th entry under
-// (logit descending, word ascending); keys, lse_T and the argmax over those lanes
+// (logit descending, word ascending); keys, lse_T and the argmax over those lanes.
+// CUT (nucleus sampling): the lanes are the candidate set in the order of the cumulated mass, so the cut is a sum over
+// <= 16 lanes - lane j is allowed iff the mass of the lanes with a LARGER logit is below top_p * Z (whole classes of equal
+// logits).  fp32 sums in lane order, the same in every lane: reproducible.
+template <bool CUT>
 __global__ __launch_bounds__(256) void vsmp_topk_kernel(const uint32_t* __restrict__ cand, int n, int V, int nchunks, int k, float inv_t,
                                                        uint32_t seed, long long* __restrict__ words, float* __restrict__ logprob,
-                                                       float* __restrict__ key_out) {
+                                                       float* __restrict__ key_out, float top_p, float* __restrict__ cut_out) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
@@ -432,12 +450,269 @@ __global__ __launch_bounds__(256) void vsmp_topk_kernel(const uint32_t* __restri
     k64 = vsmp_key64(__fmaf_rn(x, inv_t, -vsmp_log_e((uint32_t)row * (uint32_t)V + word, seed)), word);
   }
   const float m = wave_max(yy);
+  if constexpr (CUT) {
+    float w = mine != 0ull ? expf(__fmaf_rn(x, inv_t, -m)) : 0.f;      // (ONE rounding of x * inv_t - m; -inf: mass 0)
+    w = w == w ? w : 0.f;
+    float Z = 0.f, above = 0.f;
+    for (int i = 0; i < k; ++i) {
+      const float xi = __shfl(x, i, 64), wi = __shfl(w, i, 64);
+      Z += wi;
+      if (xi > x) above += wi;
+    }
+    const bool in = mine != 0ull && (double)above < (double)top_p * (double)Z;
+    float sa = 0.f, xc = x;
+    for (int i = 0; i < k; ++i) {
+      const float xi = __shfl(x, i, 64), wi = __shfl(w, i, 64);
+      if (__shfl((int)in, i, 64)) {        // (the allowed lanes are a prefix: the last one holds the cut)
+        sa += wi;
+        xc = xi;
+      }
+    }
+    k64 = in ? k64 : 0ull;
+    const unsigned long long win = wave_max_u64(k64);
+    if (k64 == win && win != 0ull) {
+      words[row] = (long long)word;
+      logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(sa)));
+      if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
+      if (cut_out) cut_out[row] = xc;
+    }
+    return;
+  }
   const float s = wave_sum(yy > -INFINITY ? expf(yy - m) : 0.f);
   const unsigned long long win = wave_max_u64(k64);
   if (k64 == win && win != 0ull) {
     words[row] = (long long)word;
     logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(s)));
     if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// nucleus (top-p) sampling: m3p_vocab_nucleus_sample
+// ------------------------------------------------------------------------------------------------------------------------
+// The allowed set of a row is { w : x_w >= x* }, x* the largest logit value v whose cumulated mass C(v) (all words with a
+// logit >= v, softmax of x * inv_t) reaches top_p * Z: whole classes of equal logits, an exact weighted selection over the
+// 65 536 bf16 values.  Two levels of 256 bins over the sortable 16-bit key:
+//   vs_chunk_kernel (k = 1)   the chunks' maxima -> the row's m = fl(max x * inv_t)
+//   vnuc_coarse_kernel        a workgroup per (row, chunk): per HIGH byte of the key the mass of its words, every word's mass
+//                             the INTEGER  rint(expf(fma(x, inv_t, -m)) * 2^shift)  - integer sums do not depend on their
+//                             order, so LDS and global atomics leave the result reproducible bit for bit
+//   vnuc_scan_kernel          a wave per row: Z, the coarse bin that holds the cut, the mass above that bin
+//   vnuc_fine_kernel          a workgroup per (row, chunk): per LOW byte the NUMBER of words inside that bin - all words of
+//                             one value have one mass, so count * mass(value) adds up to the bin's mass of the coarse pass
+//   vnuc_cut_kernel           a wave per row: x*, the allowed set's mass -> its log-sum-exp
+//   vsmp_chunk_kernel<true>   the Gumbel-max pass, columns below x* without a key;  vnuc_merge_kernel: the row's winner
+// A -inf logit has mass 0; x* is the value of a word with a positive mass, so it is finite.  shift = min(40, 63 - bits(V)):
+// the sum of V masses of at most 2^shift (1 + 2^-20) stays below 2^64.
+constexpr int VN_BINS = 256;
+constexpr int VN_COPIES = 8;               // copies of a workgroup's bins in LDS, by lane & 7 (padded by one bin: other banks)
+
+struct VnucLayout {
+  size_t hist, fine, wkey, rowz, pstat, cand, rowbin, bytes;
+  int shift;
+};
+VnucLayout vnuc_layout(int n, int V) {
+  const size_t rows = (size_t)n, blocks = rows * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
+  VnucLayout L;
+  size_t o = 0;
+  L.hist = o;   o += rows * VN_BINS * sizeof(unsigned long long);       // [n, 256] u64, zeroed by the launcher with ...
+  L.fine = o;   o += rows * VN_BINS * sizeof(uint32_t);                 // ... [n, 256] u32 behind it
+  L.wkey = o;   o += blocks * sizeof(unsigned long long);
+  L.rowz = o;   o += rows * 2 * sizeof(unsigned long long);             // Z [n], mass above the cut's coarse bin [n]
+  L.pstat = o;  o += blocks * 2 * sizeof(float);
+  L.cand = o;   o += blocks * sizeof(uint32_t);
+  L.rowbin = o; o += rows * 3 * sizeof(uint32_t);                       // coarse bin [n], sortable cut [n], lse [n]
+  L.bytes = o;
+  int bits = 0;
+  while (bits < 32 && ((unsigned long long)V >> bits) != 0ull) ++bits;
+  L.shift = 63 - bits < 40 ? 63 - bits : 40;
+  return L;
+}
+
+// the row's m from the chunk maxima vs_chunk_kernel left (every lane of a wave gets it)
+__device__ __forceinline__ float vnuc_row_max(const float* __restrict__ pstat, long long row, int nchunks, float inv_t, int lane) {
+  const float* ps = pstat + (size_t)row * nchunks * 2;
+  float mx = -INFINITY;
+  for (int c = lane; c < nchunks; c += 64) mx = fmaxf(mx, ps[2 * c]);
+  return __fmul_rn(wave_max(mx), inv_t);
+}
+// the integer mass of a word of logit x: one rounding of x * inv_t - m, expf (not __expf: 1 ulp, documented), 2^-shift grid
+__device__ __forceinline__ unsigned long long vnuc_mass(float x, float inv_t, float m, float scale) {
+  const float w = expf(__fmaf_rn(x, inv_t, -m)) * scale;
+  return w > 0.f && w < 0x1p62f ? (unsigned long long)rintf(w) : 0ull;       // (NaN, inf - rows outside the contract - add nothing)
+}
+// do the cumulated mass c and the row's Z satisfy  c >= top_p * Z ?  (fp64: 2^-53 relative on either side)
+__device__ __forceinline__ bool vnuc_reaches(unsigned long long c, unsigned long long Z, float top_p) {
+  return (double)c >= (double)top_p * (double)Z;
+}
+// inclusive sums over the lanes at and above this one (lane 63 holds its own value, lane 0 the total)
+__device__ __forceinline__ unsigned long long vnuc_suffix_u64(unsigned long long v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long t = (unsigned long long)__shfl_down((long long)v, o, 64);
+    if (lane + o < 64) v += t;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void vnuc_coarse_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks, float inv_t,
+                                                         float scale, const float* __restrict__ pstat,
+                                                         unsigned long long* __restrict__ hist) {
+  __shared__ unsigned long long bins[VN_COPIES][VN_BINS + 1];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+#pragma unroll
+  for (int c = 0; c < VN_COPIES; ++c) bins[c][tid] = 0ull;
+  const float m = vnuc_row_max(pstat, row, nchunks, inv_t, lane);
+  __syncthreads();
+  unsigned long long* mine = bins[tid & (VN_COPIES - 1)];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
+    const int left = V - (chunk * VS_CHUNK + lc0);          // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if (e < left) {                                       // columns at or past V hold anything: never looked at
+        const uint32_t b = v[e] == 0x8000u ? 0u : (uint32_t)v[e];
+        const unsigned long long w = vnuc_mass(__uint_as_float(b << 16), inv_t, m, scale);
+        if (w != 0ull) atomicAdd(&mine[vs_sortable16(b) >> 8], w);
+      }
+    }
+  }
+  __syncthreads();
+  unsigned long long s = 0ull;
+#pragma unroll
+  for (int c = 0; c < VN_COPIES; ++c) s += bins[c][tid];
+  if (s != 0ull) atomicAdd(hist + (size_t)row * VN_BINS + tid, s);
+}
+
+// a wave per row over its 256 coarse bins (lane l holds bins 4 l .. 4 l + 3): Z, the highest bin at which the mass cumulated
+// from the top reaches top_p * Z, and the mass above that bin.  (No bin - a row outside the contract -: bin -1, nothing below.)
+__global__ __launch_bounds__(256) void vnuc_scan_kernel(const unsigned long long* __restrict__ hist, int n, float top_p,
+                                                       unsigned long long* __restrict__ rowz, unsigned long long* __restrict__ rowabove,
+                                                       int* __restrict__ rowbin) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
+  const unsigned long long* h = hist + (size_t)row * VN_BINS + 4 * lane;
+  const unsigned long long b[4] = {h[0], h[1], h[2], h[3]};
+  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
+  const unsigned long long inc = vnuc_suffix_u64(s, lane);
+  const unsigned long long Z = (unsigned long long)__shfl((long long)inc, 0, 64);
+  unsigned long long c = inc - s, above = 0ull;
+  int best = -1;
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const unsigned long long ci = c + b[q];
+    if (best < 0 && Z != 0ull && vnuc_reaches(ci, Z, top_p)) {
+      best = 4 * lane + q;
+      above = c;
+    }
+    c = ci;
+  }
+  const int win = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
+  if (win < 0 ? lane == 0 : best == win) {                 // (a bin belongs to one lane)
+    rowz[row] = Z;
+    rowabove[row] = above;
+    rowbin[row] = win;
+  }
+}
+
+__global__ __launch_bounds__(256) void vnuc_fine_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks,
+                                                       const int* __restrict__ rowbin, uint32_t* __restrict__ fine) {
+  __shared__ uint32_t cnt[VN_COPIES][VN_BINS + 1];
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+#pragma unroll
+  for (int c = 0; c < VN_COPIES; ++c) cnt[c][tid] = 0u;
+  const uint32_t bin = (uint32_t)rowbin[row];              // (-1: no column matches)
+  __syncthreads();
+  uint32_t* mine = cnt[tid & (VN_COPIES - 1)];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
+    const int left = V - (chunk * VS_CHUNK + lc0);
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t sk = vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]);
+      if (e < left && (sk >> 8) == bin) atomicAdd(&mine[sk & 0xFFu], 1u);
+    }
+  }
+  __syncthreads();
+  uint32_t s = 0u;
+#pragma unroll
+  for (int c = 0; c < VN_COPIES; ++c) s += cnt[c][tid];
+  if (s != 0u) atomicAdd(fine + (size_t)row * VN_BINS + tid, s);
+}
+
+// a wave per row over the 256 values of the cut's coarse bin (lane l holds the low bytes 4 l .. 4 l + 3): count * mass(value),
+// cumulated from the top behind the mass above the bin -> x* (sortable, and as a float), lse of the allowed set
+__global__ __launch_bounds__(256) void vnuc_cut_kernel(const uint32_t* __restrict__ fine, const float* __restrict__ pstat,
+                                                      const unsigned long long* __restrict__ rowz,
+                                                      const unsigned long long* __restrict__ rowabove, const int* __restrict__ rowbin,
+                                                      int n, int nchunks, float inv_t, float top_p, float scale, int shift,
+                                                      uint32_t* __restrict__ cutkey, float* __restrict__ lse, float* __restrict__ cut_out) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
+  const float m = vnuc_row_max(pstat, row, nchunks, inv_t, lane);
+  const int bin = rowbin[row];
+  const unsigned long long Z = rowz[row], above0 = rowabove[row];
+  unsigned long long b[4] = {0ull, 0ull, 0ull, 0ull};
+  if (bin >= 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t c = fine[(size_t)row * VN_BINS + 4 * lane + q];
+      if (c != 0u) b[q] = (unsigned long long)c * vnuc_mass(vs_value16((uint32_t)bin << 8 | (uint32_t)(4 * lane + q)), inv_t, m, scale);
+    }
+  }
+  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
+  unsigned long long c = above0 + (vnuc_suffix_u64(s, lane) - s), at = 0ull;
+  int best = -1;
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const unsigned long long ci = c + b[q];
+    if (best < 0 && b[q] != 0ull && vnuc_reaches(ci, Z, top_p)) {
+      best = 4 * lane + q;
+      at = ci;
+    }
+    c = ci;
+  }
+  const int win = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
+  if (win < 0 ? lane == 0 : best == win) {
+    // (no value - a row outside the contract -: no cut, every word allowed)
+    const uint32_t sk = win < 0 ? 0u : ((uint32_t)bin << 8 | (uint32_t)win);
+    const unsigned long long mass = win < 0 ? Z : at;
+    cutkey[row] = sk;
+    lse[row] = (float)((double)m + (log((double)mass) - (double)shift * 0.693147180559945309417));
+    if (cut_out) cut_out[row] = win < 0 ? -INFINITY : vs_value16(sk);
+  }
+}
+
+// a wave per row: the row's winner among its chunks' winners; logprob against the allowed set's lse
+__global__ __launch_bounds__(256) void vnuc_merge_kernel(const bf16* __restrict__ logits, int ld, int n, int V, int nchunks, float inv_t,
+                                                        const unsigned long long* __restrict__ wkey, const float* __restrict__ lse,
+                                                        long long* __restrict__ words, float* __restrict__ logprob,
+                                                        float* __restrict__ key_out) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
+  const unsigned long long* wk = wkey + (size_t)row * nchunks;
+  unsigned long long best = 0ull;
+  for (int c = lane; c < nchunks; c += 64) best = wk[c] > best ? wk[c] : best;
+  best = wave_max_u64(best);
+  if (lane == 0) {
+    const uint32_t word = min(~(uint32_t)best, (uint32_t)(V - 1));      // (a chunk's winner is a column below V; the clamp guards the read)
+    const float x = __uint_as_float((uint32_t)reinterpret_cast<const unsigned short*>(logits)[(size_t)row * ld + word] << 16);
+    words[row] = (long long)word;
+    logprob[row] = __fmaf_rn(x, inv_t, -lse[row]);
+    if (key_out) key_out[row] = vs_value32((uint32_t)(best >> 32));
   }
 }
 
@@ -503,8 +778,8 @@ int m3p_vocab_sample(const void* logits, int ld, int n, int V, float inv_t, int 
   if (top_k == 0) {
     unsigned long long* wkey = (unsigned long long*)workspace;
     float* pstat = (float*)(wkey + (size_t)n * nchunks);
-    hipLaunchKernelGGL(vsmp_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld,
-                       V, nchunks, inv_t, seed, wkey, pstat);
+    hipLaunchKernelGGL(vsmp_chunk_kernel<false>, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16*)logits, ld, V, nchunks, inv_t, seed, wkey, pstat, (const uint32_t*)nullptr);
     M3P_CHECK_LAUNCH();
     hipLaunchKernelGGL(vsmp_merge_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, n, V, nchunks,
                        inv_t, (const unsigned long long*)wkey, (const float*)pstat, words, logprob, key);
@@ -516,8 +791,79 @@ int m3p_vocab_sample(const void* logits, int ld, int n, int V, float inv_t, int 
   hipLaunchKernelGGL(vs_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, V,
                      nchunks, top_k, pstat, cand);
   M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsmp_topk_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)cand, n, V, nchunks, top_k,
-                     inv_t, seed, words, logprob, key);
+  hipLaunchKernelGGL(vsmp_topk_kernel<false>, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)cand, n, V, nchunks,
+                     top_k, inv_t, seed, words, logprob, key, 1.f, (float*)nullptr);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_vocab_nucleus_plan(int n, int V, int ld, int top_k) { return vsmp_plan(n, V, ld, top_k); }
+
+size_t m3p_vocab_nucleus_workspace_bytes(int n, int V, int top_k) {
+  if (n <= 0 || V <= 0 || top_k < 0) return 0;
+  const size_t plain = m3p_vocab_sample_workspace_bytes(n, V, top_k);       // (top_p >= 1 is m3p_vocab_sample itself)
+  if (top_k > 0) return plain;
+  const size_t nuc = vnuc_layout(n, V).bytes;
+  return nuc > plain ? nuc : plain;
+}
+
+int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed,
+                             void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key, float* cut,
+                             void* stream) {
+  const int rc = vsmp_plan(n, V, ld, top_k);
+  if (rc != M3P_OK) return rc;
+  if (!(inv_t > 0.f) || isinf(inv_t) || !(top_p > 0.f)) return M3P_EINVAL;
+  if (!logits || !workspace || !words || !logprob || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
+  if (workspace_bytes < m3p_vocab_nucleus_workspace_bytes(n, V, top_k)) return M3P_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (top_p >= 1.f) {                                      // no cut: today's draw, bit for bit; cut = -inf
+    if (cut && hipMemsetD32Async((hipDeviceptr_t)cut, (int)0xFF800000u, (size_t)n, st) != hipSuccess) return M3P_EINVAL;
+    return m3p_vocab_sample(logits, ld, n, V, inv_t, top_k, seed, workspace, workspace_bytes, words, logprob, key, stream);
+  }
+  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
+  const unsigned rows4 = (unsigned)((n + 3) / 4), blocks = (unsigned)(n * nchunks);
+  if (top_k > 0) {
+    float* pstat = (float*)workspace;                     // (the chunks' unscaled (max, sum): written, not read here)
+    uint32_t* cand = (uint32_t*)(pstat + (size_t)n * nchunks * 2);
+    hipLaunchKernelGGL(vs_chunk_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, top_k, pstat, cand);
+    M3P_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vsmp_topk_kernel<true>, dim3(rows4), dim3(256), 0, st, (const uint32_t*)cand, n, V, nchunks, top_k, inv_t,
+                       seed, words, logprob, key, top_p, cut);
+    M3P_CHECK_LAUNCH();
+    return M3P_OK;
+  }
+  const VnucLayout L = vnuc_layout(n, V);
+  char* ws = (char*)workspace;
+  unsigned long long* hist = (unsigned long long*)(ws + L.hist);
+  uint32_t* fine = (uint32_t*)(ws + L.fine);
+  unsigned long long* wkey = (unsigned long long*)(ws + L.wkey);
+  unsigned long long* rowz = (unsigned long long*)(ws + L.rowz);
+  unsigned long long* rowabove = rowz + n;
+  float* pstat = (float*)(ws + L.pstat);
+  uint32_t* cand = (uint32_t*)(ws + L.cand);
+  int* rowbin = (int*)(ws + L.rowbin);
+  uint32_t* cutkey = (uint32_t*)rowbin + n;
+  float* lse = (float*)rowbin + 2 * (size_t)n;
+  const float scale = ldexpf(1.f, L.shift);
+  if (hipMemsetAsync(hist, 0, (size_t)n * VN_BINS * (sizeof(unsigned long long) + sizeof(uint32_t)), st) != hipSuccess) return M3P_EINVAL;
+  hipLaunchKernelGGL(vs_chunk_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, 1, pstat, cand);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_coarse_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, inv_t, scale,
+                     (const float*)pstat, hist);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_scan_kernel, dim3(rows4), dim3(256), 0, st, (const unsigned long long*)hist, n, top_p, rowz, rowabove, rowbin);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_fine_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin, fine);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_cut_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)fine, (const float*)pstat,
+                     (const unsigned long long*)rowz, (const unsigned long long*)rowabove, (const int*)rowbin, n, nchunks, inv_t, top_p,
+                     scale, L.shift, cutkey, lse, cut);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsmp_chunk_kernel<true>, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, inv_t, seed, wkey,
+                     (float*)nullptr, (const uint32_t*)cutkey);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_merge_kernel, dim3(rows4), dim3(256), 0, st, (const bf16*)logits, ld, n, V, nchunks, inv_t,
+                     (const unsigned long long*)wkey, (const float*)lse, words, logprob, key);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }

@@ -20,7 +20,8 @@ the row whose slot holds that position's keys / values (``advance_owner`` after 
 reads through it), and with ``cache['beam']`` the source's keys / values are kept once per sentence, not once per beam.
 ``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, unseeded sampling and wider beams run the torch code below unchanged.
 ``generate(sample_seed=...)`` draws the next word by the seeded Gumbel-max contract of ``ops.vocab_sample`` (csrc/select.hip;
-NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation and the sampled words' log-probabilities.
+NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation, a nucleus (top-p) cut
+(``sample_top_p``: ``ops.vocab_nucleus_sample``) and the sampled words' log-probabilities.
 
 This module is forward only; the teacher-forced training pass of the same stream is ``functional.DecoderFn``
 (``TransformerModel.crossfwd`` picks it in training mode), and calling ``decoder_forward`` itself with autograd enabled on
@@ -244,15 +245,15 @@ def _select(logits, V, beam_scores, beam, k):
     return res
 
 
-def _sample_twin(scores, inv_t, seed, top_k):
-    """The seeded draw on fp32 scores [bs, V] through the NumPy twin of m3p_vocab_sample (a CPU model, a shape the launcher
-    declines, VOCAB_SELECT_MAX_K == 0) -> (words int64 [bs], logprob fp32 [bs]) on the scores' device."""
-    words, logprob, _ = rng.sample_words(scores.detach().cpu().numpy(), inv_t, seed, top_k)
+def _sample_twin(scores, inv_t, seed, top_k, top_p=None):
+    """The seeded draw on fp32 scores [bs, V] through the NumPy twin of m3p_vocab_sample / m3p_vocab_nucleus_sample (a CPU
+    model, a shape the launcher declines, VOCAB_SELECT_MAX_K == 0) -> (words int64 [bs], logprob fp32 [bs]) on the scores' device."""
+    words, logprob, _ = rng.sample_words(scores.detach().cpu().numpy(), inv_t, seed, top_k, top_p=top_p)
     return (torch.from_numpy(words).to(scores.device), torch.from_numpy(logprob.astype('float32')).to(scores.device))
 
 
 def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, sample_seed=None, sample_top_k=None,
-             return_logprobs=False):
+             return_logprobs=False, sample_top_p=None):
     """transformer.py:1216-1317: greedy (or temperature-sampled) decoding with the key / value cache.
     -> (generated (cur_len, bs) int64, gen_len (bs)).
 
@@ -262,16 +263,24 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     restricts the draw to the row's top_k words, and the step that decodes position ``cur_len`` uses the stream key
     ``rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)``.  A CUDA model whose shape the launcher takes runs
     ``ops.vocab_sample`` on the bf16 logits; everything else (a CPU model, top_k > 16, VOCAB_SELECT_MAX_K == 0) runs the NumPy
-    twin on ``word_scores`` - the same seed is the same random stream on both routes.  Torch's CPU and CUDA generators are
-    not touched, so a seeded run can be replayed exactly.  The counter of the random stream is (row of the batch, word): a
-    sentence's draw depends on its position in the batch.  ``return_logprobs`` (seeded runs only) adds a third value, fp32
-    (cur_len, bs): the log-probability, under the tempered and truncated distribution, of each sampled word; 0 at position
-    0, at pad positions and where <EOS> was forced at ``max_len``."""
+    twin on ``word_scores`` - the same seed is the same random stream on both routes.  ``sample_top_p`` (seeded runs only;
+    0 < p <= 1, None and any value >= 1.0 mean "off": every route is then bit for bit what it is without it) cuts the
+    candidates (every word, or the top_k) to the nucleus of include/m3p_hip.h (m3p_vocab_nucleus_sample): the words whose
+    logit is >= the largest logit value at which the mass cumulated from the top, under the tempered distribution over the
+    candidates, reaches p - whole classes of equal logits, the row's maximum always among them.  The routes and the stream
+    keys are the same (``ops.vocab_nucleus_sample`` on the device, ``rng.sample_words(top_p=...)`` as the twin).  Torch's CPU
+    and CUDA generators are not touched, so a seeded run can be replayed exactly.  The counter of the random stream is (row of
+    the batch, word): a sentence's draw depends on its position in the batch.  ``return_logprobs`` (seeded runs only) adds a
+    third value, fp32 (cur_len, bs): the log-probability, under the tempered, top-k and nucleus-truncated distribution, of
+    each sampled word; 0 at position 0, at pad positions and where <EOS> was forced at ``max_len``."""
     seeded = sample_seed is not None
     if sample_top_k is not None and not seeded:
         raise ValueError('sample_top_k needs sample_seed: the torch sampling path has no top-k mode')
     if return_logprobs and not seeded:
         raise ValueError('return_logprobs needs sample_seed')
+    if sample_top_p is not None and not seeded:
+        raise ValueError('sample_top_p needs sample_seed: the torch sampling path has no top-p mode')
+    top_p = rng.nucleus_top_p(sample_top_p)                  # (None: off; <= 0 or NaN raises ValueError)
     top_k = int(sample_top_k or 0)
     if top_k < 0:
         raise ValueError('sample_top_k must be >= 0, got %r' % (sample_top_k,))
@@ -296,8 +305,9 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
         temperature = 1.0 if sample_temperature is None else float(sample_temperature)
         inv_t = rng.inv_temperature(temperature)
         top_k = min(top_k, model.n_words)
+        takes = ops.vocab_sample_takes if top_p is None else ops.vocab_nucleus_takes
         sample_dev = (dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
-                      and ops.vocab_sample_takes(bs, model.n_words, model.arena().V_pad, top_k))
+                      and takes(bs, model.n_words, model.arena().V_pad, top_k))
         logprobs = torch.zeros((max_len, bs), dtype=torch.float32, device=dev) if return_logprobs else None
     while cur_len < max_len:
         tensor = decoder_forward(model, generated[:cur_len], gen_len, src_enc, src_len, positions[:cur_len],
@@ -307,12 +317,16 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
             step_seed = rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)
             if sample_dev:
                 logits, V = word_logits16(model, tensor[-1])
-                res = ops.vocab_sample(logits, V, temperature, step_seed, top_k)
+                if top_p is None:
+                    res = ops.vocab_sample(logits, V, temperature, step_seed, top_k)
+                else:
+                    res = ops.vocab_nucleus_sample(logits, V, temperature, step_seed, top_p, top_k)
                 if res is None:
-                    raise L.M3PError('m3p_vocab_sample declined (M3P_ENOTIMPL) a shape m3p_vocab_sample_plan took')
+                    name = 'm3p_vocab_sample' if top_p is None else 'm3p_vocab_nucleus_sample'
+                    raise L.M3PError('%s declined (M3P_ENOTIMPL) a shape its plan took' % name)
                 next_words, step_logprob = res[0], res[1]
             else:
-                next_words, step_logprob = _sample_twin(word_scores(model, tensor[-1]), inv_t, step_seed, top_k)
+                next_words, step_logprob = _sample_twin(word_scores(model, tensor[-1]), inv_t, step_seed, top_k, top_p)
             if return_logprobs:
                 logprobs[cur_len] = step_logprob.masked_fill(unfinished == 0, 0.0)
         elif select:                   # the first maximum of each row, from the bf16 logits

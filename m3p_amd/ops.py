@@ -491,6 +491,48 @@ def vocab_sample(logits, V, temperature, seed, top_k=0):
     return words, logprob, key
 
 
+def vocab_nucleus_takes(n, V, ld, top_k):
+    """Does the launcher of vocab_nucleus_sample take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
+    rc = L.load().m3p_vocab_nucleus_plan(n, V, ld, top_k)
+    if rc == _ENOTIMPL:
+        return False
+    L.check(rc, 'm3p_vocab_nucleus_plan')
+    return True
+
+
+def vocab_nucleus_sample(logits, V, temperature, seed, top_p, top_k=0):
+    """Seeded nucleus (top-p) sampling of a decoding step (csrc/select.hip; the contract is in include/m3p_hip.h, the NumPy
+    twin in m3p_amd/rng.py: nucleus_cut, sample_words(top_p=...)): vocab_sample with its allowed set cut to the words whose
+    logit is >= the row's cut x* = the largest logit value whose cumulated mass under softmax(float(logit) * inv_t) over the
+    candidates (every word, or the row's top_k) reaches top_p - whole classes of equal logits.
+    -> (words int64 [n], logprob fp32 [n], key fp32 [n], cut fp32 [n]); logprob is taken over the cut set, cut is x*.
+    top_p None or >= 1.0 is "off": vocab_sample's own result, bit for bit, and cut = -inf; top_p <= 0 raises ValueError.
+    None when the launcher does not take the shape (M3P_ENOTIMPL: top_k > 16, n * V >= 2^32)."""
+    top_p = rng.nucleus_top_p(top_p)
+    if top_p is None:
+        top_p = 1.0                                # (the launcher's "off": it runs m3p_vocab_sample and fills cut with -inf)
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
+    n = logits.shape[0]
+    lib = L.load()
+    rc = lib.m3p_vocab_nucleus_plan(n, V, logits.stride(0), top_k)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_vocab_nucleus_plan')
+    dev = logits.device
+    ws_bytes = lib.m3p_vocab_nucleus_workspace_bytes(n, V, top_k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    words = torch.empty((n,), dtype=torch.int64, device=dev)
+    logprob = torch.empty((n,), dtype=torch.float32, device=dev)
+    key = torch.empty((n,), dtype=torch.float32, device=dev)
+    cut = torch.empty((n,), dtype=torch.float32, device=dev)
+    rc = lib.m3p_vocab_nucleus_sample(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k, top_p,
+                                      int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, words.data_ptr(), logprob.data_ptr(),
+                                      key.data_ptr(), cut.data_ptr(), L.stream())
+    L.check(rc, 'm3p_vocab_nucleus_sample')
+    return words, logprob, key, cut
+
+
 def attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, seed=0, p_drop=0.0):
     """Training form of attn_query_fwd: dropout on the probabilities, returns (ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq])."""
     _chk_bf16(q, kv)

@@ -25,7 +25,13 @@ the logits, divide, softmax, torch.multinomial on torch's generator) against gen
 random streams), so outputs are not compared; the device route stands on reproducibility, the number gates nothing.
     timeout -k 10 600 python tools/decode_bench.py --sample > profiles/decode_sample_vs_torch.txt
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/decode_bench.py --trace sample
-    python tools/decode_bench.py --stats <dir>/.../*_kernel_stats.csv sample >> profiles/decode_sample_vs_torch.txt"""
+    python tools/decode_bench.py --stats <dir>/.../*_kernel_stats.csv sample >> profiles/decode_sample_vs_torch.txt
+
+`--sample --top-p P` measures the nucleus cut instead: generate(sample_seed=...) against generate(sample_seed=...,
+sample_top_p=P) (csrc/select.hip: m3p_vocab_nucleus_sample), both on the device - the parent of the cut has no device top-p,
+seeded sampling without it is the fair neighbour.  Same geometry, warm-up and pairs; `--trace nucleus --top-p P` is the run
+for the profiler, `--stats ... nucleus` its per-kernel lines.
+    timeout -k 10 600 python tools/decode_bench.py --sample --top-p 0.9 > profiles/decode_nucleus.txt"""
 import csv
 import os
 import sys
@@ -40,6 +46,7 @@ D, HEADS, LAYERS, V, S, MAX_LEN = 768, 12, 12, 250002, 164, 64
 RUNS = {'beam4': ('generate_beam', 32, 4), 'beam5': ('generate_beam', 64, 5), 'greedy': ('generate', 128, 1)}
 SAMPLE = ('sample', 128, 1)       # the --sample run: T = 1.0, seeded device route against torch.multinomial
 SAMPLE_SEED = 17
+TOP_P = [0.9]                     # --top-p: the nucleus of the `nucleus` runs
 PAIRS = 3
 HBM_PEAK = 8.0e12               # bytes/s of an MI355X (HBM3E)
 
@@ -68,6 +75,8 @@ def call(m, kind, src, src_len, beam):
             return m.generate(src, src_len, 1, max_len=MAX_LEN)
         if kind == 'sample':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED)
+        if kind == 'nucleus':
+            return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED, sample_top_p=TOP_P[0])
         if kind == 'sample_torch':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0)
         return m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=MAX_LEN)
@@ -186,8 +195,31 @@ def bench_sample(m):
     print('       bytes of logits per step (n * V * 2): %.1f MB' % (bs * V * 2 / 1e6))
 
 
+def bench_nucleus(m):
+    _, bs, beam = SAMPLE
+    print('sampled decoding step (T = 1.0), %d layers, d = %d, V = %d, S = %d, max_len = %d, %d sentences; ms per decoding step, '
+          '%d alternating pairs; seeded sampling on the device without and with top_p = %g; ratio = with / without' % (
+              LAYERS, D, V, S, MAX_LEN, bs, PAIRS, TOP_P[0]))
+    src, src_len = inputs(bs)
+    call(m, 'sample', src, src_len, beam)                    # warm-up of both routes
+    call(m, 'nucleus', src, src_len, beam)
+    old, new = [], []
+    for _ in range(PAIRS):
+        t, out_old = timed(lambda: call(m, 'sample', src, src_len, beam))
+        old.append(t)
+        t, out_new = timed(lambda: call(m, 'nucleus', src, src_len, beam))
+        new.append(t)
+    assert out_old[0].shape[0] == MAX_LEN and out_new[0].shape[0] == MAX_LEN, 'a sentence ended early'
+    print('nucleus generate      bs %3d          (%3d rows)  seeded ms %s  top-p ms %s  ratio %s' % (
+        bs, bs, ' '.join('%7.3f' % v for v in old), ' '.join('%7.3f' % v for v in new),
+        ' '.join('%5.2f' % (b / a) for a, b in zip(old, new))))
+    again = call(m, 'nucleus', src, src_len, beam)
+    print('       a further top-p run gives the same tokens: %s' % torch.equal(again[0], out_new[0]))
+    print('       bytes of logits per step (n * V * 2): %.1f MB' % (bs * V * 2 / 1e6))
+
+
 def trace(m, name):
-    kind, bs, beam = SAMPLE if name == 'sample' else RUNS[name]
+    kind, bs, beam = ('nucleus',) + SAMPLE[1:] if name == 'nucleus' else SAMPLE if name == 'sample' else RUNS[name]
     src, src_len = inputs(bs)
     call(m, kind, src, src_len, beam)
     torch.cuda.synchronize()
@@ -214,7 +246,7 @@ def own_kernel(kname):
 def stats(path, name):
     """Kernel shares of a `--trace NAME` run from rocprofv3's kernel stats (Name, Calls, TotalDurationNs, ...): shares of
     the summed KERNEL time, not of the step's wall time (host gaps between launches are in neither term)."""
-    kind, bs, beam = SAMPLE if name == 'sample' else RUNS[name]
+    kind, bs, beam = SAMPLE if name in ('sample', 'nucleus') else RUNS[name]
     rows = bs * beam
     total = own = 0.0
     sel, others = {}, []
@@ -225,14 +257,18 @@ def stats(path, name):
             own += ns
         else:
             others.append((ns, calls, kname))
-        for key in ('vs_chunk_kernel', 'vs_merge_kernel', 'vsmp_chunk_kernel', 'vsmp_merge_kernel', 'vsmp_topk_kernel'):
+        for key in ('vs_chunk_kernel', 'vs_merge_kernel', 'vsmp_chunk_kernel', 'vsmp_merge_kernel', 'vsmp_topk_kernel',
+                    'vnuc_coarse_kernel', 'vnuc_scan_kernel', 'vnuc_fine_kernel', 'vnuc_cut_kernel', 'vnuc_merge_kernel'):
             if key in kname:
                 sel[key] = (ns / calls, calls)
     print('\nkernel shares, %s (%d rows), %s, from a profiled run of its own (warm-up + one timed run)' % (
-        name, rows, 'seeded sampling' if name == 'sample' else 'select path'))
+        name, rows, {'sample': 'seeded sampling', 'nucleus': 'seeded nucleus sampling'}.get(name, 'select path')))
     for key, (avg, calls) in sorted(sel.items()):
         print('  %-16s %5d calls  %8.1f us per call' % (key, calls, avg / 1e3))
-    if len(sel) == 2:
+    if name == 'nucleus':
+        every = sum(v[0] for v in sel.values())
+        print('  nucleus sampling (all of the above): %.1f us per step over %.1f MB of logits' % (every / 1e3, rows * V * 2 / 1e6))
+    elif len(sel) == 2:
         both = sum(v[0] for v in sel.values())
         bps = rows * V * 2 / (both * 1e-9)
         print('  selection (both kernels): %.1f us per step for %.1f MB of logits = %.2f TB/s, %.0f %% of the %.1f TB/s HBM peak' % (
@@ -249,6 +285,15 @@ if __name__ == '__main__':
         stats(sys.argv[2], sys.argv[3])
         sys.exit(0)
     assert torch.cuda.is_available(), 'decode_bench.py measures on a GPU'
+    if '--top-p' in sys.argv:
+        at = sys.argv.index('--top-p')
+        TOP_P[0] = float(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
+        assert 0.0 < TOP_P[0] < 1.0, '--top-p P: 0 < P < 1'
+        if len(sys.argv) >= 2 and sys.argv[1] == '--sample':
+            print(torch.cuda.get_device_name(0))
+            bench_nucleus(model())
+            sys.exit(0)
     if len(sys.argv) >= 3 and sys.argv[1] == '--trace':
         trace(model(), sys.argv[2])
     elif len(sys.argv) >= 2 and sys.argv[1] == '--sample':
