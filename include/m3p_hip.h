@@ -361,6 +361,34 @@ M3P_API int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, f
                                      void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key,
                                      float* cut, void* stream);
 
+/* Decoding constraints (csrc/constrain.hip; torch twin: m3p_amd/decoder.py constrain_scores_): edits the bf16 logits of a
+ * decoding step IN PLACE, in front of m3p_vocab_select / m3p_vocab_sample / m3p_vocab_nucleus_sample, which take a -inf logit
+ * as "never chosen, mass 0".  ONE rule for every route of the search loops:
+ * At the step that decodes position cur_len, row r has the history H = generated[1:cur_len, r] of length L = cur_len - 1; the
+ * <EOS> that serves as <BOS> at position 0 is NOT part of H.  The row's V logits x[w] are changed in this order:
+ *   1. repetition penalty theta (finite, > 0; 1 is off): every DISTINCT word w of H with 0 <= w < V, once however often it
+ *      occurs:  x[w] <- bf16_rne(fl32(x[w] * (x[w] > 0 ? inv_theta : theta))).  theta and inv_theta = fl32(1 / theta) are both
+ *      formed by the caller: one fp32 multiply, no divide.  0, -0 and -inf keep their bits.
+ *   2. no repeated n-gram, ngram = n >= 1 (0 is off): for every j in [0, L - n] with H[j + i] == H[L - n + 1 + i] for all i in
+ *      [0, n - 2], the word H[j + n - 1] gets -inf.  n = 1 bans every word of H; nothing happens while L < n.
+ *   3. minimum length: x[eos_or_minus1] <- -inf unless eos_or_minus1 is -1 (the caller passes <EOS> while cur_len <= min_len).
+ *   4. banned words: every id of banned[0 .. n_banned - 1] gets -inf.
+ * Everything else keeps its bits: the other words, the columns V .. ld-1, the other rows.  A history word or banned id outside
+ * [0, V) is skipped.  Under beam search the edit happens before the row's log-sum-exp: the scores are log_softmax of the
+ * constrained logits plus the beam score; the log-probabilities of a sampled word are those of the constrained row.
+ *   logits  bf16 [n, ld], ld >= V, written in place
+ *   hist    int64, points at generated[1]: element (p, r) at hist[p*hist_ld + r], hist_ld >= n, p < hist_len = L; row r of the
+ *           logits reads COLUMN r.  May be NULL when hist_len is 0.
+ *   banned  int64 [n_banned] on the device; may be NULL when n_banned is 0.
+ * One launch (none when the step has nothing to edit), a workgroup per row, plain 2-byte stores, no atomics; every penalised
+ * word has one writer.  Limits: hist_len <= 1024, ngram <= 16, n_banned <= 4096 - above them M3P_ENOTIMPL (the caller applies
+ * the twin); M3P_EINVAL for a malformed shape, theta or inv_theta not finite and > 0, eos_or_minus1 outside [-1, V).
+ * m3p_logits_constrain_plan answers what the launcher would for a shape, without launching; it depends on shapes alone. */
+M3P_API int m3p_logits_constrain_plan(int n, int V, int ld, int hist_len, int ngram, int n_banned);
+M3P_API int m3p_logits_constrain(void* logits, int ld, int n, int V, const long long* hist, long long hist_ld, int hist_len,
+                                 float theta, float inv_theta, int ngram, int eos_or_minus1, const long long* banned,
+                                 int n_banned, void* stream);
+
 /* The same attention for the TRAINING of the causal / cross-attention sub-layers (teacher forcing: Tq = the whole target
  * sequence, pos0 = 0): dropout on the probabilities (stream (seed, thresh24) indexed ((b*H + h)*Tq + t)*Lk + key) and the
  * log-sum-exp lse fp32 [B, H, Tq] kept for backward.  B*H*Tq*Lk < 2^32. */

@@ -22,6 +22,10 @@ reads through it), and with ``cache['beam']`` the source's keys / values are kep
 ``generate(sample_seed=...)`` draws the next word by the seeded Gumbel-max contract of ``ops.vocab_sample`` (csrc/select.hip;
 NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation, a nucleus (top-p) cut
 (``sample_top_p``: ``ops.vocab_nucleus_sample``) and the sampled words' log-probabilities.
+Both loops take decoding constraints - ``min_len``, ``repetition_penalty``, ``no_repeat_ngram``, ``banned_words`` - by ONE rule
+for every route (include/m3p_hip.h: m3p_logits_constrain): where the words are selected on the device, ``ops.logits_constrain``
+(csrc/constrain.hip) edits the step's bf16 logits in place in front of the selection kernels, everywhere else the torch twin
+``constrain_scores_`` edits ``word_scores``; with all four off no route changes by a bit.
 
 This module is forward only; the teacher-forced training pass of the same stream is ``functional.DecoderFn``
 (``TransformerModel.crossfwd`` picks it in training mode), and calling ``decoder_forward`` itself with autograd enabled on
@@ -252,8 +256,122 @@ def _sample_twin(scores, inv_t, seed, top_k, top_p=None):
     return (torch.from_numpy(words).to(scores.device), torch.from_numpy(logprob.astype('float32')).to(scores.device))
 
 
+def penalty_pair(repetition_penalty):
+    """The two fp32 factors of the repetition penalty (include/m3p_hip.h: m3p_logits_constrain), as Python floats:
+    (theta, inv_theta) = (fl32(penalty), fl32(1 / fl32(penalty))) - a positive logit is multiplied by inv_theta, every other by
+    theta, in ONE fp32 multiply on every route.  None is off: (1.0, 1.0).  ValueError unless finite and > 0."""
+    if repetition_penalty is None:
+        return 1.0, 1.0
+    theta = torch.tensor(float(repetition_penalty), dtype=torch.float32)
+    inv = 1.0 / theta
+    if not (math.isfinite(float(theta)) and float(theta) > 0.0 and math.isfinite(float(inv)) and float(inv) > 0.0):
+        raise ValueError('repetition_penalty must be finite and > 0, got %r' % (repetition_penalty,))
+    return float(theta), float(inv)
+
+
+def constrain_scores_(scores, V, generated, cur_len, theta=1.0, inv_theta=1.0, ngram=0, eos=-1, banned=None):
+    """The torch twin of m3p_logits_constrain (include/m3p_hip.h holds the contract; csrc/constrain.hip the kernel): plain
+    torch, any device, IN PLACE on fp32 scores or bf16 logits [n, >= V]; returns `scores`.  It is the route of a model that is
+    not on CUDA, of VOCAB_SELECT_MAX_K == 0 and of a shape the launcher declines.
+
+    At the step that decodes position cur_len, row r has the history H = generated[1:cur_len, r], L = cur_len - 1 words; the
+    <EOS> at position 0 (it serves as <BOS>) is not part of H.  In this order:
+      1. every DISTINCT word w of H, 0 <= w < V:  x[w] <- bf16_rne(fl32(x[w] * (x[w] > 0 ? inv_theta : theta))), once however
+         often w occurs ((theta, inv_theta) = penalty_pair(...); (1.0, 1.0) is off).  The penalised value is rounded to bf16 on
+         fp32 scores too, so that the routes can be compared with torch.equal; 0, -0 and -inf keep their bits;
+      2. ngram = n >= 1 (0: off): for every j in [0, L - n] with H[j + i] == H[L - n + 1 + i] for all i in [0, n - 2] the word
+         H[j + n - 1] gets -inf (n = 1 bans every word of H; nothing happens while L < n; the suffix does not match itself);
+      3. eos >= 0: that word gets -inf (the loops pass <EOS> while cur_len <= min_len);
+      4. every id of `banned` (int64 tensor or None) gets -inf.
+    A history word or banned id outside [0, V) is skipped; columns at or past V and everything else keep their bits."""
+    n = scores.shape[0]
+    assert scores.dim() == 2 and scores.shape[1] >= V and generated.shape[1] == n and 1 <= cur_len <= generated.shape[0]
+    dev = scores.device
+    H = generated[1:cur_len].t().to(dev)                                    # [n, L]
+    Ln = cur_len - 1
+    x = scores[:, :V]
+
+    def marks(words, on):
+        """bool [n, V]: the words of `words` [n, m] (where `on`) that lie inside [0, V)."""
+        ok = on & (words >= 0) & (words < V)
+        m = torch.zeros((n, V + 1), dtype=torch.bool, device=dev)
+        m.scatter_(1, torch.where(ok, words, torch.full_like(words, V)), True)      # (skipped entries all land on column V)
+        return m[:, :V]
+
+    if (theta != 1.0 or inv_theta != 1.0) and Ln > 0:
+        x32 = x.float()
+        factor = torch.where(x32 > 0, torch.tensor(inv_theta, dtype=torch.float32, device=dev),
+                             torch.tensor(theta, dtype=torch.float32, device=dev))
+        pen = (x32 * factor).to(BF16).to(scores.dtype)
+        x.copy_(torch.where(marks(H, torch.ones_like(H, dtype=torch.bool)), pen, x))
+    ban = torch.zeros((n, V), dtype=torch.bool, device=dev)
+    if ngram >= 1 and Ln >= ngram:
+        win = H.unfold(1, ngram, 1)                                         # [n, L - n + 1, n]: j = 0 .. L - n
+        match = (win[:, :, :ngram - 1] == H[:, None, Ln - ngram + 1:]).all(dim=2)
+        ban |= marks(win[:, :, ngram - 1], match)
+    if eos >= 0:
+        assert eos < V
+        ban[:, eos] = True
+    if banned is not None and banned.numel():
+        b = banned.to(dev).view(-1)
+        ban[:, b[(b >= 0) & (b < V)]] = True
+    x.masked_fill_(ban, float('-inf'))
+    return scores
+
+
+class _Constraints:
+    """The decoding constraints of one generate / generate_beam call, validated once; `on` is False when all four are off
+    (the loops then run exactly as they did without the keywords: no launch, no copy)."""
+
+    def __init__(self, model, max_len, min_len, repetition_penalty, no_repeat_ngram, banned_words, dev):
+        self.theta, self.inv_theta = penalty_pair(repetition_penalty)
+        self.ngram, self.min_len = int(no_repeat_ngram or 0), int(min_len or 0)
+        if self.ngram < 0:
+            raise ValueError('no_repeat_ngram must be >= 0, got %r' % (no_repeat_ngram,))
+        if self.min_len < 0 or self.min_len > max_len - 2:
+            raise ValueError('min_len must lie in [0, max_len - 2] (position max_len - 1 is the forced <EOS>), got %r with '
+                             'max_len %d' % (min_len, max_len))
+        ids = sorted(set(int(w) for w in (banned_words if banned_words is not None else ())))
+        for w in ids:
+            if w < 0 or w >= model.n_words:
+                raise ValueError('banned word %d is outside [0, n_words = %d)' % (w, model.n_words))
+            if w == model.eos_index:
+                raise ValueError('<EOS> (%d) cannot be banned: every sentence ends with it (use min_len)' % w)
+        self.banned = torch.tensor(ids, dtype=torch.long, device=dev) if ids else None
+        self.n_banned = len(ids)
+        self.eos_index = int(model.eos_index)
+        self.on = self.theta != 1.0 or self.inv_theta != 1.0 or self.ngram > 0 or self.min_len > 0 or self.n_banned > 0
+
+    def args(self, cur_len):
+        """The trailing arguments of ops.logits_constrain / constrain_scores_ at the step that decodes position cur_len."""
+        return self.theta, self.inv_theta, self.ngram, self.eos_index if cur_len <= self.min_len else -1, self.banned
+
+    def takes(self, n, V, ld, max_len):
+        return ops.logits_constrain_takes(n, V, ld, max_len - 1, self.ngram, self.n_banned)
+
+
+def _constrained_logits16(model, tensor, cons, on_device, generated, cur_len):
+    """word_logits16 with the call's constraints applied in place: the kernel where its plan took the shape, else the twin."""
+    logits, V = word_logits16(model, tensor)
+    if cons.on:
+        if on_device:
+            if ops.logits_constrain(logits, V, generated, cur_len, *cons.args(cur_len)) is None:
+                raise L.M3PError('m3p_logits_constrain declined (M3P_ENOTIMPL) a shape m3p_logits_constrain_plan took')
+        else:
+            constrain_scores_(logits, V, generated, cur_len, *cons.args(cur_len))
+    return logits, V
+
+
+def _constrained_scores(model, tensor, cons, generated, cur_len):
+    """word_scores with the call's constraints applied by the twin (the torch routes)."""
+    scores = word_scores(model, tensor)
+    if cons.on:
+        constrain_scores_(scores, model.n_words, generated, cur_len, *cons.args(cur_len))
+    return scores
+
+
 def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, sample_seed=None, sample_top_k=None,
-             return_logprobs=False, sample_top_p=None):
+             return_logprobs=False, sample_top_p=None, min_len=0, repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
     """transformer.py:1216-1317: greedy (or temperature-sampled) decoding with the key / value cache.
     -> (generated (cur_len, bs) int64, gen_len (bs)).
 
@@ -272,7 +390,21 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     and CUDA generators are not touched, so a seeded run can be replayed exactly.  The counter of the random stream is (row of
     the batch, word): a sentence's draw depends on its position in the batch.  ``return_logprobs`` (seeded runs only) adds a
     third value, fp32 (cur_len, bs): the log-probability, under the tempered, top-k and nucleus-truncated distribution, of
-    each sampled word; 0 at position 0, at pad positions and where <EOS> was forced at ``max_len``."""
+    each sampled word; 0 at position 0, at pad positions and where <EOS> was forced at ``max_len``.
+
+    Decoding constraints (the contract is in include/m3p_hip.h: m3p_logits_constrain; all four off by default, and then every
+    route is bit for bit what it is without the keywords, with no launch added).  At the step that decodes position
+    ``cur_len`` row r has the history ``generated[1:cur_len, r]`` (the <EOS> at position 0 is not part of it), and its logits
+    are changed in this order: ``repetition_penalty`` theta (finite, > 0; None or 1.0: off) multiplies the logit of every
+    distinct history word by 1 / theta if it is positive and by theta otherwise, rounded to bf16; ``no_repeat_ngram`` n (0: off)
+    gives -inf to every word that would complete an n-gram the history already holds; ``min_len`` gives -inf to <EOS> while
+    cur_len <= min_len, so every sentence has at least min_len words between its two <EOS> (min_len <= max_len - 2);
+    ``banned_words`` (ids in [0, n_words), not <EOS>) get -inf.  Where the words are selected on the device
+    (``ops.vocab_select`` / ``vocab_sample`` / ``vocab_nucleus_sample``) and ``ops.logits_constrain_takes`` the shape (asked
+    once, with max_len - 1 as the history bound), ``ops.logits_constrain`` edits the bf16 logits in place - one launch per
+    step - and the selection runs unchanged behind it; a declined shape gets the twin ``constrain_scores_`` on those logits, and
+    every torch route (greedy, seeded, ``torch.multinomial``) the twin on ``word_scores``.  Log-probabilities are those of the
+    constrained distribution."""
     seeded = sample_seed is not None
     if sample_top_k is not None and not seeded:
         raise ValueError('sample_top_k needs sample_seed: the torch sampling path has no top-k mode')
@@ -287,6 +419,7 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     bs = len(src_len)
     assert src_enc.size(0) == bs
     dev = model.embeddings.weight.device
+    cons = _Constraints(model, max_len, min_len, repetition_penalty, no_repeat_ngram, banned_words, dev)
     src_len = src_len.to(dev)
     generated = torch.full((max_len, bs), model.pad_index, dtype=torch.long, device=dev)
     generated[0].fill_(model.eos_index)                       # <EOS> doubles as <BOS>
@@ -309,6 +442,9 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
         sample_dev = (dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
                       and takes(bs, model.n_words, model.arena().V_pad, top_k))
         logprobs = torch.zeros((max_len, bs), dtype=torch.float32, device=dev) if return_logprobs else None
+    # (the constraint kernel sits in front of a device selection only; its plan is asked once, like the others)
+    cons_dev = (cons.on and (sample_dev if seeded else select)
+                and cons.takes(bs, model.n_words, model.arena().V_pad, max_len))
     while cur_len < max_len:
         tensor = decoder_forward(model, generated[:cur_len], gen_len, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
@@ -316,7 +452,7 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
         if seeded:
             step_seed = rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)
             if sample_dev:
-                logits, V = word_logits16(model, tensor[-1])
+                logits, V = _constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len)
                 if top_p is None:
                     res = ops.vocab_sample(logits, V, temperature, step_seed, top_k)
                 else:
@@ -326,15 +462,17 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
                     raise L.M3PError('%s declined (M3P_ENOTIMPL) a shape its plan took' % name)
                 next_words, step_logprob = res[0], res[1]
             else:
-                next_words, step_logprob = _sample_twin(word_scores(model, tensor[-1]), inv_t, step_seed, top_k, top_p)
+                next_words, step_logprob = _sample_twin(_constrained_scores(model, tensor[-1], cons, generated, cur_len), inv_t,
+                                                        step_seed, top_k, top_p)
             if return_logprobs:
                 logprobs[cur_len] = step_logprob.masked_fill(unfinished == 0, 0.0)
         elif select:                   # the first maximum of each row, from the bf16 logits
-            next_words = _select(*word_logits16(model, tensor[-1]), None, 1, 1)[1].squeeze(1)
+            logits, V = _constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len)
+            next_words = _select(logits, V, None, 1, 1)[1].squeeze(1)
         elif sample_temperature is None:
-            next_words = torch.topk(word_scores(model, tensor[-1]), 1)[1].squeeze(1)
+            next_words = torch.topk(_constrained_scores(model, tensor[-1], cons, generated, cur_len), 1)[1].squeeze(1)
         else:
-            scores = word_scores(model, tensor[-1])
+            scores = _constrained_scores(model, tensor[-1], cons, generated, cur_len)
             next_words = torch.multinomial(torch.softmax(scores / sample_temperature, dim=1), 1).squeeze(1)
         generated[cur_len] = next_words * unfinished + model.pad_index * (1 - unfinished)
         gen_len.add_(unfinished)
@@ -394,19 +532,27 @@ class BeamHypotheses(object):
         return full and (self.early_stopping or self.worst_score >= best_sum_logprobs / self._norm)
 
 
-def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200):
+def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200, min_len=0,
+                  repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
     """transformer.py:1319-1515: beam search; the beam is folded into the batch dimension (bs * beam_size rows).  On the torch
     path the key / value caches are re-ordered by the surviving beams' source rows after every step; on the select path
     (module docstring) they stay in place behind cache['owner'] and the source is kept once per sentence.
-    -> (decoded (max tgt_len, bs) int64, tgt_len (bs))."""
+    -> (decoded (max tgt_len, bs) int64, tgt_len (bs)).
+
+    ``min_len`` / ``repetition_penalty`` / ``no_repeat_ngram`` / ``banned_words``: the decoding constraints of ``generate``, by
+    the same contract and the same routes, per hypothesis row (the history of a row is the hypothesis it continues).  The edit
+    happens on the logits before the row's log-sum-exp: the scores are log_softmax of the constrained logits plus the beam
+    score.  All four off: no route changes by a bit."""
     assert src_enc.size(0) == src_len.size(0) and beam_size >= 1
     bs = len(src_len)
     n_words = model.n_words
     dev = model.embeddings.weight.device
+    cons = _Constraints(model, max_len, min_len, repetition_penalty, no_repeat_ngram, banned_words, dev)
     src_len = src_len.to(dev)
     n = bs * beam_size
     select = (dev.type == 'cuda' and 2 * beam_size <= VOCAB_SELECT_MAX_K
               and ops.vocab_select_takes(n, n_words, model.arena().V_pad, beam_size, 2 * beam_size))
+    cons_dev = cons.on and select and cons.takes(n, n_words, model.arena().V_pad, max_len)
     if select:
         src_enc = src_enc.to(dev)
     else:
@@ -434,9 +580,10 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
                                  None if langs is None else langs[:cur_len], cache)
         assert tensor.size() == (1, bs * beam_size, model.dim)
         if select:
-            next_scores, next_words, _ = _select(*word_logits16(model, tensor[-1]), beam_scores, beam_size, 2 * beam_size)
+            next_scores, next_words, _ = _select(*_constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len),
+                                                 beam_scores, beam_size, 2 * beam_size)
         else:
-            scores = torch.log_softmax(word_scores(model, tensor[-1]), dim=-1)
+            scores = torch.log_softmax(_constrained_scores(model, tensor[-1], cons, generated, cur_len), dim=-1)
             _scores = (scores + beam_scores[:, None]).view(bs, beam_size * n_words)
             next_scores, next_words = torch.topk(_scores, 2 * beam_size, dim=1, largest=True, sorted=True)
         next_scores_h, next_words_h = next_scores.tolist(), next_words.tolist()       # one host copy per step

@@ -534,16 +534,22 @@ class TransformerModel(nn.Module):
         return Fn.mlm_eval_head(self, tensor, pred_mask, y)
 
     def generate(self, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, cross_modal=True, sample_seed=None,
-                 sample_top_k=None, return_logprobs=False, sample_top_p=None):
+                 sample_top_k=None, return_logprobs=False, sample_top_p=None, min_len=0, repetition_penalty=None,
+                 no_repeat_ngram=0, banned_words=None):
         """transformer.py:1216-1317 (greedy / sampled decoding); sample_seed / sample_top_k / sample_top_p / return_logprobs:
-        the seeded sampling of decoder.generate (top-k and nucleus truncation)."""
+        the seeded sampling of decoder.generate (top-k and nucleus truncation); min_len / repetition_penalty / no_repeat_ngram /
+        banned_words: its decoding constraints."""
         from .. import decoder
         return decoder.generate(self, src_enc, src_len, tgt_lang_id, max_len=max_len, sample_temperature=sample_temperature,
                                 sample_seed=sample_seed, sample_top_k=sample_top_k, return_logprobs=return_logprobs,
-                                sample_top_p=sample_top_p)
+                                sample_top_p=sample_top_p, min_len=min_len, repetition_penalty=repetition_penalty,
+                                no_repeat_ngram=no_repeat_ngram, banned_words=banned_words)
 
-    def generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200):
-        """transformer.py:1319-1515 (beam search)."""
+    def generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200, min_len=0,
+                      repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
+        """transformer.py:1319-1515 (beam search); min_len / repetition_penalty / no_repeat_ngram / banned_words: the decoding
+        constraints of decoder.generate_beam."""
         from .. import decoder
         return decoder.generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping,
-                                     max_len=max_len)
+                                     max_len=max_len, min_len=min_len, repetition_penalty=repetition_penalty,
+                                     no_repeat_ngram=no_repeat_ngram, banned_words=banned_words)

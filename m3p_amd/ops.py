@@ -533,6 +533,48 @@ def vocab_nucleus_sample(logits, V, temperature, seed, top_p, top_k=0):
     return words, logprob, key, cut
 
 
+def logits_constrain_takes(n, V, ld, hist_len, ngram=0, n_banned=0):
+    """Does the launcher of logits_constrain take the shape?  (False: it would answer M3P_ENOTIMPL - hist_len > 1024, ngram > 16,
+    n_banned > 4096; a malformed one raises.)  The answer depends on shapes alone: a search loop asks once, with max_len - 1 as
+    the history bound."""
+    rc = L.load().m3p_logits_constrain_plan(n, V, ld, hist_len, ngram, n_banned)
+    if rc == _ENOTIMPL:
+        return False
+    L.check(rc, 'm3p_logits_constrain_plan')
+    return True
+
+
+def logits_constrain(logits, V, generated, cur_len, theta=1.0, inv_theta=1.0, ngram=0, eos=-1, banned=None):
+    """Decoding constraints of the step that decodes position cur_len (csrc/constrain.hip; the contract is in include/m3p_hip.h,
+    the torch twin is decoder.constrain_scores_): edits logits bf16 [n, ld >= V] IN PLACE and returns them.  generated int64
+    [>= cur_len, n] on the device, row-major: row r of the logits has the history generated[1:cur_len, r] (position 0, the
+    <EOS> that serves as <BOS>, is not part of it; no copy and no transpose is made).  In this order: the repetition penalty
+    (theta, inv_theta) = decoder.penalty_pair(...) on every distinct history word ((1.0, 1.0): off), -inf for the word that would
+    complete a repeated n-gram (ngram = 0: off), -inf for the word `eos` (-1: off; the loop passes <EOS> while cur_len <=
+    min_len), -inf for every id of `banned` (int64 device tensor or None).  None when the launcher does not take the shape
+    (M3P_ENOTIMPL: cur_len - 1 > 1024, ngram > 16, more than 4096 banned ids); the logits are then untouched."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
+    n = logits.shape[0]
+    assert generated.dtype == torch.int64 and generated.is_cuda and generated.dim() == 2 and generated.stride(1) == 1
+    assert 1 <= cur_len <= generated.shape[0] and generated.shape[1] == n and generated.stride(0) >= n
+    n_banned = 0
+    if banned is not None:
+        assert banned.dtype == torch.int64 and banned.is_cuda and banned.dim() == 1 and banned.is_contiguous()
+        n_banned = banned.numel()
+    hist_len = cur_len - 1
+    lib = L.load()
+    rc = lib.m3p_logits_constrain_plan(n, V, logits.stride(0), hist_len, ngram, n_banned)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_logits_constrain_plan')
+    hist = generated.data_ptr() + generated.stride(0) * generated.element_size() if hist_len > 0 else None
+    rc = lib.m3p_logits_constrain(logits.data_ptr(), logits.stride(0), n, V, hist, generated.stride(0), hist_len, float(theta),
+                                  float(inv_theta), int(ngram), int(eos), L.ptr(banned) if n_banned else None, n_banned, L.stream())
+    L.check(rc, 'm3p_logits_constrain')
+    return logits
+
+
 def attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, seed=0, p_drop=0.0):
     """Training form of attn_query_fwd: dropout on the probabilities, returns (ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq])."""
     _chk_bf16(q, kv)

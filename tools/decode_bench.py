@@ -31,7 +31,17 @@ random streams), so outputs are not compared; the device route stands on reprodu
 sample_top_p=P) (csrc/select.hip: m3p_vocab_nucleus_sample), both on the device - the parent of the cut has no device top-p,
 seeded sampling without it is the fair neighbour.  Same geometry, warm-up and pairs; `--trace nucleus --top-p P` is the run
 for the profiler, `--stats ... nucleus` its per-kernel lines.
-    timeout -k 10 600 python tools/decode_bench.py --sample --top-p 0.9 > profiles/decode_nucleus.txt"""
+    timeout -k 10 600 python tools/decode_bench.py --sample --top-p 0.9 > profiles/decode_nucleus.txt
+
+`--constraints` measures the decoding constraints (csrc/constrain.hip: m3p_logits_constrain in front of the selection kernels)
+with no_repeat_ngram = 3, repetition_penalty = 1.2, min_len = 8 on greedy x 128 and beam 4 x 32: (a) the device route with the
+constraints against the same route without them - the difference is the kernel's cost per step, launch included -, (b) the
+device route against the fallback route (decoder.VOCAB_SELECT_MAX_K = 0: the torch twin on the fp32 scores in front of
+log_softmax / topk), both with the constraints, outputs compared (for beam search with the score gap at which the two
+selections part on the same constrained logits, as in the plain run).  Same geometry, warm-up and pairs.  `--trace greedy
+--constraints` (or beam4) is the run for the profiler, `--stats ... greedy` then lists lc_constrain_kernel beside the selection
+kernels.  The constraints-off path is not timed against its parent: it issues no launch (tests/test_logit_constraints.py).
+    timeout -k 10 900 python tools/decode_bench.py --constraints > profiles/decode_constraints.txt"""
 import csv
 import os
 import sys
@@ -47,6 +57,7 @@ RUNS = {'beam4': ('generate_beam', 32, 4), 'beam5': ('generate_beam', 64, 5), 'g
 SAMPLE = ('sample', 128, 1)       # the --sample run: T = 1.0, seeded device route against torch.multinomial
 SAMPLE_SEED = 17
 TOP_P = [0.9]                     # --top-p: the nucleus of the `nucleus` runs
+CONSTRAINTS = dict(no_repeat_ngram=3, repetition_penalty=1.2, min_len=8)      # the --constraints runs
 PAIRS = 3
 HBM_PEAK = 8.0e12               # bytes/s of an MI355X (HBM3E)
 
@@ -69,17 +80,17 @@ def inputs(bs):
     return src, src_len
 
 
-def call(m, kind, src, src_len, beam):
+def call(m, kind, src, src_len, beam, **cons):
     with torch.no_grad():
         if kind == 'generate':
-            return m.generate(src, src_len, 1, max_len=MAX_LEN)
+            return m.generate(src, src_len, 1, max_len=MAX_LEN, **cons)
         if kind == 'sample':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED)
         if kind == 'nucleus':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED, sample_top_p=TOP_P[0])
         if kind == 'sample_torch':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0)
-        return m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=MAX_LEN)
+        return m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=MAX_LEN, **cons)
 
 
 def timed(fn):
@@ -112,7 +123,7 @@ def differing(a, b):
     return out
 
 
-def selection_gaps(m, src, src_len, beam):
+def selection_gaps(m, src, src_len, beam, **cons):
     """Where do the two selections part?  One generate_beam on the select path; at every step the torch selection
     (log_softmax of the fp32 logits + beam_scores, topk) is taken from the SAME logits.  The hidden states of the two paths
     are bit-identical up to a sentence's first differing selection, so that step is where its outputs part.  -> per sentence
@@ -132,7 +143,7 @@ def selection_gaps(m, src, src_len, beam):
         return res
     decoder._select = both
     try:
-        call(m, 'generate_beam', src, src_len, beam)
+        call(m, 'generate_beam', src, src_len, beam, **cons)
     finally:
         decoder._select = real
     return sorted((s, st, g) for s, (st, g) in first.items())
@@ -218,13 +229,54 @@ def bench_nucleus(m):
     print('       bytes of logits per step (n * V * 2): %.1f MB' % (bs * V * 2 / 1e6))
 
 
-def trace(m, name):
+def bench_constraints(m):
+    print('decoding constraints %s, %d layers, d = %d, V = %d, S = %d, max_len = %d; ms per decoding step, %d alternating pairs' % (
+        CONSTRAINTS, LAYERS, D, V, S, MAX_LEN, PAIRS))
+    rule = decoder.VOCAB_SELECT_MAX_K
+    for name in ('greedy', 'beam4'):
+        kind, bs, beam = RUNS[name]
+        src, src_len = inputs(bs)
+        plain = lambda: call(m, kind, src, src_len, beam)                          # noqa: E731
+        cons = lambda: call(m, kind, src, src_len, beam, **CONSTRAINTS)            # noqa: E731
+        plain()                                                                    # warm-up of the three routes
+        cons()
+        with_rule(0, cons)
+        off, on, on_b, fall = [], [], [], []
+        for _ in range(PAIRS):
+            off.append(timed(plain)[0])
+            t, out_on = timed(cons)
+            on.append(t)
+        for _ in range(PAIRS):
+            t, out_fall = timed(lambda: with_rule(0, cons))
+            fall.append(t)
+            t, out_on = timed(lambda: with_rule(rule, cons))
+            on_b.append(t)
+        assert out_on[0].shape[0] == MAX_LEN and out_fall[0].shape[0] == MAX_LEN, 'a sentence ended early'
+        fmt = lambda v: ' '.join('%7.3f' % x for x in v)                            # noqa: E731
+        print('%-6s %-13s bs %3d beam %d (%3d rows)' % (name, kind, bs, beam, bs * beam))
+        print('       (a) device route: without constraints ms %s  with ms %s  difference us per step %s' % (
+            fmt(off), fmt(on), ' '.join('%6.1f' % (1e3 * (b - a)) for a, b in zip(off, on))))
+        print('       (b) with constraints: fallback route ms %s  device route ms %s  ratio %s' % (
+            fmt(fall), fmt(on_b), ' '.join('%5.2f' % (a / b) for a, b in zip(fall, on_b))))
+        diff = differing(out_fall, out_on)
+        print('       outputs of the two routes on the timed inputs: %d of %d sentences differ%s' % (
+            len(diff), bs, (' ' + str(diff)) if diff else ''))
+        if kind == 'generate_beam':
+            gaps = selection_gaps(m, src, src_len, beam, **CONSTRAINTS)
+            print('       selections on the same constrained logits (kernel against log_softmax + topk): %d of %d sentences see a '
+                  'different list at some step; score gap at the first difference: max %.3g' % (
+                      len(gaps), bs, max([g for _, _, g in gaps] or [0.0])))
+
+
+def trace(m, name, cons=None):
     kind, bs, beam = ('nucleus',) + SAMPLE[1:] if name == 'nucleus' else SAMPLE if name == 'sample' else RUNS[name]
     src, src_len = inputs(bs)
-    call(m, kind, src, src_len, beam)
+    cons = cons or {}
+    call(m, kind, src, src_len, beam, **cons)
     torch.cuda.synchronize()
-    t, _ = timed(lambda: call(m, kind, src, src_len, beam))
-    print('%s under the profiler: %.3f ms per step (slower than the timed runs: tracing)' % (name, t))
+    t, _ = timed(lambda: call(m, kind, src, src_len, beam, **cons))
+    print('%s%s under the profiler: %.3f ms per step (slower than the timed runs: tracing)' % (
+        name, ' with constraints' if cons else '', t))
 
 
 def own_kernel(kname):
@@ -258,7 +310,8 @@ def stats(path, name):
         else:
             others.append((ns, calls, kname))
         for key in ('vs_chunk_kernel', 'vs_merge_kernel', 'vsmp_chunk_kernel', 'vsmp_merge_kernel', 'vsmp_topk_kernel',
-                    'vnuc_coarse_kernel', 'vnuc_scan_kernel', 'vnuc_fine_kernel', 'vnuc_cut_kernel', 'vnuc_merge_kernel'):
+                    'vnuc_coarse_kernel', 'vnuc_scan_kernel', 'vnuc_fine_kernel', 'vnuc_cut_kernel', 'vnuc_merge_kernel',
+                    'lc_constrain_kernel'):
             if key in kname:
                 sel[key] = (ns / calls, calls)
     print('\nkernel shares, %s (%d rows), %s, from a profiled run of its own (warm-up + one timed run)' % (
@@ -268,8 +321,8 @@ def stats(path, name):
     if name == 'nucleus':
         every = sum(v[0] for v in sel.values())
         print('  nucleus sampling (all of the above): %.1f us per step over %.1f MB of logits' % (every / 1e3, rows * V * 2 / 1e6))
-    elif len(sel) == 2:
-        both = sum(v[0] for v in sel.values())
+    elif len(sel) - ('lc_constrain_kernel' in sel) == 2:
+        both = sum(v[0] for k, v in sel.items() if k != 'lc_constrain_kernel')
         bps = rows * V * 2 / (both * 1e-9)
         print('  selection (both kernels): %.1f us per step for %.1f MB of logits = %.2f TB/s, %.0f %% of the %.1f TB/s HBM peak' % (
             both / 1e3, rows * V * 2 / 1e6, bps / 1e12, 100 * bps / HBM_PEAK, HBM_PEAK / 1e12))
@@ -285,6 +338,13 @@ if __name__ == '__main__':
         stats(sys.argv[2], sys.argv[3])
         sys.exit(0)
     assert torch.cuda.is_available(), 'decode_bench.py measures on a GPU'
+    constrained = '--constraints' in sys.argv
+    if constrained:
+        sys.argv.remove('--constraints')
+        if len(sys.argv) == 1:
+            print(torch.cuda.get_device_name(0))
+            bench_constraints(model())
+            sys.exit(0)
     if '--top-p' in sys.argv:
         at = sys.argv.index('--top-p')
         TOP_P[0] = float(sys.argv[at + 1])
@@ -295,7 +355,7 @@ if __name__ == '__main__':
             bench_nucleus(model())
             sys.exit(0)
     if len(sys.argv) >= 3 and sys.argv[1] == '--trace':
-        trace(model(), sys.argv[2])
+        trace(model(), sys.argv[2], CONSTRAINTS if constrained else None)
     elif len(sys.argv) >= 2 and sys.argv[1] == '--sample':
         print(torch.cuda.get_device_name(0))
         bench_sample(model())
