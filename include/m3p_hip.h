@@ -361,6 +361,35 @@ M3P_API int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, f
                                      void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key,
                                      float* cut, void* stream);
 
+/* Seeded top-k sampling over more than 16 candidates, nucleus cut included (csrc/select.hip; the NumPy twin is the same:
+ * rng.sample_allowed / nucleus_cut / sample_words take any top_k <= V).  The semantics are m3p_vocab_nucleus_sample's with
+ * 1 <= top_k <= m3p_vocab_sample_wide_max_k() (1024):
+ *   candidate set K   the row's first top_k words under (logit descending, word ascending): with v_k the k-th logit value,
+ *                     every word above v_k and, of the words equal to v_k, as many as still fit - the lowest word ids
+ *   key(r, w)         fma(x_w, inv_t, -log E), E = -log u, u from m3p_hash32(r*V + w, seed) as above: the counter, the
+ *                     logarithms and so the key bits of m3p_vocab_sample
+ *   top_p >= 1        no cut: the allowed set is K, cut = -inf
+ *   0 < top_p < 1     the allowed set is { w in K : x_w >= x* }, x* = max{ v : C(v) >= top_p*Z } with mass, C and Z over K as
+ *                     defined above; where the class at v_k is only partly inside K it counts the words that are in K
+ *   words[r]          the argmax of key over the allowed set, ties to the lowest word
+ *   logprob[r]        x_w*inv_t - log-sum-exp of x*inv_t over the allowed set;  key[r] the winning key (may be NULL);
+ *   cut[r]            x* or -inf (may be NULL)
+ * top_k > max_k returns M3P_ENOTIMPL; top_k < 1 or top_k > V M3P_EINVAL; the pointer, alignment, ld % 8, n*V < 2^32, inv_t and
+ * top_p checks are those of m3p_vocab_nucleus_sample.  Columns at or past V may hold NaN or inf and are never chosen; a -inf
+ * logit below V has mass 0, may sit in K when the row has fewer than top_k finite logits, and never wins while the row holds
+ * a finite one.  K is found by an exact two-level count selection over the 65 536 bf16 values, compacted to [n, top_k] and
+ * finished per row in one workgroup; the masses are integers on a 2^-40 grid, summed exactly, so a row whose cumulated mass
+ * lands on top_p*Z to within 2e-6 Z may cut one class earlier or later (the bound is derived in
+ * tests/test_vocab_sample_wide_cpu.py).  Integer atomics only, no floating-point atomics: the same inputs give the same bits.
+ * workspace: m3p_vocab_sample_wide_workspace_bytes(n, V, top_k) bytes, 16-byte aligned, contents irrelevant.  The entry takes
+ * top_k <= 16 too (the words and key bits of m3p_vocab_sample; logprob to rounding) - the decoding loop sends only top_k > 16. */
+M3P_API int m3p_vocab_sample_wide_max_k(void);
+M3P_API int m3p_vocab_sample_wide_plan(int n, int V, int ld, int top_k);
+M3P_API size_t m3p_vocab_sample_wide_workspace_bytes(int n, int V, int top_k);
+M3P_API int m3p_vocab_sample_wide(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed,
+                                  void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key,
+                                  float* cut, void* stream);
+
 /* Decoding constraints (csrc/constrain.hip; torch twin: m3p_amd/decoder.py constrain_scores_): edits the bf16 logits of a
  * decoding step IN PLACE, in front of m3p_vocab_select / m3p_vocab_sample / m3p_vocab_nucleus_sample, which take a -inf logit
  * as "never chosen, mass 0".  ONE rule for every route of the search loops:

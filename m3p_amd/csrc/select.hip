@@ -47,6 +47,12 @@
 // Nucleus (top-p) sampling (decoder.py: generate(sample_top_p=...); m3p_vocab_nucleus_sample) cuts that allowed set to the
 // words whose logit is at least x*, the largest logit value whose cumulated mass reaches top_p - see the block in front of
 // vnuc_coarse_kernel; with 1 <= top_k <= 16 the cut is a sum over the lanes of vsmp_topk_kernel<true>.
+//
+// More than VS_MAX_K candidates (generate(sample_top_k=40 ...); m3p_vocab_sample_wide, 1 <= top_k <= VSW_MAX_K = 1024, with or
+// without the nucleus cut) keep that contract - the same counter, keys, tie rule and outputs - but find the candidate set by
+// an exact count selection over the 16-bit keys instead of top_k rounds of a maximum, compact it to [n, top_k] entries and
+// finish each row in one workgroup in LDS - see the block in front of vsw_coarse_kernel.  The decoding loop sends top_k > 16
+// there; nothing leaves the device for any top_k <= 1024.
 #include "common.hpp"
 #include <math.h>
 
@@ -725,6 +731,323 @@ int vsmp_plan(int n, int V, int ld, int top_k) {
   return M3P_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// seeded sampling over more than VS_MAX_K candidates: m3p_vocab_sample_wide (1 <= top_k <= VSW_MAX_K), nucleus cut included
+// ------------------------------------------------------------------------------------------------------------------------
+// k rounds of a block-wide maximum (vs_chunk_kernel: every chunk hands on its own first k, a wave then merges chunks * k
+// candidates in k more rounds) cost k barriers per workgroup and k * chunks * k merge work per row - 62 chunks at k = 50 are
+// 3 100 candidates scanned 50 times by one wave, at k = 1024 it is 65 million reads per row.  Here the candidate set K is
+// found by an exact SELECTION instead, and only K is ever sorted:
+//   vsw_coarse_kernel    a workgroup per (row, chunk): the NUMBER of words per HIGH byte of the sortable 16-bit key (LDS
+//                        and global integer atomics: counts do not depend on their order)
+//   vsw_scan_kernel      a wave per row: the coarse bin at which the count cumulated from the top reaches top_k
+//   vnuc_fine_kernel     (the nucleus route's, as it is) the number of words per LOW byte inside that bin
+//   vsw_scan_kernel      again, behind the count above the bin: the k-th value v_k and above = #{x > v_k}
+//   vsw_tie_kernel       per (row, chunk) the words above v_k and the words equal to it
+//   vsw_compact_kernel   K -> ent[row, top_k] as (sortable logit << 32 | ~word): every word above v_k, and of the class at v_k
+//                        the quota q = top_k - above in COLUMN order - the chunks before this one hold so many of the class
+//                        (a sum over chunkcnt), inside the chunk a block prefix sum over (tid * 8 + e, then 2048 + tid * 8 + e)
+//   vsw_draw_kernel      a workgroup per row, K in LDS: a bitonic sort (logit descending, word ascending), masses as the
+//                        integers of vnuc_mass (shift 40: 1024 of them stay below 2^51), their prefix sums, the nucleus cut
+//                        at the first class end whose cumulated mass reaches top_p * Z, the keys of the allowed entries by
+//                        vsmp_log_e, the winner, lse = m + log(mass) - shift ln 2 in fp64.  top_p >= 1: no cut, cut = -inf.
+// The selection is on integer keys alone, so every kernel agrees on K; integer atomics only; the same inputs, the same bits.
+constexpr int VSW_MAX_K = 1024;
+constexpr int VSW_SHIFT = 40;
+
+struct VswLayout {
+  size_t ent, hist, fine, chunkcnt, rowbin, rowlow, above0, above1, bytes;
+};
+VswLayout vsw_layout(int n, int V, int top_k) {
+  const size_t rows = (size_t)n, blocks = rows * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
+  VswLayout L;
+  size_t o = 0;
+  L.ent = o;      o += rows * (size_t)top_k * sizeof(unsigned long long);
+  L.hist = o;     o += rows * VN_BINS * sizeof(uint32_t);                 // [n, 256] u32, zeroed by the launcher with ...
+  L.fine = o;     o += rows * VN_BINS * sizeof(uint32_t);                 // ... [n, 256] u32 behind it
+  L.chunkcnt = o; o += blocks * 2 * sizeof(uint32_t);                     // per (row, chunk): words above v_k, words equal to it
+  L.rowbin = o;   o += rows * sizeof(int);                                // high byte of v_k's key
+  L.rowlow = o;   o += rows * sizeof(int);                                // low byte
+  L.above0 = o;   o += rows * sizeof(uint32_t);                           // words above the coarse bin
+  L.above1 = o;   o += rows * sizeof(uint32_t);                           // words above v_k
+  L.bytes = o;
+  return L;
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  return v;
+}
+// the sortable key of v_k (0x10000, above every key, when a scan found none - a row outside the contract)
+__device__ __forceinline__ uint32_t vsw_kth(const int* __restrict__ rowbin, const int* __restrict__ rowlow, int row) {
+  const int b = rowbin[row], l = rowlow[row];
+  return b < 0 || l < 0 ? 0x10000u : ((uint32_t)b << 8 | (uint32_t)l);
+}
+// exclusive prefix of v over the 256 threads of a workgroup and the workgroup's total (sh: 4 words of LDS of this call's own)
+__device__ __forceinline__ unsigned long long vsw_block_excl(unsigned long long v, int tid, unsigned long long* sh,
+                                                             unsigned long long& total) {
+  const int lane = tid & 63, wv = tid >> 6;
+  unsigned long long inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long t = (unsigned long long)__shfl_up((long long)inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) sh[wv] = inc;
+  __syncthreads();
+  unsigned long long base = 0ull;
+  total = 0ull;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (q < wv) base += sh[q];
+    total += sh[q];
+  }
+  return base + (inc - v);
+}
+
+__global__ __launch_bounds__(256) void vsw_coarse_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks,
+                                                        uint32_t* __restrict__ hist) {
+  __shared__ uint32_t cnt[VN_COPIES][VN_BINS + 1];
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+#pragma unroll
+  for (int c = 0; c < VN_COPIES; ++c) cnt[c][tid] = 0u;
+  __syncthreads();
+  uint32_t* mine = cnt[tid & (VN_COPIES - 1)];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
+    const int left = V - (chunk * VS_CHUNK + lc0);          // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t sk = vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]);
+      if (e < left) atomicAdd(&mine[sk >> 8], 1u);          // columns at or past V hold anything: never counted
+    }
+  }
+  __syncthreads();
+  uint32_t s = 0u;
+#pragma unroll
+  for (int c = 0; c < VN_COPIES; ++c) s += cnt[c][tid];
+  if (s != 0u) atomicAdd(hist + (size_t)row * VN_BINS + tid, s);
+}
+
+// a wave per row over 256 counts (lane l holds bins 4 l .. 4 l + 3): the highest bin at which the count cumulated from the
+// top, behind above_in[row] (NULL: 0), reaches top_k, and the count above that bin.  (No bin: -1 and 0.)
+__global__ __launch_bounds__(256) void vsw_scan_kernel(const uint32_t* __restrict__ cnt, int n, uint32_t top_k,
+                                                      const uint32_t* __restrict__ above_in, int* __restrict__ bin_out,
+                                                      uint32_t* __restrict__ above_out) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
+  const uint32_t* h = cnt + (size_t)row * VN_BINS + 4 * lane;
+  const unsigned long long b[4] = {h[0], h[1], h[2], h[3]};
+  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
+  unsigned long long c = (above_in ? (unsigned long long)above_in[row] : 0ull) + (vnuc_suffix_u64(s, lane) - s), above = 0ull;
+  int best = -1;
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const unsigned long long ci = c + b[q];
+    if (best < 0 && b[q] != 0ull && ci >= (unsigned long long)top_k) {
+      best = 4 * lane + q;
+      above = c;
+    }
+    c = ci;
+  }
+  const int win = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
+  if (win < 0 ? lane == 0 : best == win) {                 // (a bin belongs to one lane)
+    bin_out[row] = win;
+    above_out[row] = win < 0 ? 0u : (uint32_t)above;
+  }
+}
+
+__global__ __launch_bounds__(256) void vsw_tie_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks,
+                                                     const int* __restrict__ rowbin, const int* __restrict__ rowlow,
+                                                     uint32_t* __restrict__ chunkcnt) {
+  __shared__ uint32_t red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+  const uint32_t kth = vsw_kth(rowbin, rowlow, row);
+  uint32_t c = 0u;                                          // words above << 16 | words equal (a chunk holds 4096: 13 bits each)
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
+    const int left = V - (chunk * VS_CHUNK + lc0);
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t sk = vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]);
+      if (e < left) c += sk > kth ? 0x10000u : (sk == kth ? 1u : 0u);
+    }
+  }
+  c = wave_sum_u32(c);
+  if (lane == 0) red[wv] = c;
+  __syncthreads();
+  if (tid == 0) {
+    c = (red[0] + red[1]) + (red[2] + red[3]);
+    chunkcnt[(size_t)blockIdx.x * 2] = c >> 16;
+    chunkcnt[(size_t)blockIdx.x * 2 + 1] = c & 0xFFFFu;
+  }
+}
+
+__global__ __launch_bounds__(256) void vsw_compact_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks, int top_k,
+                                                         const int* __restrict__ rowbin, const int* __restrict__ rowlow,
+                                                         const uint32_t* __restrict__ rowabove, const uint32_t* __restrict__ chunkcnt,
+                                                         unsigned long long* __restrict__ ent) {
+  __shared__ unsigned long long sh[2][4];
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+  const uint32_t kth = vsw_kth(rowbin, rowlow, row);
+  const uint32_t above = min(rowabove[row], (uint32_t)top_k), quota = (uint32_t)top_k - above;
+  // the chunks in front of this one: their words above v_k (slots 0 .. above - 1) and their members of the class at v_k
+  const uint32_t* cc = chunkcnt + (size_t)row * nchunks * 2;
+  unsigned long long before = 0ull, total;
+  for (int c = tid; c < chunk; c += 256) before += (unsigned long long)cc[2 * c] << 32 | (unsigned long long)cc[2 * c + 1];
+  vsw_block_excl(before, tid, sh[0], total);
+  const uint32_t a0 = (uint32_t)(total >> 32), t0 = (uint32_t)total;
+  if (cc[2 * chunk] == 0u && (cc[2 * chunk + 1] == 0u || t0 >= quota)) return;       // (the same in every thread) nothing of K here
+  uint32_t sk[16];
+  unsigned long long mine = 0ull;                           // words above << 40 | class members of half 1 << 20 | of half 0
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
+    const int left = V - (chunk * VS_CHUNK + lc0);
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint32_t s = e < left ? vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]) : 0xFFFFFFFFu;    // (no column)
+      sk[half * 8 + e] = s;
+      if (s != 0xFFFFFFFFu) mine += s > kth ? 1ull << 40 : (s == kth ? 1ull << (20 * half) : 0ull);
+    }
+  }
+  const unsigned long long excl = vsw_block_excl(mine, tid, sh[1], total);
+  uint32_t pa = a0 + (uint32_t)(excl >> 40);                                           // the slot of this thread's next word above v_k
+  uint32_t pt[2] = {t0 + (uint32_t)(excl & 0xFFFFFu),                                  // the class rank of its next member, per half
+                    t0 + (uint32_t)(total & 0xFFFFFu) + (uint32_t)((excl >> 20) & 0xFFFFFu)};
+  unsigned long long* out = ent + (size_t)row * top_k;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const uint32_t s = sk[e];
+    if (s == 0xFFFFFFFFu) continue;
+    const uint32_t word = (uint32_t)chunk * VS_CHUNK + (uint32_t)((e >> 3) * (VS_CHUNK / 2) + tid * 8 + (e & 7));
+    uint32_t slot = 0xFFFFFFFFu;
+    if (s > kth) slot = pa++;
+    else if (s == kth) {
+      const uint32_t rank = pt[e >> 3]++;
+      if (rank < quota) slot = above + rank;
+    }
+    if (slot < (uint32_t)top_k) out[slot] = (unsigned long long)s << 32 | (unsigned long long)(~word);
+  }
+}
+
+__global__ __launch_bounds__(256) void vsw_draw_kernel(const unsigned long long* __restrict__ ent, int V, int top_k, int N,
+                                                      float inv_t, float top_p, uint32_t seed, long long* __restrict__ words,
+                                                      float* __restrict__ logprob, float* __restrict__ key_out,
+                                                      float* __restrict__ cut_out) {
+  __shared__ unsigned long long keys[VSW_MAX_K];
+  __shared__ unsigned long long sh[4], redk[4], s_mass;
+  __shared__ int rede[4];
+  __shared__ uint32_t s_cut;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int row = blockIdx.x;
+  // N = the power of two at or above top_k (at least 2): the entries, then zeros - below every entry
+  for (int i = tid; i < N; i += 256) keys[i] = i < top_k ? ent[(size_t)row * top_k + i] : 0ull;
+  __syncthreads();
+  for (int k2 = 2; k2 <= N; k2 <<= 1)                       // bitonic sort, descending: (logit descending, word ascending)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < N / 2; t += 256) {
+        const int i = 2 * t - (t & (j - 1)), l = i + j;
+        const unsigned long long a = keys[i], b = keys[l];
+        if ((a < b) == ((i & k2) == 0)) {
+          keys[i] = b;
+          keys[l] = a;
+        }
+      }
+      __syncthreads();
+    }
+  // thread t holds the entries t * per .. t * per + per - 1
+  const int per = N > 256 ? N / 256 : 1, i0 = tid * per;
+  const float m = __fmul_rn(vs_value16((uint32_t)(keys[0] >> 32)), inv_t);
+  const float scale = (float)(1ull << VSW_SHIFT);
+  unsigned long long kk[4], w[4], mine = 0ull;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = i0 + q;
+    kk[q] = q < per && i < top_k ? keys[i] : 0ull;
+    w[q] = kk[q] != 0ull ? vnuc_mass(vs_value16((uint32_t)(kk[q] >> 32)), inv_t, m, scale) : 0ull;
+    mine += w[q];
+  }
+  unsigned long long Z;
+  const unsigned long long excl = vsw_block_excl(mine, tid, sh, Z);
+  // the last allowed entry: the first end of a class of equal logits at which the cumulated mass reaches top_p * Z
+  int cand = top_k - 1;
+  if (top_p < 1.f && Z != 0ull) {
+    unsigned long long c = excl;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (kk[q] == 0ull) continue;
+      const int i = i0 + q;
+      c += w[q];
+      const bool end = i == top_k - 1 || (uint32_t)(keys[i + 1] >> 32) != (uint32_t)(kk[q] >> 32);
+      if (end && vnuc_reaches(c, Z, top_p)) cand = min(cand, i);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+  if (lane == 0) rede[wv] = cand;
+  __syncthreads();
+  const int last = min(min(rede[0], rede[1]), min(rede[2], rede[3]));
+  if (last >= i0 && last < i0 + per) {                      // (one thread)
+    unsigned long long c = excl;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (i0 + q <= last) c += w[q];
+    s_mass = c;
+    s_cut = (uint32_t)(keys[last] >> 32);
+  }
+  unsigned long long best = 0ull;
+  float xbest = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (kk[q] == 0ull || i0 + q > last) continue;
+    const uint32_t word = ~(uint32_t)kk[q];
+    const float x = vs_value16((uint32_t)(kk[q] >> 32));
+    const unsigned long long k64 = vsmp_key64(__fmaf_rn(x, inv_t, -vsmp_log_e((uint32_t)row * (uint32_t)V + word, seed)), word);
+    if (k64 > best) {
+      best = k64;
+      xbest = x;
+    }
+  }
+  unsigned long long win = wave_max_u64(best);
+  if (lane == 0) redk[wv] = win;
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) win = redk[q] > win ? redk[q] : win;
+  if (best == win && win != 0ull) {                         // the word is part of the key: one thread
+    const float lse = (float)((double)m + (log((double)s_mass) - (double)VSW_SHIFT * 0.693147180559945309417));
+    words[row] = (long long)(~(uint32_t)win);
+    logprob[row] = __fmaf_rn(xbest, inv_t, -lse);
+    if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
+    if (cut_out) cut_out[row] = top_p < 1.f ? vs_value16(s_cut) : -INFINITY;
+  }
+}
+
+int vsw_plan(int n, int V, int ld, int top_k) {
+  if (n <= 0 || V <= 0 || top_k < 1 || ld < V || (ld % 8) != 0 || top_k > V) return M3P_EINVAL;
+  if (top_k > VSW_MAX_K) return M3P_ENOTIMPL;
+  if ((long long)n * V >= (1ll << 32)) return M3P_ENOTIMPL;                          // the hash counter r * V + w is 32 bits
+  const long long nchunks = ((long long)V + VS_CHUNK - 1) / VS_CHUNK;
+  if ((long long)n * nchunks * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block indices (the bound of vsmp_plan)
+  return M3P_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -864,6 +1187,61 @@ int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, float inv
   M3P_CHECK_LAUNCH();
   hipLaunchKernelGGL(vnuc_merge_kernel, dim3(rows4), dim3(256), 0, st, (const bf16*)logits, ld, n, V, nchunks, inv_t,
                      (const unsigned long long*)wkey, (const float*)lse, words, logprob, key);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_vocab_sample_wide_max_k(void) { return VSW_MAX_K; }
+
+int m3p_vocab_sample_wide_plan(int n, int V, int ld, int top_k) { return vsw_plan(n, V, ld, top_k); }
+
+size_t m3p_vocab_sample_wide_workspace_bytes(int n, int V, int top_k) {
+  if (n <= 0 || V <= 0 || top_k < 1) return 0;
+  return vsw_layout(n, V, top_k).bytes;
+}
+
+int m3p_vocab_sample_wide(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed,
+                          void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key, float* cut,
+                          void* stream) {
+  const int rc = vsw_plan(n, V, ld, top_k);
+  if (rc != M3P_OK) return rc;
+  if (!(inv_t > 0.f) || isinf(inv_t) || !(top_p > 0.f)) return M3P_EINVAL;
+  if (!logits || !workspace || !words || !logprob || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
+  if (workspace_bytes < m3p_vocab_sample_wide_workspace_bytes(n, V, top_k)) return M3P_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
+  const unsigned rows4 = (unsigned)((n + 3) / 4), blocks = (unsigned)(n * nchunks);
+  const VswLayout L = vsw_layout(n, V, top_k);
+  char* ws = (char*)workspace;
+  unsigned long long* ent = (unsigned long long*)(ws + L.ent);
+  uint32_t* hist = (uint32_t*)(ws + L.hist);
+  uint32_t* fine = (uint32_t*)(ws + L.fine);
+  uint32_t* chunkcnt = (uint32_t*)(ws + L.chunkcnt);
+  int* rowbin = (int*)(ws + L.rowbin);
+  int* rowlow = (int*)(ws + L.rowlow);
+  uint32_t* above0 = (uint32_t*)(ws + L.above0);
+  uint32_t* above1 = (uint32_t*)(ws + L.above1);
+  int N = 2;
+  while (N < top_k) N <<= 1;
+  if (hipMemsetAsync(hist, 0, (size_t)n * VN_BINS * 2 * sizeof(uint32_t), st) != hipSuccess) return M3P_EINVAL;
+  hipLaunchKernelGGL(vsw_coarse_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, hist);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_scan_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)hist, n, (uint32_t)top_k,
+                     (const uint32_t*)nullptr, rowbin, above0);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_fine_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin, fine);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_scan_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)fine, n, (uint32_t)top_k,
+                     (const uint32_t*)above0, rowlow, above1);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_tie_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin,
+                     (const int*)rowlow, chunkcnt);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_compact_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, top_k,
+                     (const int*)rowbin, (const int*)rowlow, (const uint32_t*)above1, (const uint32_t*)chunkcnt, ent);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_draw_kernel, dim3((unsigned)n), dim3(256), 0, st, (const unsigned long long*)ent, V, top_k, N, inv_t,
+                     top_p, seed, words, logprob, key, cut);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }

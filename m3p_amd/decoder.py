@@ -21,7 +21,8 @@ reads through it), and with ``cache['beam']`` the source's keys / values are kep
 ``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, unseeded sampling and wider beams run the torch code below unchanged.
 ``generate(sample_seed=...)`` draws the next word by the seeded Gumbel-max contract of ``ops.vocab_sample`` (csrc/select.hip;
 NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation, a nucleus (top-p) cut
-(``sample_top_p``: ``ops.vocab_nucleus_sample``) and the sampled words' log-probabilities.
+(``sample_top_p``: ``ops.vocab_nucleus_sample``) and the sampled words' log-probabilities; more than 16 and up to 1024
+top-k candidates take ``ops.vocab_sample_wide`` (a count selection in place of k rounds of a maximum), nucleus cut included.
 Both loops take decoding constraints - ``min_len``, ``repetition_penalty``, ``no_repeat_ngram``, ``banned_words`` - by ONE rule
 for every route (include/m3p_hip.h: m3p_logits_constrain): where the words are selected on the device, ``ops.logits_constrain``
 (csrc/constrain.hip) edits the step's bf16 logits in place in front of the selection kernels, everywhere else the torch twin
@@ -380,13 +381,15 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     include/m3p_hip.h (m3p_vocab_sample): ``sample_temperature`` defaults to 1.0, ``sample_top_k`` (None or 0: every word)
     restricts the draw to the row's top_k words, and the step that decodes position ``cur_len`` uses the stream key
     ``rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)``.  A CUDA model whose shape the launcher takes runs
-    ``ops.vocab_sample`` on the bf16 logits; everything else (a CPU model, top_k > 16, VOCAB_SELECT_MAX_K == 0) runs the NumPy
-    twin on ``word_scores`` - the same seed is the same random stream on both routes.  ``sample_top_p`` (seeded runs only;
+    ``ops.vocab_sample`` on the bf16 logits, with 16 < top_k <= 1024 ``ops.vocab_sample_wide`` (the same contract by a count
+    selection; ``sample_top_p`` rides along); everything else (a CPU model, top_k > 1024, VOCAB_SELECT_MAX_K == 0) runs the
+    NumPy twin on ``word_scores`` - the same seed is the same random stream on both routes.  ``sample_top_p`` (seeded runs only;
     0 < p <= 1, None and any value >= 1.0 mean "off": every route is then bit for bit what it is without it) cuts the
     candidates (every word, or the top_k) to the nucleus of include/m3p_hip.h (m3p_vocab_nucleus_sample): the words whose
     logit is >= the largest logit value at which the mass cumulated from the top, under the tempered distribution over the
     candidates, reaches p - whole classes of equal logits, the row's maximum always among them.  The routes and the stream
-    keys are the same (``ops.vocab_nucleus_sample`` on the device, ``rng.sample_words(top_p=...)`` as the twin).  Torch's CPU
+    keys are the same (``ops.vocab_nucleus_sample`` or ``ops.vocab_sample_wide`` on the device, ``rng.sample_words(top_p=...)``
+    as the twin).  Torch's CPU
     and CUDA generators are not touched, so a seeded run can be replayed exactly.  The counter of the random stream is (row of
     the batch, word): a sentence's draw depends on its position in the batch.  ``return_logprobs`` (seeded runs only) adds a
     third value, fp32 (cur_len, bs): the log-probability, under the tempered, top-k and nucleus-truncated distribution, of
@@ -400,7 +403,7 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     gives -inf to every word that would complete an n-gram the history already holds; ``min_len`` gives -inf to <EOS> while
     cur_len <= min_len, so every sentence has at least min_len words between its two <EOS> (min_len <= max_len - 2);
     ``banned_words`` (ids in [0, n_words), not <EOS>) get -inf.  Where the words are selected on the device
-    (``ops.vocab_select`` / ``vocab_sample`` / ``vocab_nucleus_sample``) and ``ops.logits_constrain_takes`` the shape (asked
+    (``ops.vocab_select`` / ``vocab_sample`` / ``vocab_nucleus_sample`` / ``vocab_sample_wide``) and ``ops.logits_constrain_takes`` the shape (asked
     once, with max_len - 1 as the history bound), ``ops.logits_constrain`` edits the bf16 logits in place - one launch per
     step - and the selection runs unchanged behind it; a declined shape gets the twin ``constrain_scores_`` on those logits, and
     every torch route (greedy, seeded, ``torch.multinomial``) the twin on ``word_scores``.  Log-probabilities are those of the
@@ -441,6 +444,10 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
         takes = ops.vocab_sample_takes if top_p is None else ops.vocab_nucleus_takes
         sample_dev = (dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
                       and takes(bs, model.n_words, model.arena().V_pad, top_k))
+        # (more than 16 candidates: the count-selection route, asked once where the plan above declined)
+        sample_wide = (not sample_dev and top_k >= 1 and dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
+                       and ops.vocab_sample_wide_takes(bs, model.n_words, model.arena().V_pad, top_k))
+        sample_dev = sample_dev or sample_wide
         logprobs = torch.zeros((max_len, bs), dtype=torch.float32, device=dev) if return_logprobs else None
     # (the constraint kernel sits in front of a device selection only; its plan is asked once, like the others)
     cons_dev = (cons.on and (sample_dev if seeded else select)
@@ -453,12 +460,14 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
             step_seed = rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)
             if sample_dev:
                 logits, V = _constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len)
-                if top_p is None:
+                if sample_wide:
+                    res = ops.vocab_sample_wide(logits, V, temperature, step_seed, top_k, top_p)
+                elif top_p is None:
                     res = ops.vocab_sample(logits, V, temperature, step_seed, top_k)
                 else:
                     res = ops.vocab_nucleus_sample(logits, V, temperature, step_seed, top_p, top_k)
                 if res is None:
-                    name = 'm3p_vocab_sample' if top_p is None else 'm3p_vocab_nucleus_sample'
+                    name = 'm3p_vocab_sample_wide' if sample_wide else 'm3p_vocab_sample' if top_p is None else 'm3p_vocab_nucleus_sample'
                     raise L.M3PError('%s declined (M3P_ENOTIMPL) a shape its plan took' % name)
                 next_words, step_logprob = res[0], res[1]
             else:

@@ -533,6 +533,54 @@ def vocab_nucleus_sample(logits, V, temperature, seed, top_p, top_k=0):
     return words, logprob, key, cut
 
 
+def vocab_sample_wide_max_k():
+    """VSW_MAX_K of csrc/select.hip: the most candidates per row m3p_vocab_sample_wide takes."""
+    return int(L.load().m3p_vocab_sample_wide_max_k())
+
+
+def vocab_sample_wide_takes(n, V, ld, top_k):
+    """Does the launcher of vocab_sample_wide take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
+    rc = L.load().m3p_vocab_sample_wide_plan(n, V, ld, top_k)
+    if rc == _ENOTIMPL:
+        return False
+    L.check(rc, 'm3p_vocab_sample_wide_plan')
+    return True
+
+
+def vocab_sample_wide(logits, V, temperature, seed, top_k, top_p=None):
+    """Seeded top-k sampling of a decoding step over 1 <= top_k <= vocab_sample_wide_max_k() (1024) candidates, with the
+    nucleus cut when top_p is given (csrc/select.hip; the contract is in include/m3p_hip.h, the NumPy twin in m3p_amd/rng.py:
+    sample_allowed, nucleus_cut, sample_words): the semantics of vocab_nucleus_sample - the row's first top_k words under
+    (logit descending, word ascending), cut to the words whose logit is >= x*, the largest logit value whose cumulated mass
+    over those candidates reaches top_p, and the Gumbel-max draw over what is left - by a count selection instead of top_k
+    rounds of a maximum.  -> (words int64 [n], logprob fp32 [n], key fp32 [n], cut fp32 [n]).  top_p None or >= 1.0 is "off":
+    no cut, cut = -inf; top_p <= 0 raises ValueError.  None when the launcher does not take the shape (M3P_ENOTIMPL: top_k >
+    1024, n * V >= 2^32); top_k < 1 or > V raises."""
+    top_p = rng.nucleus_top_p(top_p)
+    if top_p is None:
+        top_p = 1.0                                # (the launcher's "off")
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
+    n = logits.shape[0]
+    lib = L.load()
+    rc = lib.m3p_vocab_sample_wide_plan(n, V, logits.stride(0), top_k)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_vocab_sample_wide_plan')
+    dev = logits.device
+    ws_bytes = lib.m3p_vocab_sample_wide_workspace_bytes(n, V, top_k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    words = torch.empty((n,), dtype=torch.int64, device=dev)
+    logprob = torch.empty((n,), dtype=torch.float32, device=dev)
+    key = torch.empty((n,), dtype=torch.float32, device=dev)
+    cut = torch.empty((n,), dtype=torch.float32, device=dev)
+    rc = lib.m3p_vocab_sample_wide(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k, top_p,
+                                   int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, words.data_ptr(), logprob.data_ptr(),
+                                   key.data_ptr(), cut.data_ptr(), L.stream())
+    L.check(rc, 'm3p_vocab_sample_wide')
+    return words, logprob, key, cut
+
+
 def logits_constrain_takes(n, V, ld, hist_len, ngram=0, n_banned=0):
     """Does the launcher of logits_constrain take the shape?  (False: it would answer M3P_ENOTIMPL - hist_len > 1024, ngram > 16,
     n_banned > 4096; a malformed one raises.)  The answer depends on shapes alone: a search loop asks once, with max_len - 1 as

@@ -41,7 +41,18 @@ log_softmax / topk), both with the constraints, outputs compared (for beam searc
 selections part on the same constrained logits, as in the plain run).  Same geometry, warm-up and pairs.  `--trace greedy
 --constraints` (or beam4) is the run for the profiler, `--stats ... greedy` then lists lc_constrain_kernel beside the selection
 kernels.  The constraints-off path is not timed against its parent: it issues no launch (tests/test_logit_constraints.py).
-    timeout -k 10 900 python tools/decode_bench.py --constraints > profiles/decode_constraints.txt"""
+    timeout -k 10 900 python tools/decode_bench.py --constraints > profiles/decode_constraints.txt
+
+`--sample --top-k K [--top-p P]` measures seeded sampling over more than 16 candidates (csrc/select.hip: m3p_vocab_sample_wide):
+(a) generate(sample_seed=..., sample_top_k=K[, sample_top_p=P]) on the device against the fallback route of the same call in
+the same process (decoder.VOCAB_SELECT_MAX_K = 0: an fp32 copy of the logits, a device-to-host read and the NumPy twin of
+m3p_amd/rng.py - the code this call ran before the kernels existed, as long as rng.py and decoder._sample_twin are untouched);
+the fallback takes seconds per step, so its runs decode FALLBACK_LEN - 1 steps, and both sides are reported in ms per step.
+(b) without --top-p, the device route's neighbours: ms per step at top_k = 0 and 16 (the routes of m3p_vocab_sample) beside K
+and 1024.  Same geometry, 128 sentences, warm-up and three alternating pairs.  `--trace wide --top-k K [--top-p P]` is the run
+for the profiler, `--stats ... wide` its per-kernel lines.
+    timeout -k 10 900 python tools/decode_bench.py --sample --top-k 50 > profiles/decode_topk_wide.txt
+    timeout -k 10 900 python tools/decode_bench.py --sample --top-k 50 --top-p 0.9 >> profiles/decode_topk_wide.txt"""
 import csv
 import os
 import sys
@@ -57,6 +68,8 @@ RUNS = {'beam4': ('generate_beam', 32, 4), 'beam5': ('generate_beam', 64, 5), 'g
 SAMPLE = ('sample', 128, 1)       # the --sample run: T = 1.0, seeded device route against torch.multinomial
 SAMPLE_SEED = 17
 TOP_P = [0.9]                     # --top-p: the nucleus of the `nucleus` runs
+TOP_K = [0]                       # --top-k: the candidates of the `wide` runs (0: not given)
+FALLBACK_LEN = 3                  # max_len of the fallback runs of --top-k: two decoding steps of seconds each
 CONSTRAINTS = dict(no_repeat_ngram=3, repetition_penalty=1.2, min_len=8)      # the --constraints runs
 PAIRS = 3
 HBM_PEAK = 8.0e12               # bytes/s of an MI355X (HBM3E)
@@ -88,19 +101,21 @@ def call(m, kind, src, src_len, beam, **cons):
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED)
         if kind == 'nucleus':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0, sample_seed=SAMPLE_SEED, sample_top_p=TOP_P[0])
+        if kind == 'wide':
+            return m.generate(src, src_len, 1, sample_temperature=1.0, sample_seed=SAMPLE_SEED, **cons)
         if kind == 'sample_torch':
             return m.generate(src, src_len, 1, max_len=MAX_LEN, sample_temperature=1.0)
         return m.generate_beam(src, src_len, 1, beam, 1.0, False, max_len=MAX_LEN, **cons)
 
 
-def timed(fn):
+def timed(fn, max_len=MAX_LEN):
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     out = fn()
     e1.record()
     torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (MAX_LEN - 1), out
+    return e0.elapsed_time(e1) / (max_len - 1), out
 
 
 def with_rule(rule, fn):
@@ -229,6 +244,54 @@ def bench_nucleus(m):
     print('       bytes of logits per step (n * V * 2): %.1f MB' % (bs * V * 2 / 1e6))
 
 
+def bench_wide(m):
+    _, bs, beam = SAMPLE
+    K, P = TOP_K[0], TOP_P[0]
+    print('sampled decoding step (T = 1.0), %d layers, d = %d, V = %d, S = %d, %d sentences; ms per decoding step, %d alternating '
+          'pairs; seeded sampling with top_k = %d%s' % (LAYERS, D, V, S, bs, PAIRS, K, '' if P is None else ', top_p = %g' % P))
+    src, src_len = inputs(bs)
+    kw = dict(sample_top_k=K, sample_top_p=P)
+    dev = lambda: call(m, 'wide', src, src_len, beam, max_len=MAX_LEN, **kw)                              # noqa: E731
+    fall = lambda n: with_rule(0, lambda: call(m, 'wide', src, src_len, beam, max_len=n, **kw))           # noqa: E731
+    dev()                                                    # warm-up of both routes
+    fall(2)
+    old, new = [], []
+    for _ in range(PAIRS):
+        t, out_old = timed(lambda: fall(FALLBACK_LEN), FALLBACK_LEN)
+        old.append(t)
+        t, out_new = timed(dev)
+        new.append(t)
+    ratios = [a / b for a, b in zip(old, new)]
+    assert out_old[0].shape[0] == FALLBACK_LEN and out_new[0].shape[0] == MAX_LEN, 'a sentence ended early'
+    print('(a) top_k %4d%s  bs %3d (%3d rows)  fallback ms %s (max_len %d)  device ms %s (max_len %d)  ratio %s  the device route %s' % (
+        K, '' if P is None else ' top_p %g' % P, bs, bs, ' '.join('%9.1f' % v for v in old), FALLBACK_LEN,
+        ' '.join('%7.3f' % v for v in new), MAX_LEN, ' '.join('%7.1f' % v for v in ratios),
+        'wins all three' if min(ratios) > 1 else 'does NOT win all three'))
+    print('    the fallback is decoder.VOCAB_SELECT_MAX_K = 0 in this process: rng.sample_words on a host copy of the fp32 scores')
+    drawn = FALLBACK_LEN - 1                                 # (the fallback's last position is the forced <EOS>)
+    same = int((out_old[0][:drawn] == out_new[0][:drawn]).all(0).sum())
+    print('    drawn positions the two runs share: %d; the routes agree there in %d of %d sentences' % (drawn - 1, same, bs))
+    again = dev()
+    print('    a further device run gives the same tokens: %s' % torch.equal(again[0], out_new[0]))
+    print('    bytes of logits per step (n * V * 2): %.1f MB' % (bs * V * 2 / 1e6))
+    if P is not None:
+        return
+    ks = sorted(set((0, 16, K, 1024)))
+    runs = {k: (lambda k=k: call(m, 'wide', src, src_len, beam, max_len=MAX_LEN, sample_top_k=k or None)) for k in ks}
+    for k in ks:
+        runs[k]()
+    ms = {k: [] for k in ks}
+    for _ in range(PAIRS):
+        for k in ks:
+            ms[k].append(timed(runs[k])[0])
+    for k in ks:
+        route = 'm3p_vocab_sample' if k <= 16 else 'm3p_vocab_sample_wide'
+        print('(b) top_k %4d  %-22s device ms %s' % (k, route, ' '.join('%7.3f' % v for v in ms[k])))
+    print('    the wide route against the narrow one at 16: %s us per step more at top_k %d, %s at 1024' % (
+        ' '.join('%6.1f' % (1e3 * (a - b)) for a, b in zip(ms[K], ms[16])), K,
+        ' '.join('%6.1f' % (1e3 * (a - b)) for a, b in zip(ms[1024], ms[16]))))
+
+
 def bench_constraints(m):
     print('decoding constraints %s, %d layers, d = %d, V = %d, S = %d, max_len = %d; ms per decoding step, %d alternating pairs' % (
         CONSTRAINTS, LAYERS, D, V, S, MAX_LEN, PAIRS))
@@ -269,9 +332,11 @@ def bench_constraints(m):
 
 
 def trace(m, name, cons=None):
-    kind, bs, beam = ('nucleus',) + SAMPLE[1:] if name == 'nucleus' else SAMPLE if name == 'sample' else RUNS[name]
+    kind, bs, beam = (name,) + SAMPLE[1:] if name in ('nucleus', 'wide') else SAMPLE if name == 'sample' else RUNS[name]
     src, src_len = inputs(bs)
     cons = cons or {}
+    if name == 'wide':
+        cons = dict(max_len=MAX_LEN, sample_top_k=TOP_K[0], sample_top_p=TOP_P[0])
     call(m, kind, src, src_len, beam, **cons)
     torch.cuda.synchronize()
     t, _ = timed(lambda: call(m, kind, src, src_len, beam, **cons))
@@ -298,7 +363,7 @@ def own_kernel(kname):
 def stats(path, name):
     """Kernel shares of a `--trace NAME` run from rocprofv3's kernel stats (Name, Calls, TotalDurationNs, ...): shares of
     the summed KERNEL time, not of the step's wall time (host gaps between launches are in neither term)."""
-    kind, bs, beam = SAMPLE if name in ('sample', 'nucleus') else RUNS[name]
+    kind, bs, beam = SAMPLE if name in ('sample', 'nucleus', 'wide') else RUNS[name]
     rows = bs * beam
     total = own = 0.0
     sel, others = {}, []
@@ -311,14 +376,20 @@ def stats(path, name):
             others.append((ns, calls, kname))
         for key in ('vs_chunk_kernel', 'vs_merge_kernel', 'vsmp_chunk_kernel', 'vsmp_merge_kernel', 'vsmp_topk_kernel',
                     'vnuc_coarse_kernel', 'vnuc_scan_kernel', 'vnuc_fine_kernel', 'vnuc_cut_kernel', 'vnuc_merge_kernel',
-                    'lc_constrain_kernel'):
+                    'lc_constrain_kernel', 'vsw_coarse_kernel', 'vsw_scan_kernel', 'vsw_tie_kernel', 'vsw_compact_kernel',
+                    'vsw_draw_kernel'):
             if key in kname:
                 sel[key] = (ns / calls, calls)
     print('\nkernel shares, %s (%d rows), %s, from a profiled run of its own (warm-up + one timed run)' % (
-        name, rows, {'sample': 'seeded sampling', 'nucleus': 'seeded nucleus sampling'}.get(name, 'select path')))
+        name, rows, {'sample': 'seeded sampling', 'nucleus': 'seeded nucleus sampling',
+                     'wide': 'seeded sampling over more than 16 candidates'}.get(name, 'select path')))
     for key, (avg, calls) in sorted(sel.items()):
-        print('  %-16s %5d calls  %8.1f us per call' % (key, calls, avg / 1e3))
-    if name == 'nucleus':
+        print('  %-18s %5d calls  %8.1f us per call' % (key, calls, avg / 1e3))
+    if name == 'wide':
+        every = sum(avg * calls for avg, calls in sel.values()) / max(v[1] for k, v in sel.items() if k == 'vsw_draw_kernel')
+        print('  wide sampling (all of the above, vsw_scan_kernel twice): %.1f us per step over %.1f MB of logits read four times' % (
+            every / 1e3, rows * V * 2 / 1e6))
+    elif name == 'nucleus':
         every = sum(v[0] for v in sel.values())
         print('  nucleus sampling (all of the above): %.1f us per step over %.1f MB of logits' % (every / 1e3, rows * V * 2 / 1e6))
     elif len(sel) - ('lc_constrain_kernel' in sel) == 2:
@@ -345,15 +416,26 @@ if __name__ == '__main__':
             print(torch.cuda.get_device_name(0))
             bench_constraints(model())
             sys.exit(0)
+    if '--top-k' in sys.argv:
+        at = sys.argv.index('--top-k')
+        TOP_K[0] = int(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
+        assert 16 < TOP_K[0] <= 1024, '--top-k K: 16 < K <= 1024 (up to 16 is the route of --sample)'
+        if '--top-p' not in sys.argv:
+            TOP_P[0] = None
     if '--top-p' in sys.argv:
         at = sys.argv.index('--top-p')
         TOP_P[0] = float(sys.argv[at + 1])
         del sys.argv[at:at + 2]
         assert 0.0 < TOP_P[0] < 1.0, '--top-p P: 0 < P < 1'
-        if len(sys.argv) >= 2 and sys.argv[1] == '--sample':
+        if len(sys.argv) >= 2 and sys.argv[1] == '--sample' and not TOP_K[0]:
             print(torch.cuda.get_device_name(0))
             bench_nucleus(model())
             sys.exit(0)
+    if TOP_K[0] and len(sys.argv) >= 2 and sys.argv[1] == '--sample':
+        print(torch.cuda.get_device_name(0))
+        bench_wide(model())
+        sys.exit(0)
     if len(sys.argv) >= 3 and sys.argv[1] == '--trace':
         trace(model(), sys.argv[2], CONSTRAINTS if constrained else None)
     elif len(sys.argv) >= 2 and sys.argv[1] == '--sample':
