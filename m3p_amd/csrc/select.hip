@@ -53,14 +53,27 @@
 // an exact count selection over the 16-bit keys instead of top_k rounds of a maximum, compact it to [n, top_k] entries and
 // finish each row in one workgroup in LDS - see the block in front of vsw_coarse_kernel.  The decoding loop sends top_k > 16
 // there; nothing leaves the device for any top_k <= 1024.
+//
+// Shared pieces, each defined once (the kernels are thin bodies over them):
+//   chunk reader   VsChunk / vs_chunk_of_block / vs_chunk_run -> VsRun / vs_slot_column: which columns a thread of workgroup
+//                  (row, chunk) owns, the load guard at V, the fold of -0, the sortable key - the seven (row, chunk) kernels
+//   histogram      VnHist<T>: 256 bins in replicated LDS copies, zero / add / flush - vnuc_coarse, vnuc_fine, vsw_coarse
+//   bin scan       vn_bin_scan: the highest bin at which the value cumulated from the top satisfies a predicate - vnuc_scan,
+//                  vnuc_cut, vsw_scan
+//   row lse        vs_row_lse: log-sum-exp from the chunks' (max, sum) - vs_merge, vsmp_merge
+//   draw epilogue  vsmp_write_draw (word, logprob, key, cut) and vsmp_merge_row (the body of vsmp_merge and vnuc_merge)
+//   host side      vs_nchunks, vsmp_plan (the seeded draws' plan, by the bounds on top_k), vs_args_ok, vsmp_launch_topk
 #include "common.hpp"
 #include <math.h>
+#include <initializer_list>
 
 namespace {
 
 constexpr int VS_CHUNK = 4096;        // columns per workgroup of phase 1: 256 threads x 2 loads x 8 bf16
 constexpr int VS_MAX_K = 16;          // entries per sentence (2 * beam of the search loop: beams up to 8)
 constexpr int VS_MAX_BEAM = 64;       // rows per sentence (their lse sit in LDS in phase 2)
+
+int vs_nchunks(int V) { return (int)(((long long)V + VS_CHUNK - 1) / VS_CHUNK); }      // workgroups of phase 1 per row
 
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 
@@ -82,6 +95,66 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   return v;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// the chunk reader: workgroup (row, chunk) of 256 threads over its VS_CHUNK columns, 16 per thread
+// ------------------------------------------------------------------------------------------------------------------------
+// Thread tid owns VS_RUNS runs of VS_RUN consecutive columns, a run per half of the chunk (one 16-byte load each, the
+// workgroup's loads of a half contiguous): its slot s = run * VS_RUN + e is the chunk's column vs_slot_column(tid, s).  A kernel
+// walks  for run: VsRun r = vs_chunk_run(...); for e: ...  with both loops unrolled, so slots index registers.  Columns at or
+// past V hold anything (NaN, inf): in(e) is false there and NOTHING else of such a column may reach a result - this guard is the
+// only thing that keeps them out.  (Two plain loops in the kernel, not a visitor taking a lambda or one flat loop over the 16
+// slots: either compiles several of the kernels to a branch per column where this form gives selects.  For the same reason a
+// kernel reads sk(e) in front of its in(e) test, not behind it.)
+constexpr int VS_RUNS = 2, VS_RUN = 8;
+struct VsChunk {
+  int row, chunk;
+  const unsigned short* base;                // the chunk's column 0 in the row
+};
+__device__ __forceinline__ VsChunk vs_chunk_of_block(const bf16* __restrict__ logits, int ld, int nchunks) {
+  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  return {row, chunk, reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK};
+}
+__device__ __forceinline__ int vs_slot_column(int tid, int slot) {
+  return (slot / VS_RUN) * (VS_CHUNK / VS_RUNS) + tid * VS_RUN + slot % VS_RUN;
+}
+struct VsRun {
+  int lc0, left;                             // the run's first column in the chunk; valid columns from there on (<= 0: none)
+  u16x8 v;                                   // the bf16 bits (zeros where the whole run is past V)
+  __device__ __forceinline__ int lc(int e) const { return lc0 + e; }                          // column in the chunk
+  __device__ __forceinline__ bool in(int e) const { return e < left; }                        // below V
+  __device__ __forceinline__ uint32_t raw(int e) const { return v[e]; }                       // the bf16 as loaded
+  __device__ __forceinline__ uint32_t bits(int e) const { return v[e] == 0x8000u ? 0u : (uint32_t)v[e]; }      // -0 folded into +0
+  __device__ __forceinline__ uint32_t sk(int e) const { return vs_sortable16(bits(e)); }     // the sortable 16-bit key
+};
+__device__ __forceinline__ VsRun vs_chunk_run(const VsChunk& c, int V, int tid, int run) {
+  VsRun r;
+  r.lc0 = vs_slot_column(tid, run * VS_RUN);
+  r.left = V - (c.chunk * VS_CHUNK + r.lc0);               // (ld % 8 == 0: a load that starts below V ends inside the row)
+  r.v = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  if (r.left > 0) r.v = *reinterpret_cast<const u16x8*>(c.base + r.lc0);
+  return r;
+}
+
+// the row's (max, sum exp(x - max)) from its chunks' pairs ps[2 c + {0, 1}] -> log-sum-exp, in every lane of the wave.
+// also(c): what else the caller has to fetch per chunk c of this lane, riding along the first pass (a loop of its own would
+// put one more memory latency into a kernel that is nothing but latency)
+template <class F>
+__device__ __forceinline__ float vs_row_lse(const float* __restrict__ ps, int nchunks, int lane, F&& also) {
+  float m = -INFINITY;
+  for (int c = lane; c < nchunks; c += 64) {
+    also(c);
+    m = fmaxf(m, ps[2 * c]);
+  }
+  m = wave_max(m);
+  float s = 0.f;
+  for (int c = lane; c < nchunks; c += 64) {
+    const float pm = ps[2 * c];
+    if (pm > -INFINITY) s += ps[2 * c + 1] * expf(pm - m);
+  }
+  s = wave_sum(s);
+  return m + logf(s);
+}
+
 // logits bf16 [n, ld]; block (row, chunk) -> pstat[(row * nchunks + chunk) * 2 + {0, 1}] = {max, sum exp(x - max)},
 // cand[(row * nchunks + chunk) * k + j] = key of the chunk's j-th entry (0: the chunk holds fewer than j + 1 columns)
 __global__ __launch_bounds__(256) void vs_chunk_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks, int k,
@@ -89,22 +162,14 @@ __global__ __launch_bounds__(256) void vs_chunk_kernel(const bf16* __restrict__ 
   __shared__ uint32_t red[2][4];
   __shared__ float reds[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
-  // 16 keys per thread; columns at or past V hold anything (NaN, inf) and become the key 0, below every real entry
+  // 16 keys per thread; a column at or past V becomes the key 0, below every real entry
+  const VsChunk c = vs_chunk_of_block(logits, ld, nchunks);
   uint32_t key[16];
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (chunk * VS_CHUNK + lc0);          // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(c, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      uint32_t b = v[e];
-      if (b == 0x8000u) b = 0;
-      key[half * 8 + e] = e < left ? (vs_sortable16(b) << 16 | (uint32_t)(0xFFFF - (lc0 + e))) : 0u;
-    }
+    for (int e = 0; e < VS_RUN; ++e) key[run * VS_RUN + e] = r.in(e) ? (r.sk(e) << 16 | (uint32_t)(0xFFFF - r.lc(e))) : 0u;
   }
   uint32_t lm = 0;
 #pragma unroll
@@ -159,17 +224,7 @@ __global__ __launch_bounds__(256) void vs_merge_kernel(const float* __restrict__
   const int sent = blockIdx.x;
   for (int r = wv; r < beam; r += 4) {             // a wave per row: merge the chunks' (max, sum)
     const size_t row = (size_t)sent * beam + r;
-    const float* ps = pstat + row * nchunks * 2;
-    float m = -INFINITY;
-    for (int c = lane; c < nchunks; c += 64) m = fmaxf(m, ps[2 * c]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int c = lane; c < nchunks; c += 64) {
-      const float pm = ps[2 * c];
-      if (pm > -INFINITY) s += ps[2 * c + 1] * expf(pm - m);
-    }
-    s = wave_sum(s);
-    const float l = m + logf(s);
+    const float l = vs_row_lse(pstat + row * nchunks * 2, nchunks, lane, [](int) {});
     if (lane == 0) {
       s_lse[r] = l;
       lse[row] = l;
@@ -234,11 +289,9 @@ int vs_plan(int n, int V, int ld, int beam, int k) {
   if (n <= 0 || V <= 0 || beam <= 0 || k <= 0 || n % beam != 0 || ld < V || (ld % 8) != 0) return M3P_EINVAL;
   if ((long long)beam * V < k) return M3P_EINVAL;
   if (k > VS_MAX_K || beam > VS_MAX_BEAM) return M3P_ENOTIMPL;
-  const long long nchunks = ((long long)V + VS_CHUNK - 1) / VS_CHUNK;
-  if ((long long)n * nchunks * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block and candidate indices
+  if ((long long)n * vs_nchunks(V) * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block and candidate indices
   return M3P_OK;
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------------
 // seeded sampling
@@ -294,40 +347,40 @@ __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict_
   __shared__ float redm[4];
   __shared__ float reds[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
-  const uint32_t col0 = (uint32_t)chunk * VS_CHUNK;
-  const uint32_t idx0 = (uint32_t)row * (uint32_t)V + col0;        // (the launcher holds n * V below 2^32)
+  const VsChunk c = vs_chunk_of_block(logits, ld, nchunks);
+  const uint32_t col0 = (uint32_t)c.chunk * VS_CHUNK;
+  const uint32_t idx0 = (uint32_t)c.row * (uint32_t)V + col0;      // (the launcher holds n * V below 2^32)
   float y[16], ka[16];                     // x * inv_t (-inf: no column) and the approximate key (NaN: no column)
   float mx = -INFINITY, amax = -INFINITY;
   uint32_t ck = 0u;
-  if constexpr (CUT) ck = cutkey[row];
+  if constexpr (CUT) ck = cutkey[c.row];
   int lbest = -1;                          // column in the chunk of the approximate maximum (-1: the thread holds no column)
   float xbest = 0.f;
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (int)(col0 + lc0);                // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(c, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
+    for (int e = 0; e < VS_RUN; ++e) {
       float yy = -INFINITY, k = __builtin_nanf("");
-      bool take = e < left;                                // columns at or past V hold anything: never looked at
-      if constexpr (CUT) take = take && vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]) >= ck;
+      // (the column's values in front of the guard: taken inside it, the update of the maximum below compiles to a branch per
+      // column instead of three selects - and this is the kernel whose VALU work shows)
+      const uint32_t raw = r.raw(e), sk = r.sk(e);
+      const int lc = r.lc(e);
+      bool take = r.in(e);
+      if constexpr (CUT) take = take && sk >= ck;
       if (take) {
-        const float x = __uint_as_float((uint32_t)v[e] << 16);
+        const float x = __uint_as_float(raw << 16);        // (the bits as loaded: -0 keeps its sign in y and in the key)
         yy = __fmul_rn(x, inv_t);
-        k = __fmaf_rn(x, inv_t, -vsmp_log_e_approx(idx0 + (uint32_t)(lc0 + e), seed));
+        k = __fmaf_rn(x, inv_t, -vsmp_log_e_approx(idx0 + (uint32_t)lc, seed));
         mx = fmaxf(mx, yy);
         if (lbest < 0 || k > amax) {                       // (the first column, then strictly better ones)
           amax = k;
-          lbest = lc0 + e;
+          lbest = lc;
           xbest = x;
         }
       }
-      y[half * 8 + e] = yy;
-      ka[half * 8 + e] = k;
+      y[run * VS_RUN + e] = yy;
+      ka[run * VS_RUN + e] = k;
     }
   }
   unsigned long long best = 0ull;          // 0: no entry (a key's upper word is 0 for one NaN pattern only)
@@ -336,15 +389,13 @@ __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict_
   const float thr = amax - (VSMP_BAND + fabsf(amax) * 0x1p-20f);
   uint32_t pending = 0u;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int lc = (e >> 3) * (VS_CHUNK / 2) + tid * 8 + (e & 7);
-    if (ka[e] >= thr && lc != lbest) pending |= 1u << e;
-  }
+  for (int e = 0; e < 16; ++e)
+    if (ka[e] >= thr && vs_slot_column(tid, e) != lbest) pending |= 1u << e;
   while (pending) {
     const int e = __builtin_ctz(pending);
     pending &= pending - 1u;
-    const int lc = (e >> 3) * (VS_CHUNK / 2) + tid * 8 + (e & 7);      // (a column below V: ka is NaN elsewhere)
-    const float x = __uint_as_float((uint32_t)base[lc] << 16);
+    const int lc = vs_slot_column(tid, e);                 // (a column below V: ka is NaN elsewhere)
+    const float x = __uint_as_float((uint32_t)c.base[lc] << 16);
     const unsigned long long k64 = vsmp_key64(__fmaf_rn(x, inv_t, -vsmp_log_e(idx0 + (uint32_t)lc, seed)), col0 + (uint32_t)lc);
     best = k64 > best ? k64 : best;
   }
@@ -378,37 +429,59 @@ __global__ __launch_bounds__(256) void vsmp_chunk_kernel(const bf16* __restrict_
   }
 }
 
+// The draw of a row, written by the one thread that holds the winner win = (sortable key << 32 | ~word) of a word of logit x:
+// logprob is ONE fma against the allowed set's lse.  cut() is the row's cut, asked for only if cut_out wants it and behind the
+// other stores (vsw_draw_kernel's sits in LDS: read ahead of its fp64 logarithm it lengthens the kernel's tail); the second
+// form is for the kernels without a cut.
+template <class C>
+__device__ __forceinline__ void vsmp_write_draw(long long row, unsigned long long win, uint32_t word, float x, float inv_t, float lse,
+                                                long long* __restrict__ words, float* __restrict__ logprob,
+                                                float* __restrict__ key_out, float* __restrict__ cut_out, C&& cut) {
+  words[row] = (long long)word;
+  logprob[row] = __fmaf_rn(x, inv_t, -lse);
+  if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
+  if (cut_out) cut_out[row] = cut();
+}
+__device__ __forceinline__ void vsmp_write_draw(long long row, unsigned long long win, uint32_t word, float x, float inv_t, float lse,
+                                                long long* __restrict__ words, float* __restrict__ logprob,
+                                                float* __restrict__ key_out) {
+  vsmp_write_draw(row, win, word, x, inv_t, lse, words, logprob, key_out, nullptr, [] { return 0.f; });
+}
+
+// a wave per row (four rows per workgroup): the row's winner among its chunks' winners wkey; logprob from the winner's own
+// logit against lse[row] (LSE_GIVEN), or against the log-sum-exp merged from the chunks' (max, sum) in pstat
+template <bool LSE_GIVEN>
+__device__ __forceinline__ void vsmp_merge_row(const bf16* __restrict__ logits, int ld, int n, int V, int nchunks, float inv_t,
+                                               const unsigned long long* __restrict__ wkey, const float* __restrict__ pstat,
+                                               const float* __restrict__ lse, long long* __restrict__ words,
+                                               float* __restrict__ logprob, float* __restrict__ key_out) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;                                    // (wave-uniform; the callers have no barrier)
+  const unsigned long long* wk = wkey + (size_t)row * nchunks;
+  unsigned long long best = 0ull;
+  auto winner = [&](int c) { best = wk[c] > best ? wk[c] : best; };
+  float l;
+  if constexpr (LSE_GIVEN) {
+    for (int c = lane; c < nchunks; c += 64) winner(c);
+    l = lse[row];
+  } else {
+    l = vs_row_lse(pstat + (size_t)row * nchunks * 2, nchunks, lane, winner);
+  }
+  best = wave_max_u64(best);
+  if (lane == 0) {
+    const uint32_t word = min(~(uint32_t)best, (uint32_t)(V - 1));      // (a chunk's winner is a column below V; the clamp guards the read)
+    const float x = __uint_as_float((uint32_t)reinterpret_cast<const unsigned short*>(logits)[(size_t)row * ld + word] << 16);
+    vsmp_write_draw(row, best, word, x, inv_t, l, words, logprob, key_out);
+  }
+}
+
 // a wave per row: the row's winner among its chunks' winners, lse_T from the chunks' (max, sum)
 __global__ __launch_bounds__(256) void vsmp_merge_kernel(const bf16* __restrict__ logits, int ld, int n, int V, int nchunks, float inv_t,
                                                         const unsigned long long* __restrict__ wkey,
                                                         const float* __restrict__ pstat, long long* __restrict__ words,
                                                         float* __restrict__ logprob, float* __restrict__ key_out) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
-  const unsigned long long* wk = wkey + (size_t)row * nchunks;
-  const float* ps = pstat + (size_t)row * nchunks * 2;
-  unsigned long long best = 0ull;
-  float m = -INFINITY;
-  for (int c = lane; c < nchunks; c += 64) {
-    best = wk[c] > best ? wk[c] : best;
-    m = fmaxf(m, ps[2 * c]);
-  }
-  best = wave_max_u64(best);
-  m = wave_max(m);
-  float s = 0.f;
-  for (int c = lane; c < nchunks; c += 64) {
-    const float pm = ps[2 * c];
-    if (pm > -INFINITY) s += ps[2 * c + 1] * expf(pm - m);
-  }
-  s = wave_sum(s);
-  if (lane == 0) {
-    const uint32_t word = min(~(uint32_t)best, (uint32_t)(V - 1));      // (a chunk's winner is a column below V; the clamp guards the read)
-    const float x = __uint_as_float((uint32_t)reinterpret_cast<const unsigned short*>(logits)[(size_t)row * ld + word] << 16);
-    words[row] = (long long)word;
-    logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(s)));
-    if (key_out) key_out[row] = vs_value32((uint32_t)(best >> 32));
-  }
+  vsmp_merge_row<false>(logits, ld, n, V, nchunks, inv_t, wkey, pstat, nullptr, words, logprob, key_out);
 }
 
 // a wave per row over the candidates vs_chunk_kernel left with k = top_k: lane j ends up with the row's j-th entry under
@@ -476,21 +549,15 @@ __global__ __launch_bounds__(256) void vsmp_topk_kernel(const uint32_t* __restri
     }
     k64 = in ? k64 : 0ull;
     const unsigned long long win = wave_max_u64(k64);
-    if (k64 == win && win != 0ull) {
-      words[row] = (long long)word;
-      logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(sa)));
-      if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
-      if (cut_out) cut_out[row] = xc;
-    }
+    if (k64 == win && win != 0ull)
+      vsmp_write_draw(row, win, word, x, inv_t, m + logf(sa), words, logprob, key_out, cut_out, [&] { return xc; });
     return;
   }
+  // (NOT the sum above with top_p = 1: there a term is expf of ONE fma(x, inv_t, -m) and the terms are added in lane order;
+  // here it is expf(fl(x * inv_t) - m) under the butterfly of wave_sum - the two lse differ in their last bits)
   const float s = wave_sum(yy > -INFINITY ? expf(yy - m) : 0.f);
   const unsigned long long win = wave_max_u64(k64);
-  if (k64 == win && win != 0ull) {
-    words[row] = (long long)word;
-    logprob[row] = __fmaf_rn(x, inv_t, -(m + logf(s)));
-    if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
-  }
+  if (k64 == win && win != 0ull) vsmp_write_draw(row, win, word, x, inv_t, m + logf(s), words, logprob, key_out);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -511,14 +578,36 @@ __global__ __launch_bounds__(256) void vsmp_topk_kernel(const uint32_t* __restri
 // A -inf logit has mass 0; x* is the value of a word with a positive mass, so it is finite.  shift = min(40, 63 - bits(V)):
 // the sum of V masses of at most 2^shift (1 + 2^-20) stays below 2^64.
 constexpr int VN_BINS = 256;
-constexpr int VN_COPIES = 8;               // copies of a workgroup's bins in LDS, by lane & 7 (padded by one bin: other banks)
+
+// A workgroup's VN_BINS bins of T in LDS (declare it __shared__), summed into a row's bins in memory.  Integer adds commute,
+// so neither the LDS nor the global atomics make a result depend on their order.  T* mine = zero(tid), a barrier of the
+// caller's (behind whatever else it fetches meanwhile), add(mine, bin, v) per word, flush(): 256 threads, thread tid folds
+// bin tid.  (`mine`, the thread's copy of the bins, is handed out once: an address computed per word costs two instructions.)
+template <class T>
+struct VnHist {
+  static constexpr int VN_COPIES = 8;      // copies of the bins, by tid & 7 (padded by one bin: other banks)
+  T bins[VN_COPIES][VN_BINS + 1];
+  __device__ __forceinline__ T* zero(int tid) {
+#pragma unroll
+    for (int c = 0; c < VN_COPIES; ++c) bins[c][tid] = T(0);
+    return bins[tid & (VN_COPIES - 1)];
+  }
+  static __device__ __forceinline__ void add(T* mine, uint32_t bin, T v) { atomicAdd(&mine[bin], v); }
+  __device__ __forceinline__ void flush(int tid, T* __restrict__ row_bins) {
+    __syncthreads();
+    T s = T(0);
+#pragma unroll
+    for (int c = 0; c < VN_COPIES; ++c) s += bins[c][tid];
+    if (s != T(0)) atomicAdd(row_bins + tid, s);
+  }
+};
 
 struct VnucLayout {
   size_t hist, fine, wkey, rowz, pstat, cand, rowbin, bytes;
   int shift;
 };
 VnucLayout vnuc_layout(int n, int V) {
-  const size_t rows = (size_t)n, blocks = rows * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
+  const size_t rows = (size_t)n, blocks = rows * (size_t)vs_nchunks(V);
   VnucLayout L;
   size_t o = 0;
   L.hist = o;   o += rows * VN_BINS * sizeof(unsigned long long);       // [n, 256] u64, zeroed by the launcher with ...
@@ -561,42 +650,65 @@ __device__ __forceinline__ unsigned long long vnuc_suffix_u64(unsigned long long
   return v;
 }
 
+// The bin scan of a wave over a row's 256 bins, lane l holding b = bins 4 l .. 4 l + 3: the HIGHEST bin at which the value
+// cumulated from the top, behind `carry`, satisfies reached(cumulated, total) - total = the sum of all 256 bins, carry not
+// included.  Empty bins are skipped: one cannot be the first to get there (its cumulated value is that of the next bin above,
+// or the bare carry at the top).  Every lane gets bin (-1: none) and total; `owner` is true in ONE lane, the bin's (lane 0
+// without a bin), and there above / at are the values cumulated above the bin and with it (both 0 without a bin).
+struct VnBinScan {
+  int bin;
+  bool owner;
+  unsigned long long above, at, total;
+};
+template <class P>
+__device__ __forceinline__ VnBinScan vn_bin_scan(const unsigned long long (&b)[4], unsigned long long carry, int lane, P&& reached) {
+  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
+  const unsigned long long inc = vnuc_suffix_u64(s, lane);
+  VnBinScan r;
+  r.total = (unsigned long long)__shfl((long long)inc, 0, 64);
+  r.above = r.at = 0ull;
+  unsigned long long c = carry + (inc - s);
+  int best = -1;
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const unsigned long long ci = c + b[q];
+    const bool hit = reached(ci, r.total);                 // (asked of every bin: behind the other tests its threshold is computed per bin)
+    if (best < 0 && b[q] != 0ull && hit) {
+      best = 4 * lane + q;
+      r.above = c;
+      r.at = ci;
+    }
+    c = ci;
+  }
+  r.bin = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
+  r.owner = r.bin < 0 ? lane == 0 : best == r.bin;         // (a bin belongs to one lane)
+  return r;
+}
+
 __global__ __launch_bounds__(256) void vnuc_coarse_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks, float inv_t,
                                                          float scale, const float* __restrict__ pstat,
                                                          unsigned long long* __restrict__ hist) {
-  __shared__ unsigned long long bins[VN_COPIES][VN_BINS + 1];
+  __shared__ VnHist<unsigned long long> bins;
   const int tid = threadIdx.x, lane = tid & 63;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
-#pragma unroll
-  for (int c = 0; c < VN_COPIES; ++c) bins[c][tid] = 0ull;
-  const float m = vnuc_row_max(pstat, row, nchunks, inv_t, lane);
+  const VsChunk c = vs_chunk_of_block(logits, ld, nchunks);
+  unsigned long long* mine = bins.zero(tid);
+  const float m = vnuc_row_max(pstat, c.row, nchunks, inv_t, lane);
   __syncthreads();
-  unsigned long long* mine = bins[tid & (VN_COPIES - 1)];
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (chunk * VS_CHUNK + lc0);          // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(c, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (e < left) {                                       // columns at or past V hold anything: never looked at
-        const uint32_t b = v[e] == 0x8000u ? 0u : (uint32_t)v[e];
-        const unsigned long long w = vnuc_mass(__uint_as_float(b << 16), inv_t, m, scale);
-        if (w != 0ull) atomicAdd(&mine[vs_sortable16(b) >> 8], w);
+    for (int e = 0; e < VS_RUN; ++e)
+      if (r.in(e)) {
+        const unsigned long long w = vnuc_mass(__uint_as_float(r.bits(e) << 16), inv_t, m, scale);
+        if (w != 0ull) bins.add(mine, r.sk(e) >> 8, w);
       }
-    }
   }
-  __syncthreads();
-  unsigned long long s = 0ull;
-#pragma unroll
-  for (int c = 0; c < VN_COPIES; ++c) s += bins[c][tid];
-  if (s != 0ull) atomicAdd(hist + (size_t)row * VN_BINS + tid, s);
+  bins.flush(tid, hist + (size_t)c.row * VN_BINS);
 }
 
-// a wave per row over its 256 coarse bins (lane l holds bins 4 l .. 4 l + 3): Z, the highest bin at which the mass cumulated
-// from the top reaches top_p * Z, and the mass above that bin.  (No bin - a row outside the contract -: bin -1, nothing below.)
+// a wave per row over its 256 coarse bins: Z, the highest bin at which the mass cumulated from the top reaches top_p * Z, and
+// the mass above that bin.  (No bin - a row outside the contract -: bin -1, nothing below.)
 __global__ __launch_bounds__(256) void vnuc_scan_kernel(const unsigned long long* __restrict__ hist, int n, float top_p,
                                                        unsigned long long* __restrict__ rowz, unsigned long long* __restrict__ rowabove,
                                                        int* __restrict__ rowbin) {
@@ -605,56 +717,34 @@ __global__ __launch_bounds__(256) void vnuc_scan_kernel(const unsigned long long
   if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
   const unsigned long long* h = hist + (size_t)row * VN_BINS + 4 * lane;
   const unsigned long long b[4] = {h[0], h[1], h[2], h[3]};
-  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
-  const unsigned long long inc = vnuc_suffix_u64(s, lane);
-  const unsigned long long Z = (unsigned long long)__shfl((long long)inc, 0, 64);
-  unsigned long long c = inc - s, above = 0ull;
-  int best = -1;
-#pragma unroll
-  for (int q = 3; q >= 0; --q) {
-    const unsigned long long ci = c + b[q];
-    if (best < 0 && Z != 0ull && vnuc_reaches(ci, Z, top_p)) {
-      best = 4 * lane + q;
-      above = c;
-    }
-    c = ci;
-  }
-  const int win = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
-  if (win < 0 ? lane == 0 : best == win) {                 // (a bin belongs to one lane)
-    rowz[row] = Z;
-    rowabove[row] = above;
-    rowbin[row] = win;
+  const VnBinScan r = vn_bin_scan(b, 0ull, lane, [&](unsigned long long c, unsigned long long Z) {
+    return Z != 0ull && vnuc_reaches(c, Z, top_p);
+  });
+  if (r.owner) {
+    rowz[row] = r.total;
+    rowabove[row] = r.above;
+    rowbin[row] = r.bin;
   }
 }
 
 __global__ __launch_bounds__(256) void vnuc_fine_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks,
                                                        const int* __restrict__ rowbin, uint32_t* __restrict__ fine) {
-  __shared__ uint32_t cnt[VN_COPIES][VN_BINS + 1];
+  __shared__ VnHist<uint32_t> cnt;
   const int tid = threadIdx.x;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
-#pragma unroll
-  for (int c = 0; c < VN_COPIES; ++c) cnt[c][tid] = 0u;
-  const uint32_t bin = (uint32_t)rowbin[row];              // (-1: no column matches)
+  const VsChunk c = vs_chunk_of_block(logits, ld, nchunks);
+  uint32_t* mine = cnt.zero(tid);
+  const uint32_t bin = (uint32_t)rowbin[c.row];            // (-1: no column matches)
   __syncthreads();
-  uint32_t* mine = cnt[tid & (VN_COPIES - 1)];
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (chunk * VS_CHUNK + lc0);
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(c, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint32_t sk = vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]);
-      if (e < left && (sk >> 8) == bin) atomicAdd(&mine[sk & 0xFFu], 1u);
+    for (int e = 0; e < VS_RUN; ++e) {
+      const uint32_t sk = r.sk(e);
+      if (r.in(e) && (sk >> 8) == bin) cnt.add(mine, sk & 0xFFu, 1u);
     }
   }
-  __syncthreads();
-  uint32_t s = 0u;
-#pragma unroll
-  for (int c = 0; c < VN_COPIES; ++c) s += cnt[c][tid];
-  if (s != 0u) atomicAdd(fine + (size_t)row * VN_BINS + tid, s);
+  cnt.flush(tid, fine + (size_t)c.row * VN_BINS);
 }
 
 // a wave per row over the 256 values of the cut's coarse bin (lane l holds the low bytes 4 l .. 4 l + 3): count * mass(value),
@@ -678,23 +768,12 @@ __global__ __launch_bounds__(256) void vnuc_cut_kernel(const uint32_t* __restric
       if (c != 0u) b[q] = (unsigned long long)c * vnuc_mass(vs_value16((uint32_t)bin << 8 | (uint32_t)(4 * lane + q)), inv_t, m, scale);
     }
   }
-  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
-  unsigned long long c = above0 + (vnuc_suffix_u64(s, lane) - s), at = 0ull;
-  int best = -1;
-#pragma unroll
-  for (int q = 3; q >= 0; --q) {
-    const unsigned long long ci = c + b[q];
-    if (best < 0 && b[q] != 0ull && vnuc_reaches(ci, Z, top_p)) {
-      best = 4 * lane + q;
-      at = ci;
-    }
-    c = ci;
-  }
-  const int win = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
-  if (win < 0 ? lane == 0 : best == win) {
+  const VnBinScan r = vn_bin_scan(b, above0, lane, [&](unsigned long long c, unsigned long long) { return vnuc_reaches(c, Z, top_p); });
+  if (r.owner) {
     // (no value - a row outside the contract -: no cut, every word allowed)
+    const int win = r.bin;
     const uint32_t sk = win < 0 ? 0u : ((uint32_t)bin << 8 | (uint32_t)win);
-    const unsigned long long mass = win < 0 ? Z : at;
+    const unsigned long long mass = win < 0 ? Z : r.at;
     cutkey[row] = sk;
     lse[row] = (float)((double)m + (log((double)mass) - (double)shift * 0.693147180559945309417));
     if (cut_out) cut_out[row] = win < 0 ? -INFINITY : vs_value16(sk);
@@ -706,28 +785,15 @@ __global__ __launch_bounds__(256) void vnuc_merge_kernel(const bf16* __restrict_
                                                         const unsigned long long* __restrict__ wkey, const float* __restrict__ lse,
                                                         long long* __restrict__ words, float* __restrict__ logprob,
                                                         float* __restrict__ key_out) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
-  const unsigned long long* wk = wkey + (size_t)row * nchunks;
-  unsigned long long best = 0ull;
-  for (int c = lane; c < nchunks; c += 64) best = wk[c] > best ? wk[c] : best;
-  best = wave_max_u64(best);
-  if (lane == 0) {
-    const uint32_t word = min(~(uint32_t)best, (uint32_t)(V - 1));      // (a chunk's winner is a column below V; the clamp guards the read)
-    const float x = __uint_as_float((uint32_t)reinterpret_cast<const unsigned short*>(logits)[(size_t)row * ld + word] << 16);
-    words[row] = (long long)word;
-    logprob[row] = __fmaf_rn(x, inv_t, -lse[row]);
-    if (key_out) key_out[row] = vs_value32((uint32_t)(best >> 32));
-  }
+  vsmp_merge_row<true>(logits, ld, n, V, nchunks, inv_t, wkey, nullptr, lse, words, logprob, key_out);
 }
 
-int vsmp_plan(int n, int V, int ld, int top_k) {
-  if (n <= 0 || V <= 0 || top_k < 0 || ld < V || (ld % 8) != 0 || top_k > V) return M3P_EINVAL;
-  if (top_k > VS_MAX_K) return M3P_ENOTIMPL;
+// the plan of every seeded draw: min_k <= top_k <= V, launchers up to max_k candidates
+int vsmp_plan(int n, int V, int ld, int top_k, int min_k, int max_k) {
+  if (n <= 0 || V <= 0 || top_k < min_k || ld < V || (ld % 8) != 0 || top_k > V) return M3P_EINVAL;
+  if (top_k > max_k) return M3P_ENOTIMPL;
   if ((long long)n * V >= (1ll << 32)) return M3P_ENOTIMPL;                          // the hash counter r * V + w is 32 bits
-  const long long nchunks = ((long long)V + VS_CHUNK - 1) / VS_CHUNK;
-  if ((long long)n * nchunks * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block and candidate indices
+  if ((long long)n * vs_nchunks(V) * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block and candidate indices
   return M3P_OK;
 }
 
@@ -759,7 +825,7 @@ struct VswLayout {
   size_t ent, hist, fine, chunkcnt, rowbin, rowlow, above0, above1, bytes;
 };
 VswLayout vsw_layout(int n, int V, int top_k) {
-  const size_t rows = (size_t)n, blocks = rows * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
+  const size_t rows = (size_t)n, blocks = rows * (size_t)vs_nchunks(V);
   VswLayout L;
   size_t o = 0;
   L.ent = o;      o += rows * (size_t)top_k * sizeof(unsigned long long);
@@ -808,35 +874,25 @@ __device__ __forceinline__ unsigned long long vsw_block_excl(unsigned long long 
 
 __global__ __launch_bounds__(256) void vsw_coarse_kernel(const bf16* __restrict__ logits, int ld, int V, int nchunks,
                                                         uint32_t* __restrict__ hist) {
-  __shared__ uint32_t cnt[VN_COPIES][VN_BINS + 1];
+  __shared__ VnHist<uint32_t> cnt;
   const int tid = threadIdx.x;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
-#pragma unroll
-  for (int c = 0; c < VN_COPIES; ++c) cnt[c][tid] = 0u;
+  const VsChunk c = vs_chunk_of_block(logits, ld, nchunks);
+  uint32_t* mine = cnt.zero(tid);
   __syncthreads();
-  uint32_t* mine = cnt[tid & (VN_COPIES - 1)];
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (chunk * VS_CHUNK + lc0);          // valid columns from lc0 on (ld % 8 == 0: a load that starts below V ends inside the row)
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(c, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint32_t sk = vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]);
-      if (e < left) atomicAdd(&mine[sk >> 8], 1u);          // columns at or past V hold anything: never counted
+    for (int e = 0; e < VS_RUN; ++e) {
+      const uint32_t sk = r.sk(e);
+      if (r.in(e)) cnt.add(mine, sk >> 8, 1u);
     }
   }
-  __syncthreads();
-  uint32_t s = 0u;
-#pragma unroll
-  for (int c = 0; c < VN_COPIES; ++c) s += cnt[c][tid];
-  if (s != 0u) atomicAdd(hist + (size_t)row * VN_BINS + tid, s);
+  cnt.flush(tid, hist + (size_t)c.row * VN_BINS);
 }
 
-// a wave per row over 256 counts (lane l holds bins 4 l .. 4 l + 3): the highest bin at which the count cumulated from the
-// top, behind above_in[row] (NULL: 0), reaches top_k, and the count above that bin.  (No bin: -1 and 0.)
+// a wave per row over 256 counts: the highest bin at which the count cumulated from the top, behind above_in[row] (NULL: 0),
+// reaches top_k, and the count above that bin.  (No bin: -1 and 0.)
 __global__ __launch_bounds__(256) void vsw_scan_kernel(const uint32_t* __restrict__ cnt, int n, uint32_t top_k,
                                                       const uint32_t* __restrict__ above_in, int* __restrict__ bin_out,
                                                       uint32_t* __restrict__ above_out) {
@@ -845,22 +901,11 @@ __global__ __launch_bounds__(256) void vsw_scan_kernel(const uint32_t* __restric
   if (row >= n) return;                                    // (wave-uniform; the kernel has no barrier)
   const uint32_t* h = cnt + (size_t)row * VN_BINS + 4 * lane;
   const unsigned long long b[4] = {h[0], h[1], h[2], h[3]};
-  const unsigned long long s = (b[0] + b[1]) + (b[2] + b[3]);
-  unsigned long long c = (above_in ? (unsigned long long)above_in[row] : 0ull) + (vnuc_suffix_u64(s, lane) - s), above = 0ull;
-  int best = -1;
-#pragma unroll
-  for (int q = 3; q >= 0; --q) {
-    const unsigned long long ci = c + b[q];
-    if (best < 0 && b[q] != 0ull && ci >= (unsigned long long)top_k) {
-      best = 4 * lane + q;
-      above = c;
-    }
-    c = ci;
-  }
-  const int win = (int)wave_max_u32((uint32_t)(best + 1)) - 1;
-  if (win < 0 ? lane == 0 : best == win) {                 // (a bin belongs to one lane)
-    bin_out[row] = win;
-    above_out[row] = win < 0 ? 0u : (uint32_t)above;
+  const VnBinScan r = vn_bin_scan(b, above_in ? (unsigned long long)above_in[row] : 0ull, lane,
+                                  [&](unsigned long long c, unsigned long long) { return c >= (unsigned long long)top_k; });
+  if (r.owner) {
+    bin_out[row] = r.bin;
+    above_out[row] = (uint32_t)r.above;
   }
 }
 
@@ -869,20 +914,16 @@ __global__ __launch_bounds__(256) void vsw_tie_kernel(const bf16* __restrict__ l
                                                      uint32_t* __restrict__ chunkcnt) {
   __shared__ uint32_t red[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
-  const uint32_t kth = vsw_kth(rowbin, rowlow, row);
+  const VsChunk ch = vs_chunk_of_block(logits, ld, nchunks);
+  const uint32_t kth = vsw_kth(rowbin, rowlow, ch.row);
   uint32_t c = 0u;                                          // words above << 16 | words equal (a chunk holds 4096: 13 bits each)
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (chunk * VS_CHUNK + lc0);
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(ch, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint32_t sk = vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]);
-      if (e < left) c += sk > kth ? 0x10000u : (sk == kth ? 1u : 0u);
+    for (int e = 0; e < VS_RUN; ++e) {
+      const uint32_t sk = r.sk(e);                          // (in front of the guard: the guarded add then compiles to selects)
+      if (r.in(e)) c += sk > kth ? 0x10000u : (sk == kth ? 1u : 0u);
     }
   }
   c = wave_sum_u32(c);
@@ -901,8 +942,8 @@ __global__ __launch_bounds__(256) void vsw_compact_kernel(const bf16* __restrict
                                                          unsigned long long* __restrict__ ent) {
   __shared__ unsigned long long sh[2][4];
   const int tid = threadIdx.x;
-  const int row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
-  const unsigned short* base = reinterpret_cast<const unsigned short*>(logits) + (size_t)row * ld + (size_t)chunk * VS_CHUNK;
+  const VsChunk ch = vs_chunk_of_block(logits, ld, nchunks);
+  const int row = ch.row, chunk = ch.chunk;
   const uint32_t kth = vsw_kth(rowbin, rowlow, row);
   const uint32_t above = min(rowabove[row], (uint32_t)top_k), quota = (uint32_t)top_k - above;
   // the chunks in front of this one: their words above v_k (slots 0 .. above - 1) and their members of the class at v_k
@@ -915,16 +956,13 @@ __global__ __launch_bounds__(256) void vsw_compact_kernel(const bf16* __restrict
   uint32_t sk[16];
   unsigned long long mine = 0ull;                           // words above << 40 | class members of half 1 << 20 | of half 0
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int lc0 = half * (VS_CHUNK / 2) + tid * 8;
-    const int left = V - (chunk * VS_CHUNK + lc0);
-    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (left > 0) v = *reinterpret_cast<const u16x8*>(base + lc0);
+  for (int run = 0; run < VS_RUNS; ++run) {
+    const VsRun r = vs_chunk_run(ch, V, tid, run);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint32_t s = e < left ? vs_sortable16(v[e] == 0x8000u ? 0u : (uint32_t)v[e]) : 0xFFFFFFFFu;    // (no column)
-      sk[half * 8 + e] = s;
-      if (s != 0xFFFFFFFFu) mine += s > kth ? 1ull << 40 : (s == kth ? 1ull << (20 * half) : 0ull);
+    for (int e = 0; e < VS_RUN; ++e) {
+      const uint32_t s = r.in(e) ? r.sk(e) : 0xFFFFFFFFu;   // (no column)
+      sk[run * VS_RUN + e] = s;
+      if (s != 0xFFFFFFFFu) mine += s > kth ? 1ull << 40 : (s == kth ? 1ull << (20 * run) : 0ull);
     }
   }
   const unsigned long long excl = vsw_block_excl(mine, tid, sh[1], total);
@@ -936,7 +974,7 @@ __global__ __launch_bounds__(256) void vsw_compact_kernel(const bf16* __restrict
   for (int e = 0; e < 16; ++e) {
     const uint32_t s = sk[e];
     if (s == 0xFFFFFFFFu) continue;
-    const uint32_t word = (uint32_t)chunk * VS_CHUNK + (uint32_t)((e >> 3) * (VS_CHUNK / 2) + tid * 8 + (e & 7));
+    const uint32_t word = (uint32_t)chunk * VS_CHUNK + (uint32_t)vs_slot_column(tid, e);
     uint32_t slot = 0xFFFFFFFFu;
     if (s > kth) slot = pa++;
     else if (s == kth) {
@@ -1032,19 +1070,39 @@ __global__ __launch_bounds__(256) void vsw_draw_kernel(const unsigned long long*
   for (int q = 0; q < 4; ++q) win = redk[q] > win ? redk[q] : win;
   if (best == win && win != 0ull) {                         // the word is part of the key: one thread
     const float lse = (float)((double)m + (log((double)s_mass) - (double)VSW_SHIFT * 0.693147180559945309417));
-    words[row] = (long long)(~(uint32_t)win);
-    logprob[row] = __fmaf_rn(xbest, inv_t, -lse);
-    if (key_out) key_out[row] = vs_value32((uint32_t)(win >> 32));
-    if (cut_out) cut_out[row] = top_p < 1.f ? vs_value16(s_cut) : -INFINITY;
+    vsmp_write_draw(row, win, ~(uint32_t)win, xbest, inv_t, lse, words, logprob, key_out, cut_out,
+                    [&] { return top_p < 1.f ? vs_value16(s_cut) : -INFINITY; });
   }
 }
 
-int vsw_plan(int n, int V, int ld, int top_k) {
-  if (n <= 0 || V <= 0 || top_k < 1 || ld < V || (ld % 8) != 0 || top_k > V) return M3P_EINVAL;
-  if (top_k > VSW_MAX_K) return M3P_ENOTIMPL;
-  if ((long long)n * V >= (1ll << 32)) return M3P_ENOTIMPL;                          // the hash counter r * V + w is 32 bits
-  const long long nchunks = ((long long)V + VS_CHUNK - 1) / VS_CHUNK;
-  if ((long long)n * nchunks * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block indices (the bound of vsmp_plan)
+// ------------------------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------------------------
+// What every launcher asks of its arguments behind its plan: logits, a workspace of `need` bytes and the required outputs
+// `outs`, the 16-byte alignment of the vector loads, a finite inv_t > 0 and top_p > 0 (1: a launcher without one).
+bool vs_args_ok(const void* logits, const void* workspace, size_t workspace_bytes, size_t need, std::initializer_list<const void*> outs,
+                float inv_t = 1.f, float top_p = 1.f) {
+  if (!(inv_t > 0.f) || isinf(inv_t) || !(top_p > 0.f)) return false;
+  if (!logits || !workspace || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return false;
+  for (const void* p : outs)
+    if (!p) return false;
+  return workspace_bytes >= need;
+}
+
+// 1 <= top_k <= VS_MAX_K: the chunks' first top_k entries, then a wave per row draws among the row's first top_k (CUT: behind
+// the nucleus cut at top_p).  The workspace is m3p_vocab_select's: the chunks' unscaled (max, sum) - written, not read - and cand.
+template <bool CUT>
+int vsmp_launch_topk(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed, void* workspace,
+                     long long* words, float* logprob, float* key, float* cut, hipStream_t st) {
+  const int nchunks = vs_nchunks(V);
+  float* pstat = (float*)workspace;
+  uint32_t* cand = (uint32_t*)(pstat + (size_t)n * nchunks * 2);
+  hipLaunchKernelGGL(vs_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, top_k,
+                     pstat, cand);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsmp_topk_kernel<CUT>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const uint32_t*)cand, n, V, nchunks,
+                     top_k, inv_t, seed, words, logprob, key, top_p, cut);
+  M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
 
@@ -1058,17 +1116,15 @@ int m3p_vocab_select_plan(int n, int V, int ld, int beam, int k) { return vs_pla
 
 size_t m3p_vocab_select_workspace_bytes(int n, int V, int k) {
   if (n <= 0 || V <= 0 || k <= 0) return 0;
-  const size_t blocks = (size_t)n * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
-  return blocks * (2 * sizeof(float) + (size_t)k * sizeof(uint32_t));
+  return (size_t)n * (size_t)vs_nchunks(V) * (2 * sizeof(float) + (size_t)k * sizeof(uint32_t));
 }
 
 int m3p_vocab_select(const void* logits, int ld, int n, int V, const float* beam_scores, int beam, int k, void* workspace,
                      size_t workspace_bytes, float* scores, long long* flat_idx, float* lse, void* stream) {
   const int rc = vs_plan(n, V, ld, beam, k);
   if (rc != M3P_OK) return rc;
-  if (!logits || !workspace || !scores || !flat_idx || !lse || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
-  if (workspace_bytes < m3p_vocab_select_workspace_bytes(n, V, k)) return M3P_EINVAL;
-  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
+  if (!vs_args_ok(logits, workspace, workspace_bytes, m3p_vocab_select_workspace_bytes(n, V, k), {scores, flat_idx, lse})) return M3P_EINVAL;
+  const int nchunks = vs_nchunks(V);
   float* pstat = (float*)workspace;
   uint32_t* cand = (uint32_t*)(pstat + (size_t)n * nchunks * 2);
   hipLaunchKernelGGL(vs_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, V,
@@ -1080,47 +1136,34 @@ int m3p_vocab_select(const void* logits, int ld, int n, int V, const float* beam
   return M3P_OK;
 }
 
-int m3p_vocab_sample_plan(int n, int V, int ld, int top_k) { return vsmp_plan(n, V, ld, top_k); }
+int m3p_vocab_sample_plan(int n, int V, int ld, int top_k) { return vsmp_plan(n, V, ld, top_k, 0, VS_MAX_K); }
 
 size_t m3p_vocab_sample_workspace_bytes(int n, int V, int top_k) {
   if (n <= 0 || V <= 0 || top_k < 0) return 0;
   if (top_k > 0) return m3p_vocab_select_workspace_bytes(n, V, top_k);
-  const size_t blocks = (size_t)n * (((size_t)V + VS_CHUNK - 1) / VS_CHUNK);
-  return blocks * (sizeof(unsigned long long) + 2 * sizeof(float));
+  return (size_t)n * (size_t)vs_nchunks(V) * (sizeof(unsigned long long) + 2 * sizeof(float));
 }
 
 int m3p_vocab_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, uint32_t seed, void* workspace,
                      size_t workspace_bytes, long long* words, float* logprob, float* key, void* stream) {
-  const int rc = vsmp_plan(n, V, ld, top_k);
+  const int rc = m3p_vocab_sample_plan(n, V, ld, top_k);
   if (rc != M3P_OK) return rc;
-  if (!(inv_t > 0.f) || isinf(inv_t)) return M3P_EINVAL;
-  if (!logits || !workspace || !words || !logprob || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
-  if (workspace_bytes < m3p_vocab_sample_workspace_bytes(n, V, top_k)) return M3P_EINVAL;
-  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
-  const unsigned rows4 = (unsigned)((n + 3) / 4);
-  if (top_k == 0) {
-    unsigned long long* wkey = (unsigned long long*)workspace;
-    float* pstat = (float*)(wkey + (size_t)n * nchunks);
-    hipLaunchKernelGGL(vsmp_chunk_kernel<false>, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16*)logits, ld, V, nchunks, inv_t, seed, wkey, pstat, (const uint32_t*)nullptr);
-    M3P_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vsmp_merge_kernel, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, n, V, nchunks,
-                       inv_t, (const unsigned long long*)wkey, (const float*)pstat, words, logprob, key);
-    M3P_CHECK_LAUNCH();
-    return M3P_OK;
-  }
-  float* pstat = (float*)workspace;                       // (the chunks' unscaled (max, sum): written, not read here)
-  uint32_t* cand = (uint32_t*)(pstat + (size_t)n * nchunks * 2);
-  hipLaunchKernelGGL(vs_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, (hipStream_t)stream, (const bf16*)logits, ld, V,
-                     nchunks, top_k, pstat, cand);
+  if (!vs_args_ok(logits, workspace, workspace_bytes, m3p_vocab_sample_workspace_bytes(n, V, top_k), {words, logprob}, inv_t)) return M3P_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (top_k > 0) return vsmp_launch_topk<false>(logits, ld, n, V, inv_t, top_k, 1.f, seed, workspace, words, logprob, key, nullptr, st);
+  const int nchunks = vs_nchunks(V);
+  unsigned long long* wkey = (unsigned long long*)workspace;
+  float* pstat = (float*)(wkey + (size_t)n * nchunks);
+  hipLaunchKernelGGL(vsmp_chunk_kernel<false>, dim3((unsigned)(n * nchunks)), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks,
+                     inv_t, seed, wkey, pstat, (const uint32_t*)nullptr);
   M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsmp_topk_kernel<false>, dim3(rows4), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)cand, n, V, nchunks,
-                     top_k, inv_t, seed, words, logprob, key, 1.f, (float*)nullptr);
+  hipLaunchKernelGGL(vsmp_merge_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const bf16*)logits, ld, n, V, nchunks, inv_t,
+                     (const unsigned long long*)wkey, (const float*)pstat, words, logprob, key);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
 
-int m3p_vocab_nucleus_plan(int n, int V, int ld, int top_k) { return vsmp_plan(n, V, ld, top_k); }
+int m3p_vocab_nucleus_plan(int n, int V, int ld, int top_k) { return m3p_vocab_sample_plan(n, V, ld, top_k); }
 
 size_t m3p_vocab_nucleus_workspace_bytes(int n, int V, int top_k) {
   if (n <= 0 || V <= 0 || top_k < 0) return 0;
@@ -1133,28 +1176,17 @@ size_t m3p_vocab_nucleus_workspace_bytes(int n, int V, int top_k) {
 int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed,
                              void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key, float* cut,
                              void* stream) {
-  const int rc = vsmp_plan(n, V, ld, top_k);
+  const int rc = m3p_vocab_nucleus_plan(n, V, ld, top_k);
   if (rc != M3P_OK) return rc;
-  if (!(inv_t > 0.f) || isinf(inv_t) || !(top_p > 0.f)) return M3P_EINVAL;
-  if (!logits || !workspace || !words || !logprob || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
-  if (workspace_bytes < m3p_vocab_nucleus_workspace_bytes(n, V, top_k)) return M3P_EINVAL;
+  if (!vs_args_ok(logits, workspace, workspace_bytes, m3p_vocab_nucleus_workspace_bytes(n, V, top_k), {words, logprob}, inv_t, top_p)) return M3P_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (top_p >= 1.f) {                                      // no cut: today's draw, bit for bit; cut = -inf
     if (cut && hipMemsetD32Async((hipDeviceptr_t)cut, (int)0xFF800000u, (size_t)n, st) != hipSuccess) return M3P_EINVAL;
     return m3p_vocab_sample(logits, ld, n, V, inv_t, top_k, seed, workspace, workspace_bytes, words, logprob, key, stream);
   }
-  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
+  if (top_k > 0) return vsmp_launch_topk<true>(logits, ld, n, V, inv_t, top_k, top_p, seed, workspace, words, logprob, key, cut, st);
+  const int nchunks = vs_nchunks(V);
   const unsigned rows4 = (unsigned)((n + 3) / 4), blocks = (unsigned)(n * nchunks);
-  if (top_k > 0) {
-    float* pstat = (float*)workspace;                     // (the chunks' unscaled (max, sum): written, not read here)
-    uint32_t* cand = (uint32_t*)(pstat + (size_t)n * nchunks * 2);
-    hipLaunchKernelGGL(vs_chunk_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, top_k, pstat, cand);
-    M3P_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vsmp_topk_kernel<true>, dim3(rows4), dim3(256), 0, st, (const uint32_t*)cand, n, V, nchunks, top_k, inv_t,
-                       seed, words, logprob, key, top_p, cut);
-    M3P_CHECK_LAUNCH();
-    return M3P_OK;
-  }
   const VnucLayout L = vnuc_layout(n, V);
   char* ws = (char*)workspace;
   unsigned long long* hist = (unsigned long long*)(ws + L.hist);
@@ -1193,7 +1225,7 @@ int m3p_vocab_nucleus_sample(const void* logits, int ld, int n, int V, float inv
 
 int m3p_vocab_sample_wide_max_k(void) { return VSW_MAX_K; }
 
-int m3p_vocab_sample_wide_plan(int n, int V, int ld, int top_k) { return vsw_plan(n, V, ld, top_k); }
+int m3p_vocab_sample_wide_plan(int n, int V, int ld, int top_k) { return vsmp_plan(n, V, ld, top_k, 1, VSW_MAX_K); }
 
 size_t m3p_vocab_sample_wide_workspace_bytes(int n, int V, int top_k) {
   if (n <= 0 || V <= 0 || top_k < 1) return 0;
@@ -1203,13 +1235,11 @@ size_t m3p_vocab_sample_wide_workspace_bytes(int n, int V, int top_k) {
 int m3p_vocab_sample_wide(const void* logits, int ld, int n, int V, float inv_t, int top_k, float top_p, uint32_t seed,
                           void* workspace, size_t workspace_bytes, long long* words, float* logprob, float* key, float* cut,
                           void* stream) {
-  const int rc = vsw_plan(n, V, ld, top_k);
+  const int rc = m3p_vocab_sample_wide_plan(n, V, ld, top_k);
   if (rc != M3P_OK) return rc;
-  if (!(inv_t > 0.f) || isinf(inv_t) || !(top_p > 0.f)) return M3P_EINVAL;
-  if (!logits || !workspace || !words || !logprob || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return M3P_EINVAL;
-  if (workspace_bytes < m3p_vocab_sample_wide_workspace_bytes(n, V, top_k)) return M3P_EINVAL;
+  if (!vs_args_ok(logits, workspace, workspace_bytes, m3p_vocab_sample_wide_workspace_bytes(n, V, top_k), {words, logprob}, inv_t, top_p)) return M3P_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int nchunks = (V + VS_CHUNK - 1) / VS_CHUNK;
+  const int nchunks = vs_nchunks(V);
   const unsigned rows4 = (unsigned)((n + 3) / 4), blocks = (unsigned)(n * nchunks);
   const VswLayout L = vsw_layout(n, V, top_k);
   char* ws = (char*)workspace;

@@ -441,13 +441,16 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
         temperature = 1.0 if sample_temperature is None else float(sample_temperature)
         inv_t = rng.inv_temperature(temperature)
         top_k = min(top_k, model.n_words)
-        takes = ops.vocab_sample_takes if top_p is None else ops.vocab_nucleus_takes
-        sample_dev = (dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
-                      and takes(bs, model.n_words, model.arena().V_pad, top_k))
-        # (more than 16 candidates: the count-selection route, asked once where the plan above declined)
-        sample_wide = (not sample_dev and top_k >= 1 and dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
-                       and ops.vocab_sample_wide_takes(bs, model.n_words, model.arena().V_pad, top_k))
-        sample_dev = sample_dev or sample_wide
+        # the device route, picked once: (launcher, its plan, the op, the op's arguments behind the seed).  Up to 16 candidates or
+        # every word go by rounds of a maximum, with or without the nucleus cut; more than 16, where that plan declined, by the
+        # count selection.  Each plan is asked once.
+        routes = [('m3p_vocab_sample', ops.vocab_sample_takes, ops.vocab_sample, (top_k,)) if top_p is None else
+                  ('m3p_vocab_nucleus_sample', ops.vocab_nucleus_takes, ops.vocab_nucleus_sample, (top_p, top_k))]
+        if top_k >= 1:
+            routes.append(('m3p_vocab_sample_wide', ops.vocab_sample_wide_takes, ops.vocab_sample_wide, (top_k, top_p)))
+        on_dev = dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
+        draw = next((r for r in routes if on_dev and r[1](bs, model.n_words, model.arena().V_pad, top_k)), None)
+        sample_dev = draw is not None
         logprobs = torch.zeros((max_len, bs), dtype=torch.float32, device=dev) if return_logprobs else None
     # (the constraint kernel sits in front of a device selection only; its plan is asked once, like the others)
     cons_dev = (cons.on and (sample_dev if seeded else select)
@@ -460,15 +463,9 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
             step_seed = rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)
             if sample_dev:
                 logits, V = _constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len)
-                if sample_wide:
-                    res = ops.vocab_sample_wide(logits, V, temperature, step_seed, top_k, top_p)
-                elif top_p is None:
-                    res = ops.vocab_sample(logits, V, temperature, step_seed, top_k)
-                else:
-                    res = ops.vocab_nucleus_sample(logits, V, temperature, step_seed, top_p, top_k)
+                res = draw[2](logits, V, temperature, step_seed, *draw[3])
                 if res is None:
-                    name = 'm3p_vocab_sample_wide' if sample_wide else 'm3p_vocab_sample' if top_p is None else 'm3p_vocab_nucleus_sample'
-                    raise L.M3PError('%s declined (M3P_ENOTIMPL) a shape its plan took' % name)
+                    raise L.M3PError('%s declined (M3P_ENOTIMPL) a shape its plan took' % draw[0])
                 next_words, step_logprob = res[0], res[1]
             else:
                 next_words, step_logprob = _sample_twin(_constrained_scores(model, tensor[-1], cons, generated, cur_len), inv_t,

@@ -415,13 +415,18 @@ def vocab_select_max_k():
     return int(L.load().m3p_vocab_select_max_k())
 
 
-def vocab_select_takes(n, V, ld, beam, k):
-    """Does the launcher of vocab_select take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
-    rc = L.load().m3p_vocab_select_plan(n, V, ld, beam, k)
+def _plan_takes(plan, *shape):
+    """A launcher's plan as a yes or no: False where it would answer M3P_ENOTIMPL; a malformed shape raises."""
+    rc = getattr(L.load(), plan)(*shape)
     if rc == _ENOTIMPL:
         return False
-    L.check(rc, 'm3p_vocab_select_plan')
+    L.check(rc, plan)
     return True
+
+
+def vocab_select_takes(n, V, ld, beam, k):
+    """Does the launcher of vocab_select take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
+    return _plan_takes('m3p_vocab_select_plan', n, V, ld, beam, k)
 
 
 def vocab_select(logits, V, beam_scores, beam, k):
@@ -454,13 +459,33 @@ def vocab_select(logits, V, beam_scores, beam, k):
     return scores, flat_idx, lse
 
 
+def _vocab_draw(stem, call, logits, V, temperature, seed, top_k, top_p=None):
+    """The seeded draws' common course - plan (stem + '_plan'), workspace (stem + '_workspace_bytes'), outputs, call, check:
+    -> (words int64 [n], logprob fp32 [n], key fp32 [n]) and, with top_p (a launcher that cuts), cut fp32 [n]; None when the
+    plan answers M3P_ENOTIMPL."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
+    n = logits.shape[0]
+    lib = L.load()
+    rc = getattr(lib, stem + '_plan')(n, V, logits.stride(0), top_k)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, stem + '_plan')
+    dev = logits.device
+    ws_bytes = getattr(lib, stem + '_workspace_bytes')(n, V, top_k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    outs = [torch.empty((n,), dtype=torch.int64, device=dev)]
+    outs += [torch.empty((n,), dtype=torch.float32, device=dev) for _ in range(2 if top_p is None else 3)]
+    cut_args = () if top_p is None else (top_p,)
+    rc = getattr(lib, call)(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k, *cut_args,
+                            int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, *[o.data_ptr() for o in outs], L.stream())
+    L.check(rc, call)
+    return tuple(outs)
+
+
 def vocab_sample_takes(n, V, ld, top_k):
     """Does the launcher of vocab_sample take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
-    rc = L.load().m3p_vocab_sample_plan(n, V, ld, top_k)
-    if rc == _ENOTIMPL:
-        return False
-    L.check(rc, 'm3p_vocab_sample_plan')
-    return True
+    return _plan_takes('m3p_vocab_sample_plan', n, V, ld, top_k)
 
 
 def vocab_sample(logits, V, temperature, seed, top_k=0):
@@ -470,34 +495,12 @@ def vocab_sample(logits, V, temperature, seed, top_k=0):
     inv_t = rng.inv_temperature(temperature); top_k = 0 allows every word, 1 .. 16 the row's top_k under (logit descending, word
     ascending); logprob = x_w * inv_t - log-sum-exp over the allowed set; key = the winning key.  None when the launcher does
     not take the shape (M3P_ENOTIMPL: top_k > 16, n * V >= 2^32)."""
-    _chk_bf16(logits)
-    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
-    n = logits.shape[0]
-    lib = L.load()
-    rc = lib.m3p_vocab_sample_plan(n, V, logits.stride(0), top_k)
-    if rc == _ENOTIMPL:
-        return None
-    L.check(rc, 'm3p_vocab_sample_plan')
-    dev = logits.device
-    ws_bytes = lib.m3p_vocab_sample_workspace_bytes(n, V, top_k)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    words = torch.empty((n,), dtype=torch.int64, device=dev)
-    logprob = torch.empty((n,), dtype=torch.float32, device=dev)
-    key = torch.empty((n,), dtype=torch.float32, device=dev)
-    rc = lib.m3p_vocab_sample(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k,
-                              int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, words.data_ptr(), logprob.data_ptr(), key.data_ptr(),
-                              L.stream())
-    L.check(rc, 'm3p_vocab_sample')
-    return words, logprob, key
+    return _vocab_draw('m3p_vocab_sample', 'm3p_vocab_sample', logits, V, temperature, seed, top_k)
 
 
 def vocab_nucleus_takes(n, V, ld, top_k):
     """Does the launcher of vocab_nucleus_sample take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
-    rc = L.load().m3p_vocab_nucleus_plan(n, V, ld, top_k)
-    if rc == _ENOTIMPL:
-        return False
-    L.check(rc, 'm3p_vocab_nucleus_plan')
-    return True
+    return _plan_takes('m3p_vocab_nucleus_plan', n, V, ld, top_k)
 
 
 def vocab_nucleus_sample(logits, V, temperature, seed, top_p, top_k=0):
@@ -511,26 +514,7 @@ def vocab_nucleus_sample(logits, V, temperature, seed, top_p, top_k=0):
     top_p = rng.nucleus_top_p(top_p)
     if top_p is None:
         top_p = 1.0                                # (the launcher's "off": it runs m3p_vocab_sample and fills cut with -inf)
-    _chk_bf16(logits)
-    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
-    n = logits.shape[0]
-    lib = L.load()
-    rc = lib.m3p_vocab_nucleus_plan(n, V, logits.stride(0), top_k)
-    if rc == _ENOTIMPL:
-        return None
-    L.check(rc, 'm3p_vocab_nucleus_plan')
-    dev = logits.device
-    ws_bytes = lib.m3p_vocab_nucleus_workspace_bytes(n, V, top_k)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    words = torch.empty((n,), dtype=torch.int64, device=dev)
-    logprob = torch.empty((n,), dtype=torch.float32, device=dev)
-    key = torch.empty((n,), dtype=torch.float32, device=dev)
-    cut = torch.empty((n,), dtype=torch.float32, device=dev)
-    rc = lib.m3p_vocab_nucleus_sample(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k, top_p,
-                                      int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, words.data_ptr(), logprob.data_ptr(),
-                                      key.data_ptr(), cut.data_ptr(), L.stream())
-    L.check(rc, 'm3p_vocab_nucleus_sample')
-    return words, logprob, key, cut
+    return _vocab_draw('m3p_vocab_nucleus', 'm3p_vocab_nucleus_sample', logits, V, temperature, seed, top_k, top_p)
 
 
 def vocab_sample_wide_max_k():
@@ -540,11 +524,7 @@ def vocab_sample_wide_max_k():
 
 def vocab_sample_wide_takes(n, V, ld, top_k):
     """Does the launcher of vocab_sample_wide take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
-    rc = L.load().m3p_vocab_sample_wide_plan(n, V, ld, top_k)
-    if rc == _ENOTIMPL:
-        return False
-    L.check(rc, 'm3p_vocab_sample_wide_plan')
-    return True
+    return _plan_takes('m3p_vocab_sample_wide_plan', n, V, ld, top_k)
 
 
 def vocab_sample_wide(logits, V, temperature, seed, top_k, top_p=None):
@@ -559,37 +539,14 @@ def vocab_sample_wide(logits, V, temperature, seed, top_k, top_p=None):
     top_p = rng.nucleus_top_p(top_p)
     if top_p is None:
         top_p = 1.0                                # (the launcher's "off")
-    _chk_bf16(logits)
-    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V
-    n = logits.shape[0]
-    lib = L.load()
-    rc = lib.m3p_vocab_sample_wide_plan(n, V, logits.stride(0), top_k)
-    if rc == _ENOTIMPL:
-        return None
-    L.check(rc, 'm3p_vocab_sample_wide_plan')
-    dev = logits.device
-    ws_bytes = lib.m3p_vocab_sample_wide_workspace_bytes(n, V, top_k)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    words = torch.empty((n,), dtype=torch.int64, device=dev)
-    logprob = torch.empty((n,), dtype=torch.float32, device=dev)
-    key = torch.empty((n,), dtype=torch.float32, device=dev)
-    cut = torch.empty((n,), dtype=torch.float32, device=dev)
-    rc = lib.m3p_vocab_sample_wide(logits.data_ptr(), logits.stride(0), n, V, rng.inv_temperature(temperature), top_k, top_p,
-                                   int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, words.data_ptr(), logprob.data_ptr(),
-                                   key.data_ptr(), cut.data_ptr(), L.stream())
-    L.check(rc, 'm3p_vocab_sample_wide')
-    return words, logprob, key, cut
+    return _vocab_draw('m3p_vocab_sample_wide', 'm3p_vocab_sample_wide', logits, V, temperature, seed, top_k, top_p)
 
 
 def logits_constrain_takes(n, V, ld, hist_len, ngram=0, n_banned=0):
     """Does the launcher of logits_constrain take the shape?  (False: it would answer M3P_ENOTIMPL - hist_len > 1024, ngram > 16,
     n_banned > 4096; a malformed one raises.)  The answer depends on shapes alone: a search loop asks once, with max_len - 1 as
     the history bound."""
-    rc = L.load().m3p_logits_constrain_plan(n, V, ld, hist_len, ngram, n_banned)
-    if rc == _ENOTIMPL:
-        return False
-    L.check(rc, 'm3p_logits_constrain_plan')
-    return True
+    return _plan_takes('m3p_logits_constrain_plan', n, V, ld, hist_len, ngram, n_banned)
 
 
 def logits_constrain(logits, V, generated, cur_len, theta=1.0, inv_theta=1.0, ngram=0, eos=-1, banned=None):

@@ -58,7 +58,7 @@ def nucleus_tol(V, top_k):
 
 def test_nucleus_tol_is_what_the_docstring_says():
     assert nucleus_tol(250002, 0) <= 2.0e-6 and nucleus_tol(250002, 16) <= 2.4e-6 and nucleus_tol(40, 5) <= 2.4e-6
-    for V in (40, 1000, 2 * CHUNK + 2, 250002):
+    for V in (40, 1000, 2059, 2 * CHUNK + 2, 250002):
         for top_k in (0, 5, 16):
             assert nucleus_tol(V, top_k) <= NUCLEUS_TOL <= 1e-4
     assert _shift(250002) == 40 and _shift(2 ** 24) == 38 and (2 ** 24) * 2 ** _shift(2 ** 24) < 2 ** 63
@@ -298,6 +298,7 @@ def _hold_to_twin(full, dev, V, T, seed, top_p, top_k, key64, what, min_outside=
     (1000, 1024, 1),                                # a single row
     (250002, 250112, 2),                            # the full width
     (40, 40, 4096),                                 # many rows, tiny V
+    (2059, 2304, 3),                                # a chunk's second half: one whole load, a 3-column tail, the rest past V
 ])
 def test_vocab_nucleus_against_the_twin(V, ld, n):
     full = _logits(n, V, ld, seed=V + n)

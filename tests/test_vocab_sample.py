@@ -398,6 +398,7 @@ def _hold_to_twin(full, dev, V, T, seed, top_k, key64, what):
     (1000, 1024, 1),                                # a single row
     (250002, 250112, 2),                            # the full width
     (40, 40, 4096),                                 # many rows, tiny V
+    (2059, 2304, 3),                                # a chunk's second half: one whole load, a 3-column tail, the rest past V
 ])
 def test_vocab_sample_against_the_twin(V, ld, n):
     from m3p_amd import ops

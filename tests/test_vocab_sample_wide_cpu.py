@@ -42,7 +42,8 @@ WIDE_MAX_K = 1024               # VSW_MAX_K
 CASES = [((1000, 1024, 3), (17, 40, 64, 1000)),
          ((2 * CHUNK + 2, 8448, 5), (17, 50, 256, 1024)),
          ((250002, 250112, 2), (17, 50, 1024)),
-         ((40, 40, 4096), (17, 40))]
+         ((40, 40, 4096), (17, 40)),
+         ((2059, 2304, 3), (17, 64, 1024))]          # a chunk's second half: one whole load, a 3-column tail, the rest past V
 TEMPERATURES = (4.0, 1.0, 0.25)
 
 

@@ -163,6 +163,7 @@ def _beam_scores(n, seed):
     (1000, 1024, 1, 1, 1),                          # a single row
     (1000, 1024, 2, 8, 16),                         # the widest beam
     (250002, 250112, 2, 4, 8),                      # the full vocabulary width
+    (2059, 2304, 2, 3, 6),                          # a chunk's second half: one whole load, a 3-column tail, the rest past V
 ])
 def test_vocab_select_shapes(V, ld, bs, beam, k):
     assert ld % 256 == 0 and V <= ld < V + 256
