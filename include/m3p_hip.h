@@ -172,7 +172,7 @@ M3P_API int m3p_gemm_wgrad_bf16(const void* dY, int lddy, const void* X, int ldx
                                 void* stream);
 /* The same product STORED instead of accumulated: dW = alpha * dY^T X, for a gradient the caller knows to be all zeros (the
  * first product of a step into it).  Only for shapes the four-wave kernel deals out as whole tiles (N, K multiples of 256,
- * M % 64 == 0, at least four 256 x 256 tiles per CU - the tied vocabulary matrix, autograd of transformer.py:111): every tile
+ * M % 64 == 0, more 256 x 256 tiles than persistent workgroups - the tied vocabulary matrix, autograd of transformer.py:111): every tile
  * is then flushed exactly once and a plain store replaces 4-byte atomic read-modify-writes of a 768-MB matrix no cache holds.
  * Anything else returns M3P_ENOTIMPL and the caller accumulates with m3p_gemm_wgrad_bf16. */
 M3P_API int m3p_gemm_wgrad_store_bf16(const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, int M, int N, int K,
@@ -737,7 +737,8 @@ M3P_API int m3p_set_tile_queue(int32_t* counters, int n_slots);
 /* Which kernel a product of this shape WOULD run on, given the process-wide switches above (no launch, no device access): the
  * dispatch tables in csrc/gemm.hip (nt_plan / wgrad_plan) are the single place that decides, the launchers switch on the same
  * value.  Tests use it to assert that a model-level parity case really exercised the kernel family the benchmark runs on
- * (tests/test_model_parity.py[tiles]).  Returns an M3P_KERN_* id, or M3P_EINVAL for a shape the entry point would refuse.
+ * (tests/test_model_parity.py[tiles]) and that a launch under the two switches really ran the schedule it is checked for
+ * (tests/test_gemm_schedules.py).  Returns an M3P_KERN_* id, or M3P_EINVAL for a shape the entry point would refuse.
  * m3p_gemm_wgrad_plan assumes 16-byte aligned operands with pitches that are multiples of 8. */
 enum {
   M3P_KERN_NT_SKINNY = 1,        /* M <= 128: fragments straight from global memory                       */

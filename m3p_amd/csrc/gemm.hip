@@ -2968,6 +2968,12 @@ size_t m3p_gemm_wgrad_workspace_bytes(void) {
   return grid * (65536 + 272) * sizeof(float) + grid * sizeof(int);
 }
 
+// The four-wave weight-gradient kernel deals whole tiles round-robin as soon as there are more output tiles than workgroups:
+// its other mode gives every workgroup ONE (tile, M-chunk) segment, which covers at most `grid` tiles.  (The switch used to
+// sit at four tiles per workgroup, and between one and four the tiles past the grid - tile 8 of a 768 x 768 weight on a
+// persistent grid of 8, tiles 256.. of a 272-tile weight on 256 CUs - were never computed: tests/test_gemm_schedules.py.)
+static bool wgrad_w4_whole_tiles(long long ntile, int grid) { return ntile > (long long)grid; }
+
 // four-wave kernel + reduction; pb: optional second product over the same M (paired launch), nullptr = none
 static bool wgrad_w4_ok(int M, int N, int K, int lddy, int ldx, const void* dY, const void* X) {
   return (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 &&
@@ -2988,7 +2994,7 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
   const int nmt = M / 64;
   long long share = ((long long)ntile * nmt + grid - 1) / grid;
   int chunk = (int)(share < nmt ? (share < 1 ? 1 : share) : nmt);
-  if ((long long)ntile >= 4LL * grid) chunk = 0;   // many tiles: round-robin whole tiles
+  if (wgrad_w4_whole_tiles(ntile, grid)) chunk = 0;   // more tiles than workgroups: round-robin whole tiles
   if (pb_in && chunk == 0) return M3P_EINVAL;       // (pairs only in the one-segment-per-workgroup mode; the caller checks)
   if (store && chunk != 0) return M3P_ENOTIMPL;     // (a plain store needs every tile flushed exactly once: whole-tile round-robin mode)
   // workspace for first-segment partials: one 256-KB slot per workgroup + a tile-id word each, owned by the
@@ -3020,18 +3026,18 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
 //     most one tile per CU (m3p_gemm_wgrad_group_bf16,       tile over all of M, placed by XCD;       36-tile units against 1109 through the
 //     not part of wgrad_plan: the caller groups)             dW += alpha * acc once, plain stores     launches below (tools/ab_wgrad_group.py)
 //   M % 64 == 0, M >= 4096, N % 256 == 0, K % 256 == 0,    four-wave 256x256, one (tile, M-chunk)   1063 / 858 / 983 TF on FFN1 / FFN2 /
-//     >= 9 output tiles, < 4 tiles per CU                    segment per workgroup; partial tiles     QKV against 845 / 751 / 808 on the
+//     >= 9 output tiles, at most one tile per CU             segment per workgroup; partial tiles     QKV against 845 / 751 / 808 on the
 //                                                            go to the caller's workspace and a       ring kernel; no atomics, summed in
 //                                                            reduce kernel (16 x ntile blocks) sums   slot order (bit-reproducible)
 //                                                            them into dW in slot order
-//   same, >= 4 tiles per CU (the vocabulary matrix)        four-wave, whole tiles round-robin       each tile flushed once: fp32 atomics,
+//   same, more tiles than CUs (the vocabulary matrix)      four-wave, whole tiles round-robin       each tile flushed once: fp32 atomics,
 //                                                                                                    or plain stores (m3p_gemm_wgrad_store_bf16)
 //   M % 64 == 0, M >= 4096 otherwise                       ring stream-K 256x128 (atomics)          ragged N / K
 //   anything else                                          128x128 split-M (atomics)                small M (cfg1, tests)
 // ---------------------------------------------------------------------------------------------------------------------
 static int wgrad_plan(int M, int N, int K, bool aligned) {
   if (aligned && (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 && (N / 256) * (K / 256) >= 9)
-    return ((long long)(N / 256) * (K / 256) >= 4LL * num_cus()) ? M3P_KERN_WGRAD_W4_TILES : M3P_KERN_WGRAD_W4_CHUNKS;
+    return wgrad_w4_whole_tiles((long long)(N / 256) * (K / 256), num_cus()) ? M3P_KERN_WGRAD_W4_TILES : M3P_KERN_WGRAD_W4_CHUNKS;
   if ((M % BK) == 0 && M >= 4096) return M3P_KERN_WGRAD_RING;
   return M3P_KERN_WGRAD_128;
 }

@@ -453,6 +453,29 @@ def poison_outputs():
         yield
 
 
+@contextlib.contextmanager
+def gemm_schedule(grid=0, queue_slots=0):
+    """The two process-wide schedule switches of the persistent GEMMs (include/m3p_hip.h) around a block of launches:
+    m3p_set_persistent_grid(grid) and, with queue_slots > 0, a tile-queue ring of that many slots.  Yields the ring's counter
+    pool (int32 [queue_slots * 8], one slot of eight per queued launch) or None.  Both setters want no GEMM in flight, so the
+    device is synchronised before they are set and before they are put back (grid 0, queue off) - whatever the block did.
+    A queue that is armed on entry (a suite started with M3P_TILE_QUEUE=1) is an error: the block would not test what it says."""
+    from m3p_amd import ops, lib as L
+    lib = L.load()
+    dev = torch.cuda.current_device()
+    assert dev not in ops._TILE_QUEUE, 'a tile queue is armed already (M3P_TILE_QUEUE?): the schedule tests need the default schedule'
+    torch.cuda.synchronize()
+    try:
+        L.check(lib.m3p_set_persistent_grid(int(grid)), 'm3p_set_persistent_grid')
+        if queue_slots > 0:
+            ops.set_tile_queue(True, slots=int(queue_slots))
+        yield ops._TILE_QUEUE[dev] if queue_slots > 0 else None
+    finally:
+        torch.cuda.synchronize()
+        L.check(lib.m3p_set_persistent_grid(0), 'm3p_set_persistent_grid')
+        ops.set_tile_queue(False)
+
+
 def max_abs(a, b):
     return float((torch.as_tensor(a).detach().double().cpu() - torch.as_tensor(b).detach().double().cpu()).abs().max())
 
