@@ -309,6 +309,22 @@ M3P_API int m3p_vocab_select(const void* logits, int ld, int n, int V, const flo
                              void* workspace, size_t workspace_bytes, float* scores, long long* flat_idx, float* lse,
                              void* stream);
 
+/* m3p_vocab_select for wider beams (csrc/select.hip): the same contract word for word - lse, the score of an entry, the total
+ * order, flat_idx, -0 folded into +0, columns V .. ld-1 never looked at - for 1 <= k <= m3p_vocab_select_wide_max_k() (64) and
+ * beam <= 32.  lse has the bits m3p_vocab_select writes for the same logits, so for k <= 16 all three outputs are bit-equal to
+ * that entry's.  A row's first k words under (logit descending, word ascending) come from the exact count selection of
+ * m3p_vocab_sample_wide (integer atomics: counts do not depend on their order), a sentence's beam*k entries are then sorted
+ * under the total order by one workgroup in LDS: the same inputs give the same bits.  k > V is M3P_EINVAL here (a row supplies
+ * at most V entries to its own first k), like every malformed shape of m3p_vocab_select_plan; k > 64, beam > 32 or 32-bit block
+ * indices that would overflow return M3P_ENOTIMPL.  workspace: m3p_vocab_select_wide_workspace_bytes(n, V, beam, k) bytes,
+ * 16-byte aligned, contents irrelevant.  m3p_vocab_select_wide_plan answers what the launcher would, without launching. */
+M3P_API int m3p_vocab_select_wide_max_k(void);
+M3P_API int m3p_vocab_select_wide_plan(int n, int V, int ld, int beam, int k);
+M3P_API size_t m3p_vocab_select_wide_workspace_bytes(int n, int V, int beam, int k);
+M3P_API int m3p_vocab_select_wide(const void* logits, int ld, int n, int V, const float* beam_scores, int beam, int k,
+                                  void* workspace, size_t workspace_bytes, float* scores, long long* flat_idx, float* lse,
+                                  void* stream);
+
 /* Seeded temperature / top-k sampling of the next word from the same logits (csrc/select.hip), by Gumbel-max: one pass, no
  * prefix sums, and every random number is a pure function of (seed, row, word), so a draw can be replayed and checked
  * (NumPy twin: m3p_amd/rng.py sample_uniform / sample_keys / sample_words).  For row r and word w < V:

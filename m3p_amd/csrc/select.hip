@@ -54,15 +54,21 @@
 // finish each row in one workgroup in LDS - see the block in front of vsw_coarse_kernel.  The decoding loop sends top_k > 16
 // there; nothing leaves the device for any top_k <= 1024.
 //
+// More than VS_MAX_K entries per sentence (generate_beam with 9 .. 32 beams; m3p_vocab_select_wide, 1 <= k <= VSB_MAX_K = 64)
+// keep the contract of the selection at the top - the same lse bits, scores and order T - with that count selection as phase 1
+// (vsw_launch_select, shared with the seeded draw) and one sort of a sentence's beam * k entries in LDS as phase 2 - see the
+// block in front of vsb_merge_kernel.
+//
 // Shared pieces, each defined once (the kernels are thin bodies over them):
 //   chunk reader   VsChunk / vs_chunk_of_block / vs_chunk_run -> VsRun / vs_slot_column: which columns a thread of workgroup
 //                  (row, chunk) owns, the load guard at V, the fold of -0, the sortable key - the seven (row, chunk) kernels
 //   histogram      VnHist<T>: 256 bins in replicated LDS copies, zero / add / flush - vnuc_coarse, vnuc_fine, vsw_coarse
 //   bin scan       vn_bin_scan: the highest bin at which the value cumulated from the top satisfies a predicate - vnuc_scan,
 //                  vnuc_cut, vsw_scan
-//   row lse        vs_row_lse: log-sum-exp from the chunks' (max, sum) - vs_merge, vsmp_merge
+//   row lse        vs_row_lse: log-sum-exp from the chunks' (max, sum) - vs_merge, vsmp_merge, vsb_merge
 //   draw epilogue  vsmp_write_draw (word, logprob, key, cut) and vsmp_merge_row (the body of vsmp_merge and vnuc_merge)
-//   host side      vs_nchunks, vsmp_plan (the seeded draws' plan, by the bounds on top_k), vs_args_ok, vsmp_launch_topk
+//   host side      vs_nchunks, vsmp_plan (the seeded draws' plan, by the bounds on top_k), vs_args_ok, vsmp_launch_topk,
+//                  vsw_launch_select (the count selection's launches) - m3p_vocab_sample_wide, m3p_vocab_select_wide
 #include "common.hpp"
 #include <math.h>
 #include <initializer_list>
@@ -1106,6 +1112,145 @@ int vsmp_launch_topk(const void* logits, int ld, int n, int V, float inv_t, int 
   return M3P_OK;
 }
 
+int vs_pow2_at_least(int v) {           // the size of a bitonic sort over v entries (at least 2)
+  int N = 2;
+  while (N < v) N <<= 1;
+  return N;
+}
+
+// The count selection of every row's first top_k words under (logit descending, word ascending), the launches the seeded draw
+// (m3p_vocab_sample_wide) and the wide beam selection (m3p_vocab_select_wide) share: a workspace that BEGINS with
+// vsw_layout(n, V, top_k) -> *ent_out = ent[n, top_k] as (sortable logit << 32 | ~word), in no order inside a row.
+int vsw_launch_select(const void* logits, int ld, int n, int V, int top_k, void* workspace, hipStream_t st,
+                      const unsigned long long** ent_out) {
+  const int nchunks = vs_nchunks(V);
+  const unsigned rows4 = (unsigned)((n + 3) / 4), blocks = (unsigned)(n * nchunks);
+  const VswLayout L = vsw_layout(n, V, top_k);
+  char* ws = (char*)workspace;
+  unsigned long long* ent = (unsigned long long*)(ws + L.ent);
+  uint32_t* hist = (uint32_t*)(ws + L.hist);
+  uint32_t* fine = (uint32_t*)(ws + L.fine);
+  uint32_t* chunkcnt = (uint32_t*)(ws + L.chunkcnt);
+  int* rowbin = (int*)(ws + L.rowbin);
+  int* rowlow = (int*)(ws + L.rowlow);
+  uint32_t* above0 = (uint32_t*)(ws + L.above0);
+  uint32_t* above1 = (uint32_t*)(ws + L.above1);
+  if (hipMemsetAsync(hist, 0, (size_t)n * VN_BINS * 2 * sizeof(uint32_t), st) != hipSuccess) return M3P_EINVAL;
+  hipLaunchKernelGGL(vsw_coarse_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, hist);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_scan_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)hist, n, (uint32_t)top_k,
+                     (const uint32_t*)nullptr, rowbin, above0);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vnuc_fine_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin, fine);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_scan_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)fine, n, (uint32_t)top_k,
+                     (const uint32_t*)above0, rowlow, above1);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_tie_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin,
+                     (const int*)rowlow, chunkcnt);
+  M3P_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vsw_compact_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, top_k,
+                     (const int*)rowbin, (const int*)rowlow, (const uint32_t*)above1, (const uint32_t*)chunkcnt, ent);
+  M3P_CHECK_LAUNCH();
+  *ent_out = ent;
+  return M3P_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// beam search beyond VS_MAX_K entries per sentence: m3p_vocab_select_wide (1 <= k <= VSB_MAX_K, beam <= VSB_MAX_BEAM)
+// ------------------------------------------------------------------------------------------------------------------------
+// The contract of m3p_vocab_select for wider beams.  Phase 1 is the count selection above with top_k = k: a row's first k
+// entries under (logit descending, word ascending) are what T leaves of the row, whatever its lse and beam score, so a
+// sentence's first k under T lie among its beam * k <= 2048 entries of ent.  vs_chunk_kernel at k = 1 supplies the chunks'
+// (max, sum) - its sum does not depend on k, so lse has the bits m3p_vocab_select gives.  Phase 2 (vsb_merge_kernel, a workgroup
+// per sentence): lse per row as in vs_merge_kernel, the VsKey of every entry into LDS, ONE bitonic sort over the power of two
+// at or above beam * k in place of k rounds of a maximum, the first k out.  Keys are unique ((beam, word) is part of them): the
+// sorted order is T itself, and the outputs for k <= VS_MAX_K are those of m3p_vocab_select bit for bit.  No atomics here.
+constexpr int VSB_MAX_K = 64;          // entries per sentence (2 * beam: beams up to 32)
+constexpr int VSB_MAX_BEAM = 32;       // rows per sentence
+constexpr int VSB_MAX_ENT = VSB_MAX_K * VSB_MAX_BEAM;      // keys of a sentence in LDS: 2048 x 12 bytes
+
+struct VsbLayout {
+  size_t pstat, cand, bytes;           // behind vsw_layout(n, V, k): the chunks' (max, sum) and the k = 1 candidates of vs_chunk_kernel
+};
+VsbLayout vsb_layout(int n, int V, int k) {
+  const size_t blocks = (size_t)n * (size_t)vs_nchunks(V);
+  VsbLayout B;
+  size_t o = (vsw_layout(n, V, k).bytes + 15) & ~(size_t)15;
+  B.pstat = o; o += blocks * 2 * sizeof(float);
+  B.cand = o;  o += blocks * sizeof(uint32_t);
+  B.bytes = o;
+  return B;
+}
+
+int vsb_plan(int n, int V, int ld, int beam, int k) {
+  if (n <= 0 || V <= 0 || beam <= 0 || k <= 0 || n % beam != 0 || ld < V || (ld % 8) != 0) return M3P_EINVAL;
+  if (k > V) return M3P_EINVAL;                              // a row supplies at most V entries to its own first k
+  if (k > VSB_MAX_K || beam > VSB_MAX_BEAM) return M3P_ENOTIMPL;
+  if ((long long)n * vs_nchunks(V) * VS_MAX_K >= (1ll << 31)) return M3P_ENOTIMPL;       // 32-bit block and candidate indices
+  return M3P_OK;
+}
+
+// ent [n, k] as vsw_compact_kernel left it; N = the power of two at or above beam * k (at least 2, at most VSB_MAX_ENT)
+__global__ __launch_bounds__(256) void vsb_merge_kernel(const float* __restrict__ pstat, const unsigned long long* __restrict__ ent,
+                                                       const float* __restrict__ beam_scores, float* __restrict__ scores,
+                                                       long long* __restrict__ flat_idx, float* __restrict__ lse, int V, int nchunks,
+                                                       int beam, int k, int N) {
+  __shared__ unsigned long long s_hi[VSB_MAX_ENT];
+  __shared__ uint32_t s_lo[VSB_MAX_ENT];
+  __shared__ float s_lse[VSB_MAX_BEAM];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int sent = blockIdx.x;
+  const int total = beam * k;
+  if (beam > VSB_MAX_BEAM || N > VSB_MAX_ENT || total > N) return;      // (the launcher's plan holds all three; uniform)
+  for (int r = wv; r < beam; r += 4) {             // a wave per row: merge the chunks' (max, sum)
+    const size_t row = (size_t)sent * beam + r;
+    const float l = vs_row_lse(pstat + row * nchunks * 2, nchunks, lane, [](int) {});
+    if (lane == 0) {
+      s_lse[r] = l;
+      lse[row] = l;
+    }
+  }
+  __syncthreads();
+  const unsigned long long* es = ent + (size_t)sent * total;       // (the sentence's rows are consecutive: [beam, k])
+  for (int i = tid; i < N; i += 256) {
+    VsKey x = {0ull, 0u};                          // past the entries: zeros, below every entry
+    if (i < total) {
+      const unsigned long long e = es[i];
+      const int r = i / k;
+      const uint32_t sk = (uint32_t)(e >> 32) & 0xFFFFu;
+      const float bsc = beam_scores ? beam_scores[(size_t)sent * beam + r] : 0.f;
+      const float sc = (vs_value16(sk) - s_lse[r]) + bsc;
+      x.hi = (unsigned long long)vs_sortable32(sc) << 32 | (unsigned long long)(uint32_t)(0xFFFF - r) << 16 | sk;
+      x.lo = (uint32_t)e;                          // ~word
+    }
+    s_hi[i] = x.hi;
+    s_lo[i] = x.lo;
+  }
+  __syncthreads();
+  for (int k2 = 2; k2 <= N; k2 <<= 1)              // bitonic sort, descending under vs_less: the order T
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < N / 2; t += 256) {
+        const int i = 2 * t - (t & (j - 1)), l = i + j;
+        const VsKey a = {s_hi[i], s_lo[i]}, b = {s_hi[l], s_lo[l]};
+        if (vs_less(a, b) == ((i & k2) == 0)) {
+          s_hi[i] = b.hi;
+          s_lo[i] = b.lo;
+          s_hi[l] = a.hi;
+          s_lo[l] = a.lo;
+        }
+      }
+      __syncthreads();
+    }
+  for (int j = tid; j < k; j += 256) {             // (k <= total <= N)
+    const VsKey win = {s_hi[j], s_lo[j]};
+    const bool have = win.hi != 0ull;              // (the plan asks for k <= V: every row supplies k entries - always)
+    const int r = 0xFFFF - (int)((win.hi >> 16) & 0xFFFFu);
+    scores[(size_t)sent * k + j] = have ? vs_value32((uint32_t)(win.hi >> 32)) : -INFINITY;
+    flat_idx[(size_t)sent * k + j] = have ? (long long)r * V + (long long)(~win.lo) : 0ll;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1239,39 +1384,43 @@ int m3p_vocab_sample_wide(const void* logits, int ld, int n, int V, float inv_t,
   if (rc != M3P_OK) return rc;
   if (!vs_args_ok(logits, workspace, workspace_bytes, m3p_vocab_sample_wide_workspace_bytes(n, V, top_k), {words, logprob}, inv_t, top_p)) return M3P_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  const unsigned long long* ent = nullptr;
+  const int rc2 = vsw_launch_select(logits, ld, n, V, top_k, workspace, st, &ent);
+  if (rc2 != M3P_OK) return rc2;
+  hipLaunchKernelGGL(vsw_draw_kernel, dim3((unsigned)n), dim3(256), 0, st, ent, V, top_k, vs_pow2_at_least(top_k), inv_t, top_p,
+                     seed, words, logprob, key, cut);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_vocab_select_wide_max_k(void) { return VSB_MAX_K; }
+
+int m3p_vocab_select_wide_plan(int n, int V, int ld, int beam, int k) { return vsb_plan(n, V, ld, beam, k); }
+
+size_t m3p_vocab_select_wide_workspace_bytes(int n, int V, int beam, int k) {
+  if (n <= 0 || V <= 0 || beam <= 0 || k <= 0) return 0;
+  return vsb_layout(n, V, k).bytes;
+}
+
+int m3p_vocab_select_wide(const void* logits, int ld, int n, int V, const float* beam_scores, int beam, int k, void* workspace,
+                          size_t workspace_bytes, float* scores, long long* flat_idx, float* lse, void* stream) {
+  const int rc = vsb_plan(n, V, ld, beam, k);
+  if (rc != M3P_OK) return rc;
+  if (!vs_args_ok(logits, workspace, workspace_bytes, m3p_vocab_select_wide_workspace_bytes(n, V, beam, k), {scores, flat_idx, lse})) return M3P_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
   const int nchunks = vs_nchunks(V);
-  const unsigned rows4 = (unsigned)((n + 3) / 4), blocks = (unsigned)(n * nchunks);
-  const VswLayout L = vsw_layout(n, V, top_k);
-  char* ws = (char*)workspace;
-  unsigned long long* ent = (unsigned long long*)(ws + L.ent);
-  uint32_t* hist = (uint32_t*)(ws + L.hist);
-  uint32_t* fine = (uint32_t*)(ws + L.fine);
-  uint32_t* chunkcnt = (uint32_t*)(ws + L.chunkcnt);
-  int* rowbin = (int*)(ws + L.rowbin);
-  int* rowlow = (int*)(ws + L.rowlow);
-  uint32_t* above0 = (uint32_t*)(ws + L.above0);
-  uint32_t* above1 = (uint32_t*)(ws + L.above1);
-  int N = 2;
-  while (N < top_k) N <<= 1;
-  if (hipMemsetAsync(hist, 0, (size_t)n * VN_BINS * 2 * sizeof(uint32_t), st) != hipSuccess) return M3P_EINVAL;
-  hipLaunchKernelGGL(vsw_coarse_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, hist);
+  const VsbLayout B = vsb_layout(n, V, k);
+  float* pstat = (float*)((char*)workspace + B.pstat);
+  uint32_t* cand = (uint32_t*)((char*)workspace + B.cand);
+  // the chunks' (max, sum) exactly as m3p_vocab_select takes them (the sum does not depend on k): the same lse bits
+  hipLaunchKernelGGL(vs_chunk_kernel, dim3((unsigned)(n * nchunks)), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, 1, pstat,
+                     cand);
   M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsw_scan_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)hist, n, (uint32_t)top_k,
-                     (const uint32_t*)nullptr, rowbin, above0);
-  M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vnuc_fine_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin, fine);
-  M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsw_scan_kernel, dim3(rows4), dim3(256), 0, st, (const uint32_t*)fine, n, (uint32_t)top_k,
-                     (const uint32_t*)above0, rowlow, above1);
-  M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsw_tie_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, (const int*)rowbin,
-                     (const int*)rowlow, chunkcnt);
-  M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsw_compact_kernel, dim3(blocks), dim3(256), 0, st, (const bf16*)logits, ld, V, nchunks, top_k,
-                     (const int*)rowbin, (const int*)rowlow, (const uint32_t*)above1, (const uint32_t*)chunkcnt, ent);
-  M3P_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vsw_draw_kernel, dim3((unsigned)n), dim3(256), 0, st, (const unsigned long long*)ent, V, top_k, N, inv_t,
-                     top_p, seed, words, logprob, key, cut);
+  const unsigned long long* ent = nullptr;
+  const int rc2 = vsw_launch_select(logits, ld, n, V, k, workspace, st, &ent);
+  if (rc2 != M3P_OK) return rc2;
+  hipLaunchKernelGGL(vsb_merge_kernel, dim3((unsigned)(n / beam)), dim3(256), 0, st, (const float*)pstat, ent, beam_scores, scores,
+                     flat_idx, lse, V, nchunks, beam, k, vs_pow2_at_least(beam * k));
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }

@@ -18,7 +18,9 @@ the best entries of its beam * V scores straight from the bf16 logits - no fp32 
 beam search the caches then stay in place: ``cache['owner']`` (int32 [rows, capacity]) names, per hypothesis and position,
 the row whose slot holds that position's keys / values (``advance_owner`` after every step; ``m3p_attn_query_owner_fwd``
 reads through it), and with ``cache['beam']`` the source's keys / values are kept once per sentence, not once per beam.
-``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, unseeded sampling and wider beams run the torch code below unchanged.
+Beams of 9 to 32 (17 <= 2 * beam_size <= ``BEAM_SELECT_WIDE_MAX_K``) take ``ops.vocab_select_wide`` - the same contract by a
+count selection and one sort per sentence - and everything behind the selection is the same in-place-cache code.
+``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, unseeded sampling and beams above 32 run the torch code below unchanged.
 ``generate(sample_seed=...)`` draws the next word by the seeded Gumbel-max contract of ``ops.vocab_sample`` (csrc/select.hip;
 NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation, a nucleus (top-p) cut
 (``sample_top_p``: ``ops.vocab_nucleus_sample``) and the sampled words' log-probabilities; more than 16 and up to 1024
@@ -48,6 +50,13 @@ BF16 = torch.bfloat16
 # asks for k <= VOCAB_SELECT_MAX_K entries per sentence (greedy: 1, beam search: 2 * beam_size) where the launcher takes
 # the shape (VS_MAX_K = 16 of csrc/select.hip); 0 sends every call to the torch path.
 VOCAB_SELECT_MAX_K = 16
+
+# Beam search asks for k = 2 * beam_size entries per sentence: from BEAM_SELECT_WIDE_MIN_K on, and up to
+# BEAM_SELECT_WIDE_MAX_K, the select route asks ops.vocab_select_wide (VSB_MAX_K = 64 of csrc/select.hip: beams up to 32)
+# instead of ops.vocab_select; below it today's rule holds.  VOCAB_SELECT_MAX_K = 0 switches both off.  The upper bound is
+# set by measurement ("Beam search beyond 8 beams"; profiles/decode_beam_wide.txt).
+BEAM_SELECT_WIDE_MIN_K = 17
+BEAM_SELECT_WIDE_MAX_K = 64
 
 # Stream-key site of the seeded sampling draws (rng.stream_seed(sample_seed, position, SAMPLE_SITE)): outside the dropout
 # sites of the encoder (< 2^20), the refiner (functional._REF_SITE0 = 2^20 + ...) and the causal stream (_DEC_SITE0 = 2^21 + ...).
@@ -243,10 +252,11 @@ def advance_owner(owner, beam_idx, next_pos):
     return new
 
 
-def _select(logits, V, beam_scores, beam, k):
-    res = ops.vocab_select(logits, V, beam_scores, beam, k)
+def _select(logits, V, beam_scores, beam, k, wide=False):
+    name = 'vocab_select_wide' if wide else 'vocab_select'
+    res = getattr(ops, name)(logits, V, beam_scores, beam, k)
     if res is None:
-        raise L.M3PError('m3p_vocab_select declined (M3P_ENOTIMPL) a shape m3p_vocab_select_plan took')
+        raise L.M3PError('m3p_%s declined (M3P_ENOTIMPL) a shape m3p_%s_plan took' % (name, name))
     return res
 
 
@@ -542,7 +552,8 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
                   repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
     """transformer.py:1319-1515: beam search; the beam is folded into the batch dimension (bs * beam_size rows).  On the torch
     path the key / value caches are re-ordered by the surviving beams' source rows after every step; on the select path
-    (module docstring) they stay in place behind cache['owner'] and the source is kept once per sentence.
+    (module docstring: ``ops.vocab_select`` up to 8 beams, ``ops.vocab_select_wide`` from 9 to 32) they stay in place behind
+    cache['owner'] and the source is kept once per sentence.
     -> (decoded (max tgt_len, bs) int64, tgt_len (bs)).
 
     ``min_len`` / ``repetition_penalty`` / ``no_repeat_ngram`` / ``banned_words``: the decoding constraints of ``generate``, by
@@ -556,8 +567,16 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     cons = _Constraints(model, max_len, min_len, repetition_penalty, no_repeat_ngram, banned_words, dev)
     src_len = src_len.to(dev)
     n = bs * beam_size
-    select = (dev.type == 'cuda' and 2 * beam_size <= VOCAB_SELECT_MAX_K
-              and ops.vocab_select_takes(n, n_words, model.arena().V_pad, beam_size, 2 * beam_size))
+    sel_k = 2 * beam_size
+    # (each plan is asked once; sel_k > n_words is malformed for the wide entry - a row supplies at most V entries to its own
+    # first k - and takes the torch path)
+    wide = BEAM_SELECT_WIDE_MIN_K <= sel_k <= min(BEAM_SELECT_WIDE_MAX_K, n_words)
+    if dev.type != 'cuda' or VOCAB_SELECT_MAX_K < 1:
+        select = wide = False
+    elif sel_k < BEAM_SELECT_WIDE_MIN_K:
+        select = sel_k <= VOCAB_SELECT_MAX_K and ops.vocab_select_takes(n, n_words, model.arena().V_pad, beam_size, sel_k)
+    else:
+        select = wide = wide and ops.vocab_select_wide_takes(n, n_words, model.arena().V_pad, beam_size, sel_k)
     cons_dev = cons.on and select and cons.takes(n, n_words, model.arena().V_pad, max_len)
     if select:
         src_enc = src_enc.to(dev)
@@ -587,7 +606,7 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
         assert tensor.size() == (1, bs * beam_size, model.dim)
         if select:
             next_scores, next_words, _ = _select(*_constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len),
-                                                 beam_scores, beam_size, 2 * beam_size)
+                                                 beam_scores, beam_size, sel_k, wide)
         else:
             scores = torch.log_softmax(_constrained_scores(model, tensor[-1], cons, generated, cur_len), dim=-1)
             _scores = (scores + beam_scores[:, None]).view(bs, beam_size * n_words)

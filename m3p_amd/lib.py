@@ -80,6 +80,10 @@ SIGNATURES = {
     'm3p_vocab_nucleus_plan': (_i, [_i, _i, _i, _i]),
     'm3p_vocab_nucleus_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'm3p_vocab_nucleus_sample': (_i, [_p, _i, _i, _i, _f, _i, _f, _u32, _p, C.c_size_t, _p, _p, _p, _p, _p]),
+    'm3p_vocab_select_wide_max_k': (_i, []),
+    'm3p_vocab_select_wide_plan': (_i, [_i, _i, _i, _i, _i]),
+    'm3p_vocab_select_wide_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i]),
+    'm3p_vocab_select_wide': (_i, [_p, _i, _i, _i, _p, _i, _i, _p, C.c_size_t, _p, _p, _p, _p]),
     'm3p_vocab_sample_wide_max_k': (_i, []),
     'm3p_vocab_sample_wide_plan': (_i, [_i, _i, _i, _i]),
     'm3p_vocab_sample_wide_workspace_bytes': (C.c_size_t, [_i, _i, _i]),

@@ -459,6 +459,46 @@ def vocab_select(logits, V, beam_scores, beam, k):
     return scores, flat_idx, lse
 
 
+def vocab_select_wide_max_k():
+    """VSB_MAX_K of csrc/select.hip: the most entries per sentence m3p_vocab_select_wide returns."""
+    return int(L.load().m3p_vocab_select_wide_max_k())
+
+
+def vocab_select_wide_takes(n, V, ld, beam, k):
+    """Does the launcher of vocab_select_wide take the shape?  (False: it would answer M3P_ENOTIMPL; a malformed one raises.)"""
+    return _plan_takes('m3p_vocab_select_wide_plan', n, V, ld, beam, k)
+
+
+def vocab_select_wide(logits, V, beam_scores, beam, k):
+    """vocab_select for wider beams (csrc/select.hip: m3p_vocab_select_wide): the same arguments, the same contract and the
+    same results - (scores fp32 [bs, k], flat_idx int64 [bs, k], lse fp32 [n]) - for 1 <= k <= vocab_select_wide_max_k() (64)
+    and beam <= 32, by a count selection of every row's first k words and one sort of the sentence's beam * k entries instead
+    of k rounds of a maximum; lse has the bits of vocab_select, and so have scores and flat_idx for k <= 16.  None when the
+    launcher does not take the shape (M3P_ENOTIMPL: k > 64, beam > 32); k > V raises."""
+    _chk_bf16(logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    n = logits.shape[0]
+    assert n % beam == 0 and logits.shape[1] >= V
+    if beam_scores is not None:
+        assert beam_scores.dtype == torch.float32 and beam_scores.is_cuda and beam_scores.is_contiguous() and beam_scores.numel() == n
+    lib = L.load()
+    rc = lib.m3p_vocab_select_wide_plan(n, V, logits.stride(0), beam, k)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_vocab_select_wide_plan')
+    bs = n // beam
+    dev = logits.device
+    ws_bytes = lib.m3p_vocab_select_wide_workspace_bytes(n, V, beam, k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    scores = torch.empty((bs, k), dtype=torch.float32, device=dev)
+    flat_idx = torch.empty((bs, k), dtype=torch.int64, device=dev)
+    lse = torch.empty((n,), dtype=torch.float32, device=dev)
+    rc = lib.m3p_vocab_select_wide(logits.data_ptr(), logits.stride(0), n, V, L.ptr(beam_scores), beam, k, ws.data_ptr(), ws_bytes,
+                                   scores.data_ptr(), flat_idx.data_ptr(), lse.data_ptr(), L.stream())
+    L.check(rc, 'm3p_vocab_select_wide')
+    return scores, flat_idx, lse
+
+
 def _vocab_draw(stem, call, logits, V, temperature, seed, top_k, top_p=None):
     """The seeded draws' common course - plan (stem + '_plan'), workspace (stem + '_workspace_bytes'), outputs, call, check:
     -> (words int64 [n], logprob fp32 [n], key fp32 [n]) and, with top_p (a launcher that cuts), cut fp32 [n]; None when the

@@ -52,7 +52,16 @@ the fallback takes seconds per step, so its runs decode FALLBACK_LEN - 1 steps, 
 and 1024.  Same geometry, 128 sentences, warm-up and three alternating pairs.  `--trace wide --top-k K [--top-p P]` is the run
 for the profiler, `--stats ... wide` its per-kernel lines.
     timeout -k 10 900 python tools/decode_bench.py --sample --top-k 50 > profiles/decode_topk_wide.txt
-    timeout -k 10 900 python tools/decode_bench.py --sample --top-k 50 --top-p 0.9 >> profiles/decode_topk_wide.txt"""
+    timeout -k 10 900 python tools/decode_bench.py --sample --top-k 50 --top-p 0.9 >> profiles/decode_topk_wide.txt
+
+`--beam B --sentences N` measures ONE beam-search shape instead of the three runs above - generate_beam on N sentences x beam B,
+the shapes beyond 8 beams that csrc/select.hip takes through m3p_vocab_select_wide (17 <= 2 B <= 64) - by the protocol of the
+plain run: the device route against the torch route of the same call in the same process (decoder.VOCAB_SELECT_MAX_K = 0, the
+code this call ran before the wide entry existed), warm-up on both, three alternating pairs, outputs and selections compared.
+The run is named beamB: `--beam B --sentences N --trace beamB` is the run for the profiler, `--beam B --sentences N --stats
+<csv> beamB` its per-kernel lines (vs_chunk_kernel, the six launches of the count selection, vsb_merge_kernel).
+    timeout -k 10 600 python tools/decode_bench.py --beam 12 --sentences 32 > profiles/decode_beam_wide.txt
+    timeout -k 10 600 python tools/decode_bench.py --beam 32 --sentences 16 >> profiles/decode_beam_wide.txt"""
 import csv
 import os
 import sys
@@ -146,8 +155,8 @@ def selection_gaps(m, src, src_len, beam, **cons):
     differing rank of its first differing step."""
     real, step, first = decoder._select, [0], {}
 
-    def both(logits, V_, beam_scores, beam_, k):
-        res = real(logits, V_, beam_scores, beam_, k)
+    def both(logits, V_, beam_scores, beam_, k, *route):
+        res = real(logits, V_, beam_scores, beam_, k, *route)
         t = (torch.log_softmax(logits[:, :V_].float(), dim=-1) + beam_scores[:, None]).view(-1, beam_ * V_)
         _, ti = torch.topk(t, k, dim=1, largest=True, sorted=True)
         for s in (ti != res[1]).any(1).nonzero().view(-1).tolist():
@@ -181,7 +190,7 @@ def bench(m):
             new.append(t)
         ratios = [a / b for a, b in zip(old, new)]
         rows = bs * beam
-        print('%-6s %-13s bs %3d beam %d (%3d rows)  torch ms %s  select ms %s  ratio %s  select %s' % (
+        print('%-6s %-13s bs %3d beam %2d (%3d rows)  torch ms %s  select ms %s  ratio %s  select %s' % (
             name, kind, bs, beam, rows, ' '.join('%7.3f' % v for v in old), ' '.join('%7.3f' % v for v in new),
             ' '.join('%5.2f' % v for v in ratios), 'wins all three' if min(ratios) > 1 else 'does NOT win all three'))
         assert out_old[0].shape[0] == MAX_LEN and out_new[0].shape[0] == MAX_LEN, 'a sentence ended early'
@@ -377,7 +386,7 @@ def stats(path, name):
         for key in ('vs_chunk_kernel', 'vs_merge_kernel', 'vsmp_chunk_kernel', 'vsmp_merge_kernel', 'vsmp_topk_kernel',
                     'vnuc_coarse_kernel', 'vnuc_scan_kernel', 'vnuc_fine_kernel', 'vnuc_cut_kernel', 'vnuc_merge_kernel',
                     'lc_constrain_kernel', 'vsw_coarse_kernel', 'vsw_scan_kernel', 'vsw_tie_kernel', 'vsw_compact_kernel',
-                    'vsw_draw_kernel'):
+                    'vsw_draw_kernel', 'vsb_merge_kernel'):
             if key in kname:
                 sel[key] = (ns / calls, calls)
     print('\nkernel shares, %s (%d rows), %s, from a profiled run of its own (warm-up + one timed run)' % (
@@ -389,6 +398,10 @@ def stats(path, name):
         every = sum(avg * calls for avg, calls in sel.values()) / max(v[1] for k, v in sel.items() if k == 'vsw_draw_kernel')
         print('  wide sampling (all of the above, vsw_scan_kernel twice): %.1f us per step over %.1f MB of logits read four times' % (
             every / 1e3, rows * V * 2 / 1e6))
+    elif 'vsb_merge_kernel' in sel:
+        every = sum(avg * calls for avg, calls in sel.values()) / sel['vsb_merge_kernel'][1]
+        print('  wide beam selection (all of the above, vsw_scan_kernel twice): %.1f us per step over %.1f MB of logits read five '
+              'times' % (every / 1e3, rows * V * 2 / 1e6))
     elif name == 'nucleus':
         every = sum(v[0] for v in sel.values())
         print('  nucleus sampling (all of the above): %.1f us per step over %.1f MB of logits' % (every / 1e3, rows * V * 2 / 1e6))
@@ -405,6 +418,17 @@ def stats(path, name):
 
 
 if __name__ == '__main__':
+    if '--beam' in sys.argv:
+        at = sys.argv.index('--beam')
+        one_beam = int(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
+        assert '--sentences' in sys.argv, '--beam B --sentences N'
+        at = sys.argv.index('--sentences')
+        one_bs = int(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
+        assert one_beam >= 1 and one_bs >= 1
+        RUNS.clear()
+        RUNS['beam%d' % one_beam] = ('generate_beam', one_bs, one_beam)
     if len(sys.argv) >= 4 and sys.argv[1] == '--stats':
         stats(sys.argv[2], sys.argv[3])
         sys.exit(0)
