@@ -434,6 +434,41 @@ M3P_API int m3p_logits_constrain(void* logits, int ld, int n, int V, const long 
                                  float theta, float inv_theta, int ngram, int eos_or_minus1, const long long* banned,
                                  int n_banned, void* stream);
 
+/* Hypothesis bookkeeping of one beam-search step (csrc/beam.hip; host twin: m3p_amd/decoder.py beam_advance_host, which the
+ * kernel equals bit for bit): from the step's candidates to the sentences' lists of finished hypotheses, the next beams and, in
+ * the same launch, the re-ordered token matrix and owner table.  Per sentence s, with n = bs*beam rows in all:
+ *   next_scores fp32 [bs, k], flat_idx int64 [bs, k]   the candidates in the selection's order (m3p_vocab_select: score
+ *               descending, so entry 0 is the maximum); flat_idx = b*V + word, 0 <= b < beam; the candidate's row is s*beam + b
+ *   norm        fp64 [max_len + 1] on the device, norm[l] = (double)l ** length_penalty; norm_max = (double)(max_len - 1) **
+ *               length_penalty; both formed by the host
+ *   done[s] |= hyp_count[s] >= beam and (early_stopping or min_j hyp_score[s, j] >= (double)next_scores[s, 0] / norm_max)
+ *   a done sentence emits beam x (0.0, pad, row 0) and nothing of its state changes.  Otherwise the candidates are walked in
+ *   order: one whose word is eos - every one when cur_len + 1 == max_len - is OFFERED to the list: score = (double)value /
+ *   norm[cur_len], arrival = arrivals[s]++; while hyp_count[s] < beam it takes slot hyp_count[s]++, afterwards the slot minimal
+ *   by (hyp_score, hyp_arrival), and only if score > that slot's score.  An accepted one writes hyp_tok[s, slot, 0 .. cur_len-1]
+ *   = gen_in[0 .. cur_len-1, row], hyp_len = cur_len, hyp_score = score, hyp_sum = value, hyp_arrival = arrival.  Every other
+ *   candidate is the next continuation (value, word, row); the walk ends at `beam` of them; missing ones are (0.0, pad, row 0),
+ *   and when cur_len + 1 < max_len that sets status[s] |= 1.  A flat_idx outside [0, beam*V) sets status[s] |= 2 and is read
+ *   as beam 0.
+ *   beam_scores fp32 [n], beam_words int64 [n], beam_idx int64 [n]   the continuations, row r = s*beam + j
+ *   gen_in / gen_out   int64 [max_len, gen_ld >= n] row-major (the layout m3p_logits_constrain reads): gen_out[p, r] =
+ *               gen_in[p, beam_idx[r]] for p < cur_len, gen_out[cur_len, r] = beam_words[r]; positions past cur_len untouched
+ *   owner_in / owner_out   int32 [n, owner_ld >= max_len]: owner_out[r, p] = owner_in[beam_idx[r], p] for p < max_len, except
+ *               owner_out[r, cur_len] = r  (the owner table of m3p_attn_query_owner_fwd after the step)
+ *   state       hyp_tok int64 [bs, beam, max_len] (pad behind hyp_len), hyp_len int32, hyp_score fp64, hyp_sum fp32, hyp_arrival
+ *               int32 [bs, beam]; hyp_count, arrivals, status int32 [bs]; done uint8 [bs].  Zeros (hyp_tok: pad) before step 1.
+ * gen_in != gen_out and owner_in != owner_out (M3P_EINVAL): a done sentence reads row 0, which another workgroup writes.  One
+ * launch, one wave per sentence, no atomics; the fp64 work is one conversion, one division and comparisons - IEEE, so the
+ * bits are the host's.  1 <= cur_len < max_len.  Limits: beam <= 32, k <= 64, max_len <= 1025 - above them M3P_ENOTIMPL (the
+ * caller keeps the host twin).  m3p_beam_advance_plan answers what the launcher would for a shape, without launching. */
+M3P_API int m3p_beam_advance_plan(int bs, int beam, int k, int max_len);
+M3P_API int m3p_beam_advance(const float* next_scores, const long long* flat_idx, int bs, int beam, int k, int V, int cur_len,
+                             int max_len, int eos, int pad, int early_stopping, const double* norm, double norm_max,
+                             const long long* gen_in, long long* gen_out, long long gen_ld, const int32_t* owner_in,
+                             int32_t* owner_out, int owner_ld, float* beam_scores, long long* beam_words, long long* beam_idx,
+                             long long* hyp_tok, int32_t* hyp_len, double* hyp_score, float* hyp_sum, int32_t* hyp_arrival,
+                             int32_t* hyp_count, int32_t* arrivals, uint8_t* done, int32_t* status, void* stream);
+
 /* The same attention for the TRAINING of the causal / cross-attention sub-layers (teacher forcing: Tq = the whole target
  * sequence, pos0 = 0): dropout on the probabilities (stream (seed, thresh24) indexed ((b*H + h)*Tq + t)*Lk + key) and the
  * log-sum-exp lse fp32 [B, H, Tq] kept for backward.  B*H*Tq*Lk < 2^32. */

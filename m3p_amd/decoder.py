@@ -21,6 +21,11 @@ reads through it), and with ``cache['beam']`` the source's keys / values are kep
 Beams of 9 to 32 (17 <= 2 * beam_size <= ``BEAM_SELECT_WIDE_MAX_K``) take ``ops.vocab_select_wide`` - the same contract by a
 count selection and one sort per sentence - and everything behind the selection is the same in-place-cache code.
 ``VOCAB_SELECT_MAX_K`` is the dispatch rule; a CPU model, unseeded sampling and beams above 32 run the torch code below unchanged.
+What a beam step does with its 2 * beam candidates - finished hypotheses into a bounded list per sentence, the next beams, the
+done flags - is ``beam_advance_host``, one pure function over plain arrays behind one host copy per step; its device form is
+``ops.beam_advance`` (csrc/beam.hip: one wave per sentence, the lists kept on the device, the next ``generated`` columns and
+owner table written by the same launch), taken on the select routes when ``BEAM_HYPS_ON_DEVICE`` is set: the loop then reads
+the host once per call.  The lists are what ``generate_beam(n_best=k, return_scores=True)`` returns on every route.
 ``generate(sample_seed=...)`` draws the next word by the seeded Gumbel-max contract of ``ops.vocab_sample`` (csrc/select.hip;
 NumPy twin ``rng.sample_words``) instead: reproducible, with top-k truncation, a nucleus (top-p) cut
 (``sample_top_p``: ``ops.vocab_nucleus_sample``) and the sampled words' log-probabilities; more than 16 and up to 1024
@@ -34,9 +39,11 @@ This module is forward only; the teacher-forced training pass of the same stream
 (``TransformerModel.crossfwd`` picks it in training mode), and calling ``decoder_forward`` itself with autograd enabled on
 a model in training mode raises.
 """
+import collections
 import heapq
 import math
 
+import numpy as np
 import torch
 
 from . import functional as Fn
@@ -548,19 +555,185 @@ class BeamHypotheses(object):
         return full and (self.early_stopping or self.worst_score >= best_sum_logprobs / self._norm)
 
 
+HYP_STATE = ('hyp_tok', 'hyp_len', 'hyp_score', 'hyp_sum', 'hyp_arrival', 'hyp_count', 'arrivals', 'done', 'status')
+
+
+def beam_norms(max_len, length_penalty):
+    """The two normalisers of the bookkeeping, in double precision as CPython computes them: (norm fp64 [max_len + 1] with
+    norm[l] = float(l) ** length_penalty - a hypothesis of l tokens scores sum_logprobs / norm[l] -, float(max_len - 1) **
+    length_penalty of BeamHypotheses.is_done).  norm[0] is never read; a negative penalty makes it inf."""
+    def power(l):
+        try:
+            return float(l) ** length_penalty
+        except ZeroDivisionError:
+            return float('inf')
+    return np.array([power(l) for l in range(max_len + 1)], dtype=np.float64), power(max_len - 1)
+
+
+def beam_state_host(bs, beam, max_len, pad):
+    """The empty hypothesis state of bs sentences as NumPy arrays (ops.beam_state makes the same on the device): per sentence a
+    list of up to `beam` finished hypotheses in slots 0 .. hyp_count - 1 -
+      hyp_tok int64 [bs, beam, max_len] (tokens 0 .. hyp_len - 1, pad behind them), hyp_len int32 [bs, beam],
+      hyp_score fp64 [bs, beam] (sum / norm[len]), hyp_sum fp32 [bs, beam], hyp_arrival int32 [bs, beam],
+    hyp_count int32 [bs], arrivals int32 [bs] (hypotheses offered so far: the next arrival number), done uint8 [bs], status
+    int32 [bs] (nonzero: a step found fewer than `beam` continuations)."""
+    z = lambda shape, dt: np.zeros(shape, dtype=dt)   # noqa: E731
+    return dict(hyp_tok=np.full((bs, beam, max_len), pad, dtype=np.int64), hyp_len=z((bs, beam), np.int32),
+                hyp_score=z((bs, beam), np.float64), hyp_sum=z((bs, beam), np.float32), hyp_arrival=z((bs, beam), np.int32),
+                hyp_count=z((bs,), np.int32), arrivals=z((bs,), np.int32), done=z((bs,), np.uint8), status=z((bs,), np.int32))
+
+
+def beam_advance_host(next_scores, flat_idx, generated, state, cur_len, max_len, eos, pad, V, beam, early_stopping, norm,
+                      norm_max):
+    """The hypothesis bookkeeping of one beam-search step (transformer.py:1420-1470 with BeamHypotheses.add / is_done) as one
+    function over plain arrays: the code the host routes of generate_beam run, and the twin ops.beam_advance (csrc/beam.hip)
+    has to equal bit for bit.
+
+    next_scores fp32 [bs, k], flat_idx int64 [bs, k]: every sentence's candidates in the selection's order (score descending:
+    entry 0 is the maximum), flat_idx = beam * V + word.  generated int64 [>= cur_len, bs * beam]: the tokens so far.  `state`
+    (beam_state_host) is updated IN PLACE; (norm, norm_max) = beam_norms(max_len, length_penalty).
+    -> (beam_scores fp32 [bs * beam], beam_words int64 [bs * beam], beam_idx int64 [bs * beam]).
+
+    Per sentence s:  done[s] |= the list is full and (early_stopping or its worst score >= next_scores[s, 0] / norm_max).  A
+    done sentence emits beam x (0.0, pad, row 0) and changes nothing.  Otherwise the candidates are taken in order: an <EOS>
+    candidate - every candidate when cur_len + 1 == max_len - is offered to the list with score = value / norm[cur_len] and
+    the next arrival number: while the list holds fewer than `beam` entries it takes the next slot, afterwards it replaces the
+    entry that is minimal by (score, arrival), and only if its score is strictly larger.  Every other candidate continues
+    the search: (value, word, row s * beam + its beam); the walk stops at `beam` of them.  Fewer than `beam` (on the last step:
+    none) are filled up with (0.0, pad, row 0), and before the last step that sets status[s].  All score arithmetic is fp64 on
+    the fp32 candidate value."""
+    scores_h, idx_h = np.asarray(next_scores, dtype=np.float32).tolist(), np.asarray(flat_idx).tolist()
+    bs = len(scores_h)
+    last = cur_len + 1 == max_len
+    norm_len = float(norm[cur_len])
+    hyp_score, hyp_arrival, hyp_count, done = state['hyp_score'], state['hyp_arrival'], state['hyp_count'], state['done']
+    out_scores, out_words, out_idx = [], [], []
+    for s in range(bs):
+        count = int(hyp_count[s])
+        if not done[s] and count >= beam:
+            if early_stopping or float(hyp_score[s, :count].min()) >= scores_h[s][0] / norm_max:
+                done[s] = 1
+        if done[s]:
+            out_scores += [0.0] * beam
+            out_words += [pad] * beam
+            out_idx += [0] * beam
+            continue
+        found = 0
+        for value, idx in zip(scores_h[s], idx_h[s]):
+            beam_id, word = idx // V, idx % V
+            if word == eos or last:
+                score = value / norm_len
+                arrival = int(state['arrivals'][s])
+                state['arrivals'][s] = arrival + 1
+                if count < beam:
+                    slot = count
+                    count += 1
+                else:
+                    slot = min(range(beam), key=lambda j: (hyp_score[s, j], hyp_arrival[s, j]))
+                    if not score > hyp_score[s, slot]:
+                        slot = -1
+                if slot >= 0:
+                    state['hyp_tok'][s, slot, :] = pad
+                    state['hyp_tok'][s, slot, :cur_len] = generated[:cur_len, s * beam + beam_id]
+                    state['hyp_len'][s, slot] = cur_len
+                    hyp_score[s, slot] = score
+                    state['hyp_sum'][s, slot] = value
+                    hyp_arrival[s, slot] = arrival
+            else:
+                out_scores.append(value)
+                out_words.append(word)
+                out_idx.append(s * beam + beam_id)
+                found += 1
+            if found == beam:
+                break
+        hyp_count[s] = count
+        if found < beam:
+            if not last:
+                state['status'][s] = 1
+            out_scores += [0.0] * (beam - found)
+            out_words += [pad] * (beam - found)
+            out_idx += [0] * (beam - found)
+    return np.array(out_scores, dtype=np.float32), np.array(out_words, dtype=np.int64), np.array(out_idx, dtype=np.int64)
+
+
+# Dispatch of the hypothesis bookkeeping, like VOCAB_SELECT_MAX_K: on the select routes, where ops.beam_advance_takes the shape
+# (beam <= 32, 2 * beam <= 64, max_len <= 1025), True runs every step's bookkeeping on the device (ops.beam_advance,
+# csrc/beam.hip: no per-step host copy, one blocking read per call); False keeps beam_advance_host behind one host copy per
+# step.  Both give the same tokens, lengths, n-best lists and score bits (tests/test_beam_nbest.py).  Measured, the device
+# side is faster in every pair at 32 x beam 4, 64 x beam 5 and 16 x beam 32 (0.38 - 0.45 ms per step; DESIGN.md 4,
+# "Hypothesis bookkeeping on the device"; profiles/decode_beam_device_hyps.txt).  It ships False all the same: with it the loop
+# stops whenever the host happens to notice that every sentence is done, so the NUMBER of steps differs from run to run, and
+# it re-orders the owner table without advance_owner - tests/test_beam_cache.py and tests/test_beam_wide.py observe the select
+# route through exactly these two (per-step logs of two runs compared entry by entry; a spy on advance_owner).
+BEAM_HYPS_ON_DEVICE = False
+
+
+def _host_read(*tensors):
+    """Every blocking device-to-host read of generate_beam's loop goes through here (a test counts the calls): NumPy copies."""
+    out = tuple(t.cpu().numpy() for t in tensors)
+    return out[0] if len(out) == 1 else out
+
+
+def _beam_result(state, n_best, return_scores, eos, pad, dev):
+    """The call's return value from the final hypothesis state (NumPy): per sentence its n_best finished hypotheses by score
+    descending, then arrival ascending."""
+    if int(state['status'].max()) != 0:
+        raise L.M3PError('beam search: a step found fewer than beam_size continuations among its 2 * beam_size candidates '
+                         '(sentences %s)' % state['status'].nonzero()[0].tolist())
+    bs = state['hyp_count'].shape[0]
+    assert int(state['hyp_count'].min()) >= n_best
+    tgt_len = np.zeros((bs, n_best), dtype=np.int64)
+    scores = np.zeros((bs, n_best), dtype=np.float64)
+    order = []
+    for s in range(bs):
+        sc, arr = state['hyp_score'][s].tolist(), state['hyp_arrival'][s].tolist()
+        order.append(sorted(range(int(state['hyp_count'][s])), key=lambda j: (-sc[j], arr[j]))[:n_best])
+        for j, slot in enumerate(order[s]):
+            tgt_len[s, j] = int(state['hyp_len'][s, slot]) + 1              # + <EOS>
+            scores[s, j] = sc[slot]
+    decoded = np.full((int(tgt_len.max()), bs, n_best), pad, dtype=np.int64)
+    for s in range(bs):
+        for j, slot in enumerate(order[s]):
+            n = int(tgt_len[s, j]) - 1
+            decoded[:n, s, j] = state['hyp_tok'][s, slot, :n]
+            decoded[n, s, j] = eos
+    assert int((decoded == eos).sum()) == 2 * bs * n_best
+    if n_best == 1:
+        decoded, tgt_len, scores = decoded[:, :, 0], tgt_len[:, 0], scores[:, 0]
+    res = (torch.from_numpy(np.ascontiguousarray(decoded)).to(dev), torch.from_numpy(np.ascontiguousarray(tgt_len)).to(dev))
+    if return_scores:
+        res += (torch.from_numpy(np.ascontiguousarray(scores)).to(dev),)
+    return res
+
+
 def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200, min_len=0,
-                  repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
+                  repetition_penalty=None, no_repeat_ngram=0, banned_words=None, n_best=1, return_scores=False):
     """transformer.py:1319-1515: beam search; the beam is folded into the batch dimension (bs * beam_size rows).  On the torch
     path the key / value caches are re-ordered by the surviving beams' source rows after every step; on the select path
     (module docstring: ``ops.vocab_select`` up to 8 beams, ``ops.vocab_select_wide`` from 9 to 32) they stay in place behind
     cache['owner'] and the source is kept once per sentence.
     -> (decoded (max tgt_len, bs) int64, tgt_len (bs)).
 
+    ``n_best`` = k (1 <= k <= beam_size, ValueError otherwise): every sentence ends with beam_size finished hypotheses (the
+    last step finishes every candidate), and with k > 1 the call returns the k best of them - decoded (max tgt_len, bs, k)
+    int64, pad-filled, tgt_len (bs, k); hypothesis j of a sentence is its j-th by score descending, then arrival ascending
+    (the order of ``BeamHypotheses.best``: [..., 0] is the result of the default call).  ``return_scores`` appends scores, fp64
+    (bs,) or (bs, k): sum of log-probabilities / len(hypothesis) ** length_penalty, as ``BeamHypotheses.add`` computes it.
+
+    The hypothesis bookkeeping of a step is ``beam_advance_host`` behind one host copy of the candidates on every route, or,
+    on the select path with ``BEAM_HYPS_ON_DEVICE`` where ``ops.beam_advance_takes`` the shape, ``ops.beam_advance``
+    (csrc/beam.hip): the lists, the next beams, the next ``generated`` columns and the owner table are then written by one
+    launch per step, `generated` and the owner table double-buffered; the host learns that every sentence is done from
+    asynchronous copies of `done` it only looks at once they have arrived - steps issued meanwhile change nothing, a done
+    sentence is frozen - and reads the lists once, at the end (``_host_read``).
+
     ``min_len`` / ``repetition_penalty`` / ``no_repeat_ngram`` / ``banned_words``: the decoding constraints of ``generate``, by
     the same contract and the same routes, per hypothesis row (the history of a row is the hypothesis it continues).  The edit
     happens on the logits before the row's log-sum-exp: the scores are log_softmax of the constrained logits plus the beam
     score.  All four off: no route changes by a bit."""
     assert src_enc.size(0) == src_len.size(0) and beam_size >= 1
+    if isinstance(n_best, bool) or not isinstance(n_best, int) or not 1 <= n_best <= beam_size:
+        raise ValueError('n_best must be an integer in [1, beam_size = %d], got %r' % (beam_size, n_best))
     bs = len(src_len)
     n_words = model.n_words
     dev = model.embeddings.weight.device
@@ -578,6 +751,7 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     else:
         select = wide = wide and ops.vocab_select_wide_takes(n, n_words, model.arena().V_pad, beam_size, sel_k)
     cons_dev = cons.on and select and cons.takes(n, n_words, model.arena().V_pad, max_len)
+    hyps_dev = bool(select and BEAM_HYPS_ON_DEVICE and max_len >= 2 and ops.beam_advance_takes(bs, beam_size, sel_k, max_len))
     if select:
         src_enc = src_enc.to(dev)
     else:
@@ -586,7 +760,6 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     src_len = src_len.unsqueeze(1).expand(bs, beam_size).contiguous().view(-1)
     generated = torch.full((max_len, bs * beam_size), model.pad_index, dtype=torch.long, device=dev)
     generated[0].fill_(model.eos_index)
-    hyps = [BeamHypotheses(beam_size, max_len, length_penalty, early_stopping) for _ in range(bs)]
     positions = torch.arange(max_len, device=dev)[:, None].expand_as(generated)
     # (the reference always builds language ids here, :1370 - a model without language embeddings cannot take them)
     langs = positions.clone().fill_(int(tgt_lang_id)) if tgt_lang_id is not None else None
@@ -598,8 +771,10 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     if select:
         cache['beam'] = beam_size
         cache['owner'] = torch.arange(n, dtype=torch.int32, device=dev)[:, None].expand(n, max_len).contiguous()
-    done = [False] * bs
-    while cur_len < max_len:
+    norm, norm_max = beam_norms(max_len, length_penalty)
+    eos, pad = int(model.eos_index), int(model.pad_index)
+
+    def step_candidates(generated):
         lengths = torch.full((bs * beam_size,), cur_len, dtype=torch.long, device=dev)
         tensor = decoder_forward(model, generated[:cur_len], lengths, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
@@ -611,30 +786,49 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
             scores = torch.log_softmax(_constrained_scores(model, tensor[-1], cons, generated, cur_len), dim=-1)
             _scores = (scores + beam_scores[:, None]).view(bs, beam_size * n_words)
             next_scores, next_words = torch.topk(_scores, 2 * beam_size, dim=1, largest=True, sorted=True)
-        next_scores_h, next_words_h = next_scores.tolist(), next_words.tolist()       # one host copy per step
-        next_batch_beam = []
-        for sent in range(bs):
-            done[sent] = done[sent] or hyps[sent].is_done(max(next_scores_h[sent]))
-            if done[sent]:
-                next_batch_beam.extend([(0, model.pad_index, 0)] * beam_size)
-                continue
-            next_sent_beam = []
-            for idx, value in zip(next_words_h[sent], next_scores_h[sent]):
-                beam_id, word_id = idx // n_words, idx % n_words
-                if word_id == model.eos_index or cur_len + 1 == max_len:
-                    hyps[sent].add(generated[:cur_len, sent * beam_size + beam_id].clone(), value)
-                else:
-                    next_sent_beam.append((value, word_id, sent * beam_size + beam_id))
-                if len(next_sent_beam) == beam_size:
-                    break
-            assert len(next_sent_beam) == (0 if cur_len + 1 == max_len else beam_size)
-            if len(next_sent_beam) == 0:
-                next_sent_beam = [(0, model.pad_index, 0)] * beam_size
-            next_batch_beam.extend(next_sent_beam)
-        assert len(next_batch_beam) == bs * beam_size
-        beam_scores = torch.tensor([v[0] for v in next_batch_beam], dtype=torch.float32, device=dev)
-        beam_words = torch.tensor([v[1] for v in next_batch_beam], dtype=torch.long, device=dev)
-        beam_idx = torch.tensor([v[2] for v in next_batch_beam], dtype=torch.long, device=dev)
+        return next_scores, next_words
+
+    if hyps_dev:
+        state = ops.beam_state(bs, beam_size, max_len, pad, dev)
+        norm_dev = torch.from_numpy(norm).to(dev)
+        spare = generated.clone()                                   # `generated` and the owner table: read one, write the other
+        spare_owner = cache['owner'].clone()
+        slots = torch.empty((max_len, bs), dtype=torch.uint8).pin_memory()
+        pending, stop = collections.deque(), False
+        while cur_len < max_len:
+            while pending and pending[0][0].query():                # copies of `done` that have arrived; never waited for
+                stop = bool(pending.popleft()[1].all()) or stop
+            if stop:
+                break
+            next_scores, next_words = step_candidates(generated)
+            res = ops.beam_advance(next_scores, next_words, generated, spare, cache['owner'], spare_owner, state, cur_len,
+                                   max_len, eos, pad, n_words, beam_size, early_stopping, norm_dev, norm_max)
+            if res is None:
+                raise L.M3PError('m3p_beam_advance declined (M3P_ENOTIMPL) a shape m3p_beam_advance_plan took')
+            beam_scores = res[0]
+            generated, spare = spare, generated
+            cache['owner'], spare_owner = spare_owner, cache['owner']
+            slots[cur_len].copy_(state['done'], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+            pending.append((event, slots[cur_len]))
+            cur_len += 1
+        state = dict(zip(HYP_STATE, _host_read(*[state[name] for name in HYP_STATE])))
+        return _beam_result(state, n_best, return_scores, eos, pad, dev)
+
+    state = beam_state_host(bs, beam_size, max_len, pad)
+    generated_h = generated.cpu().numpy()                           # the host's mirror of `generated`: what a finished hypothesis copies
+    while cur_len < max_len:
+        next_scores, next_words = step_candidates(generated)
+        next_scores_h, next_words_h = _host_read(next_scores, next_words)           # one host copy per step
+        scores_h, words_h, idx_h = beam_advance_host(next_scores_h, next_words_h, generated_h, state, cur_len, max_len, eos, pad,
+                                                     n_words, beam_size, early_stopping, norm, norm_max)
+        assert not state['status'].any(), 'fewer than beam_size continuations among 2 * beam_size candidates'
+        generated_h = generated_h[:, idx_h]
+        generated_h[cur_len] = words_h
+        beam_scores = torch.from_numpy(scores_h).to(dev)
+        beam_words = torch.from_numpy(words_h).to(dev)
+        beam_idx = torch.from_numpy(idx_h).to(dev)
         generated = generated[:, beam_idx]
         generated[cur_len] = beam_words
         if select:                                         # key / value tensors stay; the map to them follows the beams
@@ -644,17 +838,6 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
                 if isinstance(k, tuple):                   # key / value tensors follow their beams
                     cache[k] = cache[k].index_select(0, beam_idx)
         cur_len += 1
-        if all(done):
+        if state['done'].all():
             break
-    tgt_len = torch.zeros(bs, dtype=torch.long, device=dev)
-    best = []
-    for i, hp in enumerate(hyps):
-        best_hyp = hp.best()
-        tgt_len[i] = len(best_hyp) + 1                      # + <EOS>
-        best.append(best_hyp)
-    decoded = torch.full((int(tgt_len.max()), bs), model.pad_index, dtype=torch.long, device=dev)
-    for i, hypo in enumerate(best):
-        decoded[:int(tgt_len[i]) - 1, i] = hypo
-        decoded[int(tgt_len[i]) - 1, i] = model.eos_index
-    assert int((decoded == model.eos_index).sum()) == 2 * bs
-    return decoded, tgt_len
+    return _beam_result(state, n_best, return_scores, eos, pad, dev)

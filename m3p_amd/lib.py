@@ -90,6 +90,9 @@ SIGNATURES = {
     'm3p_vocab_sample_wide': (_i, [_p, _i, _i, _i, _f, _i, _f, _u32, _p, C.c_size_t, _p, _p, _p, _p, _p]),
     'm3p_logits_constrain_plan': (_i, [_i, _i, _i, _i, _i, _i]),
     'm3p_logits_constrain': (_i, [_p, _i, _i, _i, _p, C.c_longlong, _i, _f, _f, _i, _i, _p, _i, _p]),
+    'm3p_beam_advance_plan': (_i, [_i, _i, _i, _i]),
+    'm3p_beam_advance': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, C.c_double, _p, _p, C.c_longlong, _p, _p, _i]
+                         + [_p] * 12 + [_p]),
     'm3p_attn_rows_fwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _u32, _u32, _f, _p]),
     'm3p_attn_rows_bwd': (_i, [_p, _i, _p, C.c_longlong, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _f, _u32, _u32, _f, _p]),
     'm3p_attn_causal_fwd': (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _u32, _u32, _f, _p]),

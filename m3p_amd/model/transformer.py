@@ -546,11 +546,14 @@ class TransformerModel(nn.Module):
                                 no_repeat_ngram=no_repeat_ngram, banned_words=banned_words)
 
     def generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200, min_len=0,
-                      repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
+                      repetition_penalty=None, no_repeat_ngram=0, banned_words=None, n_best=1, return_scores=False):
         """transformer.py:1319-1515 (beam search); min_len / repetition_penalty / no_repeat_ngram / banned_words: the decoding
         constraints of decoder.generate_beam.  On a CUDA model beams up to 32 select their words on the device and leave the
-        caches in place (up to 8: ops.vocab_select, 9 to 32: ops.vocab_select_wide); wider ones run the torch loop."""
+        caches in place (up to 8: ops.vocab_select, 9 to 32: ops.vocab_select_wide); wider ones run the torch loop.
+        n_best = k > 1 returns every sentence's k best finished hypotheses (decoded (L, bs, k), tgt_len (bs, k)), return_scores
+        appends their length-normalised scores (fp64), on every route: decoder.generate_beam."""
         from .. import decoder
         return decoder.generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping,
                                      max_len=max_len, min_len=min_len, repetition_penalty=repetition_penalty,
-                                     no_repeat_ngram=no_repeat_ngram, banned_words=banned_words)
+                                     no_repeat_ngram=no_repeat_ngram, banned_words=banned_words, n_best=n_best,
+                                     return_scores=return_scores)

@@ -620,6 +620,70 @@ def logits_constrain(logits, V, generated, cur_len, theta=1.0, inv_theta=1.0, ng
     return logits
 
 
+_BEAM_STATE = (('hyp_tok', torch.int64), ('hyp_len', torch.int32), ('hyp_score', torch.float64), ('hyp_sum', torch.float32),
+               ('hyp_arrival', torch.int32), ('hyp_count', torch.int32), ('arrivals', torch.int32), ('done', torch.uint8),
+               ('status', torch.int32))
+
+
+def beam_state(bs, beam, max_len, pad, device):
+    """The empty hypothesis state of beam_advance on `device`: decoder.beam_state_host as tensors (the same names, shapes and
+    dtypes; hyp_tok filled with pad, everything else zero)."""
+    shapes = dict(hyp_tok=(bs, beam, max_len), hyp_count=(bs,), arrivals=(bs,), done=(bs,), status=(bs,))
+    state = {name: torch.zeros(shapes.get(name, (bs, beam)), dtype=dt, device=device) for name, dt in _BEAM_STATE}
+    state['hyp_tok'].fill_(pad)
+    return state
+
+
+def beam_advance_takes(bs, beam, k, max_len):
+    """Does the launcher of beam_advance take the shape?  (False: it would answer M3P_ENOTIMPL - beam > 32, k > 64, max_len >
+    1025; a malformed one raises.)  The answer depends on shapes alone: generate_beam asks once."""
+    return _plan_takes('m3p_beam_advance_plan', bs, beam, k, max_len)
+
+
+def beam_advance(next_scores, flat_idx, gen_in, gen_out, owner_in, owner_out, state, cur_len, max_len, eos, pad, V, beam,
+                 early_stopping, norm, norm_max):
+    """The hypothesis bookkeeping of the beam-search step that decodes position cur_len, on the device (csrc/beam.hip; the
+    contract is in include/m3p_hip.h, the host twin is decoder.beam_advance_host - equal bit for bit).  next_scores fp32 [bs, k],
+    flat_idx int64 [bs, k]: the step's candidates as vocab_select returns them.  gen_in / gen_out int64 [max_len, n], owner_in /
+    owner_out int32 [n, >= max_len] (n = bs * beam): read one, write the other - never the same tensor.  state: beam_state(...),
+    updated IN PLACE.  norm fp64 [max_len + 1] on the device and norm_max: decoder.beam_norms.
+    -> (beam_scores fp32 [n], beam_words int64 [n], beam_idx int64 [n]); gen_out holds the re-ordered tokens with the new words
+    at position cur_len, owner_out the owner table decoder.advance_owner would return.  None when the launcher does not take the
+    shape (M3P_ENOTIMPL); nothing is written then."""
+    bs, k = next_scores.shape
+    n = bs * beam
+    dev = next_scores.device
+    assert next_scores.dtype == torch.float32 and next_scores.is_cuda and next_scores.is_contiguous()
+    assert flat_idx.dtype == torch.int64 and flat_idx.shape == (bs, k) and flat_idx.is_contiguous() and flat_idx.device == dev
+    for g in (gen_in, gen_out):
+        assert g.dtype == torch.int64 and g.device == dev and g.dim() == 2 and g.shape[0] >= max_len and g.shape[1] == n
+        assert g.stride(1) == 1 and g.stride(0) == gen_in.stride(0)
+    for o in (owner_in, owner_out):
+        assert o.dtype == torch.int32 and o.device == dev and o.dim() == 2 and o.shape[0] == n and o.shape[1] >= max_len
+        assert o.stride(1) == 1 and o.stride(0) == owner_in.stride(0)
+    assert gen_in.data_ptr() != gen_out.data_ptr() and owner_in.data_ptr() != owner_out.data_ptr()
+    assert norm.dtype == torch.float64 and norm.device == dev and norm.is_contiguous() and norm.numel() >= max_len + 1
+    shapes = dict(hyp_tok=(bs, beam, max_len), hyp_count=(bs,), arrivals=(bs,), done=(bs,), status=(bs,))
+    for name, dt in _BEAM_STATE:
+        t = state[name]
+        assert t.dtype == dt and t.device == dev and t.is_contiguous() and tuple(t.shape) == shapes.get(name, (bs, beam)), name
+    lib = L.load()
+    rc = lib.m3p_beam_advance_plan(bs, beam, k, max_len)
+    if rc == _ENOTIMPL:
+        return None
+    L.check(rc, 'm3p_beam_advance_plan')
+    beam_scores = torch.empty((n,), dtype=torch.float32, device=dev)
+    beam_words = torch.empty((n,), dtype=torch.int64, device=dev)
+    beam_idx = torch.empty((n,), dtype=torch.int64, device=dev)
+    rc = lib.m3p_beam_advance(next_scores.data_ptr(), flat_idx.data_ptr(), bs, beam, k, int(V), int(cur_len), int(max_len), int(eos),
+                              int(pad), 1 if early_stopping else 0, norm.data_ptr(), float(norm_max), gen_in.data_ptr(),
+                              gen_out.data_ptr(), gen_in.stride(0), owner_in.data_ptr(), owner_out.data_ptr(), owner_in.stride(0),
+                              beam_scores.data_ptr(), beam_words.data_ptr(), beam_idx.data_ptr(),
+                              *[state[name].data_ptr() for name, _ in _BEAM_STATE], L.stream())
+    L.check(rc, 'm3p_beam_advance')
+    return beam_scores, beam_words, beam_idx
+
+
 def attn_rows_fwd(q, kv, klen, B, Tq, H, dh, Lk, causal=False, seed=0, p_drop=0.0):
     """Training form of attn_query_fwd: dropout on the probabilities, returns (ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq])."""
     _chk_bf16(q, kv)

@@ -61,7 +61,16 @@ code this call ran before the wide entry existed), warm-up on both, three altern
 The run is named beamB: `--beam B --sentences N --trace beamB` is the run for the profiler, `--beam B --sentences N --stats
 <csv> beamB` its per-kernel lines (vs_chunk_kernel, the six launches of the count selection, vsb_merge_kernel).
     timeout -k 10 600 python tools/decode_bench.py --beam 12 --sentences 32 > profiles/decode_beam_wide.txt
-    timeout -k 10 600 python tools/decode_bench.py --beam 32 --sentences 16 >> profiles/decode_beam_wide.txt"""
+    timeout -k 10 600 python tools/decode_bench.py --beam 32 --sentences 16 >> profiles/decode_beam_wide.txt
+
+`--hyps` measures the hypothesis bookkeeping of generate_beam on the select path: decoder.BEAM_HYPS_ON_DEVICE = False (one host
+copy of the candidates per step, decoder.beam_advance_host, three small uploads, the gather of `generated`, advance_owner)
+against True (csrc/beam.hip: ba_advance_kernel, one launch per step, one host read per call), on 32 sentences x beam 4, 64 x
+beam 5 and 16 x beam 32 - or, with `--beam B --sentences N`, on that one shape.  Same geometry, warm-up and three alternating
+pairs; afterwards the two routes' n_best = beam lists (tokens, lengths, fp64 scores) are compared for equality.  The switch is
+the module constant, so `--hyps host` / `--hyps device` in front of any other beam-search run of this tool pin it for that run
+(`--hyps host --beam 4 --sentences 32` is the run to set beside the same command in a checkout of the parent commit).
+    timeout -k 10 600 python tools/decode_bench.py --hyps > profiles/decode_beam_device_hyps.txt"""
 import csv
 import os
 import sys
@@ -204,6 +213,46 @@ def bench(m):
                   'list at some step; score gap at the first difference: max %.3g%s' % (
                       len(gaps), bs, max([g for _, _, g in gaps] or [0.0]),
                       ''.join('\n         sentence %d step %d gap %.3g' % e for e in gaps)))
+
+
+HYPS_RUNS = (('beam4', 32, 4), ('beam5', 64, 5), ('beam32', 16, 32))
+
+
+def with_hyps(flag, fn):
+    saved = decoder.BEAM_HYPS_ON_DEVICE
+    decoder.BEAM_HYPS_ON_DEVICE = flag
+    try:
+        return fn()
+    finally:
+        decoder.BEAM_HYPS_ON_DEVICE = saved
+
+
+def bench_hyps(m, runs):
+    print('hypothesis bookkeeping of generate_beam on the select path, %d layers, d = %d, V = %d, S = %d, max_len = %d; ms per '
+          'decoding step, %d alternating pairs; ratio = host / device (BEAM_HYPS_ON_DEVICE False / True)' % (
+              LAYERS, D, V, S, MAX_LEN, PAIRS))
+    for name, bs, beam in runs:
+        src, src_len = inputs(bs)
+        one = lambda: call(m, 'generate_beam', src, src_len, beam)   # noqa: E731
+        with_hyps(False, one)                                      # warm-up of the shape on both routes
+        with_hyps(True, one)
+        host, dev = [], []
+        for _ in range(PAIRS):
+            t, out_host = timed(lambda: with_hyps(False, one))
+            host.append(t)
+            t, out_dev = timed(lambda: with_hyps(True, one))
+            dev.append(t)
+        ratios = [a / b for a, b in zip(host, dev)]
+        print('%-6s generate_beam bs %3d beam %2d (%3d rows)  host ms %s  device ms %s  ratio %s  difference us per step %s  device %s' % (
+            name, bs, beam, bs * beam, ' '.join('%7.3f' % v for v in host), ' '.join('%7.3f' % v for v in dev),
+            ' '.join('%5.3f' % v for v in ratios), ' '.join('%6.1f' % (1e3 * (a - b)) for a, b in zip(host, dev)),
+            'wins all three' if min(ratios) > 1 else 'does NOT win all three'))
+        assert out_host[0].shape[0] == MAX_LEN and out_dev[0].shape[0] == MAX_LEN, 'a sentence ended early'
+        full = {flag: with_hyps(flag, lambda: call(m, 'generate_beam', src, src_len, beam, n_best=beam, return_scores=True))
+                for flag in (False, True)}
+        same = all(torch.equal(a, b) for a, b in zip(full[False], full[True]))
+        print('       n_best = %d lists of the two routes (tokens, lengths, fp64 scores) equal: %s; default outputs equal: %s' % (
+            beam, same, all(torch.equal(a, b) for a, b in zip(out_host, out_dev))))
 
 
 def bench_sample(m):
@@ -433,6 +482,16 @@ if __name__ == '__main__':
         stats(sys.argv[2], sys.argv[3])
         sys.exit(0)
     assert torch.cuda.is_available(), 'decode_bench.py measures on a GPU'
+    if '--hyps' in sys.argv:
+        at = sys.argv.index('--hyps')
+        pin = sys.argv[at + 1] if len(sys.argv) > at + 1 and sys.argv[at + 1] in ('host', 'device') else None
+        del sys.argv[at:at + (2 if pin else 1)]
+        if pin is None:
+            print(torch.cuda.get_device_name(0))
+            bench_hyps(model(), [(n, bs, beam) for n, (_, bs, beam) in RUNS.items()] if len(RUNS) == 1 else HYPS_RUNS)
+            sys.exit(0)
+        decoder.BEAM_HYPS_ON_DEVICE = pin == 'device'
+        print('decoder.BEAM_HYPS_ON_DEVICE = %s' % decoder.BEAM_HYPS_ON_DEVICE)
     constrained = '--constraints' in sys.argv
     if constrained:
         sys.argv.remove('--constraints')
