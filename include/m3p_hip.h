@@ -510,6 +510,18 @@ M3P_API int m3p_attn_causal_bwd(const void* qkv, int ld_qkv, const void* dctx, c
 M3P_API int m3p_attn_cross_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen,
                                void* ctx, float* lse, int B, int Tq, int H, int dh, int Lk, uint32_t seed, uint32_t thresh24,
                                float inv_keep, void* stream);
+/* PREFILL of a prompted decoding call on the same tiled MFMA body: causal attention of a block of Tq new queries over a
+ * key / value cache that already holds their own rows - exactly m3p_attn_query_fwd(causal = 1, klen = NULL,
+ * Lk = pos0 + Tq, pos0).  Layouts as m3p_attn_cross_fwd: q bf16 [B*Tq, ld_q], biased and scaled; key j of sequence b, head h
+ * at kv + b*kv_bstride + j*ld_kv + h*dh, its value H*dh elements further.  Query t (position pos0 + t) sees keys
+ * 0 .. pos0 + t; fp32 softmax, no dropout, no klen.  ctx bf16 [B*Tq, H*dh]; lse fp32 [B, H, Tq] (natural log) or NULL.
+ * Cache rows at or past pos0 + Tq are never read and may hold anything (NaN included).  With pos0 = 0 over a packed
+ * q | k | v buffer (kv = qkv + H*dh, ld_kv = ld_qkv, kv_bstride = T*ld_qkv) ctx and lse equal m3p_attn_causal_fwd without
+ * dropout bit for bit.  Forward only.
+ * dh in {32, 64}, 1 <= Tq <= 512, pos0 >= 0, pos0 + Tq <= 1024, strides multiples of 8 and 16-byte aligned q, kv, ctx; any
+ * other shape returns M3P_ENOTIMPL (the caller then keeps m3p_attn_query_fwd, a complete fallback). */
+M3P_API int m3p_attn_prefix_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, void* ctx, float* lse,
+                                int B, int Tq, int H, int dh, int pos0, void* stream);
 /* Backward: dq bf16 [B*Tq, ld_dq] = gradient of the UNSCALED query projection (x qscale, like m3p_attn_rows_bwd); dkv BF16
  * [B, Lk, ld_dkv] (keys | values per position, ld_dkv >= 2*H*dh): every one of the Lk rows' 2*H*dh columns is written
  * exactly once - fp32 accumulators rounded once, exact zeros for keys >= nk - so the caller zeroes nothing and casts

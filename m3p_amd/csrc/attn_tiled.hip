@@ -6,6 +6,9 @@
 //   source   the encoder-attention sub-layer of the seq2seq steps (crossfwd(..., src_enc=...), transformer.py:149-210 with
 //            kv = the source encoding): Tq query rows of every (sequence, head) attend the first nk = min(klen[b], Lk) rows
 //            of a separate key | value tensor, no causal mask.
+//   prefix   (forward only) the prefill of a prompted decoding call: Tq new queries behind pos0 positions of a key | value
+//            cache that already holds the new rows; query t attends keys 0 .. pos0 + t.  The causal mask shifted by pos0, so
+//            the diagonal is not tile-aligned: it is classified per wave and 16-key sub-tile (attn_fwd_body).
 //
 // The rows kernels of decode.hip serve short target sequences: a wave per (sequence, head, query), no MFMAs, and a backward
 // that adds dk / dv with two 64-float atomics per (query, key) pair.  This file computes what m3p_attn_rows_fwd / _bwd
@@ -127,6 +130,8 @@ __device__ __forceinline__ float xa_rounded(float v) {
 //   forward       source 4: left alone the DH = 64 instantiation takes 160 registers - three - and with the cap 128, still
 //                 without scratch, like the causal forward, which gets there unasked
 //   query blocks  source three (D) / two (dQ): one more than that spills at DH = 64, left alone both passes take two
+//   prefix fwd    not asked (CA_PREFIX_WAVES = 0, launch bounds 256 threads): DH = 64 takes 108 registers - four waves -, DH = 32
+//                 72 - five -, both without scratch: the occupancy of the causal forward
 //   key blocks    two for both: left alone the DH = 64 instantiation takes 276 registers - one wave per SIMD - and with the
 //                 cap 198 (causal), still without scratch
 // (The causal query-block kernels are also told that the pitches are positive, which the launchers have checked: row * pitch in the tile
@@ -136,6 +141,10 @@ enum CaKernel { CA_FWD, CA_BWD_D, CA_BWD_DQ, CA_BWD_KV };
 constexpr int ca_waves(CaKernel k, bool causal) {
   return k == CA_BWD_KV ? 2 : causal ? 0 : k == CA_FWD ? 4 : k == CA_BWD_D ? 3 : 2;
 }
+// The forward body knows three masks; the third, the prefix mask of a prefill (m3p_attn_prefix_fwd: Tq new queries behind pos0
+// cached positions, query t sees keys 0 .. pos0 + t), has a forward only and its own kernel name around the same body.
+enum CaMask { CA_SOURCE = 0, CA_CAUSAL = 1, CA_PREFIX = 2 };
+constexpr int CA_PREFIX_WAVES = 0;
 
 // query block of a workgroup.  Causal work grows with the query block: heaviest (last) query blocks first.  (Key blocks are
 // handed out in plain order under both masks: causal work shrinks with the key block.)
@@ -148,28 +157,31 @@ template <bool CAUSAL> __device__ __forceinline__ int query_block(int BH, int Tq
 // ---------------------------------------------------------------------------------------
 // forward: workgroup = (sequence, head, 64-query block), wave = 16 queries, lane = query column fq, keys 4 fg + r of a tile
 // ---------------------------------------------------------------------------------------
-template <int DH, bool CAUSAL>
-__global__ __launch_bounds__(256, ca_waves(CA_FWD, CAUSAL)) void attn_fwd_kernel(
+template <int DH, int MASK>
+__device__ __forceinline__ void attn_fwd_body(
     const bf16* __restrict__ q, int ld_q, const bf16* __restrict__ kv, long long kv_bstride, int ld_kv,
     const int32_t* __restrict__ klen, bf16* __restrict__ ctx, float* __restrict__ lse, int Tq, int H, int BH, int Lk,
     uint32_t seed, uint32_t thresh24, float inv_keep) {
   using Cf = CaCfg<DH>;
+  constexpr bool CAUSAL = MASK == CA_CAUSAL, PREFIX = MASK == CA_PREFIX;
   __shared__ __attribute__((aligned(16))) char sK[Cf::TILEB];
   __shared__ __attribute__((aligned(16))) char sV[Cf::TILEB];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fq = lane & 15, fg = lane >> 4;
-  const int qb = query_block<CAUSAL>(BH, Tq);
+  const int qb = query_block<CAUSAL || PREFIX>(BH, Tq);
   const int bh = (int)(blockIdx.x % BH), b = bh / H, h = bh - b * H;
   const int d = H * DH;
-  if constexpr (CAUSAL) __builtin_assume(ld_q > 0 && ld_kv > 0);      // (see ca_waves)
-  const int nk = CAUSAL ? Lk : xa_nkeys(klen, b, Lk);      // (causal: every key exists, klen is not read)
-  const int nkt = CAUSAL ? qb + 1 : (nk + 63) >> 6;      // key tiles: up to the diagonal / holding a key
+  if constexpr (CAUSAL || PREFIX) __builtin_assume(ld_q > 0 && ld_kv > 0);      // (see ca_waves)
+  const int nk = (CAUSAL || PREFIX) ? Lk : xa_nkeys(klen, b, Lk);      // (causal, prefix: every key exists, klen is not read)
+  const int pos0 = Lk - Tq;      // prefix: query t sits at position pos0 + t of the cache
+  // key tiles: up to the diagonal (prefix: of the block's last existing row) / holding a key
+  const int nkt = CAUSAL ? qb + 1 : PREFIX ? ((pos0 + min(64 * qb + 63, Tq - 1)) >> 6) + 1 : (nk + 63) >> 6;
   const bf16* Qg = q + (size_t)b * Tq * ld_q + h * DH;
   const bf16* Kg = kv + (size_t)b * kv_bstride + h * DH;
   const bf16* Vg = Kg + d;
   const int qrow = qb * 64 + wid * 16 + fq;
-  const bool wave_on = CAUSAL || qb * 64 + wid * 16 < Tq;      // source: (wave-uniform) at least one of this wave's rows exists
+  const bool wave_on = CAUSAL || qb * 64 + wid * 16 < Tq;      // source, prefix: (wave-uniform) at least one of this wave's rows exists
   bf16x8 qf[Cf::KK];
 #pragma unroll
   for (int kk = 0; kk < Cf::KK; ++kk)
@@ -201,10 +213,17 @@ __global__ __launch_bounds__(256, ca_waves(CA_FWD, CAUSAL)) void attn_fwd_kernel
     }
     if (!wave_on) continue;
     // 16-key sub-tiles 0 .. nsub - 1 are computed (every wave has sub-tile 0), the last of them masked per element where
-    // the tile is the diagonal one (causal: sub-tiles at or below this wave's queries) or the ragged last one (source)
+    // the tile is the diagonal one (causal: sub-tiles at or below this wave's queries) or the ragged last one (source).
+    // Prefix: the diagonal of this wave's first row enters the tile at key dlt (wave-uniform; negative: the tile lies above
+    // the wave, beyond 63: below it).  Sub-tiles 0 .. nfull - 1 are wholly visible to all 16 rows, nfull .. nsub - 1 (at most
+    // two, and they may fall into two key tiles) are crossed by the diagonal and masked per element, the rest is skipped;
+    // tile 0 always has nsub >= 1 (key 0 is visible to every query), so m is finite from the first tile on.
     const bool diag = CAUSAL && kt == qb;
-    const int rem = CAUSAL ? 64 : nk - 64 * kt;        // keys of this tile that exist (>= 1)
-    const int nsub = CAUSAL ? (diag ? wid + 1 : 4) : (rem >= 64 ? 4 : (rem + 15) >> 4);
+    const int rem = (CAUSAL || PREFIX) ? 64 : nk - 64 * kt;        // keys of this tile that exist (>= 1)
+    const int dlt = PREFIX ? pos0 + qb * 64 + wid * 16 - 64 * kt : 0;
+    const int nfull = PREFIX ? (dlt + 1) >> 4 : 0;
+    const int nsub = CAUSAL ? (diag ? wid + 1 : 4) : PREFIX ? min(max((dlt + 31) >> 4, 0), 4) : (rem >= 64 ? 4 : (rem + 15) >> 4);
+    if (PREFIX && nsub == 0) continue;
     f32x4 s[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -222,9 +241,11 @@ __global__ __launch_bounds__(256, ca_waves(CA_FWD, CAUSAL)) void attn_fwd_kernel
     for (int t = 0; t < 4; ++t) {
       if (t >= nsub) {
         s[t] = f32x4{CA_MASKED, CA_MASKED, CA_MASKED, CA_MASKED};
-      } else if (CAUSAL ? diag && t == wid : t == nsub - 1 && rem < 64) {
+      } else if (CAUSAL ? diag && t == wid : PREFIX ? t >= nfull : t == nsub - 1 && rem < 64) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) s[t][r] = (CAUSAL ? 4 * fg + r <= fq : 16 * t + 4 * fg + r < rem) ? s[t][r] : CA_MASKED;
+        for (int r = 0; r < 4; ++r)
+          s[t][r] = (CAUSAL ? 4 * fg + r <= fq : PREFIX ? 16 * t + 4 * fg + r <= dlt + fq : 16 * t + 4 * fg + r < rem) ? s[t][r]
+                                                                                                                    : CA_MASKED;
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[t][r]);
@@ -256,7 +277,7 @@ __global__ __launch_bounds__(256, ca_waves(CA_FWD, CAUSAL)) void attn_fwd_kernel
       for (int hf = 0; hf < 2; ++hf) {
         const int t = 2 * kk2 + hf;
         float kf4[4] = {1.f, 1.f, 1.f, 1.f};
-        if (thresh24 != 0 && t < nsub) keep4(rbase + (uint32_t)(64 * kt + 16 * t + 4 * fg), seed, thresh24, 1.f, kf4);
+        if (!PREFIX && thresh24 != 0 && t < nsub) keep4(rbase + (uint32_t)(64 * kt + 16 * t + 4 * fg), seed, thresh24, 1.f, kf4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) p8[4 * hf + r] = s[t][r] * kf4[r];
       }
@@ -273,13 +294,31 @@ __global__ __launch_bounds__(256, ca_waves(CA_FWD, CAUSAL)) void attn_fwd_kernel
   }
   if (qrow < Tq) {
     // (nk == 0 - a sequence without keys: the loop never ran, l = 0 - gives ctx = 0 and lse = 0 like the rows kernels)
-    const bool keys = CAUSAL || nk > 0;
+    const bool keys = CAUSAL || PREFIX || nk > 0;
     const float inv = keys ? inv_keep / l : 0.f;
     bf16* orow = ctx + ((size_t)b * Tq + qrow) * d + h * DH + 4 * fg;
 #pragma unroll
     for (int n = 0; n < Cf::NT; ++n) *reinterpret_cast<bf16x4*>(orow + 16 * n) = ca_round4(o[n], inv);
-    if (fg == 0) lse[(size_t)bh * Tq + qrow] = keys ? m + __logf(l) : 0.f;
+    if (fg == 0 && (!PREFIX || lse)) lse[(size_t)bh * Tq + qrow] = keys ? m + __logf(l) : 0.f;      // (prefix: lse may be NULL)
   }
+}
+
+// The kernels around the one body.  attn_fwd_kernel<DH, CAUSAL> keeps its name, template parameters and arguments: the
+// resource test reads its four instantiations off their mangled names.
+template <int DH, bool CAUSAL>
+__global__ __launch_bounds__(256, ca_waves(CA_FWD, CAUSAL)) void attn_fwd_kernel(
+    const bf16* __restrict__ q, int ld_q, const bf16* __restrict__ kv, long long kv_bstride, int ld_kv,
+    const int32_t* __restrict__ klen, bf16* __restrict__ ctx, float* __restrict__ lse, int Tq, int H, int BH, int Lk,
+    uint32_t seed, uint32_t thresh24, float inv_keep) {
+  attn_fwd_body<DH, CAUSAL ? CA_CAUSAL : CA_SOURCE>(q, ld_q, kv, kv_bstride, ld_kv, klen, ctx, lse, Tq, H, BH, Lk, seed, thresh24,
+                                                    inv_keep);
+}
+// the prefix mask: Lk = pos0 + Tq keys, no klen, no dropout
+template <int DH>
+__global__ __launch_bounds__(256, CA_PREFIX_WAVES) void attn_prefix_fwd_kernel(
+    const bf16* __restrict__ q, int ld_q, const bf16* __restrict__ kv, long long kv_bstride, int ld_kv, bf16* __restrict__ ctx,
+    float* __restrict__ lse, int Tq, int H, int BH, int Lk) {
+  attn_fwd_body<DH, CA_PREFIX>(q, ld_q, kv, kv_bstride, ld_kv, nullptr, ctx, lse, Tq, H, BH, Lk, 0u, 0u, 1.f);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -593,6 +632,13 @@ template <bool CAUSAL, class... A> int ca_fwd(int dh, A... a) {
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
+template <int DH>
+void ca_launch_prefix_fwd(hipStream_t st, const bf16* q, int ld_q, const bf16* kv, long long kv_bstride, int ld_kv, bf16* ctx,
+                          float* lse, int B, int Tq, int H, int Lk) {
+  const int BH = B * H;
+  hipLaunchKernelGGL((attn_prefix_fwd_kernel<DH>), dim3((unsigned)((Tq + 63) / 64 * BH)), dim3(256), 0, st, q, ld_q, kv, kv_bstride,
+                     ld_kv, ctx, lse, Tq, H, BH, Lk);
+}
 template <bool CAUSAL, class... A> int ca_bwd(int dh, A... a) {
   if (dh == 64) ca_launch_bwd<64, CAUSAL>(a...);
   else ca_launch_bwd<32, CAUSAL>(a...);
@@ -643,6 +689,22 @@ int m3p_attn_cross_fwd(const void* q, int ld_q, const void* kv, long long kv_bst
     return M3P_ENOTIMPL;
   return ca_fwd<false>(dh, (hipStream_t)stream, (const bf16*)q, ld_q, (const bf16*)kv, kv_bstride, ld_kv, klen, (bf16*)ctx, lse, B,
                        Tq, H, Lk, seed, thresh24, inv_keep);
+}
+
+// The prefill: the queries are the last Tq of Lk = pos0 + Tq positions, and the kernel reads pos0 back as Lk - Tq.
+int m3p_attn_prefix_fwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, void* ctx, float* lse, int B,
+                        int Tq, int H, int dh, int pos0, void* stream) {
+  if (!q || !kv || !ctx || B <= 0 || Tq <= 0 || H <= 0 || pos0 < 0) return M3P_EINVAL;
+  // (no dropout, so no bound from the stream index; pos0 is compared on its own before pos0 + Tq could overflow)
+  if ((dh != 32 && dh != 64) || Tq > CA_MAX_T || pos0 > XA_MAX_KEYS || pos0 + Tq > XA_MAX_KEYS) return M3P_ENOTIMPL;
+  if (ld_q < H * dh || ld_kv < 2 * H * dh) return M3P_EINVAL;
+  if ((ld_q % 8) != 0 || (ld_kv % 8) != 0 || (kv_bstride % 8) != 0 || ca_misaligned(q) || ca_misaligned(kv) || ca_misaligned(ctx))
+    return M3P_ENOTIMPL;
+  const hipStream_t st = (hipStream_t)stream;
+  if (dh == 64) ca_launch_prefix_fwd<64>(st, (const bf16*)q, ld_q, (const bf16*)kv, kv_bstride, ld_kv, (bf16*)ctx, lse, B, Tq, H, pos0 + Tq);
+  else ca_launch_prefix_fwd<32>(st, (const bf16*)q, ld_q, (const bf16*)kv, kv_bstride, ld_kv, (bf16*)ctx, lse, B, Tq, H, pos0 + Tq);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
 }
 
 int m3p_attn_cross_bwd(const void* q, int ld_q, const void* kv, long long kv_bstride, int ld_kv, const int32_t* klen,

@@ -34,6 +34,10 @@ Both loops take decoding constraints - ``min_len``, ``repetition_penalty``, ``no
 for every route (include/m3p_hip.h: m3p_logits_constrain): where the words are selected on the device, ``ops.logits_constrain``
 (csrc/constrain.hip) edits the step's bf16 logits in place in front of the selection kernels, everywhere else the torch twin
 ``constrain_scores_`` edits ``word_scores``; with all four off no route changes by a bit.
+Both loops can start from a prompt (``prefix`` / ``prefix_len``; with it no source encoding is needed: generation from the
+causal language model): the common part of the prompts is prefilled by ONE ``decoder_forward`` call - several new positions
+over the cache, on the prefix mask of the tiled MFMA forward (``ops.attn_prefix_fwd``, csrc/attn_tiled.hip) from
+``PREFILL_TILED_MIN_T`` positions on - and the rest of longer prompts is forced step by step behind the selection.
 
 This module is forward only; the teacher-forced training pass of the same stream is ``functional.DecoderFn``
 (``TransformerModel.crossfwd`` picks it in training mode), and calling ``decoder_forward`` itself with autograd enabled on
@@ -64,6 +68,16 @@ VOCAB_SELECT_MAX_K = 16
 # set by measurement ("Beam search beyond 8 beams"; profiles/decode_beam_wide.txt).
 BEAM_SELECT_WIDE_MIN_K = 17
 BEAM_SELECT_WIDE_MAX_K = 64
+
+# Dispatch of the self-attention of a cached call that brings several new positions (the prefill of a prompted generate /
+# generate_beam) over a cache that asks for it (cache['tiled_prefill'], which the two loops set; any other cache keeps the
+# decoding kernels): from PREFILL_TILED_MIN_T new positions on, where no owner table is in use and the launcher takes the shape,
+# it runs on ops.attn_prefix_fwd (csrc/attn_tiled.hip) over the layer's cache tensor, and the encoder attention of that call
+# on ops.attn_cross_fwd by functional.cross_attn_tiled; below it, and for the single new position of every later step, the
+# rows kernel stays.  0 switches the route off; a value below 8 is not allowed (callers feed short first pieces through the
+# cache and rely on their bits).  The value is the smallest measured Tq from which the tiled kernel won every alternation
+# (tools/bench_prefill.py, profiles/decode_prefill.txt; DESIGN.md 4, "Prompted decoding and the prefill kernel").
+PREFILL_TILED_MIN_T = 8
 
 # Stream-key site of the seeded sampling draws (rng.stream_seed(sample_seed, position, SAMPLE_SITE)): outside the dropout
 # sites of the encoder (< 2^20), the refiner (functional._REF_SITE0 = 2^20 + ...) and the causal stream (_DEC_SITE0 = 2^21 + ...).
@@ -169,7 +183,13 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
                 cache['cross_owner'] = xowner = (torch.arange(bs, device=dev) // beam).to(torch.int32)
     # without a cache every position is scored at once: the attentions of the training pass, by its rules, without dropout
     tiled = cache is None and slen >= Fn.CAUSAL_TILED_MIN_T
-    xtiled = cache is None and src_enc is not None and Fn.cross_attn_tiled(slen, S)
+    # with a cache, several new positions at once are a prefill: the prefix mask of the tiled forward over the layer's cache
+    # (caches that stay in place behind an owner table keep the rows kernel, which reads through it).  The cache asks for it
+    # (cache['tiled_prefill'], set by generate / generate_beam): a bare {'slen': 0} cache keeps the decoding kernels for
+    # every call, as it always did
+    assert PREFILL_TILED_MIN_T == 0 or PREFILL_TILED_MIN_T >= 8
+    prefill = cache is not None and bool(cache.get('tiled_prefill')) and owner is None and 1 <= PREFILL_TILED_MIN_T <= n_new
+    xtiled = (cache is None or (prefill and beam == 1)) and src_enc is not None and Fn.cross_attn_tiled(n_new, S)
     for i in range(model.n_layers):
         a, f = 'attentions.%d.' % i, 'ffns.%d.' % i
         wqkv, bqkv = ar.qkv_w16(i), ar.qkv_bias(i)
@@ -190,7 +210,13 @@ def decoder_forward(model, x, lengths, src_enc=None, src_len=None, positions=Non
                 store[:, pos0:slen] = kv
                 kv = store
             assert owner is None or (owner.shape[0] == bs and owner.shape[1] >= slen)
-            ctx = ops.attn_query_fwd(q, kv, None, bs, n_new, H, dh, slen, causal=True, pos0=pos0, owner=owner)
+            res = ops.attn_prefix_fwd(q, kv, bs, n_new, H, dh, pos0) if prefill else None
+            if res is None:                 # (the first layer decides for the pass, as above)
+                assert i == 0 or not prefill
+                prefill = False
+                ctx = ops.attn_query_fwd(q, kv, None, bs, n_new, H, dh, slen, causal=True, pos0=pos0, owner=owner)
+            else:
+                ctx = res[0]
         pre = ops.gemm_nt(ctx, ar.w(a + 'out_lin.weight'), L.EPI_BIAS_DROP_RES, bias=ar.p(a + 'out_lin.bias'), aux=h16)
         h16, _, _ = ops.layernorm_fwd(pre, ar.p('layer_norm1.%d.weight' % i), ar.p('layer_norm1.%d.bias' % i))
         if cw is not None:
@@ -388,8 +414,61 @@ def _constrained_scores(model, tensor, cons, generated, cur_len):
     return scores
 
 
+class _Prefix:
+    """The forced target prefix of one generate / generate_beam call, validated once.  prefix int64 (P, bs), prefix_len (bs)
+    with 0 <= prefix_len[b] <= P: sentence b starts <EOS>, prefix[0, b], ..., prefix[prefix_len[b] - 1, b].  `lo` / `hi` are
+    the shortest / longest length; the loop prefills positions 0 .. lo in one decoder_forward call and forces the rest of the
+    longer prompts step by step (`force`).  Both None: no prefix (`on` False, and the loops run exactly as without the keywords)."""
+
+    def __init__(self, model, prefix, prefix_len, bs, max_len, dev, equal=False):
+        self.on = prefix is not None
+        self.lo = self.hi = 0
+        if not self.on:
+            if prefix_len is not None:
+                raise ValueError('prefix_len needs prefix')
+            return
+        if prefix_len is None:
+            raise ValueError('prefix needs prefix_len')
+        prefix, plen = torch.as_tensor(prefix).to(dev).long(), torch.as_tensor(prefix_len).to(dev).long()
+        if prefix.dim() != 2 or plen.dim() != 1 or prefix.size(1) != plen.size(0) or (bs is not None and plen.size(0) != bs):
+            raise ValueError('prefix must be (P, bs) with prefix_len (bs), got %s and %s' % (tuple(prefix.shape), tuple(plen.shape)))
+        P = prefix.size(0)
+        if plen.numel() == 0:
+            raise ValueError('prefix holds no sentence')
+        self.lo, self.hi = int(plen.min()), int(plen.max())
+        if self.lo < 0 or self.hi > P:
+            raise ValueError('prefix_len must lie in [0, P = %d], got [%d, %d]' % (P, self.lo, self.hi))
+        if equal and self.lo != self.hi:
+            raise ValueError('beam search takes prefixes of equal length only (all prefix_len equal), got [%d, %d]'
+                             % (self.lo, self.hi))
+        if 1 + self.hi > max_len - 1:
+            raise ValueError('the prefix is too long: 1 + max(prefix_len) = %d > max_len - 1 = %d (position max_len - 1 is the '
+                             'forced <EOS>)' % (1 + self.hi, max_len - 1))
+        inside = torch.arange(P, device=dev)[:, None] < plen[None, :]
+        bad = inside & ((prefix == model.eos_index) | (prefix == model.pad_index) | (prefix < 0) | (prefix >= model.n_words))
+        if bool(bad.any()):
+            raise ValueError('a prefix word is <EOS>, pad or outside [0, n_words = %d)' % model.n_words)
+        self.words, self.len = prefix, plen
+
+    def fill(self, generated, rows_per_sentence=1):
+        """The common part of the prompts into generated[1 : 1 + lo] -> the position the loop starts at."""
+        if self.lo:
+            generated[1:1 + self.lo] = self.words[:self.lo].repeat_interleave(rows_per_sentence, dim=1)
+        return 1 + self.lo
+
+    def force(self, next_words, cur_len, step_logprob=None):
+        """The words of the step that decodes position cur_len, with the prompts that reach it put in place (log-probability 0)."""
+        if cur_len > self.hi:
+            return next_words, step_logprob
+        forced = self.len >= cur_len
+        if step_logprob is not None:
+            step_logprob = step_logprob.masked_fill(forced, 0.0)
+        return torch.where(forced, self.words[cur_len - 1].to(next_words.dtype), next_words), step_logprob
+
+
 def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, sample_seed=None, sample_top_k=None,
-             return_logprobs=False, sample_top_p=None, min_len=0, repetition_penalty=None, no_repeat_ngram=0, banned_words=None):
+             return_logprobs=False, sample_top_p=None, min_len=0, repetition_penalty=None, no_repeat_ngram=0, banned_words=None,
+             prefix=None, prefix_len=None):
     """transformer.py:1216-1317: greedy (or temperature-sampled) decoding with the key / value cache.
     -> (generated (cur_len, bs) int64, gen_len (bs)).
 
@@ -424,7 +503,20 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     once, with max_len - 1 as the history bound), ``ops.logits_constrain`` edits the bf16 logits in place - one launch per
     step - and the selection runs unchanged behind it; a declined shape gets the twin ``constrain_scores_`` on those logits, and
     every torch route (greedy, seeded, ``torch.multinomial``) the twin on ``word_scores``.  Log-probabilities are those of the
-    constrained distribution."""
+    constrained distribution.
+
+    Prompted decoding: ``prefix`` int64 (P, bs) with ``prefix_len`` (bs), 0 <= prefix_len[b] <= P, forces the first words of
+    every sentence: ``generated[1 : 1 + prefix_len[b], b] = prefix[:prefix_len[b], b]`` behind the leading <EOS>.  A prefix
+    word inside its length that is <EOS>, pad or outside [0, n_words), and 1 + max(prefix_len) > max_len - 1, raise
+    ValueError.  With a prefix ``src_enc = src_len = None`` is allowed (a zero-length prefix too: it gives bs): the model
+    then decodes without the encoder-attention sub-layer - generation from a causal language model.  The ragged rule: the
+    loop starts at cur_len = 1 + min(prefix_len), and its first ``decoder_forward`` call covers positions 0 .. cur_len - 1 at
+    once - the prefill, on the tiled prefix kernel from ``PREFILL_TILED_MIN_T`` positions on; only this common part of the
+    prompts is prefilled.  The rest of the longer prompts is forced step by step: at the step that decodes position cur_len
+    the rows with 1 + prefix_len[b] > cur_len take ``prefix[cur_len - 1, b]`` in place of the selected word, on every route
+    (the selection still runs for the whole batch: stream keys and counters are those of the unprompted call).  Returned
+    log-probabilities are 0 at prefix positions.  The constraints' history is ``generated[1:cur_len]``, prefix included, and
+    ``min_len`` counts prefix words.  Without ``prefix`` nothing changes by a bit."""
     seeded = sample_seed is not None
     if sample_top_k is not None and not seeded:
         raise ValueError('sample_top_k needs sample_seed: the torch sampling path has no top-k mode')
@@ -436,21 +528,27 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     top_k = int(sample_top_k or 0)
     if top_k < 0:
         raise ValueError('sample_top_k must be >= 0, got %r' % (sample_top_k,))
-    bs = len(src_len)
-    assert src_enc.size(0) == bs
     dev = model.embeddings.weight.device
+    if (src_enc is None) != (src_len is None):
+        raise ValueError('src_enc and src_len come together (both None: decoder-only generation from a prefix)')
+    if src_enc is None and prefix is None:
+        raise ValueError('generation without a source encoding needs a prefix (a zero-length one gives the batch size)')
+    bs = len(src_len) if src_len is not None else int(torch.as_tensor(prefix_len).numel()) if prefix_len is not None else None
+    assert src_enc is None or src_enc.size(0) == bs
+    pre = _Prefix(model, prefix, prefix_len, bs, max_len, dev)
     cons = _Constraints(model, max_len, min_len, repetition_penalty, no_repeat_ngram, banned_words, dev)
-    src_len = src_len.to(dev)
+    if src_len is not None:
+        src_len = src_len.to(dev)
     generated = torch.full((max_len, bs), model.pad_index, dtype=torch.long, device=dev)
     generated[0].fill_(model.eos_index)                       # <EOS> doubles as <BOS>
     positions = torch.arange(max_len, device=dev)[:, None].expand(max_len, bs)
     langs = None
     if tgt_lang_id is not None:
         langs = torch.full((max_len, bs), int(tgt_lang_id), dtype=torch.long, device=dev)
-    cur_len = 1
-    gen_len = torch.ones(bs, dtype=torch.long, device=dev)
+    cur_len = pre.fill(generated)          # (1 without a prefix; else the first call covers positions 0 .. cur_len - 1: the prefill)
+    gen_len = torch.full((bs,), cur_len, dtype=torch.long, device=dev)
     unfinished = torch.ones(bs, dtype=torch.long, device=dev)
-    cache = {'slen': 0, 'max_len': max_len}
+    cache = {'slen': 0, 'max_len': max_len, 'tiled_prefill': True}
     # (a launcher that would answer M3P_ENOTIMPL - it is asked once, the answer depends on the shape alone - leaves the torch path)
     select = (sample_temperature is None and not seeded and dev.type == 'cuda' and VOCAB_SELECT_MAX_K >= 1
               and ops.vocab_select_takes(bs, model.n_words, model.arena().V_pad, 1, 1))
@@ -475,7 +573,8 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
     while cur_len < max_len:
         tensor = decoder_forward(model, generated[:cur_len], gen_len, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
-        assert tensor.size() == (1, bs, model.dim)
+        assert tensor.size()[1:] == (bs, model.dim) and tensor.size(0) in (1, cur_len)      # (cur_len rows: the prefill)
+        step_logprob = None
         if seeded:
             step_seed = rng.stream_seed(sample_seed, cur_len, SAMPLE_SITE)
             if sample_dev:
@@ -487,8 +586,6 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
             else:
                 next_words, step_logprob = _sample_twin(_constrained_scores(model, tensor[-1], cons, generated, cur_len), inv_t,
                                                         step_seed, top_k, top_p)
-            if return_logprobs:
-                logprobs[cur_len] = step_logprob.masked_fill(unfinished == 0, 0.0)
         elif select:                   # the first maximum of each row, from the bf16 logits
             logits, V = _constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len)
             next_words = _select(logits, V, None, 1, 1)[1].squeeze(1)
@@ -497,6 +594,10 @@ def generate(model, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperatu
         else:
             scores = _constrained_scores(model, tensor[-1], cons, generated, cur_len)
             next_words = torch.multinomial(torch.softmax(scores / sample_temperature, dim=1), 1).squeeze(1)
+        if pre.on:                     # rows whose prompt reaches this position take its word, on every route
+            next_words, step_logprob = pre.force(next_words, cur_len, step_logprob)
+        if return_logprobs:
+            logprobs[cur_len] = step_logprob.masked_fill(unfinished == 0, 0.0)
         generated[cur_len] = next_words * unfinished + model.pad_index * (1 - unfinished)
         gen_len.add_(unfinished)
         unfinished.mul_(next_words.ne(model.eos_index).long())
@@ -707,7 +808,8 @@ def _beam_result(state, n_best, return_scores, eos, pad, dev):
 
 
 def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200, min_len=0,
-                  repetition_penalty=None, no_repeat_ngram=0, banned_words=None, n_best=1, return_scores=False):
+                  repetition_penalty=None, no_repeat_ngram=0, banned_words=None, n_best=1, return_scores=False, prefix=None,
+                  prefix_len=None):
     """transformer.py:1319-1515: beam search; the beam is folded into the batch dimension (bs * beam_size rows).  On the torch
     path the key / value caches are re-ordered by the surviving beams' source rows after every step; on the select path
     (module docstring: ``ops.vocab_select`` up to 8 beams, ``ops.vocab_select_wide`` from 9 to 32) they stay in place behind
@@ -730,15 +832,27 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     ``min_len`` / ``repetition_penalty`` / ``no_repeat_ngram`` / ``banned_words``: the decoding constraints of ``generate``, by
     the same contract and the same routes, per hypothesis row (the history of a row is the hypothesis it continues).  The edit
     happens on the logits before the row's log-sum-exp: the scores are log_softmax of the constrained logits plus the beam
-    score.  All four off: no route changes by a bit."""
-    assert src_enc.size(0) == src_len.size(0) and beam_size >= 1
+    score.  All four off: no route changes by a bit.
+
+    ``prefix`` / ``prefix_len``: the forced target prefix of ``generate``, by the same rules, but all prefix_len must be equal
+    (ValueError otherwise); ``src_enc = src_len = None`` is allowed with it.  The loop starts at cur_len = 1 + prefix_len and
+    its first call prefills positions 0 .. cur_len - 1 on the expanded bs * beam_size rows (the select routes read the cache
+    through the owner table and keep the rows kernel for it).  Beam scores start as without a prefix - the prefix adds 0 -
+    so a hypothesis' score is the sum of the GENERATED words' log-probabilities over its total length, prefix included, to
+    the power length_penalty.  Without ``prefix`` nothing changes by a bit."""
+    assert beam_size >= 1
+    if (src_enc is None) != (src_len is None):
+        raise ValueError('src_enc and src_len come together (both None: decoder-only generation from a prefix)')
+    if src_enc is None and prefix is None:
+        raise ValueError('generation without a source encoding needs a prefix (a zero-length one gives the batch size)')
+    assert src_enc is None or src_enc.size(0) == src_len.size(0)
     if isinstance(n_best, bool) or not isinstance(n_best, int) or not 1 <= n_best <= beam_size:
         raise ValueError('n_best must be an integer in [1, beam_size = %d], got %r' % (beam_size, n_best))
-    bs = len(src_len)
+    bs = len(src_len) if src_len is not None else int(torch.as_tensor(prefix_len).numel()) if prefix_len is not None else None
     n_words = model.n_words
     dev = model.embeddings.weight.device
+    pre = _Prefix(model, prefix, prefix_len, bs, max_len, dev, equal=True)
     cons = _Constraints(model, max_len, min_len, repetition_penalty, no_repeat_ngram, banned_words, dev)
-    src_len = src_len.to(dev)
     n = bs * beam_size
     sel_k = 2 * beam_size
     # (each plan is asked once; sel_k > n_words is malformed for the wide entry - a row supplies at most V entries to its own
@@ -752,12 +866,15 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
         select = wide = wide and ops.vocab_select_wide_takes(n, n_words, model.arena().V_pad, beam_size, sel_k)
     cons_dev = cons.on and select and cons.takes(n, n_words, model.arena().V_pad, max_len)
     hyps_dev = bool(select and BEAM_HYPS_ON_DEVICE and max_len >= 2 and ops.beam_advance_takes(bs, beam_size, sel_k, max_len))
-    if select:
+    if src_enc is None:
+        pass
+    elif select:
         src_enc = src_enc.to(dev)
     else:
         src_enc = src_enc.to(dev).unsqueeze(1).expand((bs, beam_size) + src_enc.shape[1:]).contiguous().view(
             (bs * beam_size,) + src_enc.shape[1:])
-    src_len = src_len.unsqueeze(1).expand(bs, beam_size).contiguous().view(-1)
+    if src_len is not None:
+        src_len = src_len.to(dev).unsqueeze(1).expand(bs, beam_size).contiguous().view(-1)
     generated = torch.full((max_len, bs * beam_size), model.pad_index, dtype=torch.long, device=dev)
     generated[0].fill_(model.eos_index)
     positions = torch.arange(max_len, device=dev)[:, None].expand_as(generated)
@@ -766,8 +883,8 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
     beam_scores = torch.zeros((bs, beam_size), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9
     beam_scores = beam_scores.view(-1)
-    cur_len = 1
-    cache = {'slen': 0, 'max_len': max_len}
+    cur_len = pre.fill(generated, beam_size)      # (1 without a prefix; else the first call is the prefill of every row)
+    cache = {'slen': 0, 'max_len': max_len, 'tiled_prefill': True}
     if select:
         cache['beam'] = beam_size
         cache['owner'] = torch.arange(n, dtype=torch.int32, device=dev)[:, None].expand(n, max_len).contiguous()
@@ -778,7 +895,7 @@ def generate_beam(model, src_enc, src_len, tgt_lang_id, beam_size, length_penalt
         lengths = torch.full((bs * beam_size,), cur_len, dtype=torch.long, device=dev)
         tensor = decoder_forward(model, generated[:cur_len], lengths, src_enc, src_len, positions[:cur_len],
                                  None if langs is None else langs[:cur_len], cache)
-        assert tensor.size() == (1, bs * beam_size, model.dim)
+        assert tensor.size()[1:] == (bs * beam_size, model.dim) and tensor.size(0) in (1, cur_len)
         if select:
             next_scores, next_words, _ = _select(*_constrained_logits16(model, tensor[-1], cons, cons_dev, generated, cur_len),
                                                  beam_scores, beam_size, sel_k, wide)

@@ -535,20 +535,23 @@ class TransformerModel(nn.Module):
 
     def generate(self, src_enc, src_len, tgt_lang_id, max_len=200, sample_temperature=None, cross_modal=True, sample_seed=None,
                  sample_top_k=None, return_logprobs=False, sample_top_p=None, min_len=0, repetition_penalty=None,
-                 no_repeat_ngram=0, banned_words=None):
+                 no_repeat_ngram=0, banned_words=None, prefix=None, prefix_len=None):
         """transformer.py:1216-1317 (greedy / sampled decoding); sample_seed / sample_top_k / sample_top_p / return_logprobs:
         the seeded sampling of decoder.generate (top-k and nucleus truncation); min_len / repetition_penalty / no_repeat_ngram /
-        banned_words: its decoding constraints."""
+        banned_words: its decoding constraints; prefix / prefix_len: its forced target prefix (with it src_enc = src_len = None
+        generates from the causal language model)."""
         from .. import decoder
         return decoder.generate(self, src_enc, src_len, tgt_lang_id, max_len=max_len, sample_temperature=sample_temperature,
                                 sample_seed=sample_seed, sample_top_k=sample_top_k, return_logprobs=return_logprobs,
                                 sample_top_p=sample_top_p, min_len=min_len, repetition_penalty=repetition_penalty,
-                                no_repeat_ngram=no_repeat_ngram, banned_words=banned_words)
+                                no_repeat_ngram=no_repeat_ngram, banned_words=banned_words, prefix=prefix,
+                                prefix_len=prefix_len)
 
     def generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping, max_len=200, min_len=0,
-                      repetition_penalty=None, no_repeat_ngram=0, banned_words=None, n_best=1, return_scores=False):
+                      repetition_penalty=None, no_repeat_ngram=0, banned_words=None, n_best=1, return_scores=False, prefix=None,
+                      prefix_len=None):
         """transformer.py:1319-1515 (beam search); min_len / repetition_penalty / no_repeat_ngram / banned_words: the decoding
-        constraints of decoder.generate_beam.  On a CUDA model beams up to 32 select their words on the device and leave the
+        constraints of decoder.generate_beam; prefix / prefix_len: its forced target prefix (equal lengths).  On a CUDA model beams up to 32 select their words on the device and leave the
         caches in place (up to 8: ops.vocab_select, 9 to 32: ops.vocab_select_wide); wider ones run the torch loop.
         n_best = k > 1 returns every sentence's k best finished hypotheses (decoded (L, bs, k), tgt_len (bs, k)), return_scores
         appends their length-normalised scores (fp64), on every route: decoder.generate_beam."""
@@ -556,4 +559,4 @@ class TransformerModel(nn.Module):
         return decoder.generate_beam(self, src_enc, src_len, tgt_lang_id, beam_size, length_penalty, early_stopping,
                                      max_len=max_len, min_len=min_len, repetition_penalty=repetition_penalty,
                                      no_repeat_ngram=no_repeat_ngram, banned_words=banned_words, n_best=n_best,
-                                     return_scores=return_scores)
+                                     return_scores=return_scores, prefix=prefix, prefix_len=prefix_len)

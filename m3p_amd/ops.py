@@ -778,6 +778,25 @@ def attn_cross_fwd(q, kv, klen, B, Tq, H, dh, Lk, seed=0, p_drop=0.0, out=None):
     return ctx, lse
 
 
+def attn_prefix_fwd(q, kv, B, Tq, H, dh, pos0, out=None):
+    """The prefill of a prompted decoding call on the tiled MFMA kernels (csrc/attn_tiled.hip): q bf16 [B*Tq, >= H*dh]
+    (scaled), kv bf16 [B, >= pos0 + Tq, >= 2*H*dh] (the cache, the Tq new rows already stored at pos0 ..) ->
+    (ctx bf16 [B*Tq, H*dh], lse fp32 [B, H, Tq]), the results of attn_query_fwd(causal=True, klen=None, Lk=pos0 + Tq,
+    pos0=pos0); cache rows at or past pos0 + Tq may hold anything.  Returns None when the kernel does not take the shape
+    (M3P_ENOTIMPL: dh not in {32, 64}, Tq > 512, pos0 + Tq > 1024, ...) - the caller then runs the rows kernel.
+    out = (ctx, lse) to write into."""
+    _chk_bf16(q, kv)
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[0] == B * Tq and pos0 >= 0
+    assert kv.dim() == 3 and kv.stride(2) == 1 and kv.shape[0] == B and kv.shape[1] >= pos0 + Tq
+    ctx, lse = _attn_tiled_fwd_out(out, B, Tq, H, dh, q.device)
+    rc = L.load().m3p_attn_prefix_fwd(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), kv.stride(1), ctx.data_ptr(),
+                                      lse.data_ptr(), B, Tq, H, dh, pos0, L.stream())
+    if rc == -2:            # (M3P_ENOTIMPL)
+        return None
+    L.check(rc, 'm3p_attn_prefix_fwd')
+    return ctx, lse
+
+
 def attn_cross_bwd(q, kv, klen, dctx, lse, B, Tq, H, dh, Lk, qscale, seed=0, p_drop=0.0, out=None):
     """-> (dq bf16 [B*Tq, H*dh] of the unscaled projection, dkv BF16 [B, Lk, 2*H*dh]: every row written once, exact zeros
     for keys >= klen[b], no atomics - nothing to zero or cast), or written into out = (dq, dkv) (row pitches
