@@ -177,6 +177,19 @@ M3P_API int m3p_gemm_wgrad_bf16(const void* dY, int lddy, const void* X, int ldx
  * Anything else returns M3P_ENOTIMPL and the caller accumulates with m3p_gemm_wgrad_bf16. */
 M3P_API int m3p_gemm_wgrad_store_bf16(const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, int M, int N, int K,
                                       float alpha, void* workspace, size_t workspace_bytes, void* stream);
+/* The whole-tile product (stored: store != 0, or accumulated) that also leaves the weighted column sums of its first operand,
+ * bsum[i] = sum_m w[m] dY[m, i] (w fp32 [M], bsum fp32 [N], every element written once with a plain store): the output-bias
+ * gradient of the vocabulary projection from the fragments the K loop already holds, instead of a pass of its own over the
+ * 2.4-GB operand (m3p_ce_shift_colsum); the weights enter rounded to bf16, the sums are fp32.  dW is bit-identical to m3p_gemm_wgrad_store_bf16 / m3p_gemm_wgrad_bf16 on the same
+ * operands.  bsum must not overlap dW.  Returns M3P_ENOTIMPL - and launches nothing - wherever the four-wave kernel would not
+ * deal out whole tiles (see m3p_gemm_wgrad_store_bf16), for M > 16384 (the weights live in LDS) or a misaligned operand. */
+/* The same through the existing entry points: arms the calling thread's NEXT m3p_gemm_wgrad_store_bf16 / m3p_gemm_wgrad_bf16 call - if
+ * that call runs the whole-tile schedule (and M <= 16384) it is the launch above with these operands, otherwise it is what it
+ * always was.  Returns 1 if a launch has taken the operands armed before this call, else 0, and replaces them: (NULL, NULL)
+ * disarms.  Arm, call, then disarm and read whether the sums were written. */
+M3P_API int m3p_gemm_wgrad_bias_arm(const float* w, float* bsum);
+M3P_API int m3p_gemm_wgrad_bias_bf16(const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, int M, int N, int K,
+                                     float alpha, const float* w, float* bsum, int store, void* stream);
 /* Two weight gradients over the same M rows in ONE launch of the four-wave kernel (and one reduction): dWa += dYa^T Xa,
  * dWb += dYb^T Xb.  The attention sub-layer's out_lin (768 x 768: 9 output tiles) and q/k/v (27 tiles) gradients of
  * MultiHeadAttention (transformer.py:178-181, :208) together fill the 256 CUs as evenly as one FFN gradient does - apart they

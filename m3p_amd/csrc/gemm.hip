@@ -2005,6 +2005,11 @@ struct WgradGroup {
   uint32_t place[256];
 };
 __device__ __forceinline__ const WgradGroup& wgrad_group_of(const WgradGroup& g) { return g; }      // (the kernel's trailing pack)
+// bias sums of a whole-tile launch (m3p_gemm_wgrad_bias_bf16): bsum[i] = sum_m w[m] dY[m, i], w fp32 [M], bsum fp32 [N]
+struct WgradBias {
+  const float* w; float* bsum;
+};
+__device__ __forceinline__ const WgradBias& wgrad_bias_of(const WgradBias& b) { return b; }
 
 // ---------------------------------------------------------------------------------
 // NT kernel, stream-K version with fp32 atomic output: Cf[M,N] += alpha * A[M,K] W[N,K]^T for
@@ -2974,6 +2979,19 @@ size_t m3p_gemm_wgrad_workspace_bytes(void) {
 // persistent grid of 8, tiles 256.. of a 272-tile weight on 256 CUs - were never computed: tests/test_gemm_schedules.py.)
 static bool wgrad_w4_whole_tiles(long long ntile, int grid) { return ntile > (long long)grid; }
 
+// m3p_gemm_wgrad_bias_arm: the calling thread's next whole-tile launch through m3p_gemm_wgrad_store_bf16 / m3p_gemm_wgrad_bf16
+// is the BIAS instantiation with these operands (the callers of those entry points keep their call and its return code)
+static thread_local const float* g_bias_w = nullptr;
+static thread_local float* g_bias_out = nullptr;
+static thread_local int g_bias_taken = 0;
+int m3p_gemm_wgrad_bias_arm(const float* w, float* bsum) {
+  const int taken = g_bias_taken;
+  g_bias_taken = 0;
+  g_bias_w = (w && bsum && !((uintptr_t)w & 3) && !((uintptr_t)bsum & 3)) ? w : nullptr;
+  g_bias_out = g_bias_w ? bsum : nullptr;
+  return taken;
+}
+
 // four-wave kernel + reduction; pb: optional second product over the same M (paired launch), nullptr = none
 static bool wgrad_w4_ok(int M, int N, int K, int lddy, int ldx, const void* dY, const void* X) {
   return (M % 64) == 0 && M >= 4096 && (N % 256) == 0 && (K % 256) == 0 &&
@@ -2997,6 +3015,20 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
   if (wgrad_w4_whole_tiles(ntile, grid)) chunk = 0;   // more tiles than workgroups: round-robin whole tiles
   if (pb_in && chunk == 0) return M3P_EINVAL;       // (pairs only in the one-segment-per-workgroup mode; the caller checks)
   if (store && chunk != 0) return M3P_ENOTIMPL;     // (a plain store needs every tile flushed exactly once: whole-tile round-robin mode)
+  if constexpr (!YROWS) {
+    if (g_bias_w && chunk == 0 && !pb_in && 2 * 65536 + (size_t)M * 2 <= 160 * 1024) {
+      // armed (m3p_gemm_wgrad_bias_arm): the same whole-tile launch, column tile 0 also sums the first operand's weighted columns
+      if (int rc = set_max_lds<gemm_wgrad_w4_kernel<false, WgradBias>>(160 * 1024)) return rc;
+      hipLaunchKernelGGL((gemm_wgrad_w4_kernel<false, WgradBias>), dim3(grid), dim3(256), 2 * 65536 + (size_t)M * 2,
+                         (hipStream_t)stream, (const bf16*)dY, lddy, (const bf16*)X, ldx, dW, lddw, M, N, K, alpha, ti, tj, 0,
+                         (float*)nullptr, (int*)nullptr, store ? 1 : 0, WgradProblem{}, WgradBias{g_bias_w, g_bias_out});
+      M3P_CHECK_LAUNCH();
+      g_bias_w = nullptr;
+      g_bias_out = nullptr;
+      g_bias_taken = 1;
+      return M3P_OK;
+    }
+  }
   // workspace for first-segment partials: one 256-KB slot per workgroup + a tile-id word each, owned by the
   // CALLER (m3p_gemm_wgrad_workspace_bytes): launches that may overlap on different streams need one each.
   // Without it the partial tiles go to dW with fp32 atomics (slower: DESIGN.md section 4).
@@ -3031,7 +3063,9 @@ static int launch_wgrad_w4(const void* dY, int lddy, const void* X, int ldx, flo
 //                                                            reduce kernel (16 x ntile blocks) sums   slot order (bit-reproducible)
 //                                                            them into dW in slot order
 //   same, more tiles than CUs (the vocabulary matrix)      four-wave, whole tiles round-robin       each tile flushed once: fp32 atomics,
-//                                                                                                    or plain stores (m3p_gemm_wgrad_store_bf16)
+//                                                                                                    or plain stores (m3p_gemm_wgrad_store_bf16);
+//                                                                                                    m3p_gemm_wgrad_bias_bf16: + the weighted
+//                                                                                                    column sums of dY from column tile 0
 //   M % 64 == 0, M >= 4096 otherwise                       ring stream-K 256x128 (atomics)          ragged N / K
 //   anything else                                          128x128 split-M (atomics)                small M (cfg1, tests)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -3167,6 +3201,26 @@ int m3p_gemm_wgrad_store_bf16(const void* dY, int lddy, const void* X, int ldx, 
   if (lddy < N || ldx < K || ((uintptr_t)dY & 15) || ((uintptr_t)X & 15)) return M3P_EINVAL;
   if (!wgrad_w4_ok(M, N, K, lddy, ldx, dY, X)) return M3P_ENOTIMPL;
   return launch_wgrad_w4<>(dY, lddy, X, ldx, dW, lddw, M, N, K, alpha, workspace, workspace_bytes, stream, nullptr, true);
+}
+
+// The whole-tile launch with the first operand's weighted column sums beside the product (gemm_wgrad_w4_kernel, BIAS).
+// The weight vector, in bf16, shares the workgroup's LDS with the two stages: 2 bytes per row of M in the 32 KB behind them.
+int m3p_gemm_wgrad_bias_bf16(const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, int M, int N, int K,
+                             float alpha, const float* w, float* bsum, int store, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || (lddy % 8) != 0 || (ldx % 8) != 0 || !dY || !X || !dW || !w || !bsum || lddw < K)
+    return M3P_EINVAL;
+  if (lddy < N || ldx < K) return M3P_EINVAL;
+  if (!wgrad_w4_ok(M, N, K, lddy, ldx, dY, X) || ((uintptr_t)w & 3) || ((uintptr_t)bsum & 3)) return M3P_ENOTIMPL;
+  const int ti = N / 256, tj = K / 256;
+  const int grid = num_cus();
+  const size_t lds = 2 * 65536 + (size_t)M * 2;
+  if (!wgrad_w4_whole_tiles((long long)ti * tj, grid) || lds > 160 * 1024) return M3P_ENOTIMPL;
+  if (int rc = set_max_lds<gemm_wgrad_w4_kernel<false, WgradBias>>(160 * 1024)) return rc;
+  hipLaunchKernelGGL((gemm_wgrad_w4_kernel<false, WgradBias>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
+                     (const bf16*)dY, lddy, (const bf16*)X, ldx, dW, lddw, M, N, K, alpha, ti, tj, 0, (float*)nullptr,
+                     (int*)nullptr, store ? 1 : 0, WgradProblem{}, WgradBias{w, bsum});
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
 }
 
 int m3p_gemm_wgrad_bf16(const void* dY, int lddy, const void* X, int ldx, float* dW, int lddw, int M, int N, int K,

@@ -23,13 +23,24 @@
 // through the LDS patches of the workspace flush.  No workspace, no tile-id words, no reduction.
 // It is this kernel with a WgradGroup appended to its arguments (GRP = one type; every other launch: none, and the same code as
 // before the parameter existed); the arguments in front of it are then unused.
+// BIAS (m3p_gemm_wgrad_bias_bf16, whole-tile round-robin schedule only): a WgradBias appended instead.  The workgroups of column
+// tile 0 also form bsum[i] = sum_m w[m] dY[m, i] for their 256 rows i - the output-bias gradient of the vocabulary projection,
+// whose column-sum pass re-read all of dY for it.  A lane's first-operand fragment c holds eight consecutive m of ONE row i, so
+// the sum is a VALU dot product per fragment dword (v_dot2c_f32_bf16, in MFMA shadow slots of the generated table) against
+// the weights of those m: the whole vector sits in LDS behind the stages in bf16 (round-to-nearest: each addend moves by at
+// most 2^-8 of itself, as much as the rounding of dY to bf16 may have moved it by; a (hi, lo) pair - twice the dot
+// instructions - cost 145 us beside a 1524-us launch, 0.36 of the pass it replaces), packed once in front of the K loop, and a
+// lane reads its 2 x 8 weights of a K-tile with two ds_read_b128 the table's own lgkmcnt waits cover.  The two waves of a row half see the same fragments and take four row blocks each (BMODE 1 / 2: a compile-time
+// fact of the K-tile body, like the stage).  The tile is whole over M: four lane groups are folded at its end and every bsum[i]
+// is stored once - no partials, no atomics.  The MFMA stream is untouched: dW is bit-identical to the launch without.
 template <bool YROWS, typename... GRP>
 __global__ __launch_bounds__(256)
 void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16* __restrict__ X_a, int ldx_a,
                           float* __restrict__ dW_a, int lddw_a, int M, int N, int K, float alpha,
                           int tiles_i, int tiles_j_a, int WR_CHUNK, float* __restrict__ ws, int* __restrict__ ws_tile,
                           int overwrite, WgradProblem pb, GRP... grp) {
-  constexpr bool GROUP = sizeof...(GRP) != 0;
+  constexpr bool GROUP = (std::is_same_v<GRP, WgradGroup> || ...);
+  constexpr bool BIAS = (std::is_same_v<GRP, WgradBias> || ...);
   // Two products over the same M in one launch (pb.tiles != 0; one-segment-per-workgroup mode only): the tiles of product b
   // follow those of product a in the tile numbering, every workgroup picks its product once, before the K loop.  36 tiles of
   // out_lin + q/k/v then share one launch, one end-of-kernel flush and one reduction instead of 9 tiles x 28 chunks beside
@@ -212,6 +223,34 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
                               else if constexpr ((KS) == 0) WG_TR2(yl[C], yh[C], y_addr[S][C], 0);                           \
                               else WG_TR2(yl[C], yh[C], y_addr[S][C], 16384); } while (0)
 
+  // BIAS: this wave's four row-block sums, the K-tile's weights of both k-steps and where the lane reads them
+  float bs[4] = {0.f, 0.f, 0.f, 0.f};
+  u32x4 bw0, bw1;
+  uint32_t bw_addr = 0;
+  const uint32_t bw_base = lds0 + 2 * STAGE + fg * 16;
+  bool b_on = false;
+  if constexpr (BIAS) {
+    // the weight vector in bf16, round-to-nearest-even: a lane's eight m of a k-step are 16 B
+    const float* wv = wgrad_bias_of(grp...).w;
+    unsigned short* wl = reinterpret_cast<unsigned short*>(smem + 2 * STAGE);
+    for (int m = tid; m < M; m += 256) {
+      const uint32_t u = __float_as_uint(wv[m]);
+      wl[m] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    }
+    __syncthreads();
+    b_on = (seg_tile % tiles_j) == 0;
+  }
+  // the weights of k-step KS / one dot instruction: row block J of this wave, fragment dword D
+#define WG_BW(KS) do { if constexpr (BMODE != 0) {                                                                             \
+    if constexpr ((KS) == 0) asm volatile("ds_read_b128 %0, %1" : "=&v"(bw0) : "v"(bw_addr));                                  \
+    else asm volatile("ds_read_b128 %0, %1 offset:64" : "=&v"(bw1) : "v"(bw_addr));                                            \
+    __builtin_amdgcn_sched_barrier(0); } } while (0)
+#define WG_BD(KS, J, D) do { if constexpr (BMODE != 0) {                                                                       \
+    asm volatile("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(bs[J])                                                                   \
+                 : "v"(__builtin_bit_cast(u32x4, ((KS) == 0 ? yf0 : yf1)[(BMODE - 1) * 4 + (J)])[D]),                          \
+                   "v"(((KS) == 0 ? bw0 : bw1)[D]));                                                                           \
+    __builtin_amdgcn_sched_barrier(0); } } while (0)
+
   asm volatile("" ::: "a0", "a255");     // reserve all 256 AGPRs (see gemm_nt_w4_kernel)
   // acc tile (b, a) = a[((b)*8+(a))*4 .. +3] holds D[i = 16a + 4(l >> 4) + r][j = 16b + (l & 15)]
 #define WG_ACC(B, A) "a[((" #B ")*8+(" #A "))*4:((" #B ")*8+(" #A "))*4+3]"
@@ -233,9 +272,10 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   // a barrier as soon as its k-step-1 fragments are in registers (MFMA 20), the second's at MFMA 50, the next K-tile is waited
   // for at MFMA 107 (vmcnt(16): this K-tile's own sixteen transfers stay in flight): a transfer has 1.2-1.7 K-tiles to land
   // where the two-phase form gives the last five of a K-tile 46 MFMAs and waits ~200-270 clocks per K-tile at its vmcnt(0).
-  auto wktile = [&](auto first_c, auto stage_c) {
+  auto wktile = [&](auto first_c, auto stage_c, auto bmode_c) {
     constexpr bool FIRST0 = decltype(first_c)::value;
     constexpr int s_cur = decltype(stage_c)::value;
+    constexpr int BMODE = decltype(bmode_c)::value;      // 0: no bias sums in this K-tile; 1 / 2: row blocks 0-3 / 4-7
     __builtin_amdgcn_sched_barrier(0);
     {
       constexpr bool FIRST = FIRST0;
@@ -271,8 +311,21 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
   bool first = true;
   int n_seg = 0;
   auto kstep = [&](auto stage_c, int step) {
-    if (first) wktile(std::true_type{}, stage_c);
-    else wktile(std::false_type{}, stage_c);
+    using BM0 = std::integral_constant<int, 0>;
+    if constexpr (BIAS) {
+      if (b_on) {
+        bw_addr = bw_base + (uint32_t)cc.mt * 128u;
+        if (wj == 0) {
+          if (first) wktile(std::true_type{}, stage_c, std::integral_constant<int, 1>{});
+          else wktile(std::false_type{}, stage_c, std::integral_constant<int, 1>{});
+        } else {
+          if (first) wktile(std::true_type{}, stage_c, std::integral_constant<int, 2>{});
+          else wktile(std::false_type{}, stage_c, std::integral_constant<int, 2>{});
+        }
+      } else if (first) wktile(std::true_type{}, stage_c, BM0{});
+      else wktile(std::false_type{}, stage_c, BM0{});
+    } else if (first) wktile(std::true_type{}, stage_c, BM0{});
+    else wktile(std::false_type{}, stage_c, BM0{});
     first = false;
 
     const bool last_of_tile = (cc.mt + 1 == cc.len) || (step + 1 == total);
@@ -367,6 +420,21 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
               else unsafeAtomicAdd(dcol + (size_t)(a * 16 + r) * lddw, alpha * v[a * 4 + r]);
         }
       }
+      if constexpr (BIAS) {
+        if (b_on) {
+          // (tj == 0) fold the four lane groups of a row - they hold different m - and store this wave's 4 x 16 sums
+          float* bo = wgrad_bias_of(grp...).bsum + ti * TI + wi * 128 + wj * 64 + ft;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float sum = bs[j];
+            sum += __shfl_xor(sum, 16);
+            sum += __shfl_xor(sum, 32);
+            if (fg == 0) bo[j * 16] = sum;
+            bs[j] = 0.f;
+          }
+        }
+        b_on = ((cc.t + nwg) % tiles_j) == 0;        // the next tile of this workgroup
+      }
       if (!GROUP && to_ws && tid == 0) ws_tile[slot] = tile_id0 + cc.t;
       ++n_seg;
       first = true;
@@ -384,6 +452,8 @@ void gemm_wgrad_w4_kernel(const bf16* __restrict__ dY_a, int lddy_a, const bf16*
 #undef WG_ACC
 #undef WG_M
 #undef WG_L
+#undef WG_BW
+#undef WG_BD
 }
 
 // dW[tile] += alpha * sum of the workspace slots that hold a partial of that tile.

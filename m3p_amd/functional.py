@@ -43,6 +43,9 @@ _GELU_BYTE_GRAD = int(os.environ.get('M3P_GELU_BYTE_GRAD', '2'))
 _CE_FUSED_LSE = os.environ.get('M3P_CE_FUSED_LSE', '1') != '0'
 # round 4: the vocabulary data gradient on the four-wave (tile, K-chunk) kernel instead of stream-K with atomics; 0 = round 3
 _VOCAB_DGRAD_W4 = os.environ.get('M3P_VOCAB_DGRAD_W4', '1') != '0'
+# the output-bias gradient's column sums from the vocabulary weight gradient's K loop (ops.gemm_wgrad_bias); 0 = a pass of their
+# own over e in forward, for A/B runs
+_VOCAB_WGRAD_BIAS = os.environ.get('M3P_VOCAB_WGRAD_BIAS', '1') != '0'
 
 class Arena:
     """Flat storage behind a TransformerModel's hot parameters (see model/transformer.py)."""
@@ -1421,7 +1424,11 @@ class MLMHeadFn(torch.autograd.Function):
         dbias = None
         rows = None
         if shifted:
-            loss_sum, _, row_s, row_q, dbias = ops.ce_shift_from_block_sums(logits, stats, 1.0 / n, 1.0 / n)
+            # the whole-tile weight gradient of backward sums the bias gradient's columns from the fragments it holds anyway:
+            # no pass over e for them here (backward runs that pass itself should its launcher decline)
+            skip = (_VOCAB_WGRAD_BIAS and _VOCAB_FULL_TILES and n >= 4096 and n % 64 == 0 and
+                    L.load().m3p_gemm_wgrad_plan(n, ar.V_pad, d) == L.KERN_WGRAD_W4_TILES)
+            loss_sum, _, row_s, row_q, dbias = ops.ce_shift_from_block_sums(logits, stats, 1.0 / n, 1.0 / n, colsum=not skip)
             rows = (row_s, row_q, y)
         elif fused_lse:
             loss_sum, _, dbias = ops.ce_from_block_stats(logits, V, y, stats, 1.0 / n, 1.0 / n)
@@ -1464,8 +1471,18 @@ class MLMHeadFn(torch.autograd.Function):
             lazy = will_store and ar.stale == ar.vocab_range()      # (lazily zeroed by the optimizer: a STORE covers exactly that range)
             if not lazy:
                 ar.ensure_zero()
-            ar.vocab_stored = ops.gemm_wgrad(dlogits, hs, ar.grad[o:o + ar.V_pad * d].view(ar.V_pad, d), n=ar.V_pad, k=d,
-                                             dw_is_zero=fresh, report_store=True, must_store=lazy)
+            dwv = ar.grad[o:o + ar.V_pad * d].view(ar.V_pad, d)
+            if rows is not None and dbias is None:
+                # the column sums come out of this launch, into a buffer of their own: the product's pad rows cover the head
+                # of the bias gradient, which therefore receives them behind the launch like the forward pass's sums
+                bsum = torch.empty(ar.V_pad, dtype=torch.float32, device=dlogits.device)
+                ar.vocab_stored, took = ops.gemm_wgrad(dlogits, hs, dwv, n=ar.V_pad, k=d, dw_is_zero=fresh, report_store=True,
+                                                       must_store=lazy, bias=(rows[0], bsum))
+                if took:
+                    dbias = bsum
+            else:
+                ar.vocab_stored = ops.gemm_wgrad(dlogits, hs, dwv, n=ar.V_pad, k=d, dw_is_zero=fresh, report_store=True,
+                                                 must_store=lazy)
             if lazy:
                 # (only now: had the launcher declined the store, ops.gemm_wgrad has raised instead of accumulating onto the
                 #  previous step's gradient - ADVICE r5; `stale` stays set until a store has really covered the range)
@@ -1474,6 +1491,8 @@ class MLMHeadFn(torch.autograd.Function):
                 raise RuntimeError('the dispatch table promised a stored vocabulary weight gradient, the launcher accumulated')
         else:
             ops.gemm_wgrad(dlogits, hs, ar.g('embeddings.weight'), n=V, k=d)
+        if dbias is None and rows is not None:
+            dbias = ops.ce_shift_colsum(dlogits, rows[0])       # (forward left the sums to a launch that declined)
         if dbias is not None:
             ops.axpy_dev(ar.g('pred_layer.proj.bias'), dbias[:V], g)
         else:

@@ -60,6 +60,8 @@ SIGNATURES = {
     'm3p_gemm_wgrad_workspace_bytes': (C.c_size_t, []),
     'm3p_gemm_wgrad_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
     'm3p_gemm_wgrad_store_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
+    'm3p_gemm_wgrad_bias_arm': (_i, [_p, _p]),
+    'm3p_gemm_wgrad_bias_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p]),
     'm3p_gemm_wgrad_pair_bf16': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _f, _p, C.c_size_t, _p]),
     'm3p_gemm_wgrad_group_bf16': (_i, [C.POINTER(WgradItem), _i, _i, _f, _p]),
     'm3p_gemm_wgrad_group_place': (_i, [C.POINTER(_i), C.POINTER(_i), _i, _i, C.POINTER(_u32)]),

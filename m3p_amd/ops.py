@@ -225,7 +225,24 @@ def _wgrad_workspace(device):
     return ws
 
 
-def gemm_wgrad(dy, x, dw, alpha=1.0, n=None, k=None, dw_is_zero=False, report_store=False, must_store=False):
+def gemm_wgrad(dy, x, dw, alpha=1.0, n=None, k=None, dw_is_zero=False, report_store=False, must_store=False, bias=None):
+    """_gemm_wgrad; bias = (w fp32 [M], bsum fp32 [>= N]): a whole-tile launch also leaves bsum[:N] = w @ dy (gemm_wgrad_bias: the
+    same kernel through the entry points of this call) and the result becomes (result, whether bsum was written)."""
+    if bias is None:
+        return _gemm_wgrad(dy, x, dw, alpha, n, k, dw_is_zero, report_store, must_store)
+    w, bsum = bias
+    assert w.dtype == bsum.dtype == torch.float32 and w.is_contiguous() and bsum.is_contiguous()
+    assert w.numel() == dy.shape[0] and bsum.numel() >= (dy.shape[1] if n is None else n)
+    lib = L.load()
+    armed = lib.m3p_gemm_wgrad_bias_arm(w.data_ptr(), bsum.data_ptr()) == 0        # (anything else: declined)
+    try:
+        res = _gemm_wgrad(dy, x, dw, alpha, n, k, dw_is_zero, report_store, must_store)
+    finally:
+        took = armed and lib.m3p_gemm_wgrad_bias_arm(None, None) == 1
+    return res, took
+
+
+def _gemm_wgrad(dy, x, dw, alpha=1.0, n=None, k=None, dw_is_zero=False, report_store=False, must_store=False):
     """dw[N,K] (fp32) += alpha * dy[M,N]^T @ x[M,K].  dw_is_zero: the caller knows dw[:N, :K] to hold zeros - shapes dealt out
     as whole tiles (the vocabulary matrix) are then stored instead of accumulated with atomics; same result.  must_store: dw is
     only LOGICALLY zero (the arena's lazily zeroed range): a launcher that declines the store raises here instead of
@@ -253,6 +270,27 @@ def gemm_wgrad(dy, x, dw, alpha=1.0, n=None, k=None, dw_is_zero=False, report_st
     L.check(rc, 'm3p_gemm_wgrad_bf16')
     _prof_end(e0, ('gemm_wgrad', M, N, K))
     return False if report_store else dw
+
+
+def gemm_wgrad_bias(dy, x, dw, w, bsum, alpha=1.0, n=None, k=None, store=False):
+    """The whole-tile weight gradient that also leaves bsum[:N] = w @ dy (w fp32 [M], bsum fp32 [>= N]): dw[N,K] = (store) or +=
+    alpha * dy^T @ x, bit-identical to gemm_wgrad.  Returns False - nothing launched, nothing written - where the launcher does
+    not run the whole-tile schedule (M3P_ENOTIMPL); the caller then takes gemm_wgrad and a column-sum pass."""
+    _chk_bf16(dy, x)
+    assert dw.dtype == torch.float32 and dw.stride(-1) == 1
+    M = dy.shape[0]
+    N = dy.shape[1] if n is None else n
+    K = x.shape[1] if k is None else k
+    assert x.shape[0] == M and dw.shape[0] >= N and dw.shape[1] >= K
+    assert w.dtype == bsum.dtype == torch.float32 and w.is_contiguous() and bsum.is_contiguous() and w.numel() == M and bsum.numel() >= N
+    e0 = _prof_begin(('gemm_wgrad_bias', M, N, K))
+    rc = L.load().m3p_gemm_wgrad_bias_bf16(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr(), dw.stride(0),
+                                           M, N, K, alpha, w.data_ptr(), bsum.data_ptr(), int(bool(store)), L.stream())
+    if rc == -2:
+        return False
+    L.check(rc, 'm3p_gemm_wgrad_bias_bf16')
+    _prof_end(e0, ('gemm_wgrad_bias', M, N, K))
+    return True
 
 
 def gemm_wgrad_pair(dy_a, x_a, dw_a, dy_b, x_b, dw_b, alpha=1.0):
@@ -1129,10 +1167,25 @@ def ce_shift_target(h, emb, bias, target):
     return row_t, row_ref
 
 
-def ce_shift_from_block_sums(e, stats, loss_scale, grad_scale):
+def ce_shift_colsum(e, row_s):
+    """colsum fp32 [ld] = sum_n row_s[n] e[n, :] in a pass of its own over e (bf16 [n, ld])."""
+    n, ld = e.shape[0], e.stride(0)
+    dev = e.device
+    cs = torch.empty(ld, dtype=torch.float32, device=dev)
+    need = L.load().m3p_ce_colsum_workspace_bytes(ld, n)
+    ws = _CE_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _CE_WS[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(L.load().m3p_ce_shift_colsum(e.data_ptr(), ld, n, row_s.data_ptr(), cs.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+            'm3p_ce_shift_colsum')
+    return cs
+
+
+def ce_shift_from_block_sums(e, stats, loss_scale, grad_scale, colsum=True):
     """The cross-entropy from what the shifted-exponential projection left (e bf16 [n, ld], stats fp32 [N / 64, n] block sums):
     returns (loss_sum [1], row_loss [n], row_s [n] = grad_scale / Sigma, row_q [n] = grad_scale * (p_target - 1),
-    colsum fp32 [ld] = sum_n row_s[n] e[n, :] - the output-bias gradient but for the targets' terms).  e is only read."""
+    colsum fp32 [ld] = sum_n row_s[n] e[n, :] - the output-bias gradient but for the targets' terms).  e is only read.
+    colsum=False: no pass over e, None in its place (the caller gets the sums from gemm_wgrad_bias, or ce_shift_colsum later)."""
     n, ld = e.shape[0], e.stride(0)
     dev = e.device
     assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape[1] == n
@@ -1142,13 +1195,7 @@ def ce_shift_from_block_sums(e, stats, loss_scale, grad_scale):
     scratch = torch.empty((32, n), dtype=torch.float32, device=dev)
     L.check(L.load().m3p_ce_shift_rows(stats.data_ptr(), stats.shape[0], n, grad_scale, row_loss.data_ptr(), row_s.data_ptr(),
                                        row_q.data_ptr(), scratch.data_ptr(), L.stream()), 'm3p_ce_shift_rows')
-    cs = torch.empty(ld, dtype=torch.float32, device=dev)
-    need = L.load().m3p_ce_colsum_workspace_bytes(ld, n)
-    ws = _CE_WS.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _CE_WS[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    L.check(L.load().m3p_ce_shift_colsum(e.data_ptr(), ld, n, row_s.data_ptr(), cs.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
-            'm3p_ce_shift_colsum')
+    cs = ce_shift_colsum(e, row_s) if colsum else None
     return (row_loss.sum() * loss_scale).reshape(1), row_loss, row_s, row_q, cs
 
 

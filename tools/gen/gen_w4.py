@@ -95,6 +95,20 @@ add(wkt, WGK_BAR3, 'M3P_WAIT_VM(16); M3P_BAR();')
 for r in range(16):
     add(wkt, WGK_BAR3 + 1 + r * WGK_RSTEP, ('WG_YRD(%d, s_cur ^ 1, 0);' % r) if r < 8 else ('WG_TR2(xl[%d], xh[%d], x_addr[s_cur ^ 1][%d], 0);' % (r - 8, r - 8, r - 8)))
 add(wkt, 127, 'M3P_WAIT_LGKM(0); WG_SET0();')
+# Bias sums of the whole-tile launch (WG_BW / WG_BD expand to nothing unless the K-tile body is a BMODE 1 / 2 one).  The weights'
+# reads go where an existing wait covers them, in order, at no other count: k-step 0's at MFMA 0, in front of every fragment
+# read the lgkmcnt(4) of KT_BAR1 leaves behind; k-step 1's right after that barrier, in front of the reads lgkmcnt(0) of KT_BAR2
+# waits for.  The 2 x 16 dot instructions - one per MFMA, between matrix instructions - take the slots that hold nothing else:
+# k-step 0's from its weights' wait on, k-step 1's from KT_BAR2 on (its fragments are set there) and clear of the tail's
+# fragment reads; consecutive ones go to different accumulators.
+add(wkt, 0, 'WG_BW(0);')
+add(wkt, KT_BAR1 + 1, 'WG_BW(1);')
+for ks, start in ((0, KT_BAR1 + 2), (1, KT_BAR2 + 1)):
+    dots = ['WG_BD(%d, %d, %d);' % (ks, j, dw) for dw in range(4) for j in range(4)]
+    free = [n for n in range(start, WGK_BAR3) if n not in wkt]
+    assert len(free) >= len(dots)
+    for stmt, n in zip(dots, free):
+        add(wkt, n, stmt)
 wkt_a = {n: v for n, v in wkt.items() if n < 64}
 wkt_b = {n - 64: v for n, v in wkt.items() if n >= 64}
 
