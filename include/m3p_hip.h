@@ -275,7 +275,7 @@ M3P_API int m3p_attn_fwd(const void* qkv, const int32_t* keylen, void* ctx, floa
  * dqkv into the fp32 [3*H*dh] bias gradient of the fused q/k/v projection.  The k block of
  * the bias gradient is left untouched: it is identically 0 (softmax is invariant to a
  * per-query shift of the scores; the reference's value there is fp32 noise).  Scores are recomputed from
- * qkv + lse (nothing S x S is ever stored).  S <= 384.  With dropout on (thresh24 != 0) keepmask - the words m3p_attn_fwd
+ * qkv + lse (nothing S x S is ever stored).  S <= 512.  With dropout on (thresh24 != 0) keepmask - the words m3p_attn_fwd
  * left - is REQUIRED (M3P_EINVAL without; round 6: the instantiations that re-drew the decisions from (seed, thresh24) served
  * tests only); seed is unused. */
 M3P_API int m3p_attn_bwd(const void* qkv, const int32_t* keylen, const void* ctx, const void* dctx,

@@ -155,10 +155,30 @@ void ln_bwd_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy_b,
   }
 }
 
+// 8 bf16 of a row: one 16-byte access, or two 8-byte ones where the row is only 8-byte aligned
+template <bool A16>
+__device__ __forceinline__ bf16x8 ln_load8(const bf16* p) {
+  if constexpr (A16) return *reinterpret_cast<const bf16x8*>(p);
+  const bf16x4 lo = *reinterpret_cast<const bf16x4*>(p), hi = *reinterpret_cast<const bf16x4*>(p + 4);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+template <bool A16>
+__device__ __forceinline__ void ln_store8(bf16* p, bf16x8 v) {
+  if constexpr (A16) {
+    *reinterpret_cast<bf16x8*>(p) = v;
+  } else {
+    *reinterpret_cast<bf16x4*>(p) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
+    *reinterpret_cast<bf16x4*>(p + 4) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
+  }
+}
+
 // Backward, wide variant for d = 256 * NC (768, 1024): HALF a wave per row with 16-byte
 // accesses (8 bf16 per lane per chunk), so a wave keeps two rows and twice the bytes in flight;
-// row reductions are xor-shuffles over 32 lanes.  Same arithmetic as ln_bwd_kernel.
-template <int NC>
+// row reductions are xor-shuffles over 32 lanes.  Same expressions as ln_bwd_kernel; the row sums c1, c2 are added in
+// another order (a lane's eight elements one after the other, then 32 lanes), so dx can differ from that kernel's by one bf16
+// step.  A16 = false: the same kernel with 8-byte accesses, for a row pointer that is 8 but not 16 bytes aligned - the
+// arithmetic is this kernel's, so what a call computes does not depend on where the allocator put its tensors.
+template <int NC, bool A16 = true>
 __global__ __launch_bounds__(256)
 void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy_b, const bf16* __restrict__ x,
                       const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -196,10 +216,10 @@ void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
       const int c = (sub + 32 * i) * 8;
-      bf16x8 a = *reinterpret_cast<const bf16x8*>(dy_a + ro + c);
-      const bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + ro + c);
+      bf16x8 a = ln_load8<A16>(dy_a + ro + c);
+      const bf16x8 xv = ln_load8<A16>(x + ro + c);
       bf16x8 b2;
-      if (dy_b) b2 = *reinterpret_cast<const bf16x8*>(dy_b + ro + c);
+      if (dy_b) b2 = ln_load8<A16>(dy_b + ro + c);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         float dv = (float)a[e];
@@ -220,7 +240,7 @@ void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy
       bf16x8 ob, odb;
 #pragma unroll
       for (int e = 0; e < 8; ++e) ob[e] = (bf16)((dyv[i][e] * g[i][e] - c1 - xh[i][e] * c2) * rs);
-      *reinterpret_cast<bf16x8*>(dx + ro + c) = ob;
+      ln_store8<A16>(dx + ro + c, ob);
       if (dx_drop || dbias_drop) {
         const uint32_t base = rr * (uint32_t)D + (uint32_t)c;
         bool kp[8] = {true, true, true, true, true, true, true, true};
@@ -230,7 +250,7 @@ void ln_bwd_hw_kernel(const bf16* __restrict__ dy_a, const bf16* __restrict__ dy
           odb[e] = (bf16)(kp[e] ? (float)ob[e] * (thresh24 ? inv_keep : 1.f) : 0.f);
           acc_d[i][e] += (float)odb[e];
         }
-        if (dx_drop) *reinterpret_cast<bf16x8*>(dx_drop + ro + c) = odb;
+        if (dx_drop) ln_store8<A16>(dx_drop + ro + c, odb);
       }
     }
   }
@@ -290,16 +310,18 @@ int m3p_layernorm_bwd_rows(const void* dy_a, const void* dy_b, const void* x, co
   if (!dy_a || !x || !dx || !dgamma || !dbeta) return M3P_EINVAL;
   if (((uintptr_t)x & 7) || ((uintptr_t)dy_a & 7) || ((uintptr_t)dx & 7) || ((uintptr_t)gamma & 15)) return M3P_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if ((d == 768 || d == 1024) && !(((uintptr_t)x | (uintptr_t)dy_a | (uintptr_t)dx | (uintptr_t)dy_b | (uintptr_t)dx_drop) & 15)) {
+  if (d == 768 || d == 1024) {
+    // every row pointer 16-byte aligned: 16-byte accesses; else the same kernel with 8-byte ones (x, dy_a, dx are 8-byte aligned
+    // by the check above; dy_b and dx_drop are read and written in 8-byte pieces as ln_bwd_kernel would)
+    const bool a16 = !(((uintptr_t)x | (uintptr_t)dy_a | (uintptr_t)dx | (uintptr_t)dy_b | (uintptr_t)dx_drop) & 15);
     const int blocks_hw = min((rows + 7) / 8, LN_BWD_BLOCKS);   // fewer blocks: the 3*d end-of-block atomics hit the same 2304 addresses
-    if (d == 768)
-      hipLaunchKernelGGL(ln_bwd_hw_kernel<3>, dim3(blocks_hw), dim3(256), 0, st, (const bf16*)dy_a, (const bf16*)dy_b,
-                         (const bf16*)x, gamma, mean, rstd, rowmask, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta, dbias_drop,
-                         rows, seed, thresh24, inv_keep, rng_rows);
-    else
-      hipLaunchKernelGGL(ln_bwd_hw_kernel<4>, dim3(blocks_hw), dim3(256), 0, st, (const bf16*)dy_a, (const bf16*)dy_b,
-                         (const bf16*)x, gamma, mean, rstd, rowmask, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta, dbias_drop,
-                         rows, seed, thresh24, inv_keep, rng_rows);
+#define M3P_LN_BWD_HW(NC, A16)                                                                                        \
+  hipLaunchKernelGGL((ln_bwd_hw_kernel<NC, A16>), dim3(blocks_hw), dim3(256), 0, st, (const bf16*)dy_a, (const bf16*)dy_b, \
+                     (const bf16*)x, gamma, mean, rstd, rowmask, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta, dbias_drop,  \
+                     rows, seed, thresh24, inv_keep, rng_rows)
+    if (d == 768) { if (a16) M3P_LN_BWD_HW(3, true); else M3P_LN_BWD_HW(3, false); }
+    else          { if (a16) M3P_LN_BWD_HW(4, true); else M3P_LN_BWD_HW(4, false); }
+#undef M3P_LN_BWD_HW
     M3P_CHECK_LAUNCH();
     return M3P_OK;
   }

@@ -261,6 +261,50 @@ def assert_accum_bound(got, ref64, abssum64, n_terms, extra=0.0, what=''):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Column gradients of LayerNorm (csrc/layernorm.hip: acc_g, acc_b, acc_d, gathered over waves, blocks and trips of the grid).
+# ---------------------------------------------------------------------------------------------------------------------
+def ln_stat_bounds(x64, mu64, rs64):
+    """What the LayerNorm tests allow the saved fp32 mean and rstd of each row to be off by: the denominators of
+    assert_gemm_bound(mean, mu64, mean|x|, d, F32_OUT) and assert_gemm_bound(rstd, rs64, rs64, d, F32_OUT).  -> (e_mu, e_rs), [rows]."""
+    d = x64.shape[-1]
+    acc = KAPPA * math.sqrt(d) * U32
+    return F32_OUT * mu64.abs() + acc * x64.abs().mean(-1), (F32_OUT + acc) * rs64
+
+
+def ln_dgamma_extra(dy64, x64, mu64, rs64):
+    """The part of dgamma's error that is not accumulation: the kernel's xhat = (x - mean) * rstd is formed in fp32 from the
+    saved fp32 mean and rstd, which carry the error of their own depth-d sums.  To first order
+        |xhat - xhat64| <= e_mu rs64 + |x - mu64| e_rs + F32_OUT |xhat64|
+    with (e_mu, e_rs) = ln_stat_bounds, the very bounds the mean / rstd assertions put on those two numbers, and F32_OUT for
+    the roundings of the difference, the two products and the sum dy_a + dy_b (four fp32 operations).  -> sum_r |dy| times that,
+    [d]: the `extra` of accum_bound.  Worst case over the rows (no sqrt): the errors of mean and rstd are not independent of the
+    data.  The fp32 restatement of tests/test_parity_bounds.py reaches 0.044 of the whole bound at 2051 x 132 and 0.038 at
+    4101 x 768 (the rounding errors do cancel); one lost term of median size in a column reaches 7.5 and 2.1."""
+    e_mu, e_rs = ln_stat_bounds(x64, mu64, rs64)
+    xc = x64 - mu64[:, None]
+    dxhat = (e_mu * rs64)[:, None] + xc.abs() * e_rs[:, None] + F32_OUT * (xc * rs64[:, None]).abs()
+    return (dy64.abs() * dxhat).sum(0)
+
+
+def ln_colsum_bounds(dg, db, dy64, x64, mu64, rs64):
+    """dgamma = sum_r dy xhat and dbeta = sum_r dy of LayerNorm backward, every column against fp64 with accum_bound over
+    n_terms = rows.  dy64 = the fp64 sum dy_a + dy_b with masked rows zeroed (the kernel multiplies dy by the row mask).
+    -> ((worst, at) of dgamma, (worst, at) of dbeta)."""
+    rows = x64.shape[0]
+    xhat = (x64 - mu64[:, None]) * rs64[:, None]
+    wg = accum_bound(dg, (dy64 * xhat).sum(0), (dy64.abs() * xhat.abs()).sum(0), rows, ln_dgamma_extra(dy64, x64, mu64, rs64))
+    wb = accum_bound(db, dy64.sum(0), dy64.abs().sum(0), rows)
+    return wg, wb
+
+
+def ln_dbias_bound(dbias, stored):
+    """dbias_drop against the fp64 column sums of the bf16 values the kernel stored (dx_drop, or what it would have held):
+    exact terms, so accumulation error only."""
+    s = stored.double()
+    return accum_bound(dbias, s.sum(0), s.abs().sum(0), s.shape[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The row kernels behind the shifted-exponential MLM head (csrc/heads.hip: ce_shift_*; DESIGN.md section 3).
 # ---------------------------------------------------------------------------------------------------------------------
 CE_SHIFT = 40.0                 # heads.hip CE_SHIFT: the rows' shift above the target's own logit
