@@ -697,6 +697,38 @@ M3P_API int m3p_ce_shift_target_rows(const void* h, const int64_t* target, const
 M3P_API int m3p_ce_shift_dh(const float* dh32, const void* emb, const int64_t* target, const float* row_s, const float* row_q,
                             const float* g, void* dh, int n_rows, int d, void* stream);
 
+/* Label smoothing of the tied vocabulary head (PyTorch's cross_entropy(label_smoothing = eps)) without a pass over the logits
+ * (csrc/smooth.hip; not a reference feature).  With e_bar = mean_v E[v, :], b_bar = mean_v b[v] and c = eps / n:
+ *   loss_eps = loss + c sum_r (z[r, y_r] - h_r . e_bar - b_bar),   dh_r += c (E[y_r] - e_bar),
+ *   dE[v, :] += c (sum_{r: y_r = v} h_r - (1 / V) sum_r h_r),        db[v] += c (count_v - n / V).
+ * The target parts of dE and db go through m3p_ce_shift_target_rows, z[r, y_r] comes from m3p_ce_shift_target.
+ *
+ * m3p_vocab_mean: mean[0 .. d) = e_bar, mean[d] = b_bar from emb bf16 [V, d] (16-byte aligned; exactly V rows are read) and
+ * bias fp32 [V].  Two stages in a fixed order, no atomics: the same bits on every run.  m3p_vocab_mean_plan = the number of
+ * partial sums per (row of a period of lcm(d, 8) elements, column) the second stage adds up (0: bad shape);
+ * workspace >= m3p_vocab_mean_workspace_bytes(V, d), 16-byte aligned, caller owned. */
+M3P_API int m3p_vocab_mean_plan(int V, int d);
+M3P_API size_t m3p_vocab_mean_workspace_bytes(int V, int d);
+M3P_API int m3p_vocab_mean(const void* emb, const float* bias, int V, int d, float* mean, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* out[0 .. d) = scale * sum_r h[r, :] (h bf16 [n_rows, d]) in the same fixed order; plan and workspace of
+ * m3p_vocab_mean_*(n_rows, d) */
+M3P_API int m3p_ls_colsum_rows(const void* h, int n_rows, int d, float scale, float* out, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* aux[r] = row_t[r] - h[r, :] . mean[0 .. d) - mean[d]  (fp32; row_t = m3p_ce_shift_target's target logits).  d % 4 == 0 */
+M3P_API int m3p_ls_row_aux(const void* h, const float* mean, const float* row_t, float* aux, int n_rows, int d, void* stream);
+/* out[0] = scale * sum_r v[r] (fp32), one block in a fixed order: the rows' aux terms into the loss, the same bits on every run */
+M3P_API int m3p_ls_sum_rows(const float* v, int n, float scale, float* out, void* stream);
+/* m3p_ce_shift_dh with the smoothing operand: dh[n, :] = bf16(g[0] * (row_s[n] * dh32[n, :] + (row_q[n] + c) * emb[y_n, :]
+ * - c * mean[0 .. d))), one rounding per element.  row_s / row_q NULL: 1 / 0 (dh32 is the plain routes' dlogits x E). */
+M3P_API int m3p_ce_shift_dh_smooth(const float* dh32, const void* emb, const int64_t* target, const float* row_s, const float* row_q,
+                                   const float* g, const float* mean, float c, void* dh, int n_rows, int d, void* stream);
+/* dst[v, :] (fp32 [V, d], 16-byte aligned) += g[0] * u[0 .. d) and dbias[v] += g[0] * db for v < V: one grid-stride stream of
+ * 16-byte accesses; nothing at or behind row V is touched.  d % 4 == 0.  m3p_ls_uniform_add_plan = the grid's blocks of 256
+ * threads (0: bad shape) - a shape with more than 256 * blocks chunks of four floats takes a second trip. */
+M3P_API int m3p_ls_uniform_add_plan(int V, int d);
+M3P_API int m3p_ls_uniform_add(float* dst, float* dbias, const float* u, const float* g, float db, int V, int d, void* stream);
+
 /* Validation scoring in one read-only pass over bf16 logits [n_rows, ld] (V valid columns): what the reference's evaluators take
  * from predict(..., get_scores=True) per batch - `loss.item() * len(y)` and `(word_scores.max(1)[1] == y).sum()`
  * (evaluation/xevaluator.py:433-438, :530-535, :654-659, :757-762, :861-866, :1165-1170; evaluator.py:240-270).

@@ -123,6 +123,7 @@ class Arena:
         # gradients autograd itself accumulates) and zero_grad() / readers go through ensure_zero() first.
         self.stale = None
         self.vocab_stored = False      # the last MLM-head backward took the store path
+        self._vocab_mean = None        # (key, fp32 [d + 1]) of vocab_mean()
         self._vocab_range = None
         self._layer_names = [[n for n in self.names if n.startswith(('attentions.%d.' % i, 'layer_norm1.%d.' % i,
                                                                      'ffns.%d.' % i, 'layer_norm2.%d.' % i))]
@@ -175,6 +176,16 @@ class Arena:
         if self._vocab_range is None:
             self._vocab_range = (self.offsets['embeddings.weight'][0], self.V_pad * self.model.dim)
         return self._vocab_range
+
+    def vocab_mean(self):
+        """fp32 [d + 1]: the mean row of the bf16 vocabulary matrix followed by the mean output bias, what label smoothing
+        subtracts from every row.  Computed once per state of the weights - keyed like the 8-bit weight
+        copies (Fp8State.quant_weights) - so the heads of one step share it and an optimizer step invalidates it.  Call it
+        behind refresh()."""
+        key = (self.epoch, self.master._version)
+        if self._vocab_mean is None or self._vocab_mean[0] != key:
+            self._vocab_mean = (key, ops.vocab_mean(self.w('embeddings.weight'), self.p('pred_layer.proj.bias'), self.model.n_words))
+        return self._vocab_mean[1]
 
     def ensure_zero(self):
         """Make a lazily zeroed range physically zero (a writer that accumulates, or a reader, is about to touch it)."""
@@ -1384,10 +1395,13 @@ class MLMHeadFn(torch.autograd.Function):
     projection (:111, :728-729) and mean cross-entropy (:112).  The bf16 logits are turned
     into their own gradient in place by the CE kernel, so backward is two GEMMs - or, on the benchmarked
     whole-tile path with no scores wanted, never stored at all: the projection writes exp(logit - shift)
-    and the normaliser is applied to the two GEMMs' small operands."""
+    and the normaliser is applied to the two GEMMs' small operands.
+
+    eps > 0: label smoothing (PyTorch's cross_entropy(label_smoothing=eps)) as a correction on [n, d] and [V, d] operands
+    behind whichever route the plain head takes; eps == 0 runs exactly the plain head's calls."""
 
     @staticmethod
-    def forward(ctx, tensor, model, base, row_idx, y, scores_out, sink=None):
+    def forward(ctx, tensor, model, base, row_idx, y, scores_out, sink=None, eps=0.0):
         ar = model.arena()
         ar.refresh()
         d, V = model.dim, model.n_words
@@ -1403,9 +1417,10 @@ class MLMHeadFn(torch.autograd.Function):
         # backward's two products instead (a caller that wants scores needs real logits)
         shifted = fused_lse and scores_out is None
         stats = None
+        row_t = None
         if shifted:
             o = ar.offsets['pred_layer.proj.bias'][0]
-            _, row_ref = ops.ce_shift_target(hsel, ar.w('embeddings.weight'), ar.p('pred_layer.proj.bias'), y)
+            row_t, row_ref = ops.ce_shift_target(hsel, ar.w('embeddings.weight'), ar.p('pred_layer.proj.bias'), y)
             stats = torch.empty((ar.V_pad // 64, n), dtype=torch.float32, device=hsel.device)
             ops.gemm_nt(hsel, ar.w('embeddings.weight'), L.EPI_BIAS_LSE, bias=ar.master[o:o + ar.V_pad], out=logits, n=n_cols,
                         out2=stats, scale_cols=V, row_ref=row_ref)
@@ -1440,6 +1455,16 @@ class MLMHeadFn(torch.autograd.Function):
             loss_sum, _ = ops.ce_fwd_bwd(logits, V, y, 1.0 / n, 1.0 / n)
         ctx.model = model
         ctx.saved = (hsel, logits, row_idx, tuple(tensor.shape), tuple(tensor.stride()), tensor.storage_offset(), base, dbias, rows)
+        ctx.smooth = None
+        if eps > 0:
+            # + (eps / n) sum_r (z[r, y_r] - h_r . e_bar - b_bar): the target's logit in fp32 (the shifted route has it already),
+            # the mean row from the arena's cache
+            mean = ar.vocab_mean()
+            if row_t is None:
+                row_t, _ = ops.ce_shift_target(hsel, ar.w('embeddings.weight'), ar.p('pred_layer.proj.bias'), y)
+            aux = ops.ls_row_aux(hsel, mean, row_t)
+            ctx.smooth = (float(eps), mean, y)
+            return loss_sum[0] + ops.ls_sum_rows(aux, float(eps) / n)[0]       # (the rows in a fixed order)
         return loss_sum[0].clone()
 
     @staticmethod
@@ -1459,6 +1484,7 @@ class MLMHeadFn(torch.autograd.Function):
         ctx.saved = None
         n = hsel.shape[0]
         g = gloss.reshape(1).float()
+        smooth, ctx.smooth = ctx.smooth, None
         # (shifted-exponential path: `dlogits` holds e = exp(logit - shift) with zeros at the target and pad columns, the rows'
         #  normaliser rides on the second operand and the targets' fp32 terms are added behind the product)
         hs = ops.scale_bf16_dev(hsel, g) if rows is None else ops.ce_shift_scale_rows(hsel, rows[0], g)
@@ -1497,14 +1523,27 @@ class MLMHeadFn(torch.autograd.Function):
             ops.axpy_dev(ar.g('pred_layer.proj.bias'), dbias[:V], g)
         else:
             ops.colsum(dlogits, V, ar.g('pred_layer.proj.bias'), scale=g)
-        if rows is not None:
+        if smooth is not None:
+            # label smoothing, behind the (stored) weight gradient like the targets' terms: dE[y_r] += g c h_r and db[y_r] += g c
+            # with c = eps / n ride on the targets' scatter (one call with q + c on the shifted route), the uniform part
+            # dE[v, :] -= g (c / V) sum_r h_r and db[v] -= g eps / V is one stream over the V rows of the matrix - not its pad rows
+            eps, mean, y = smooth
+            c = eps / n
+            row_c = rows[1] + c if rows is not None else torch.full((n,), c, dtype=torch.float32, device=hsel.device)
+            ops.ce_shift_target_rows(hsel, y, row_c, g, ar.g('embeddings.weight'), ar.g('pred_layer.proj.bias'))
+            ops.ls_uniform_add(ar.g('embeddings.weight'), ar.g('pred_layer.proj.bias'), ops.ls_colsum_rows(hsel, -c / V), g, -eps / V, V)
+        elif rows is not None:
             # a later accumulate into ranges the weight gradient has already stored (its pad rows cover the head of the bias gradient)
             ops.ce_shift_target_rows(hsel, rows[2], rows[1], g, ar.g('embeddings.weight'), ar.g('pred_layer.proj.bias'))
         dH32 = torch.zeros((n, d), dtype=torch.float32, device=dlogits.device)
         # E [V, d] read in place (no transposed copy); whole 256-row tiles of predictions run on the four-wave kernel, which
         # reads all V_pad rows of "the matrix" - the bf16 arena behind E, finite numbers against dlogits' exact-zero pad columns
         ops.gemm_nn(dlogits, ar.w('embeddings.weight'), dH32, k_rows_readable=ar.V_pad if _VOCAB_DGRAD_W4 else None)
-        if rows is None:
+        if smooth is not None:
+            # (eps / n) (E[y_r] - e_bar) enters the fp32 value each element of dH is rounded from: one rounding
+            dH = ops.ce_shift_dh_smooth(dH32, ar.w('embeddings.weight'), smooth[2], rows[0] if rows is not None else None,
+                                        rows[1] if rows is not None else None, g, smooth[1], smooth[0] / n)
+        elif rows is None:
             dH = ops.scale_bf16_dev(dH32, g)
         else:
             dH = ops.ce_shift_dh(dH32, ar.w('embeddings.weight'), rows[2], rows[0], rows[1], g)
@@ -1513,7 +1552,7 @@ class MLMHeadFn(torch.autograd.Function):
         dtensor = _scatter_rows_grad(dH, row_idx, base, shape, stride, soff, ctx.sink)
         if model.ddp_hook is not None:
             model.ddp_hook.mlm_head_done()     # the dense part of the tied matrix is final: reduce it now
-        return dtensor, None, None, None, None, None, None
+        return dtensor, None, None, None, None, None, None, None
 
 
 def _as_row_buffer(tensor, d):
@@ -1788,11 +1827,32 @@ def _mlm_rows(model, tensor, pred_mask, y):
     return tensor, base, row_idx, n
 
 
+def label_smoothing_ref(h, emb, bias, y, eps, g=1.0):
+    """The label-smoothing correction of the vocabulary head in fp64 torch, what MLMHeadFn adds on top of the plain head
+    (DESIGN.md section 4): with z = h emb^T + bias, e_bar / b_bar the means of emb / bias over the V words and c = eps / n,
+        loss += c sum_r (z[r, y_r] - h_r . e_bar - b_bar)          dh_r     += g c (emb[y_r] - e_bar)
+        demb[v] += g c (sum_{r: y_r = v} h_r - (1 / V) sum_r h_r)    dbias[v] += g c (count_v - n / V)
+    which makes mean cross-entropy PyTorch's ``cross_entropy(label_smoothing=eps)``.  h [n, d], emb [V, d], bias [V],
+    y int64 [n]; g = the upstream gradient.  -> (loss, dh [n, d], demb [V, d], dbias [V]) terms, fp64."""
+    h, emb, bias = h.double(), emb.double(), bias.double()
+    n, V = h.shape[0], emb.shape[0]
+    c = float(eps) / n
+    e_bar, b_bar = emb.mean(0), bias.mean()
+    z_y = (h * emb[y]).sum(1) + bias[y]
+    loss = c * (z_y - h @ e_bar - b_bar).sum()
+    dh = g * c * (emb[y] - e_bar)
+    demb = torch.zeros_like(emb).index_add_(0, y, h) - h.sum(0) / V
+    dbias = torch.bincount(y, minlength=V).double() - n / V
+    return loss, dh, g * c * demb, g * c * dbias
+
+
 def mlm_head(model, tensor, pred_mask, y, want_scores):
-    """predict() default branch on the rows ``_mlm_rows`` resolves."""
+    """predict() default branch on the rows ``_mlm_rows`` resolves.  In training mode the loss is label-smoothed by
+    ``model.label_smoothing`` (0: the plain head, call for call); evaluation is never smoothed."""
     tensor, base, row_idx, n = _mlm_rows(model, tensor, pred_mask, y)
     scores_out = [] if want_scores else None
-    loss = MLMHeadFn.apply(tensor, model, base, row_idx, y.to(tensor.device), scores_out, _sink_of(tensor, base))
+    eps = float(getattr(model, 'label_smoothing', 0.0)) if model.training else 0.0
+    loss = MLMHeadFn.apply(tensor, model, base, row_idx, y.to(tensor.device), scores_out, _sink_of(tensor, base), eps)
     return loss, (scores_out[0] if want_scores else None)
 
 

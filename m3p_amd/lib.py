@@ -124,6 +124,15 @@ SIGNATURES = {
     'm3p_ce_shift_scale_rows': (_i, [_p, _p, _p, _p, _i, _i, _p]),
     'm3p_ce_shift_target_rows': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
     'm3p_ce_shift_dh': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    'm3p_vocab_mean_plan': (_i, [_i, _i]),
+    'm3p_vocab_mean_workspace_bytes': (C.c_size_t, [_i, _i]),
+    'm3p_vocab_mean': (_i, [_p, _p, _i, _i, _p, _p, C.c_size_t, _p]),
+    'm3p_ls_colsum_rows': (_i, [_p, _i, _i, _f, _p, _p, C.c_size_t, _p]),
+    'm3p_ls_row_aux': (_i, [_p, _p, _p, _p, _i, _i, _p]),
+    'm3p_ls_sum_rows': (_i, [_p, _i, _f, _p, _p]),
+    'm3p_ce_shift_dh_smooth': (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _p, _i, _i, _p]),
+    'm3p_ls_uniform_add_plan': (_i, [_i, _i]),
+    'm3p_ls_uniform_add': (_i, [_p, _p, _p, _p, _f, _i, _i, _p]),
     'm3p_ce_eval': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     'm3p_colsum_bf16': (_i, [_p, _i, _i, _i, _p, _p, _p]),
     'm3p_sumsq_f32': (_i, [_p, C.c_longlong, _p, _p]),

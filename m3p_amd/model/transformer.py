@@ -202,6 +202,11 @@ class TransformerModel(nn.Module):
         assert self.n_layers >= 1
         self.dropout = params.dropout
         self.attention_dropout = params.attention_dropout
+        # label smoothing of the vocabulary head's training loss (not a reference flag; PyTorch's cross_entropy convention;
+        # params of older checkpoints lack it): predict()'s default branch in training mode, never evaluation
+        self.label_smoothing = float(getattr(params, 'label_smoothing', 0.0) or 0.0)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError('label_smoothing must lie in [0, 1): %r' % (self.label_smoothing,))
         assert self.dim % self.n_heads == 0, 'transformer dim must be a multiple of n_heads'
         assert self.dim // self.n_heads in (32, 64), 'attention kernels are built for head dims 32 and 64'
         assert self.dim % 64 == 0

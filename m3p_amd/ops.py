@@ -1231,6 +1231,87 @@ def ce_shift_dh(dh32, emb, target, row_s, row_q, g):
     return out
 
 
+# ---- label smoothing of the tied vocabulary head (csrc/smooth.hip)
+_LS_WS = {}
+
+
+def _ls_workspace(dev, rows, d):
+    need = L.load().m3p_vocab_mean_workspace_bytes(rows, d)
+    ws = _LS_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _LS_WS[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def vocab_mean(emb, bias, V):
+    """fp32 [d + 1]: the mean row of emb[:V] (bf16 [>= V, d], rows behind V not read) followed by the mean of bias[:V] (fp32).
+    Ordered two-stage sums: bit-reproducible."""
+    _chk_bf16(emb)
+    d = emb.shape[1]
+    assert emb.stride(0) == d and emb.stride(1) == 1 and emb.shape[0] >= V and bias.dtype == torch.float32 and bias.is_contiguous()
+    assert bias.numel() >= V
+    out = torch.empty(d + 1, dtype=torch.float32, device=emb.device)
+    ws = _ls_workspace(emb.device, V, d)
+    L.check(L.load().m3p_vocab_mean(emb.data_ptr(), bias.data_ptr(), V, d, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+            'm3p_vocab_mean')
+    return out
+
+
+def ls_colsum_rows(h, scale):
+    """fp32 [d] = scale * sum_r h[r, :] (h bf16 [n, d]), the ordered sums of vocab_mean."""
+    _chk_bf16(h)
+    n, d = h.shape
+    assert h.is_contiguous()
+    out = torch.empty(d, dtype=torch.float32, device=h.device)
+    ws = _ls_workspace(h.device, n, d)
+    L.check(L.load().m3p_ls_colsum_rows(h.data_ptr(), n, d, float(scale), out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+            'm3p_ls_colsum_rows')
+    return out
+
+
+def ls_row_aux(h, mean, row_t):
+    """fp32 [n]: row_t[r] - h[r, :] . mean[:d] - mean[d], the rows' label-smoothing term (row_t: ce_shift_target)."""
+    _chk_bf16(h)
+    n, d = h.shape
+    assert h.is_contiguous() and mean.dtype == row_t.dtype == torch.float32 and mean.numel() == d + 1 and row_t.numel() == n
+    aux = torch.empty(n, dtype=torch.float32, device=h.device)
+    L.check(L.load().m3p_ls_row_aux(h.data_ptr(), mean.data_ptr(), row_t.data_ptr(), aux.data_ptr(), n, d, L.stream()), 'm3p_ls_row_aux')
+    return aux
+
+
+def ls_sum_rows(v, scale):
+    """fp32 [1] = scale * sum(v) (v fp32 [n]) added up in a fixed order by one block: the rows' aux terms into the loss."""
+    assert v.dtype == torch.float32 and v.is_contiguous() and v.dim() == 1
+    out = torch.empty(1, dtype=torch.float32, device=v.device)
+    L.check(L.load().m3p_ls_sum_rows(v.data_ptr(), v.numel(), float(scale), out.data_ptr(), L.stream()), 'm3p_ls_sum_rows')
+    return out
+
+
+def ce_shift_dh_smooth(dh32, emb, target, row_s, row_q, g, mean, c):
+    """bf16(g[0] * (row_s[n] * dh32[n, :] + (row_q[n] + c) * emb[target[n], :] - c * mean[:d])): ce_shift_dh with the label-
+    smoothing operand, one rounding per element.  row_s = row_q = None: 1 and 0 (the plain routes' dh32 = dlogits x E)."""
+    _chk_bf16(emb)
+    n, d = dh32.shape
+    assert dh32.dtype == torch.float32 and dh32.is_contiguous() and emb.stride(0) == d and emb.stride(1) == 1
+    assert target.dtype == torch.int64 and target.numel() == n and g.dtype == mean.dtype == torch.float32 and mean.numel() == d + 1
+    assert (row_s is None) == (row_q is None)
+    if row_s is not None:
+        assert row_s.dtype == row_q.dtype == torch.float32 and row_s.numel() == row_q.numel() == n
+    out = torch.empty((n, d), dtype=BF16, device=dh32.device)
+    L.check(L.load().m3p_ce_shift_dh_smooth(dh32.data_ptr(), emb.data_ptr(), target.data_ptr(), L.ptr(row_s), L.ptr(row_q), g.data_ptr(),
+                                            mean.data_ptr(), float(c), out.data_ptr(), n, d, L.stream()), 'm3p_ce_shift_dh_smooth')
+    return out
+
+
+def ls_uniform_add(demb, dbias, u, g, db, V):
+    """demb[v, :] += g[0] * u and dbias[v] += g[0] * db for v < V (fp32 [>= V, d] and [>= V]); rows from V on are not touched."""
+    d = demb.shape[1]
+    assert demb.dtype == dbias.dtype == u.dtype == g.dtype == torch.float32 and demb.stride(0) == d and demb.stride(1) == 1
+    assert demb.shape[0] >= V and dbias.numel() >= V and dbias.is_contiguous() and u.numel() == d and g.numel() == 1
+    L.check(L.load().m3p_ls_uniform_add(demb.data_ptr(), dbias.data_ptr(), u.data_ptr(), g.data_ptr(), float(db), V, d, L.stream()),
+            'm3p_ls_uniform_add')
+
+
 def ce_eval(logits, V, target):
     """Validation scoring, one read-only pass over bf16 logits [n, ld >= V] (columns [V, ld) ignored): returns
     (row_loss fp32 [n] = logsumexp - target logit, row_argmax int32 [n] = lowest column of the row's maximum)."""

@@ -24,9 +24,9 @@ BOS, PAD, EOS = 0, 1, 2
 
 
 def model_params(emb_dim, n_heads, n_layers, n_words, dropout=0.0, attention_dropout=0.0,
-                 refine_layers=0, **extra):
+                 refine_layers=0, label_smoothing=0.0, **extra):
     """The flat ``params`` Namespace fields the TransformerModel ctor reads
-    (M3P/src/model/transformer.py:627-679, 725-729; PredLayer :88-102)."""
+    (M3P/src/model/transformer.py:627-679, 725-729; PredLayer :88-102); label_smoothing is the build's own field."""
     p = SimpleNamespace(
         n_langs=1, n_words=n_words, eos_index=EOS, pad_index=PAD, mask_index=n_words - 1,
         id2lang={0: 'en'}, lang2id={'en': 0},
@@ -34,7 +34,7 @@ def model_params(emb_dim, n_heads, n_layers, n_words, dropout=0.0, attention_dro
         dropout=dropout, attention_dropout=attention_dropout,
         sinusoidal_embeddings=False, refine_layers=refine_layers,
         attention_setting='v1', use_externel_att=False, gelu_activation=True,
-        asm=False, share_inout_emb=True,
+        asm=False, share_inout_emb=True, label_smoothing=label_smoothing,
     )
     for k, v in extra.items():
         setattr(p, k, v)
