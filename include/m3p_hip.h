@@ -776,6 +776,58 @@ M3P_API int m3p_adam_step_ranges(float* p, float* g, float* m, float* v, void* w
                                  float lr, float beta1, float beta2, float eps, float weight_decay, const double* gnorm_sq,
                                  float max_norm, float grad_scale, void* stream);
 
+/* LAMB on the flat arenas: Adam's moments, then a layer-wise trust ratio on the update.  The rule, for every parameter tensor t
+ * that received a gradient since the last zero_grad (Adam's "touched" rule), s = the tensor's step count after the increment,
+ * coef = grad_scale * clip_coef exactly as m3p_adam_step forms it:
+ *
+ *   g' = coef * g
+ *   m  = beta1 * m + (1 - beta1) * g'
+ *   v  = beta2 * v + (1 - beta2) * g' * g'
+ *   r  = (m / (1 - beta1^s)) / (sqrt(v / (1 - beta2^s)) + eps)  +  wd_t * p
+ *   phi_t = ||p_t||_2 / ||r_t||_2    if adapt_t and both norms > 0, else 1
+ *   p  = p - lr * phi_t * r
+ *
+ * ||p_t|| is taken on the fp32 master BEFORE the update.  A tensor is one parameter's range of the arena (its zero padding
+ * may be included: it adds nothing to either norm); under the sharded data-parallel exchange a tensor's norms are the sums
+ * over all ranks' shards.  Excluded tensors (by default those with fewer than two dimensions: biases, LayerNorm weights, the
+ * ITM score vector - the BERT convention) have wd_t = 0 and adapt_t = 0.  Untouched tensors are skipped entirely.
+ *
+ * Three launches however many tensors are active: m3p_lamb_update (m, v; r written over the gradient, which is dead after
+ * this pass; one (sum p^2, sum r^2) pair per workgroup), m3p_lamb_norms (each tensor's pairs added in a fixed order to one
+ * fp64 pair; no floating-point atomics - the same state and gradients give the same bits), m3p_lamb_apply (p, the bf16
+ * working copy, zeros over r where the piece says so).  Between norms and apply a sharded rank sums the norms table over the
+ * ranks.
+ *
+ * The pieces - ranges [start, start + count) of the arenas, each inside one tensor; a tensor is cut where the lazily zeroed
+ * vocabulary range or a shard of the sharded exchange begins or ends - are described by a table in DEVICE memory that the
+ * caller keeps for as long as the set of pieces stays the same.  m3p_lamb_table_build (host only, no GPU call) validates
+ * the pieces and fills the table's host image; the caller copies both arrays to the device:
+ *   pieces_out       n_pieces entries of M3P_LAMB_PIECE_BYTES: { int64 first quad; int64 quads; int32 tensor; int32 zero_grad;
+ *                    int32 class; int32 first workgroup }
+ *   tensor_blk0_out  int32 [n_tensors + 1]: tensor t's workgroups are [tensor_blk0[t], tensor_blk0[t + 1])
+ *   *n_blocks_out    workgroups of the update and apply launches; the workspace `partials` holds 2 doubles for each
+ * Pieces must come in arena order, disjoint, with borders on multiples of 4 elements, inside [0, arena_elems), the pieces of
+ * one tensor adjacent (tensor_ids non-decreasing); class_ids < n_classes <= M3P_LAMB_MAX_CLASSES.  Anything else returns
+ * M3P_EINVAL and nothing has run.  max_blocks <= 0: the default cap of 4096 workgroups (every piece gets at least one).
+ *
+ * The scalars that differ between the tensors of one launch travel by value, one set per class (HOST arrays of n_classes):
+ * rbc1 = 1 / (1 - beta1^s), rbc2 = 1 / (1 - beta2^s), wd = wd_t, adapt = adapt_t. */
+#define M3P_LAMB_PIECE_BYTES 32
+#define M3P_LAMB_MAX_CLASSES 32
+M3P_API int m3p_lamb_table_build(const long long* starts, const long long* counts, const int* tensor_ids, const int* zero_grad,
+                                 const int* class_ids, int n_pieces, int n_tensors, int n_classes, long long arena_elems,
+                                 int max_blocks, void* pieces_out, int* tensor_blk0_out, int* n_blocks_out);
+/* p, g, m, v: the arenas' bases (16-byte aligned); pieces: the DEVICE copy of pieces_out; partials: double [n_blocks][2]. */
+M3P_API int m3p_lamb_update(float* p, float* g, float* m, float* v, const void* pieces, int n_pieces, int n_blocks,
+                            const float* rbc1, const float* rbc2, const float* wd, const int* adapt, int n_classes, float beta1,
+                            float beta2, float eps, const double* gnorm_sq, float max_norm, float grad_scale, double* partials,
+                            void* stream);
+/* norms[t] = (sum p^2, sum r^2) of tensor t's workgroups, double [n_tensors][2]; tensor_blk0: the DEVICE copy. */
+M3P_API int m3p_lamb_norms(const double* partials, const int* tensor_blk0, int n_tensors, double* norms, void* stream);
+/* r: the gradient arena's base, holding r since m3p_lamb_update; w16 nullable. */
+M3P_API int m3p_lamb_apply(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks, const double* norms,
+                           const int* adapt, int n_classes, float lr, void* stream);
+
 /* h = gelu_erf(u) elementwise (transformer.py:56 applied to the lin1 output :223-224), bf16,
  * n % 8 == 0.  Used instead of M3P_EPI_BIAS_GELU when the GEMM is persistent.
  * dh (nullable, may alias u): also writes gelu_erf'(u) in bf16, which the backward FFN dgrad

@@ -685,3 +685,277 @@ int m3p_transpose_bf16(const void* src, void* dst, int rows, int cols, int ld_sr
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LAMB (include/m3p_hip.h: "LAMB on the flat arenas"): Adam's moments, then a per-tensor trust ratio ||p|| / ||r|| on the
+// update r.  Three launches however many tensors are active:
+//   update  reads p, g, m, v; writes m, v and r INTO THE GRADIENT'S PLACE (the gradient is dead after this pass), and one
+//           (sum p^2, sum r^2) pair per workgroup;
+//   norms   adds each tensor's workgroup pairs in a fixed order to one fp64 pair per tensor;
+//   apply   reads p, r and the tensor's pair; writes p, the bf16 working copy and - where the piece says so - zeros over r.
+// The pieces ([start, start + count) of the arenas, each inside ONE tensor) live in a table in device memory that the caller
+// caches (m3p_lamb_table_build fills its host image): the ~200 tensors of a model do not fit a by-value table like
+// AdamRanges.  Workgroups are dealt to the pieces in proportion to their sizes as in m3p_adam_step_ranges; a workgroup finds
+// its piece by bisection over the pieces' first blocks.  No floating-point atomics anywhere on the way to the norms: the
+// factor multiplies every weight of a tensor, and the same state must give the same bits.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct LambPiece {            // 32 bytes, the layout m3p_lamb_table_build writes
+  long long start4;           // first quad of the piece
+  long long n4;               // quads
+  int tensor;                 // index of the piece's tensor in the norms table
+  int zero_grad;              // apply leaves zeros (1) or r (0) in the gradient's place
+  int cls;                    // index into the per-launch class scalars
+  int blk0;                   // first workgroup of the piece
+};
+static_assert(sizeof(LambPiece) == M3P_LAMB_PIECE_BYTES, "LambPiece is the table entry the header documents");
+
+// scalars that differ between tensors of one launch, by value: the bias corrections follow a tensor's own step count
+// (heads that sat out steps lag behind), weight decay and the trust ratio are off for excluded tensors
+struct LambClasses {
+  float rbc1[M3P_LAMB_MAX_CLASSES];     // 1 / (1 - beta1^s)
+  float rbc2[M3P_LAMB_MAX_CLASSES];     // 1 / (1 - beta2^s)
+  float wd[M3P_LAMB_MAX_CLASSES];
+  int adapt[M3P_LAMB_MAX_CLASSES];
+};
+
+__device__ __forceinline__ int lamb_find_piece(const LambPiece* __restrict__ pieces, int n_pieces, int blk) {
+  int lo = 0, hi = n_pieces - 1;        // the last piece whose first block is <= blk
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pieces[mid].blk0 <= blk) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct LambUpdateArgs {
+  float* p; float* g; float* m; float* v;
+  const LambPiece* pieces;
+  int n_pieces, n_blocks;
+  float beta1, beta2, eps;
+  const double* gnorm_sq;
+  float max_norm, grad_scale;
+  double* partials;           // [n_blocks][2]
+};
+
+constexpr int LAMB_Q = 2;            // 16-byte quads per thread and trip, as ADAM_Q
+constexpr int LAMB_MAXBLK = 4096;
+
+__global__ __launch_bounds__(256) void lamb_update_kernel(LambUpdateArgs a, LambClasses c) {
+  __shared__ double red[4][2];
+  const int k = lamb_find_piece(a.pieces, a.n_pieces, (int)blockIdx.x);
+  const LambPiece pc = a.pieces[k];
+  const int blk_end = k + 1 < a.n_pieces ? a.pieces[k + 1].blk0 : a.n_blocks;
+  float coef = a.grad_scale;
+  if (a.gnorm_sq && a.max_norm > 0.f) {      // exactly adam_ranges_kernel's clip factor
+    const float norm = (float)sqrt(*a.gnorm_sq) * a.grad_scale;
+    const float cc = a.max_norm / (norm + 1e-6f);
+    coef *= (cc < 1.f) ? cc : 1.f;
+  }
+  const float ob1 = 1.f - a.beta1, ob2 = 1.f - a.beta2;
+  const float rbc1 = c.rbc1[pc.cls], rbc2 = c.rbc2[pc.cls], wd = c.wd[pc.cls];
+  const size_t base = (size_t)pc.start4, n4 = (size_t)pc.n4;
+  float* const P = a.p + 4 * base; float* const G = a.g + 4 * base; float* const M = a.m + 4 * base; float* const V = a.v + 4 * base;
+  const size_t stride = (size_t)(blk_end - pc.blk0) * blockDim.x;
+  constexpr int Q = LAMB_Q;
+  float spp = 0.f, srr = 0.f;          // one rounding of the running sums per quad (tests: the accumulation bound counts them)
+  for (size_t i0 = (size_t)((int)blockIdx.x - pc.blk0) * blockDim.x + threadIdx.x; i0 < n4; i0 += Q * stride) {
+    f32x4 p[Q], g[Q], m[Q], v[Q];
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        p[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(P + 4 * i));
+        g[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(G + 4 * i));
+        m[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(M + 4 * i));
+        v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(V + 4 * i));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        const f32x4 gc = g[u] * coef;
+        const f32x4 mn = m[u] * a.beta1 + gc * ob1;
+        const f32x4 vn = v[u] * a.beta2 + gc * gc * ob2;
+        f32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = (mn[j] * rbc1) / (sqrtf(vn[j] * rbc2) + a.eps) + wd * p[u][j];
+        __builtin_nontemporal_store(mn, reinterpret_cast<f32x4*>(M + 4 * i));
+        __builtin_nontemporal_store(vn, reinterpret_cast<f32x4*>(V + 4 * i));
+        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(G + 4 * i));
+        spp += (p[u][0] * p[u][0] + p[u][1] * p[u][1]) + (p[u][2] * p[u][2] + p[u][3] * p[u][3]);
+        srr += (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]);
+      }
+    }
+  }
+  spp = wave_sum(spp);
+  srr = wave_sum(srr);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = (double)spp; red[threadIdx.x >> 6][1] = (double)srr; }
+  __syncthreads();
+  if (threadIdx.x == 0) {              // every workgroup writes its pair: the workspace needs no zeroing
+    a.partials[2 * (size_t)blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    a.partials[2 * (size_t)blockIdx.x + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+  }
+}
+
+// one wave per tensor: lane l adds the pairs of workgroups first + l, first + l + 64, ... in that order, then the lanes
+// are folded by the butterfly - the same order every time
+__global__ __launch_bounds__(64) void lamb_norms_kernel(const double* __restrict__ partials, const int* __restrict__ tensor_blk0,
+                                                        double* __restrict__ norms) {
+  const int t = blockIdx.x;
+  const int b0 = tensor_blk0[t], b1 = tensor_blk0[t + 1];
+  double pp = 0.0, rr = 0.0;
+  for (int b = b0 + (int)threadIdx.x; b < b1; b += 64) {
+    pp += partials[2 * (size_t)b];
+    rr += partials[2 * (size_t)b + 1];
+  }
+  pp = wave_sum_f64(pp);
+  rr = wave_sum_f64(rr);
+  if (threadIdx.x == 0) { norms[2 * (size_t)t] = pp; norms[2 * (size_t)t + 1] = rr; }
+}
+
+struct LambApplyArgs {
+  float* p; float* r; bf16* w16;
+  const LambPiece* pieces;
+  int n_pieces, n_blocks;
+  const double* norms;        // [n_tensors][2]: sum p^2, sum r^2 (over all ranks' shards)
+  float lr;
+};
+
+__global__ __launch_bounds__(256) void lamb_apply_kernel(LambApplyArgs a, LambClasses c) {
+  const int k = lamb_find_piece(a.pieces, a.n_pieces, (int)blockIdx.x);
+  const LambPiece pc = a.pieces[k];
+  const int blk_end = k + 1 < a.n_pieces ? a.pieces[k + 1].blk0 : a.n_blocks;
+  const double pp = a.norms[2 * (size_t)pc.tensor], rr = a.norms[2 * (size_t)pc.tensor + 1];
+  const float phi = (c.adapt[pc.cls] && pp > 0.0 && rr > 0.0) ? (float)sqrt(pp / rr) : 1.f;
+  const float s = a.lr * phi;
+  const bool zero = pc.zero_grad != 0;
+  const size_t base = (size_t)pc.start4, n4 = (size_t)pc.n4;
+  float* const P = a.p + 4 * base; float* const R = a.r + 4 * base;
+  bf16* const W = a.w16 ? a.w16 + 4 * base : nullptr;
+  const size_t stride = (size_t)(blk_end - pc.blk0) * blockDim.x;
+  constexpr int Q = LAMB_Q;
+  for (size_t i0 = (size_t)((int)blockIdx.x - pc.blk0) * blockDim.x + threadIdx.x; i0 < n4; i0 += Q * stride) {
+    f32x4 p[Q], r[Q];
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        p[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(P + 4 * i));
+        r[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(R + 4 * i));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        const f32x4 pn = p[u] - r[u] * s;
+        __builtin_nontemporal_store(pn, reinterpret_cast<f32x4*>(P + 4 * i));
+        if (W) Vec4<bf16>::store(W + 4 * i, pn);       // (re-read by the very next forward: default policy)
+        if (zero) __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f32x4*>(R + 4 * i));
+      }
+    }
+  }
+}
+
+int lamb_classes(LambClasses* c, const float* rbc1, const float* rbc2, const float* wd, const int* adapt, int n_classes) {
+  if (!adapt || n_classes <= 0 || n_classes > M3P_LAMB_MAX_CLASSES) return M3P_EINVAL;
+  for (int i = 0; i < M3P_LAMB_MAX_CLASSES; ++i) {
+    const bool in = i < n_classes;
+    c->rbc1[i] = in && rbc1 ? rbc1[i] : 1.f;
+    c->rbc2[i] = in && rbc2 ? rbc2[i] : 1.f;
+    c->wd[i] = in && wd ? wd[i] : 0.f;
+    c->adapt[i] = in ? adapt[i] : 0;
+  }
+  return M3P_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int m3p_lamb_table_build(const long long* starts, const long long* counts, const int* tensor_ids, const int* zero_grad,
+                         const int* class_ids, int n_pieces, int n_tensors, int n_classes, long long arena_elems, int max_blocks,
+                         void* pieces_out, int* tensor_blk0_out, int* n_blocks_out) {
+  if (!starts || !counts || !tensor_ids || !zero_grad || !class_ids || !pieces_out || !tensor_blk0_out || !n_blocks_out) return M3P_EINVAL;
+  if (n_pieces <= 0 || n_tensors <= 0 || n_classes <= 0 || n_classes > M3P_LAMB_MAX_CLASSES || arena_elems <= 0) return M3P_EINVAL;
+  if (max_blocks <= 0) max_blocks = LAMB_MAXBLK;
+  long long total4 = 0, prev_end = 0;
+  for (int k = 0; k < n_pieces; ++k) {
+    // pieces in arena order, disjoint (two workgroups never write one element), inside the arena, on quad borders; the
+    // pieces of a tensor adjacent in the table (the norms launch adds ONE run of workgroups per tensor)
+    if (counts[k] <= 0 || (counts[k] % 4) != 0 || starts[k] < prev_end || (starts[k] % 4) != 0) return M3P_EINVAL;
+    if (counts[k] > arena_elems - starts[k]) return M3P_EINVAL;
+    if (tensor_ids[k] < 0 || tensor_ids[k] >= n_tensors || (k > 0 && tensor_ids[k] < tensor_ids[k - 1])) return M3P_EINVAL;
+    if (class_ids[k] < 0 || class_ids[k] >= n_classes) return M3P_EINVAL;
+    prev_end = starts[k] + counts[k];
+    total4 += counts[k] / 4;
+  }
+  long long want = (total4 + 255) / 256;       // one quad per thread and trip, at most max_blocks, at least one per piece
+  if (want > max_blocks) want = max_blocks;
+  if (want < n_pieces) want = n_pieces;
+  LambPiece* out = static_cast<LambPiece*>(pieces_out);
+  long long b = 0;
+  for (int t = 0; t <= n_tensors; ++t) tensor_blk0_out[t] = -1;
+  for (int k = 0; k < n_pieces; ++k) {
+    long long share = (long long)((double)(counts[k] / 4) / (double)total4 * (double)want);
+    const long long most = (counts[k] / 4 + 255) / 256;      // no workgroup without a quad
+    if (share > most) share = most;
+    if (share < 1) share = 1;
+    out[k] = LambPiece{starts[k] / 4, counts[k] / 4, tensor_ids[k], zero_grad[k] != 0, class_ids[k], (int)b};
+    if (tensor_blk0_out[tensor_ids[k]] < 0) tensor_blk0_out[tensor_ids[k]] = (int)b;
+    b += share;
+    if (b > 0x3fffffffLL) return M3P_EINVAL;
+  }
+  tensor_blk0_out[n_tensors] = (int)b;
+  for (int t = n_tensors - 1; t >= 0; --t)                   // a tensor without a piece (all of it another rank's): an empty run
+    if (tensor_blk0_out[t] < 0) tensor_blk0_out[t] = tensor_blk0_out[t + 1];
+  *n_blocks_out = (int)b;
+  return M3P_OK;
+}
+
+int m3p_lamb_update(float* p, float* g, float* m, float* v, const void* pieces, int n_pieces, int n_blocks, const float* rbc1,
+                    const float* rbc2, const float* wd, const int* adapt, int n_classes, float beta1, float beta2, float eps,
+                    const double* gnorm_sq, float max_norm, float grad_scale, double* partials, void* stream) {
+  if (!p || !g || !m || !v || !pieces || !partials || !rbc1 || !rbc2 || !wd || n_pieces <= 0 || n_blocks < n_pieces) return M3P_EINVAL;
+  if (((uintptr_t)p & 15) || ((uintptr_t)g & 15) || ((uintptr_t)m & 15) || ((uintptr_t)v & 15) || ((uintptr_t)pieces & 7) ||
+      ((uintptr_t)partials & 7))
+    return M3P_EINVAL;
+  LambClasses c;
+  if (lamb_classes(&c, rbc1, rbc2, wd, adapt, n_classes) != M3P_OK) return M3P_EINVAL;
+  LambUpdateArgs a = {p, g, m, v, static_cast<const LambPiece*>(pieces), n_pieces, n_blocks, beta1, beta2, eps, gnorm_sq, max_norm,
+                      grad_scale == 0.f ? 1.f : grad_scale, partials};
+  hipLaunchKernelGGL(lamb_update_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_lamb_norms(const double* partials, const int* tensor_blk0, int n_tensors, double* norms, void* stream) {
+  if (!partials || !tensor_blk0 || !norms || n_tensors <= 0) return M3P_EINVAL;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)tensor_blk0 & 3) || ((uintptr_t)norms & 7)) return M3P_EINVAL;
+  hipLaunchKernelGGL(lamb_norms_kernel, dim3(n_tensors), dim3(64), 0, (hipStream_t)stream, partials, tensor_blk0, norms);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+int m3p_lamb_apply(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks, const double* norms,
+                   const int* adapt, int n_classes, float lr, void* stream) {
+  if (!p || !r || !pieces || !norms || n_pieces <= 0 || n_blocks < n_pieces) return M3P_EINVAL;
+  if (((uintptr_t)p & 15) || ((uintptr_t)r & 15) || ((uintptr_t)w16 & 7) || ((uintptr_t)pieces & 7) || ((uintptr_t)norms & 7)) return M3P_EINVAL;
+  LambClasses c;
+  if (lamb_classes(&c, nullptr, nullptr, nullptr, adapt, n_classes) != M3P_OK) return M3P_EINVAL;
+  LambApplyArgs a = {p, r, (bf16*)w16, static_cast<const LambPiece*>(pieces), n_pieces, n_blocks, norms, lr};
+  hipLaunchKernelGGL(lamb_apply_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}
+
+}  // extern "C"

@@ -139,6 +139,10 @@ SIGNATURES = {
     'm3p_sumsq_ranges_f32': (_i, [_p, _p, _p, _i, _p, _p]),
     'm3p_adam_step': (_i, [_p, _p, _p, _p, _p, C.c_longlong, _f, _f, _f, _f, _f, _f, _p, _f, _f, _i, _p]),
     'm3p_adam_step_ranges': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _f, _f, _p]),
+    'm3p_lamb_table_build': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, C.c_longlong, _i, _p, _p, _p]),
+    'm3p_lamb_update': (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _f, _f, _f, _p, _f, _f, _p, _p]),
+    'm3p_lamb_norms': (_i, [_p, _p, _i, _p, _p]),
+    'm3p_lamb_apply': (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _i, _f, _p]),
     'm3p_itm_score_fwd': (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     'm3p_itm_score_bwd': (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _p]),
     'm3p_gelu_bwd': (_i, [_p, _p, _p, C.c_longlong, _p]),

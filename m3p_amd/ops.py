@@ -1372,6 +1372,78 @@ def adam_step_ranges(p, g, m, v, w16, pieces, lr, beta1, beta2, eps, weight_deca
     L.check(rc, 'm3p_adam_step_ranges')
 
 
+LAMB_MAX_CLASSES = 32          # M3P_LAMB_MAX_CLASSES of include/m3p_hip.h
+_LAMB_PIECE_BYTES = 32         # M3P_LAMB_PIECE_BYTES
+
+
+class LambTable:
+    """The piece table of the three LAMB launches (include/m3p_hip.h): validated and laid out by m3p_lamb_table_build on the
+    host, then - with `device` - copied once to device memory from pinned staging on the current stream, beside the
+    workspaces sized for it (the workgroups' partial sums, the per-tensor norms).  pieces = [(start, end, tensor id,
+    zero_grad, class id)] in arena order.  Built once per set of pieces and kept by the caller."""
+
+    def __init__(self, pieces, n_tensors, n_classes, arena_elems, device=None, max_blocks=0):
+        n = len(pieces)
+        self.pieces = [tuple(int(x) for x in q) for q in pieces]
+        self.n_pieces, self.n_tensors, self.n_classes = n, int(n_tensors), int(n_classes)
+        starts = (C.c_longlong * max(n, 1))(*[q[0] for q in self.pieces])
+        counts = (C.c_longlong * max(n, 1))(*[q[1] - q[0] for q in self.pieces])
+        tids = (C.c_int * max(n, 1))(*[q[2] for q in self.pieces])
+        zeros = (C.c_int * max(n, 1))(*[int(bool(q[3])) for q in self.pieces])
+        cls = (C.c_int * max(n, 1))(*[q[4] for q in self.pieces])
+        host_pieces = torch.zeros(max(n, 1) * _LAMB_PIECE_BYTES, dtype=torch.uint8)
+        host_tblk = torch.zeros(max(self.n_tensors, 0) + 1, dtype=torch.int32)
+        n_blocks = C.c_int(0)
+        rc = L.load().m3p_lamb_table_build(starts, counts, tids, zeros, cls, n, self.n_tensors, self.n_classes, int(arena_elems),
+                                           int(max_blocks), host_pieces.data_ptr(), host_tblk.data_ptr(), C.byref(n_blocks))
+        L.check(rc, 'm3p_lamb_table_build')
+        self.n_blocks = n_blocks.value
+        self.blk0 = host_pieces.view(torch.int32).view(n, 8)[:, 7].tolist() + [self.n_blocks]     # first workgroup of each piece
+        self.tensor_blk0 = host_tblk.tolist()
+        self.dev_pieces = self.dev_tblk = self.partials = self.norms = None
+        if device is not None:
+            self._staging = (host_pieces.pin_memory(), host_tblk.pin_memory())     # alive until the copies have run
+            self.dev_pieces = self._staging[0].to(device, non_blocking=True)
+            self.dev_tblk = self._staging[1].to(device, non_blocking=True)
+            self.partials = torch.empty(2 * self.n_blocks, dtype=torch.float64, device=device)
+            self.norms = torch.zeros((self.n_tensors, 2), dtype=torch.float64, device=device)
+
+    def quads_per_thread(self):
+        """The most 16-byte quads one thread of the update launch adds into its running sums, per piece."""
+        return [-(-((e - s) // 4) // (256 * (b1 - b0))) for (s, e, _, _, _), b0, b1 in zip(self.pieces, self.blk0, self.blk0[1:])]
+
+
+def _lamb_classes(classes, n_classes):
+    """classes = [(rbc1, rbc2, wd_t, adapt_t)] -> the four host arrays of the C entries."""
+    assert len(classes) == n_classes, (len(classes), n_classes)
+    n = len(classes)
+    return ((C.c_float * n)(*[float(c[0]) for c in classes]), (C.c_float * n)(*[float(c[1]) for c in classes]),
+            (C.c_float * n)(*[float(c[2]) for c in classes]), (C.c_int * n)(*[int(bool(c[3])) for c in classes]))
+
+
+def lamb_update(p, g, m, v, table, classes, beta1, beta2, eps, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """First LAMB launch: m, v updated, r written over g, the workgroups' (sum p^2, sum r^2) into table.partials."""
+    rbc1, rbc2, wd, adapt = _lamb_classes(classes, table.n_classes)
+    rc = L.load().m3p_lamb_update(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), table.dev_pieces.data_ptr(), table.n_pieces,
+                                  table.n_blocks, rbc1, rbc2, wd, adapt, table.n_classes, beta1, beta2, eps, L.ptr(gnorm_sq),
+                                  max_norm, grad_scale, table.partials.data_ptr(), L.stream())
+    L.check(rc, 'm3p_lamb_update')
+
+
+def lamb_norms(table):
+    """Second launch: table.norms[t] = (sum p^2, sum r^2) over tensor t's workgroups, fp64, in a fixed order."""
+    rc = L.load().m3p_lamb_norms(table.partials.data_ptr(), table.dev_tblk.data_ptr(), table.n_tensors, table.norms.data_ptr(), L.stream())
+    L.check(rc, 'm3p_lamb_norms')
+
+
+def lamb_apply(p, r, w16, table, classes, lr):
+    """Third launch: p -= lr * phi_t * r with phi_t from table.norms; bf16 copy refreshed, r zeroed where the piece says so."""
+    _, _, _, adapt = _lamb_classes(classes, table.n_classes)
+    rc = L.load().m3p_lamb_apply(p.data_ptr(), r.data_ptr(), L.ptr(w16), table.dev_pieces.data_ptr(), table.n_pieces, table.n_blocks,
+                                 table.norms.data_ptr(), adapt, table.n_classes, lr, L.stream())
+    L.check(rc, 'm3p_lamb_apply')
+
+
 def transpose_bf16(src, dst):
     """dst[c, r] = src[r, c]; dst may have a row pitch larger than rows (pad columns untouched)."""
     rows, cols = src.shape

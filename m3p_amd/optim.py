@@ -12,6 +12,10 @@ Semantics kept from the reference:
     weight decay is the decoupled ``p -= wd * lr * p`` (:81-82);
   * AdamInverseSqrtWithWarmup is constructed with lr = warmup_init_lr and moves the lr
     *after* each step (:135-139); ``param_groups[*]['num_updates']`` is checkpoint-visible.
+    AdamCosineWithWarmup (:142-209) likewise.
+
+Beyond the reference: Lamb and its two scheduled forms - Adam's moments with a per-tensor trust ratio, on the same arenas and
+state, three launches per step (m3p_lamb_update / _norms / _apply; the rule is written out in include/m3p_hip.h).
 """
 import inspect
 import math
@@ -164,36 +168,7 @@ class Adam(optim.Optimizer):
                 if covered == vc:
                     lazy = (v0, v0 + vc)
                     arena.defer_vocab_zero()
-            # every piece of every active range of a parameter group goes into ONE launch (ops.adam_step_ranges): a sharded rank
-            # steps fifteen bucket shards, and fifteen launches streamed the same bytes 24 % slower than one
-            batches = {}
-            bump = []          # (parameter, new step count): applied only once every launch below has been accepted
-            for r in active:
-                group = r['group']
-                beta1, beta2 = group['betas']
-                step = r['step'] + 1
-                bc1 = 1 - beta1 ** step
-                bc2 = 1 - beta2 ** step
-                step_size = group['lr'] * math.sqrt(bc2) / bc1
-                pieces = batches.setdefault(id(group), (group, []))[1]
-                for s, e in self._owned(arena, r['start'], r['end']):
-                    if lazy is None or e <= lazy[0] or s >= lazy[1]:
-                        pieces.append((s, e, step_size, True))
-                    else:
-                        cuts = sorted({s, e, min(max(lazy[0], s), e), min(max(lazy[1], s), e)})
-                        pieces.extend((a, b, step_size, not (lazy[0] <= a and b <= lazy[1])) for a, b in zip(cuts, cuts[1:]) if b > a)
-                bump.extend((p, step) for p in r['params'])
-            for group, pieces in batches.values():
-                # (the kernel takes pieces whose borders are multiples of four elements: a bad one is refused HERE, before any
-                #  launch of this step has changed a parameter or a step counter)
-                bad = [(a, b) for a, b, _, _ in pieces if (a | b) & 3]
-                if bad:
-                    raise ValueError('fused Adam: piece borders must be multiples of 4 elements, got %s' % bad[:3])
-            for group, pieces in batches.values():
-                beta1, beta2 = group['betas']
-                ops.adam_step_ranges(arena.master, arena.grad, ent['m'], ent['v'], arena.w16, pieces, group['lr'], beta1, beta2,
-                                     group['eps'], group['weight_decay'], gnorm_sq=ent['gnorm'] if max_norm > 0 else None,
-                                     max_norm=max_norm, grad_scale=self.grad_scale)
+            bump = self._launch_arena(arena, ent, active, lazy, max_norm)
             for p, step in bump:
                 self.state[p]['step'] = step
             # sharded exchange: the other ranks' shards of the updated master come back through an all-gather that the
@@ -202,6 +177,49 @@ class Adam(optim.Optimizer):
             gathered = hook is not None and hook.after_sharded_step([(r['start'], r['end']) for r in active], keep=lazy)
             # untouched ranges may still hold stale values only if someone wrote them by hand
             arena.after_fused_step(copies_scheduled=gathered)
+        self._step_loose(max_norm)
+        return loss
+
+    def _launch_arena(self, arena, ent, active, lazy, max_norm):
+        """The update of one arena's active ranges (lazy = the [start, end) this step leaves un-zeroed, or None).
+        -> [(parameter, new step count)], which step() applies only once every launch has been accepted."""
+        # every piece of every active range of a parameter group goes into ONE launch (ops.adam_step_ranges): a sharded rank
+        # steps fifteen bucket shards, and fifteen launches streamed the same bytes 24 % slower than one
+        batches = {}
+        bump = []          # (parameter, new step count): applied only once every launch below has been accepted (ADVICE r5)
+        for r in active:
+            group = r['group']
+            beta1, beta2 = group['betas']
+            step = r['step'] + 1
+            bc1 = 1 - beta1 ** step
+            bc2 = 1 - beta2 ** step
+            step_size = group['lr'] * math.sqrt(bc2) / bc1
+            pieces = batches.setdefault(id(group), (group, []))[1]
+            for s, e in self._owned(arena, r['start'], r['end']):
+                pieces.extend((a, b, step_size, z) for a, b, z in self._cut_lazy(s, e, lazy))
+            bump.extend((p, step) for p in r['params'])
+        for group, pieces in batches.values():
+            # (the kernel takes pieces whose borders are multiples of four elements: a bad one is refused HERE, before any
+            #  launch of this step has changed a parameter or a step counter)
+            bad = [(a, b) for a, b, _, _ in pieces if (a | b) & 3]
+            if bad:
+                raise ValueError('fused Adam: piece borders must be multiples of 4 elements, got %s' % bad[:3])
+        for group, pieces in batches.values():
+            beta1, beta2 = group['betas']
+            ops.adam_step_ranges(arena.master, arena.grad, ent['m'], ent['v'], arena.w16, pieces, group['lr'], beta1, beta2,
+                                 group['eps'], group['weight_decay'], gnorm_sq=ent['gnorm'] if max_norm > 0 else None,
+                                 max_norm=max_norm, grad_scale=self.grad_scale)
+        return bump
+
+    @staticmethod
+    def _cut_lazy(s, e, lazy):
+        """[s, e) cut at the borders of the lazily zeroed range -> [(start, end, zero_grad)]: the parts inside it are not zeroed."""
+        if lazy is None or e <= lazy[0] or s >= lazy[1]:
+            return [(s, e, True)]
+        cuts = sorted({s, e, min(max(lazy[0], s), e), min(max(lazy[1], s), e)})
+        return [(a, b, not (lazy[0] <= a and b <= lazy[1])) for a, b in zip(cuts, cuts[1:]) if b > a]
+
+    def _step_loose(self, max_norm):
         # parameters outside any arena (never the case on the hot path) — reference loop
         for group in self.param_groups:
             for p in group['params']:
@@ -220,7 +238,6 @@ class Adam(optim.Optimizer):
                 if group['weight_decay'] != 0:
                     p.data.add_(p.data, alpha=-group['weight_decay'] * group['lr'])
                 p.data.addcdiv_(state['exp_avg'], denom, value=-step_size)
-        return loss
 
 
 def inverse_sqrt_schedule(peak_lr, warmup, floor_lr, power):
@@ -233,15 +250,39 @@ def inverse_sqrt_schedule(peak_lr, warmup, floor_lr, power):
     return lr_at
 
 
-class AdamInverseSqrtWithWarmup(Adam):
-    """Adam whose lr follows `inverse_sqrt_schedule` (optim.py:89-139): built at the floor rate, every `step()` counts
-    one update per parameter group (`num_updates`, which checkpoints carry) and moves the group's lr along the curve."""
+def cosine_schedule(peak_lr, warmup, floor_lr, min_lr, period, period_mult, lr_shrink):
+    """lr(t) of optim.py:186-202: the warm-up line from `floor_lr` to `peak_lr`, then cosine periods (arXiv 1608.03983) from
+    the peak down to `min_lr`; period i is `period * period_mult ** i` updates long and both ends shrink by `lr_shrink ** i`.
+    Stated like `inverse_sqrt_schedule`, as a function of the update count: the periods are walked from the first one on
+    (equal periods are skipped in one division; growing ones are few - their lengths add up geometrically), so a period
+    border is decided by the integer arithmetic of the counts and not by a rounded logarithm."""
+    if period <= 0 or period_mult < 1:
+        raise ValueError('cosine schedule: init_period must be positive and period_mult >= 1 (periods that shrink add up to a '
+                         'finite number of updates), got %r, %r' % (period, period_mult))
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, warmup_updates=4000,
-                 warmup_init_lr=1e-7, exp_factor=0.5):
-        super().__init__(params, lr=warmup_init_lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        self.schedule = dict(peak_lr=lr, warmup=warmup_updates, floor_lr=warmup_init_lr, power=exp_factor)
-        self._lr_at = inverse_sqrt_schedule(**self.schedule)
+    def lr_at(t):
+        if t < warmup:
+            return floor_lr + (peak_lr - floor_lr) * t / warmup
+        into, length, done = t - warmup, period, 0       # updates into the current period, its length, periods completed
+        if period_mult == 1:
+            done, into = divmod(into, length)
+        else:
+            while into >= length:
+                into, length, done = into - length, length * period_mult, done + 1
+        scale = lr_shrink ** done
+        descent = (1 + math.cos(math.pi * into / length)) / 2      # 1 at the start of a period, 0 at its end
+        return scale * (min_lr + (peak_lr - min_lr) * descent)
+    return lr_at
+
+
+class _Scheduled:
+    """The schedule, apart from the update rule: mixed in FRONT of an optimizer class whose constructor was given the floor
+    rate.  Every `step()` counts one update per parameter group (`num_updates`, which checkpoints carry) and moves the
+    group's lr along `self._lr_at`; `get_lr_for_step` is what Trainer.reload_checkpoint asks after restoring the count."""
+
+    def _start_schedule(self, make, **schedule):
+        self.schedule = schedule
+        self._lr_at = make(**schedule)
         for group in self.param_groups:
             group['num_updates'] = 0
 
@@ -256,6 +297,155 @@ class AdamInverseSqrtWithWarmup(Adam):
         return out
 
 
+class AdamInverseSqrtWithWarmup(_Scheduled, Adam):
+    """Adam whose lr follows `inverse_sqrt_schedule` (optim.py:89-139): built at the floor rate, every `step()` counts
+    one update per parameter group (`num_updates`, which checkpoints carry) and moves the group's lr along the curve."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, warmup_updates=4000,
+                 warmup_init_lr=1e-7, exp_factor=0.5):
+        super().__init__(params, lr=warmup_init_lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._start_schedule(inverse_sqrt_schedule, peak_lr=lr, warmup=warmup_updates, floor_lr=warmup_init_lr, power=exp_factor)
+
+
+class AdamCosineWithWarmup(_Scheduled, Adam):
+    """Adam whose lr follows `cosine_schedule` (optim.py:142-209), constructor arguments as there."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, warmup_updates=4000,
+                 warmup_init_lr=1e-7, min_lr=1e-9, init_period=1000000, period_mult=1, lr_shrink=0.75):
+        super().__init__(params, lr=warmup_init_lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._start_schedule(cosine_schedule, peak_lr=lr, warmup=warmup_updates, floor_lr=warmup_init_lr, min_lr=min_lr,
+                             period=init_period, period_mult=period_mult, lr_shrink=lr_shrink)
+
+
+class Lamb(Adam):
+    """LAMB (arXiv 1904.00962) on the fused arena path: Adam's moments and a per-tensor trust ratio ||p|| / ||r|| on the
+    update r = m_hat / (sqrt(v_hat) + eps) + wd p - the rule is written out in include/m3p_hip.h.  Everything around the
+    launch is Adam's: the touched rule, the deferred clip, the lazily zeroed vocabulary range, the shards of the sharded
+    exchange, the state keys (`step`, `exp_avg`, `exp_avg_sq`: the same views of the moment arenas, so checkpoints are
+    interchangeable).  exclude_1d: tensors with fewer than two dimensions (biases, LayerNorm weights, the ITM score vector)
+    neither decay nor adapt - the BERT convention."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, exclude_1d=True):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.exclude_1d = bool(exclude_1d)
+        self._tables = {}        # (id(arena), id(group)) -> {pieces: ops.LambTable}: one per set of active pieces (step type)
+
+    def _tensor_rule(self, p, group):
+        """(wd_t, adapt_t) of a parameter."""
+        plain = self.exclude_1d and p.dim() < 2
+        return (0.0 if plain else group['weight_decay']), not plain
+
+    def _table(self, arena, group, pieces, n_tensors, n_classes):
+        cache = self._tables.setdefault((id(arena), id(group)), {})
+        key = (tuple(pieces), n_tensors, n_classes)
+        table = cache.get(key)
+        if table is None:
+            if len(cache) >= 64:         # (a training run alternates between a handful of step types)
+                cache.clear()
+            table = cache[key] = ops.LambTable(pieces, n_tensors, n_classes, arena.total, device=arena.device)
+        return table
+
+    def _launch_arena(self, arena, ent, active, lazy, max_norm):
+        chunks = {}           # id(group) -> [chunk]: the tensors of a group in arena order, cut where a launch's classes are full
+        bump = []
+        for r in active:
+            group = r['group']
+            beta1, beta2 = group['betas']
+            step = r['step'] + 1
+            run = chunks.setdefault(id(group), [])
+            for p in r['params']:
+                o, cnt, _ = arena.offsets[p._m3p_arena[1]]
+                end = o + (cnt + 63) // 64 * 64          # (the zero padding behind a tensor adds nothing to either norm)
+                wd_t, adapt_t = self._tensor_rule(p, group)
+                # class = the scalars tensors may differ in; numbered in order of appearance, so that the same step type
+                # finds its cached table again although the step counts have moved on.  A launch carries LAMB_MAX_CLASSES of
+                # them by value: a group whose tensors hold more distinct (step count, wd_t, adapt_t) than that - more than
+                # ~16 heads that have sat out different numbers of steps - goes on in another table and three more launches.
+                # (Every rank cuts alike: the cut depends on the tensors and their step counts only.)
+                key = (step, wd_t, adapt_t)
+                if not run or (key not in run[-1]['class_ids'] and len(run[-1]['classes']) == ops.LAMB_MAX_CLASSES):
+                    run.append(dict(group=group, pieces=[], class_ids={}, classes=[], n_tensors=0))
+                b = run[-1]
+                cls = b['class_ids'].setdefault(key, len(b['classes']))
+                if cls == len(b['classes']):
+                    b['classes'].append((1.0 / (1 - beta1 ** step), 1.0 / (1 - beta2 ** step), wd_t, adapt_t))
+                tid = b['n_tensors']                       # every rank numbers the tensors alike, whatever it owns of them
+                b['n_tensors'] += 1
+                for s, e in self._owned(arena, o, end):
+                    b['pieces'].extend((a, c, tid, z, cls) for a, c, z in self._cut_lazy(s, e, lazy))
+            bump.extend((p, step) for p in r['params'])
+        batches = [b for run in chunks.values() for b in run]
+        # (tables are validated when they are built: a piece the kernels cannot take is refused HERE, before any launch of
+        #  this step has changed a parameter or a step counter)
+        for b in batches:
+            b['table'] = self._table(arena, b['group'], b['pieces'], b['n_tensors'], len(b['classes'])) if b['pieces'] else None
+        hook = self._hook(arena)
+        for b in batches:
+            group, table, classes = b['group'], b['table'], b['classes']
+            beta1, beta2 = group['betas']
+            if table is None:
+                # a sharded rank that owns nothing of this group still takes part in the sum of the norms
+                if hook is not None:
+                    hook.all_reduce_scalar(torch.zeros((b['n_tensors'], 2), dtype=torch.float64, device=arena.device))
+                continue
+            ops.lamb_update(arena.master, arena.grad, ent['m'], ent['v'], table, classes, beta1, beta2, group['eps'],
+                            gnorm_sq=ent['gnorm'] if max_norm > 0 else None, max_norm=max_norm, grad_scale=self.grad_scale)
+            ops.lamb_norms(table)
+            if hook is not None:
+                hook.all_reduce_scalar(table.norms)      # sharded exchange: a tensor's norms are the sums over the ranks' shards
+            ops.lamb_apply(arena.master, arena.grad, arena.w16, table, classes, group['lr'])
+        return bump
+
+    def _step_loose(self, max_norm):
+        # parameters outside any arena (CPU models): the same rule as a plain torch loop
+        loose = [(group, p) for group in self.param_groups for p in group['params']
+                 if getattr(p, '_m3p_arena', None) is None and p.grad is not None]
+        if not loose:
+            return
+        coef = self.grad_scale
+        if max_norm > 0:
+            norm = math.sqrt(sum(float(p.grad.data.double().pow(2).sum()) for _, p in loose)) * self.grad_scale
+            coef *= min(1.0, max_norm / (norm + 1e-6))
+        for group, p in loose:
+            grad = p.grad.data * coef
+            state = self.state[p]
+            beta1, beta2 = group['betas']
+            wd_t, adapt_t = self._tensor_rule(p, group)
+            state['step'] += 1
+            state['exp_avg'].mul_(beta1).add_(grad, alpha=1 - beta1)
+            state['exp_avg_sq'].mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+            bc1 = 1 - beta1 ** state['step']
+            bc2 = 1 - beta2 ** state['step']
+            r = (state['exp_avg'] / bc1) / ((state['exp_avg_sq'] / bc2).sqrt() + group['eps'])
+            if wd_t != 0:
+                r = r.add(p.data, alpha=wd_t)
+            phi = 1.0
+            if adapt_t:
+                pn, rn = float(p.data.double().norm()), float(r.double().norm())
+                if pn > 0 and rn > 0:
+                    phi = pn / rn
+            p.data.add_(r, alpha=-group['lr'] * phi)
+
+
+class LambInverseSqrtWithWarmup(_Scheduled, Lamb):
+    """Lamb whose lr follows `inverse_sqrt_schedule`, arguments as AdamInverseSqrtWithWarmup's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, exclude_1d=True, warmup_updates=4000,
+                 warmup_init_lr=1e-7, exp_factor=0.5):
+        super().__init__(params, lr=warmup_init_lr, betas=betas, eps=eps, weight_decay=weight_decay, exclude_1d=exclude_1d)
+        self._start_schedule(inverse_sqrt_schedule, peak_lr=lr, warmup=warmup_updates, floor_lr=warmup_init_lr, power=exp_factor)
+
+
+class LambCosineWithWarmup(_Scheduled, Lamb):
+    """Lamb whose lr follows `cosine_schedule`, arguments as AdamCosineWithWarmup's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, exclude_1d=True, warmup_updates=4000,
+                 warmup_init_lr=1e-7, min_lr=1e-9, init_period=1000000, period_mult=1, lr_shrink=0.75):
+        super().__init__(params, lr=warmup_init_lr, betas=betas, eps=eps, weight_decay=weight_decay, exclude_1d=exclude_1d)
+        self._start_schedule(cosine_schedule, peak_lr=lr, warmup=warmup_updates, floor_lr=warmup_init_lr, min_lr=min_lr,
+                             period=init_period, period_mult=period_mult, lr_shrink=lr_shrink)
+
+
 def clip_grad_norm_(parameters, max_norm, optimizer):
     """Fused stand-in for torch.nn.utils.clip_grad_norm_ at xtrainer.py:225/237 (see
     Adam.clip_grad_norm)."""
@@ -266,6 +456,10 @@ def clip_grad_norm_(parameters, max_norm, optimizer):
 _METHODS = {
     'adam': (Adam, True),
     'adam_inverse_sqrt': (AdamInverseSqrtWithWarmup, True),
+    'adam_cosine': (AdamCosineWithWarmup, True),
+    'lamb': (Lamb, True),
+    'lamb_inverse_sqrt': (LambInverseSqrtWithWarmup, True),
+    'lamb_cosine': (LambCosineWithWarmup, True),
     'adadelta': (optim.Adadelta, False),
     'adagrad': (optim.Adagrad, False),
     'adamax': (optim.Adamax, False),
@@ -292,9 +486,10 @@ def parse_optimizer_spec(spec):
 
 
 def get_optimizer(parameters, s):
-    """Drop-in for optim.py:211-270.  adam / adam_inverse_sqrt run on the fused kernels; the torch.optim names the
-    reference also accepts pass through (they then see ordinary fp32 parameters).  Unknown methods and options
-    the optimizer's constructor does not take raise, like the reference."""
+    """Drop-in for optim.py:211-270.  adam / adam_inverse_sqrt / adam_cosine and lamb / lamb_inverse_sqrt / lamb_cosine
+    (``exclude_1d=0|1`` in the same number-only syntax) run on the fused kernels; the torch.optim names the reference also
+    accepts pass through (they then see ordinary fp32 parameters).  Unknown methods and options the optimizer's
+    constructor does not take raise, like the reference."""
     method, kwargs = parse_optimizer_spec(s)
     if method not in _METHODS:
         raise Exception('Unknown optimization method: "%s"' % method)
