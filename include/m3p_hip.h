@@ -828,6 +828,40 @@ M3P_API int m3p_lamb_norms(const double* partials, const int* tensor_blk0, int n
 M3P_API int m3p_lamb_apply(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks, const double* norms,
                            const int* adapt, int n_classes, float lr, void* stream);
 
+/* Non-finite guard of the optimizer step: the decision "skip this step" taken on the device from the reduced gradient norm,
+ * with no host read.  m3p_step_guard is one single-thread launch in front of a step's update launches:
+ *   gnorm_sq   HOST array of n_arenas DEVICE pointers, each to the double that m3p_sumsq_* reduced for one arena of the
+ *              optimizer (all ranks' shards summed where the gradients are sharded).  1 <= n_arenas <= M3P_GUARD_MAX_ARENAS;
+ *              more returns M3P_ENOTIMPL.
+ *   attempt    the step's attempt index (the host counts every step() call, skipped or not), >= 0.
+ * It writes, with plain stores from one thread (device memory, all of it caller-zeroed before the first attempt):
+ *   *skip                         1 if any of the sums is NaN or +-inf as a double, else 0
+ *   ring[attempt & 63]            the same value (M3P_GUARD_RING entries)
+ *   norm_ring[attempt & 63]       sqrt(sum of the sums) * grad_scale, the global gradient norm (non-finite on a skipped step)
+ *   counters[0 .. 2]              attempts, skipped_total, skipped_in_a_row (+1 each as they apply; a finite step resets the last)
+ * The _guarded forms of the update launches below take that `skip`.  skip == NULL is the unguarded launch, the same kernel and
+ * the same bits.  With *skip == 0 the update is the unguarded one, bit for bit.  With *skip != 0 a launch stores nothing to p,
+ * m, v, w16, partials or norms; the pieces whose zero_grad flag is set get zeros STORED over their gradient (by
+ * m3p_adam_step_ranges_guarded, and by m3p_lamb_apply_guarded for LAMB - the update and norms launches return at once), pieces
+ * whose flag is clear are not touched.  The branch is uniform per workgroup and comes before the first load of an arena: a
+ * skipped step costs one write of the gradient arena and no read. */
+#define M3P_GUARD_MAX_ARENAS 8
+#define M3P_GUARD_RING 64
+M3P_API int m3p_step_guard(const double* const* gnorm_sq, int n_arenas, float grad_scale, long long attempt, int* skip, int* ring,
+                           double* norm_ring, long long* counters, void* stream);
+M3P_API int m3p_adam_step_ranges_guarded(float* p, float* g, float* m, float* v, void* w16, const long long* starts,
+                                         const long long* counts, const float* step_sizes, const int* zero_grad, int n_ranges,
+                                         float lr, float beta1, float beta2, float eps, float weight_decay, const double* gnorm_sq,
+                                         float max_norm, float grad_scale, const int* skip, void* stream);
+M3P_API int m3p_lamb_update_guarded(float* p, float* g, float* m, float* v, const void* pieces, int n_pieces, int n_blocks,
+                                    const float* rbc1, const float* rbc2, const float* wd, const int* adapt, int n_classes,
+                                    float beta1, float beta2, float eps, const double* gnorm_sq, float max_norm, float grad_scale,
+                                    double* partials, const int* skip, void* stream);
+M3P_API int m3p_lamb_norms_guarded(const double* partials, const int* tensor_blk0, int n_tensors, double* norms, const int* skip,
+                                   void* stream);
+M3P_API int m3p_lamb_apply_guarded(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks,
+                                   const double* norms, const int* adapt, int n_classes, float lr, const int* skip, void* stream);
+
 /* h = gelu_erf(u) elementwise (transformer.py:56 applied to the lin1 output :223-224), bf16,
  * n % 8 == 0.  Used instead of M3P_EPI_BIAS_GELU when the GEMM is persistent.
  * dh (nullable, may alias u): also writes gelu_erf'(u) in bf16, which the backward FFN dgrad

@@ -568,9 +568,25 @@ struct AdamRanges {
 // loop shape of the fused update over the arena: every shape swept measured the same 6.1 TB/s (profiles/r05_adam_sweep.txt)
 constexpr int ADAM_Q = 2;            // 16-byte quads per thread and trip (x 4 read streams = loads in flight before the first use)
 constexpr int ADAM_MAXBLK = 4096;    // blocks per launch at most
-__global__ __launch_bounds__(256) void adam_ranges_kernel(AdamRanges a) {
+}  // extern "C" (a template has C++ linkage)
+
+namespace {
+// GUARD: the non-finite guard's form (include/m3p_hip.h, m3p_step_guard).  *skip is one word every workgroup reads before
+// anything else; on a skipped step the workgroup stores zeros over its share of a piece that asks for them - the same
+// elements it would have updated - and loads nothing from the arenas.  GUARD = false is the launch as it always was.
+template <bool GUARD>
+__global__ __launch_bounds__(256) void adam_ranges_kernel(AdamRanges a, const int* __restrict__ skip) {
   int r = 0;
   while (r + 1 < a.n && (int)blockIdx.x >= a.blk0[r + 1]) ++r;
+  if (GUARD && *skip != 0) {
+    if (a.zero_grad[r] == 0) return;
+    float* const G = a.c.g + 4 * (size_t)a.start4[r];
+    const size_t n4 = (size_t)a.n4[r];
+    const size_t stride = (size_t)(a.blk0[r + 1] - a.blk0[r]) * blockDim.x;
+    for (size_t i = (size_t)((int)blockIdx.x - a.blk0[r]) * blockDim.x + threadIdx.x; i < n4; i += stride)
+      __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f32x4*>(G + 4 * i));
+    return;
+  }
   float coef = a.c.grad_scale;
   if (a.c.gnorm_sq && a.c.max_norm > 0.f) {
     const float norm = (float)sqrt(*a.c.gnorm_sq) * a.c.grad_scale;
@@ -621,9 +637,21 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(AdamRanges a) {
   }
 }
 
+}  // namespace
+extern "C" {
+
 int m3p_adam_step_ranges(float* p, float* g, float* m, float* v, void* w16, const long long* starts, const long long* counts,
                          const float* step_sizes, const int* zero_grad, int n_ranges, float lr, float beta1, float beta2, float eps,
                          float weight_decay, const double* gnorm_sq, float max_norm, float grad_scale, void* stream) {
+  return m3p_adam_step_ranges_guarded(p, g, m, v, w16, starts, counts, step_sizes, zero_grad, n_ranges, lr, beta1, beta2, eps,
+                                      weight_decay, gnorm_sq, max_norm, grad_scale, nullptr, stream);
+}
+
+int m3p_adam_step_ranges_guarded(float* p, float* g, float* m, float* v, void* w16, const long long* starts, const long long* counts,
+                                 const float* step_sizes, const int* zero_grad, int n_ranges, float lr, float beta1, float beta2,
+                                 float eps, float weight_decay, const double* gnorm_sq, float max_norm, float grad_scale,
+                                 const int* skip, void* stream) {
+  if ((uintptr_t)skip & 3) return M3P_EINVAL;
   if (!p || !g || !m || !v || !starts || !counts || !step_sizes || !zero_grad || n_ranges <= 0) return M3P_EINVAL;
   if (((uintptr_t)p & 15) || ((uintptr_t)g & 15) || ((uintptr_t)m & 15) || ((uintptr_t)v & 15) || ((uintptr_t)w16 & 7)) return M3P_EINVAL;
   for (int r = 0; r < n_ranges; ++r)
@@ -656,7 +684,10 @@ int m3p_adam_step_ranges(float* p, float* g, float* m, float* v, void* w16, cons
       b += (int)share;
     }
     a.blk0[a.n] = b;
-    hipLaunchKernelGGL(adam_ranges_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, a);
+    if (skip)
+      hipLaunchKernelGGL(adam_ranges_kernel<true>, dim3(b), dim3(256), 0, (hipStream_t)stream, a, skip);
+    else
+      hipLaunchKernelGGL(adam_ranges_kernel<false>, dim3(b), dim3(256), 0, (hipStream_t)stream, a, skip);
     M3P_CHECK_LAUNCH();
   }
   return M3P_OK;
@@ -748,8 +779,13 @@ struct LambUpdateArgs {
 constexpr int LAMB_Q = 2;            // 16-byte quads per thread and trip, as ADAM_Q
 constexpr int LAMB_MAXBLK = 4096;
 
-__global__ __launch_bounds__(256) void lamb_update_kernel(LambUpdateArgs a, LambClasses c) {
+// GUARD (all three launches): the non-finite guard's forms, as adam_ranges_kernel<true>.  On a skipped step update and norms
+// return before their first load - partials and norms keep whatever they held, nothing reads them - and apply is the one
+// launch that stores the zeros.
+template <bool GUARD>
+__global__ __launch_bounds__(256) void lamb_update_kernel(LambUpdateArgs a, LambClasses c, const int* __restrict__ skip) {
   __shared__ double red[4][2];
+  if (GUARD && *skip != 0) return;
   const int k = lamb_find_piece(a.pieces, a.n_pieces, (int)blockIdx.x);
   const LambPiece pc = a.pieces[k];
   const int blk_end = k + 1 < a.n_pieces ? a.pieces[k + 1].blk0 : a.n_blocks;
@@ -808,8 +844,10 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(LambUpdateArgs a, Lamb
 
 // one wave per tensor: lane l adds the pairs of workgroups first + l, first + l + 64, ... in that order, then the lanes
 // are folded by the butterfly - the same order every time
+template <bool GUARD>
 __global__ __launch_bounds__(64) void lamb_norms_kernel(const double* __restrict__ partials, const int* __restrict__ tensor_blk0,
-                                                        double* __restrict__ norms) {
+                                                        double* __restrict__ norms, const int* __restrict__ skip) {
+  if (GUARD && *skip != 0) return;
   const int t = blockIdx.x;
   const int b0 = tensor_blk0[t], b1 = tensor_blk0[t + 1];
   double pp = 0.0, rr = 0.0;
@@ -830,10 +868,20 @@ struct LambApplyArgs {
   float lr;
 };
 
-__global__ __launch_bounds__(256) void lamb_apply_kernel(LambApplyArgs a, LambClasses c) {
+template <bool GUARD>
+__global__ __launch_bounds__(256) void lamb_apply_kernel(LambApplyArgs a, LambClasses c, const int* __restrict__ skip) {
+  const bool skipped = GUARD && *skip != 0;
   const int k = lamb_find_piece(a.pieces, a.n_pieces, (int)blockIdx.x);
   const LambPiece pc = a.pieces[k];
   const int blk_end = k + 1 < a.n_pieces ? a.pieces[k + 1].blk0 : a.n_blocks;
+  if (skipped) {              // (the piece table is the only memory a skipped workgroup reads)
+    if (pc.zero_grad == 0) return;
+    float* const R = a.r + 4 * (size_t)pc.start4;
+    const size_t n4 = (size_t)pc.n4, stride = (size_t)(blk_end - pc.blk0) * blockDim.x;
+    for (size_t i = (size_t)((int)blockIdx.x - pc.blk0) * blockDim.x + threadIdx.x; i < n4; i += stride)
+      __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f32x4*>(R + 4 * i));
+    return;
+  }
   const double pp = a.norms[2 * (size_t)pc.tensor], rr = a.norms[2 * (size_t)pc.tensor + 1];
   const float phi = (c.adapt[pc.cls] && pp > 0.0 && rr > 0.0) ? (float)sqrt(pp / rr) : 1.f;
   const float s = a.lr * phi;
@@ -925,6 +973,15 @@ int m3p_lamb_table_build(const long long* starts, const long long* counts, const
 int m3p_lamb_update(float* p, float* g, float* m, float* v, const void* pieces, int n_pieces, int n_blocks, const float* rbc1,
                     const float* rbc2, const float* wd, const int* adapt, int n_classes, float beta1, float beta2, float eps,
                     const double* gnorm_sq, float max_norm, float grad_scale, double* partials, void* stream) {
+  return m3p_lamb_update_guarded(p, g, m, v, pieces, n_pieces, n_blocks, rbc1, rbc2, wd, adapt, n_classes, beta1, beta2, eps, gnorm_sq,
+                                 max_norm, grad_scale, partials, nullptr, stream);
+}
+
+int m3p_lamb_update_guarded(float* p, float* g, float* m, float* v, const void* pieces, int n_pieces, int n_blocks, const float* rbc1,
+                            const float* rbc2, const float* wd, const int* adapt, int n_classes, float beta1, float beta2, float eps,
+                            const double* gnorm_sq, float max_norm, float grad_scale, double* partials, const int* skip,
+                            void* stream) {
+  if ((uintptr_t)skip & 3) return M3P_EINVAL;
   if (!p || !g || !m || !v || !pieces || !partials || !rbc1 || !rbc2 || !wd || n_pieces <= 0 || n_blocks < n_pieces) return M3P_EINVAL;
   if (((uintptr_t)p & 15) || ((uintptr_t)g & 15) || ((uintptr_t)m & 15) || ((uintptr_t)v & 15) || ((uintptr_t)pieces & 7) ||
       ((uintptr_t)partials & 7))
@@ -933,29 +990,102 @@ int m3p_lamb_update(float* p, float* g, float* m, float* v, const void* pieces, 
   if (lamb_classes(&c, rbc1, rbc2, wd, adapt, n_classes) != M3P_OK) return M3P_EINVAL;
   LambUpdateArgs a = {p, g, m, v, static_cast<const LambPiece*>(pieces), n_pieces, n_blocks, beta1, beta2, eps, gnorm_sq, max_norm,
                       grad_scale == 0.f ? 1.f : grad_scale, partials};
-  hipLaunchKernelGGL(lamb_update_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c);
+  if (skip)
+    hipLaunchKernelGGL(lamb_update_kernel<true>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c, skip);
+  else
+    hipLaunchKernelGGL(lamb_update_kernel<false>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c, skip);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
 
 int m3p_lamb_norms(const double* partials, const int* tensor_blk0, int n_tensors, double* norms, void* stream) {
+  return m3p_lamb_norms_guarded(partials, tensor_blk0, n_tensors, norms, nullptr, stream);
+}
+
+int m3p_lamb_norms_guarded(const double* partials, const int* tensor_blk0, int n_tensors, double* norms, const int* skip,
+                           void* stream) {
+  if ((uintptr_t)skip & 3) return M3P_EINVAL;
   if (!partials || !tensor_blk0 || !norms || n_tensors <= 0) return M3P_EINVAL;
   if (((uintptr_t)partials & 7) || ((uintptr_t)tensor_blk0 & 3) || ((uintptr_t)norms & 7)) return M3P_EINVAL;
-  hipLaunchKernelGGL(lamb_norms_kernel, dim3(n_tensors), dim3(64), 0, (hipStream_t)stream, partials, tensor_blk0, norms);
+  if (skip)
+    hipLaunchKernelGGL(lamb_norms_kernel<true>, dim3(n_tensors), dim3(64), 0, (hipStream_t)stream, partials, tensor_blk0, norms, skip);
+  else
+    hipLaunchKernelGGL(lamb_norms_kernel<false>, dim3(n_tensors), dim3(64), 0, (hipStream_t)stream, partials, tensor_blk0, norms, skip);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
 
 int m3p_lamb_apply(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks, const double* norms,
                    const int* adapt, int n_classes, float lr, void* stream) {
+  return m3p_lamb_apply_guarded(p, r, w16, pieces, n_pieces, n_blocks, norms, adapt, n_classes, lr, nullptr, stream);
+}
+
+int m3p_lamb_apply_guarded(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks, const double* norms,
+                           const int* adapt, int n_classes, float lr, const int* skip, void* stream) {
+  if ((uintptr_t)skip & 3) return M3P_EINVAL;
   if (!p || !r || !pieces || !norms || n_pieces <= 0 || n_blocks < n_pieces) return M3P_EINVAL;
   if (((uintptr_t)p & 15) || ((uintptr_t)r & 15) || ((uintptr_t)w16 & 7) || ((uintptr_t)pieces & 7) || ((uintptr_t)norms & 7)) return M3P_EINVAL;
   LambClasses c;
   if (lamb_classes(&c, nullptr, nullptr, nullptr, adapt, n_classes) != M3P_OK) return M3P_EINVAL;
   LambApplyArgs a = {p, r, (bf16*)w16, static_cast<const LambPiece*>(pieces), n_pieces, n_blocks, norms, lr};
-  hipLaunchKernelGGL(lamb_apply_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c);
+  if (skip)
+    hipLaunchKernelGGL(lamb_apply_kernel<true>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c, skip);
+  else
+    hipLaunchKernelGGL(lamb_apply_kernel<false>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, a, c, skip);
   M3P_CHECK_LAUNCH();
   return M3P_OK;
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Non-finite guard (include/m3p_hip.h, m3p_step_guard): the decision and its bookkeeping, one thread, plain stores.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct GuardArgs {
+  const double* sums[M3P_GUARD_MAX_ARENAS];
+  int n;
+  float grad_scale;
+  int slot;                   // attempt & (M3P_GUARD_RING - 1)
+  int* skip; int* ring; double* norm_ring; long long* counters;
+};
+
+__global__ __launch_bounds__(64) void step_guard_kernel(GuardArgs a) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double total = 0.0;
+  int bad = 0;
+  for (int i = 0; i < a.n; ++i) {
+    const double s = *a.sums[i];
+    // NaN or +-inf: every exponent bit set (a test on the bits: no compiler flag can reason it away)
+    if (((unsigned long long)__double_as_longlong(s) & 0x7ff0000000000000ULL) == 0x7ff0000000000000ULL) bad = 1;
+    total += s;
+  }
+  *a.skip = bad;
+  a.ring[a.slot] = bad;
+  a.norm_ring[a.slot] = sqrt(total) * (double)a.grad_scale;
+  a.counters[0] += 1;
+  a.counters[1] += bad;
+  a.counters[2] = bad ? a.counters[2] + 1 : 0;
+}
+
+}  // namespace
+
+extern "C" int m3p_step_guard(const double* const* gnorm_sq, int n_arenas, float grad_scale, long long attempt, int* skip, int* ring,
+                              double* norm_ring, long long* counters, void* stream) {
+  if (!gnorm_sq || !skip || !ring || !norm_ring || !counters || n_arenas <= 0 || attempt < 0) return M3P_EINVAL;
+  if (n_arenas > M3P_GUARD_MAX_ARENAS) return M3P_ENOTIMPL;
+  if (((uintptr_t)skip & 3) || ((uintptr_t)ring & 3) || ((uintptr_t)norm_ring & 7) || ((uintptr_t)counters & 7)) return M3P_EINVAL;
+  GuardArgs a;
+  for (int i = 0; i < M3P_GUARD_MAX_ARENAS; ++i) {
+    a.sums[i] = i < n_arenas ? gnorm_sq[i] : nullptr;
+    if (i < n_arenas && (!gnorm_sq[i] || ((uintptr_t)gnorm_sq[i] & 7))) return M3P_EINVAL;
+  }
+  a.n = n_arenas;
+  a.grad_scale = grad_scale == 0.f ? 1.f : grad_scale;
+  a.slot = (int)(attempt & (M3P_GUARD_RING - 1));
+  a.skip = skip; a.ring = ring; a.norm_ring = norm_ring; a.counters = counters;
+  hipLaunchKernelGGL(step_guard_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  M3P_CHECK_LAUNCH();
+  return M3P_OK;
+}

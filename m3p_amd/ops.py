@@ -1357,8 +1357,41 @@ def adam_step(p, g, m, v, w16, lr, beta1, beta2, eps, weight_decay, step_size, g
     L.check(rc, 'm3p_adam_step')
 
 
-def adam_step_ranges(p, g, m, v, w16, pieces, lr, beta1, beta2, eps, weight_decay, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
-    """One launch of the fused Adam update over several pieces of the flat arenas: pieces = [(start, end, step_size, zero_grad)]."""
+class StepGuard:
+    """Device state of the non-finite guard (include/m3p_hip.h, m3p_step_guard) in ONE buffer, so that a reconcile is one
+    host read: counters {attempts, skipped_total, skipped_in_a_row} (int64), the ring of norms (float64 x 64), the ring of
+    skip flags (int32 x 64) and the current step's `skip` word that the guarded update launches read."""
+    RING = 64                 # M3P_GUARD_RING
+    MAX_ARENAS = 8            # M3P_GUARD_MAX_ARENAS
+    _COUNTERS, _NORMS, _RING, _SKIP, _BYTES = 0, 32, 32 + 8 * 64, 32 + 8 * 64 + 4 * 64, 32 + 8 * 64 + 4 * 64 + 16
+
+    def __init__(self, device):
+        self.buf = torch.zeros(self._BYTES, dtype=torch.uint8, device=device)
+        self.counters = self.buf[self._COUNTERS:self._COUNTERS + 24].view(torch.int64)
+        self.norm_ring = self.buf[self._NORMS:self._RING].view(torch.float64)
+        self.ring = self.buf[self._RING:self._SKIP].view(torch.int32)
+        self.skip = self.buf[self._SKIP:self._SKIP + 4].view(torch.int32)
+
+    def read(self):
+        """One device-to-host copy -> (counters [3], norms [64], flags [64]) as Python lists."""
+        host = self.buf.cpu()
+        return (host[self._COUNTERS:self._COUNTERS + 24].view(torch.int64).tolist(), host[self._NORMS:self._RING].view(torch.float64).tolist(),
+                host[self._RING:self._SKIP].view(torch.int32).tolist())
+
+
+def step_guard(gnorm_sqs, grad_scale, attempt, guard):
+    """The guard's single-thread launch: guard.skip = any of the device scalars `gnorm_sqs` non-finite; rings and counters."""
+    n = len(gnorm_sqs)
+    ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in gnorm_sqs])
+    rc = L.load().m3p_step_guard(ptrs, n, grad_scale, int(attempt), guard.skip.data_ptr(), guard.ring.data_ptr(),
+                                 guard.norm_ring.data_ptr(), guard.counters.data_ptr(), L.stream())
+    L.check(rc, 'm3p_step_guard')
+
+
+def adam_step_ranges(p, g, m, v, w16, pieces, lr, beta1, beta2, eps, weight_decay, gnorm_sq=None, max_norm=0.0, grad_scale=1.0,
+                     skip=None):
+    """One launch of the fused Adam update over several pieces of the flat arenas: pieces = [(start, end, step_size, zero_grad)].
+    skip: the guard's device word (m3p_adam_step_ranges_guarded), or None for the unguarded entry point."""
     pieces = [q for q in pieces if q[1] > q[0]]
     if not pieces:
         return
@@ -1367,6 +1400,11 @@ def adam_step_ranges(p, g, m, v, w16, pieces, lr, beta1, beta2, eps, weight_deca
     counts = (C.c_longlong * n)(*[int(b - a) for a, b, _, _ in pieces])
     steps = (C.c_float * n)(*[float(st) for _, _, st, _ in pieces])
     zeros = (C.c_int * n)(*[int(bool(z)) for _, _, _, z in pieces])
+    if skip is not None:
+        rc = L.load().m3p_adam_step_ranges_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), L.ptr(w16), starts, counts, steps,
+                                                   zeros, n, lr, beta1, beta2, eps, weight_decay, L.ptr(gnorm_sq), max_norm, grad_scale,
+                                                   skip.data_ptr(), L.stream())
+        return L.check(rc, 'm3p_adam_step_ranges_guarded')
     rc = L.load().m3p_adam_step_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), L.ptr(w16), starts, counts, steps, zeros, n,
                                        lr, beta1, beta2, eps, weight_decay, L.ptr(gnorm_sq), max_norm, grad_scale, L.stream())
     L.check(rc, 'm3p_adam_step_ranges')
@@ -1421,24 +1459,38 @@ def _lamb_classes(classes, n_classes):
             (C.c_float * n)(*[float(c[2]) for c in classes]), (C.c_int * n)(*[int(bool(c[3])) for c in classes]))
 
 
-def lamb_update(p, g, m, v, table, classes, beta1, beta2, eps, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
-    """First LAMB launch: m, v updated, r written over g, the workgroups' (sum p^2, sum r^2) into table.partials."""
+def lamb_update(p, g, m, v, table, classes, beta1, beta2, eps, gnorm_sq=None, max_norm=0.0, grad_scale=1.0, skip=None):
+    """First LAMB launch: m, v updated, r written over g, the workgroups' (sum p^2, sum r^2) into table.partials.
+    skip (here and in the two launches below): the guard's device word -> the _guarded entry point; None -> the unguarded one."""
     rbc1, rbc2, wd, adapt = _lamb_classes(classes, table.n_classes)
+    if skip is not None:
+        rc = L.load().m3p_lamb_update_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), table.dev_pieces.data_ptr(),
+                                              table.n_pieces, table.n_blocks, rbc1, rbc2, wd, adapt, table.n_classes, beta1, beta2, eps,
+                                              L.ptr(gnorm_sq), max_norm, grad_scale, table.partials.data_ptr(), skip.data_ptr(), L.stream())
+        return L.check(rc, 'm3p_lamb_update_guarded')
     rc = L.load().m3p_lamb_update(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), table.dev_pieces.data_ptr(), table.n_pieces,
                                   table.n_blocks, rbc1, rbc2, wd, adapt, table.n_classes, beta1, beta2, eps, L.ptr(gnorm_sq),
                                   max_norm, grad_scale, table.partials.data_ptr(), L.stream())
     L.check(rc, 'm3p_lamb_update')
 
 
-def lamb_norms(table):
+def lamb_norms(table, skip=None):
     """Second launch: table.norms[t] = (sum p^2, sum r^2) over tensor t's workgroups, fp64, in a fixed order."""
+    if skip is not None:
+        rc = L.load().m3p_lamb_norms_guarded(table.partials.data_ptr(), table.dev_tblk.data_ptr(), table.n_tensors, table.norms.data_ptr(),
+                                             skip.data_ptr(), L.stream())
+        return L.check(rc, 'm3p_lamb_norms_guarded')
     rc = L.load().m3p_lamb_norms(table.partials.data_ptr(), table.dev_tblk.data_ptr(), table.n_tensors, table.norms.data_ptr(), L.stream())
     L.check(rc, 'm3p_lamb_norms')
 
 
-def lamb_apply(p, r, w16, table, classes, lr):
+def lamb_apply(p, r, w16, table, classes, lr, skip=None):
     """Third launch: p -= lr * phi_t * r with phi_t from table.norms; bf16 copy refreshed, r zeroed where the piece says so."""
     _, _, _, adapt = _lamb_classes(classes, table.n_classes)
+    if skip is not None:
+        rc = L.load().m3p_lamb_apply_guarded(p.data_ptr(), r.data_ptr(), L.ptr(w16), table.dev_pieces.data_ptr(), table.n_pieces,
+                                             table.n_blocks, table.norms.data_ptr(), adapt, table.n_classes, lr, skip.data_ptr(), L.stream())
+        return L.check(rc, 'm3p_lamb_apply_guarded')
     rc = L.load().m3p_lamb_apply(p.data_ptr(), r.data_ptr(), L.ptr(w16), table.dev_pieces.data_ptr(), table.n_pieces, table.n_blocks,
                                  table.norms.data_ptr(), adapt, table.n_classes, lr, L.stream())
     L.check(rc, 'm3p_lamb_apply')

@@ -15,7 +15,9 @@ Semantics kept from the reference:
     AdamCosineWithWarmup (:142-209) likewise.
 
 Beyond the reference: Lamb and its two scheduled forms - Adam's moments with a per-tensor trust ratio, on the same arenas and
-state, three launches per step (m3p_lamb_update / _norms / _apply; the rule is written out in include/m3p_hip.h).
+state, three launches per step (m3p_lamb_update / _norms / _apply; the rule is written out in include/m3p_hip.h).  And the
+opt-in non-finite guard (`Adam.guard_nonfinite`, `reconcile`, `roll_back`): a step whose global gradient norm is NaN or
+infinite is skipped on the device, counted there, and taken back out of the host's counts at the next reconcile.
 """
 import inspect
 import math
@@ -32,7 +34,35 @@ from . import ops
 _LAZY_VOCAB_ZERO = os.environ.get('M3P_LAZY_VOCAB_ZERO', '1') != '0'
 
 
+def roll_back(log, flags, steps, num_updates):
+    """The host side of the non-finite guard as pure arithmetic.  log: the attempts since the last reconcile, oldest first,
+    each (attempt index, [(parameter key, the step count the attempt gave it)], [group key]); flags: attempt index -> the
+    device's verdict (1 = skipped); steps: parameter key -> current step count; num_updates: group key -> current count.
+    -> (steps, num_updates) as they would stand had the skipped attempts never been made: every skipped attempt takes one off
+    the step count of the parameters it bumped and one off the update count of its groups (new dicts; the arguments are
+    left alone).  Counts only ever moved by +1 per attempt, so the order of the attempts does not matter to the result."""
+    steps, num_updates = dict(steps), dict(num_updates)
+    for index, bumped, groups in log:
+        if not flags[index]:
+            continue
+        for key, _new in bumped:
+            steps[key] -= 1
+        for g in groups:
+            num_updates[g] -= 1
+    bad = [k for k, v in list(steps.items()) + list(num_updates.items()) if v < 0]
+    if bad:
+        raise AssertionError('roll_back: more skipped attempts than counted ones for %s' % bad[:3])
+    return steps, num_updates
+
+
 class Adam(optim.Optimizer):
+    # Opt-in non-finite guard (Lamb and the scheduled classes inherit it): a step whose global gradient norm is NaN or
+    # +-inf leaves master, moments and the bf16 copy as they were and zeroes the gradients - decided, counted and logged on
+    # the device (ops.step_guard + the _guarded launches), with no host read in step().  The host cannot know the verdict,
+    # so state[p]['step'], num_updates and the lr move with every attempt; reconcile() - the one host read - takes the
+    # skipped attempts back out.  Until then bias corrections and schedule run one attempt ahead per unreconciled skip.
+    guard_nonfinite = False
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
         if not 0.0 <= lr:
             raise ValueError('Invalid learning rate: {}'.format(lr))
@@ -47,6 +77,10 @@ class Adam(optim.Optimizer):
         self._arenas = {}        # id(arena) -> dict(arena, m, v)
         self._pending_clip = None
         self.grad_scale = 1.0    # 1/world_size under data parallelism (gradient averaging)
+        self._guard = None       # ops.StepGuard, made by the first guarded step
+        self._skip = None        # the guard's device word while a guarded step() launches, else None
+        self._attempts = 0       # guarded step() calls so far = the next attempt index
+        self._guard_log = []     # unreconciled attempts: (index, [(parameter, new step)], [group])
         for group in self.param_groups:
             for p in group['params']:
                 state = self.state[p]
@@ -118,6 +152,11 @@ class Adam(optim.Optimizer):
         """clip_grad_norm_(parameters, max_norm) of xtrainer.py:225, deferred: the global
         sum of squares is reduced on the device now, the scaling is applied inside the Adam
         kernel (no host sync, no extra pass over the gradients)."""
+        self._reduce_norm()
+        self._pending_clip = float(max_norm)
+
+    def _reduce_norm(self):
+        """ent['gnorm'] of every arena = the global sum of squares of its active gradients (all ranks' shards)."""
         for ent in self._arenas.values():
             arena = ent['arena']
             if arena.model.ddp_hook is not None:
@@ -129,7 +168,6 @@ class Adam(optim.Optimizer):
             ops.sumsq_ranges(arena.grad, pieces, ent['gnorm'])      # (one launch however many shards this rank owns)
             if arena.model.ddp_hook is not None:
                 arena.model.ddp_hook.all_reduce_scalar(ent['gnorm'])     # sharded gradients: the norm is the sum over ranks
-        self._pending_clip = float(max_norm)
 
     def grad_norm(self):
         """Host value of the last reduced global norm (synchronises; for logging/tests)."""
@@ -147,8 +185,11 @@ class Adam(optim.Optimizer):
     # ------------------------------------------------------------------ step
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self.guard_nonfinite:
+            self._open_guarded_step()
         max_norm = self._pending_clip or 0.0
         self._pending_clip = None
+        bumped = []
         for ent in self._arenas.values():
             arena = ent['arena']
             if arena.model.ddp_hook is not None:
@@ -171,6 +212,7 @@ class Adam(optim.Optimizer):
             bump = self._launch_arena(arena, ent, active, lazy, max_norm)
             for p, step in bump:
                 self.state[p]['step'] = step
+            bumped.extend(bump)
             # sharded exchange: the other ranks' shards of the updated master come back through an all-gather that the
             # next forward waits for bucket by bucket (distributed.DataParallel.after_sharded_step)
             hook = arena.model.ddp_hook
@@ -178,7 +220,56 @@ class Adam(optim.Optimizer):
             # untouched ranges may still hold stale values only if someone wrote them by hand
             arena.after_fused_step(copies_scheduled=gathered)
         self._step_loose(max_norm)
+        if self._skip is not None:
+            self._guard_log.append((self._attempts, bumped, [g for g in self.param_groups if 'num_updates' in g]))
+            self._attempts += 1
+            self._skip = None
         return loss
+
+    # ------------------------------------------------------------------ non-finite guard
+    def _open_guarded_step(self):
+        """In front of a guarded step's launches: the reduced norm (clip_grad_norm's, or reduced here by the same launch and
+        the same all-reduce - without clipping), then the one-thread decision every launch of this step reads."""
+        if not self._arenas or any(getattr(p, '_m3p_arena', None) is None and p.grad is not None
+                                   for group in self.param_groups for p in group['params']):
+            raise RuntimeError('guard_nonfinite covers the fused arena path only: this optimizer holds parameters outside an arena')
+        if len(self._guard_log) >= ops.StepGuard.RING:         # the ring is full: this attempt would overwrite an unread verdict
+            self.reconcile()
+        if self._pending_clip is None:
+            self._reduce_norm()
+        if self._guard is None:
+            self._guard = ops.StepGuard(next(iter(self._arenas.values()))['arena'].device)
+        ops.step_guard([ent['gnorm'] for ent in self._arenas.values()], self.grad_scale, self._attempts, self._guard)
+        self._skip = self._guard.skip
+
+    def reconcile(self):
+        """The guard's ONE host read (it synchronises): ring, norms and counters.  Every logged attempt the device skipped is
+        taken back out of state[p]['step'], of num_updates and of the lr (`roll_back`), and the log is cleared; after it
+        master, moments, bf16 copy, step counts, num_updates and lr are what they would be had the skipped batches not existed.
+        -> dict(attempts, skipped_total, skipped_in_a_row, norms=[the finite global norms since the last call])."""
+        if self._guard is None:
+            return dict(attempts=0, skipped_total=0, skipped_in_a_row=0, norms=[])
+        counters, norm_ring, ring = self._guard.read()
+        flags = {index: ring[index % ops.StepGuard.RING] for index, _, _ in self._guard_log}
+        norms = [norm_ring[index % ops.StepGuard.RING] for index, _, _ in self._guard_log if not flags[index]]
+        log = [(index, [(id(p), step) for p, step in bumped], [id(g) for g in groups]) for index, bumped, groups in self._guard_log]
+        params = {id(p): p for _, bumped, _ in self._guard_log for p, _ in bumped}
+        groups = {id(g): g for _, _, gs in self._guard_log for g in gs}
+        steps, updates = roll_back(log, flags, {k: self.state[p]['step'] for k, p in params.items()},
+                                   {k: g['num_updates'] for k, g in groups.items()})
+        for k, p in params.items():
+            self.state[p]['step'] = steps[k]
+        for k, g in groups.items():
+            if g['num_updates'] != updates[k]:
+                g['num_updates'] = updates[k]
+                g['lr'] = self._lr_at(updates[k])
+        del self._guard_log[:]
+        return dict(attempts=counters[0], skipped_total=counters[1], skipped_in_a_row=counters[2], norms=norms)
+
+    def state_dict(self):
+        if self._guard_log:             # checkpoints carry exact counts
+            self.reconcile()
+        return super().state_dict()
 
     def _launch_arena(self, arena, ent, active, lazy, max_norm):
         """The update of one arena's active ranges (lazy = the [start, end) this step leaves un-zeroed, or None).
@@ -208,7 +299,7 @@ class Adam(optim.Optimizer):
             beta1, beta2 = group['betas']
             ops.adam_step_ranges(arena.master, arena.grad, ent['m'], ent['v'], arena.w16, pieces, group['lr'], beta1, beta2,
                                  group['eps'], group['weight_decay'], gnorm_sq=ent['gnorm'] if max_norm > 0 else None,
-                                 max_norm=max_norm, grad_scale=self.grad_scale)
+                                 max_norm=max_norm, grad_scale=self.grad_scale, skip=self._skip)
         return bump
 
     @staticmethod
@@ -389,11 +480,12 @@ class Lamb(Adam):
                     hook.all_reduce_scalar(torch.zeros((b['n_tensors'], 2), dtype=torch.float64, device=arena.device))
                 continue
             ops.lamb_update(arena.master, arena.grad, ent['m'], ent['v'], table, classes, beta1, beta2, group['eps'],
-                            gnorm_sq=ent['gnorm'] if max_norm > 0 else None, max_norm=max_norm, grad_scale=self.grad_scale)
-            ops.lamb_norms(table)
+                            gnorm_sq=ent['gnorm'] if max_norm > 0 else None, max_norm=max_norm, grad_scale=self.grad_scale,
+                            skip=self._skip)
+            ops.lamb_norms(table, skip=self._skip)
             if hook is not None:
                 hook.all_reduce_scalar(table.norms)      # sharded exchange: a tensor's norms are the sums over the ranks' shards
-            ops.lamb_apply(arena.master, arena.grad, arena.w16, table, classes, group['lr'])
+            ops.lamb_apply(arena.master, arena.grad, arena.w16, table, classes, group['lr'], skip=self._skip)
         return bump
 
     def _step_loose(self, max_norm):

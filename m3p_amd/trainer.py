@@ -71,6 +71,13 @@ class Trainer(object):
     def __init__(self, data, params):
         """xtrainer.py:37-136."""
         self.params = params
+        # non-finite guard (not a reference flag; INTEGRATION.md section 4): absent = off, so old params.pkl files load
+        self.skip_nonfinite_updates = bool(getattr(params, 'skip_nonfinite_updates', False))
+        self.max_skipped_in_a_row = int(getattr(params, 'max_skipped_in_a_row', 20))      # a policy default; <= 0 never stops
+        if self.skip_nonfinite_updates and getattr(params, 'fp8_gemm', False):
+            # the forward pass has moved the delayed-scaling amax history before the guard decides, and nothing rolls it back
+            raise ValueError('skip_nonfinite_updates cannot be combined with fp8_gemm: a skipped step would keep the fp8 '
+                             'scaling history of the batch it dropped')
         self.data = data
         self.epoch_size = params.epoch_size
         if self.epoch_size == -1:
@@ -98,6 +105,12 @@ class Trainer(object):
             logger.warning('amp == -1 requests fp32 training in the reference; this build computes in bf16 with fp32 '
                            'master weights, gradients and optimizer state (INTEGRATION.md, "precision")')
         self.set_optimizers()
+        self._skipped_seen = 0
+        if self.skip_nonfinite_updates:
+            for opt in self.optimizers.values():
+                if not hasattr(opt, 'reconcile'):
+                    raise ValueError('skip_nonfinite_updates needs one of the fused optimizers (adam*, lamb*), got %s' % type(opt).__name__)
+                opt.guard_nonfinite = True
         if getattr(params, 'multi_gpu', False):
             logger.info('Using m3p_amd.distributed.DataParallel (bucketed RCCL all-reduce) ...')
             for name in self.MODEL_NAMES:
@@ -153,7 +166,11 @@ class Trainer(object):
     def optimize(self, loss):
         """xtrainer.py:205-243 without the host round trips: backward -> (bucketed
         all-reduce overlapped with it) -> global-norm clip -> Adam -> zero_grad, the last
-        three as one fused pass over the arenas."""
+        three as one fused pass over the arenas.
+
+        With ``params.skip_nonfinite_updates`` a step whose global gradient norm is NaN or infinite changes no weight and
+        zeroes the gradients (Adam.guard_nonfinite).  Under ``accumulate_gradients`` > 1 a non-finite micro-step poisons the
+        accumulated sum: the boundary step skips and zeroes, so the WHOLE group of micro-batches is dropped, not the one."""
         params = self.params
         accumulate = max(int(getattr(params, 'accumulate_gradients', 1)), 1)
         boundary = self.n_iter % accumulate == 0   # xtrainer.py:231
@@ -195,12 +212,31 @@ class Trainer(object):
                 del vals[:]
         rates = ' - ' + ''.join(' - %s LR: %s' % (name, ' / '.join('%.4e' % g['lr'] for g in opt.param_groups))
                                 for name, opt in self.optimizers.items())
+        guard = self._reconcile_guard() if self.skip_nonfinite_updates else None
+        if guard is not None:
+            means.append('grad_norm: %7.4f' % guard['grad_norm'])
+            means.append('skipped: %d' % guard['skipped'])
         now = time.time()
         elapsed = now - self.last_time
         speed = '%7.2f sent/s - %8.2f words/s - ' % (self.stats['processed_s'] / elapsed, self.stats['processed_w'] / elapsed)
         self.stats['processed_s'] = self.stats['processed_w'] = 0
         self.last_time = now
         logger.info('%7i - ' % self.n_iter + speed + ' || '.join(means) + rates)
+        if guard is not None and 0 < self.max_skipped_in_a_row <= guard['skipped_in_a_row']:
+            raise FloatingPointError('non-finite gradients: %d optimizer steps skipped in a row (max_skipped_in_a_row = %d), %d skipped '
+                                     'in total' % (guard['skipped_in_a_row'], self.max_skipped_in_a_row, guard['skipped_total']))
+
+    def _reconcile_guard(self):
+        """The guard's host read, here where the statistics are read anyway: every optimizer takes its skipped attempts back
+        out of its step counts, update counts and lr (Adam.reconcile).  -> grad_norm = the mean of the finite global norms and
+        skipped = the skipped steps since the last print, with the running counters (the worst over the optimizers)."""
+        reports = [opt.reconcile() for opt in self.optimizers.values()]
+        norms = [x for r in reports for x in r['norms']]
+        total = sum(r['skipped_total'] for r in reports)
+        skipped, self._skipped_seen = total - self._skipped_seen, total
+        self.last_guard_report = dict(grad_norm=float(np.mean(norms)) if norms else float('nan'), skipped=skipped, skipped_total=total,
+                                      skipped_in_a_row=max(r['skipped_in_a_row'] for r in reports))
+        return self.last_guard_report
 
     # ------------------------------------------------------------------ text batches (xtrainer.py:436-509)
     def get_cross_lingual_iterator(self, iter_name, lang1, lang2, stream):
