@@ -862,6 +862,26 @@ M3P_API int m3p_lamb_norms_guarded(const double* partials, const int* tensor_blk
 M3P_API int m3p_lamb_apply_guarded(float* p, float* r, void* w16, const void* pieces, int n_pieces, int n_blocks,
                                    const double* norms, const int* adapt, int n_classes, float lr, const int* skip, void* stream);
 
+/* Exponential moving average (Polyak averaging) of the fp32 master on the flat arenas.  Both calls stream over n_ranges pieces
+ * [starts[r], starts[r] + counts[r]) of the arenas whose bases they are given, laid out like m3p_adam_step_ranges: starts /
+ * counts are HOST arrays in elements, read before the call returns; every start and count a multiple of 4, counts >= 0 (a
+ * zero-length piece is skipped); bases 16-byte aligned (w16: 8).  Anything else returns M3P_EINVAL and nothing has run.  32
+ * pieces go into one launch, a longer list into several.  Nothing outside the pieces is read or written.
+ *
+ * m3p_ema_update:  ema[i] = ema[i] + w * (p[i] - ema[i]),  w = (float)(1.0 - decay) formed in double by the caller.  The
+ * difference is rounded to fp32, then product and sum are ONE fused multiply-add, fma(w, p[i] - ema[i], ema[i]), whatever
+ * the build's contraction setting: the rule is one fixed fp32 arithmetic (w = 1 does NOT give ema = p for every pair; a
+ * caller that wants a copy copies).  skip: the non-finite guard's device word (m3p_step_guard) or NULL.  A non-NULL word that reads non-zero makes
+ * every workgroup return before it loads anything: ema keeps its bits.
+ *
+ * m3p_ema_swap:  p[i] <-> ema[i], and w16[i] = bf16(new p[i]) (round to nearest even, the conversion m3p_adam_step_ranges
+ * uses; w16 nullable) - one pass that reads two streams and writes three.  Values are moved, never computed with: NaN
+ * payloads, infinities, denormals and signed zeros pass through, and two swaps in a row restore p, ema and w16 to the bit. */
+M3P_API int m3p_ema_update(const float* p, float* ema, const long long* starts, const long long* counts, int n_ranges, float w,
+                           const int* skip, void* stream);
+M3P_API int m3p_ema_swap(float* p, float* ema, void* w16, const long long* starts, const long long* counts, int n_ranges,
+                         void* stream);
+
 /* h = gelu_erf(u) elementwise (transformer.py:56 applied to the lin1 output :223-224), bf16,
  * n % 8 == 0.  Used instead of M3P_EPI_BIAS_GELU when the GEMM is persistent.
  * dh (nullable, may alias u): also writes gelu_erf'(u) in bf16, which the backward FFN dgrad

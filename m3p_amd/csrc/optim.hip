@@ -1039,6 +1039,171 @@ int m3p_lamb_apply_guarded(float* p, float* r, void* w16, const void* pieces, in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Exponential moving average of the master weights (include/m3p_hip.h, m3p_ema_update / m3p_ema_swap): two streaming
+// kernels over pieces of the flat arenas, laid out like adam_ranges_kernel - pieces by value, workgroups dealt in proportion
+// to the pieces' sizes, 16-byte quads, non-temporal accesses, EMA_Q quads per thread and trip.  No atomics, no LDS.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int EMA_MAX_RANGES = 32;
+constexpr int EMA_Q = 2;             // 16-byte quads per thread and trip, as ADAM_Q
+constexpr int EMA_MAXBLK = 4096;     // blocks per launch at most
+struct EmaRanges {
+  unsigned long long start4[EMA_MAX_RANGES];   // first quad of the piece
+  unsigned long long n4[EMA_MAX_RANGES];
+  int blk0[EMA_MAX_RANGES + 1];
+  int n;
+};
+
+// ema = fma(w, p - ema, ema).  Two roundings per element: the difference, then ONE fused multiply-add - written as such, so
+// that the rule is the same arithmetic whatever contraction setting the file is built with (the Makefile's -ffp-contract=fast
+// fuses a separate product and sum anyway, pragmas notwithstanding).  tests/test_ema_cpu.py holds it as ema_twin(contract=True).
+// GUARD: as adam_ranges_kernel<true> - a workgroup that reads a non-zero *skip returns before it loads anything.
+template <bool GUARD>
+__global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ p, float* __restrict__ ema, EmaRanges a, float w,
+                                                         const int* __restrict__ skip) {
+  if (GUARD && *skip != 0) return;
+  int r = 0;
+  while (r + 1 < a.n && (int)blockIdx.x >= a.blk0[r + 1]) ++r;
+  const size_t base = (size_t)a.start4[r], n4 = (size_t)a.n4[r];
+  const float* const P = p + 4 * base;
+  float* const E = ema + 4 * base;
+  const size_t stride = (size_t)(a.blk0[r + 1] - a.blk0[r]) * blockDim.x;
+  constexpr int Q = EMA_Q;
+  for (size_t i0 = (size_t)((int)blockIdx.x - a.blk0[r]) * blockDim.x + threadIdx.x; i0 < n4; i0 += Q * stride) {
+    f32x4 x[Q], e[Q];
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        x[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(P + 4 * i));
+        e[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(E + 4 * i));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        const f32x4 d = x[u] - e[u];
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = __builtin_fmaf(w, d[j], e[u][j]);
+        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(E + 4 * i));
+      }
+    }
+  }
+}
+
+// p <-> ema element by element, and w16 = bf16(new p) through the Adam kernel's conversion: one pass, two streams read, three
+// written.  The values are moved, never computed with: a second swap restores all three buffers to the bit.
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ ema, bf16* __restrict__ w16, EmaRanges a) {
+  int r = 0;
+  while (r + 1 < a.n && (int)blockIdx.x >= a.blk0[r + 1]) ++r;
+  const size_t base = (size_t)a.start4[r], n4 = (size_t)a.n4[r];
+  float* const P = p + 4 * base;
+  float* const E = ema + 4 * base;
+  bf16* const W = w16 ? w16 + 4 * base : nullptr;
+  const size_t stride = (size_t)(a.blk0[r + 1] - a.blk0[r]) * blockDim.x;
+  constexpr int Q = EMA_Q;
+  for (size_t i0 = (size_t)((int)blockIdx.x - a.blk0[r]) * blockDim.x + threadIdx.x; i0 < n4; i0 += Q * stride) {
+    f32x4 x[Q], e[Q];
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        x[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(P + 4 * i));
+        e[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(E + 4 * i));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < Q; ++u) {
+      const size_t i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        __builtin_nontemporal_store(e[u], reinterpret_cast<f32x4*>(P + 4 * i));
+        __builtin_nontemporal_store(x[u], reinterpret_cast<f32x4*>(E + 4 * i));
+        if (W) Vec4<bf16>::store(W + 4 * i, e[u]);       // (re-read by the very next forward: default policy)
+      }
+    }
+  }
+}
+
+// the pieces [starts[r], starts[r] + counts[r]) validated as a whole: nothing is launched for a list with a bad piece
+bool ema_pieces_ok(const long long* starts, const long long* counts, int n_ranges) {
+  if (!starts || !counts || n_ranges <= 0) return false;
+  for (int r = 0; r < n_ranges; ++r)
+    if (counts[r] < 0 || (counts[r] % 4) != 0 || starts[r] < 0 || (starts[r] % 4) != 0) return false;
+  return true;
+}
+
+// the next launch's share of the list from *done on: up to EMA_MAX_RANGES non-empty pieces, blocks dealt in proportion to
+// their sizes (one quad per thread and trip wanted, at most EMA_MAXBLK, at least one block per piece, none without a quad).
+// -> blocks of the launch, 0 when the rest of the list is empty
+int ema_deal(const long long* starts, const long long* counts, int n_ranges, int* done, EmaRanges* a) {
+  a->n = 0;
+  long long total4 = 0;
+  for (; *done < n_ranges && a->n < EMA_MAX_RANGES; ++*done) {
+    if (counts[*done] == 0) continue;
+    a->start4[a->n] = (unsigned long long)starts[*done] / 4;
+    a->n4[a->n] = (unsigned long long)counts[*done] / 4;
+    total4 += counts[*done] / 4;
+    ++a->n;
+  }
+  if (a->n == 0) return 0;
+  long long want = (total4 + 255) / 256;
+  if (want > EMA_MAXBLK) want = EMA_MAXBLK;
+  if (want < a->n) want = a->n;
+  int b = 0;
+  for (int r = 0; r < a->n; ++r) {
+    a->blk0[r] = b;
+    long long share = (long long)((double)a->n4[r] / (double)total4 * (double)want);
+    const long long most = ((long long)a->n4[r] + 255) / 256;
+    if (share > most) share = most;
+    if (share < 1) share = 1;
+    b += (int)share;
+  }
+  a->blk0[a->n] = b;
+  return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int m3p_ema_update(const float* p, float* ema, const long long* starts, const long long* counts, int n_ranges, float w,
+                   const int* skip, void* stream) {
+  if (!p || !ema || ((uintptr_t)p & 15) || ((uintptr_t)ema & 15) || ((uintptr_t)skip & 3)) return M3P_EINVAL;
+  if (!ema_pieces_ok(starts, counts, n_ranges)) return M3P_EINVAL;
+  int done = 0;
+  while (done < n_ranges) {
+    EmaRanges a;
+    const int b = ema_deal(starts, counts, n_ranges, &done, &a);
+    if (b == 0) continue;
+    if (skip)
+      hipLaunchKernelGGL(ema_update_kernel<true>, dim3(b), dim3(256), 0, (hipStream_t)stream, p, ema, a, w, skip);
+    else
+      hipLaunchKernelGGL(ema_update_kernel<false>, dim3(b), dim3(256), 0, (hipStream_t)stream, p, ema, a, w, skip);
+    M3P_CHECK_LAUNCH();
+  }
+  return M3P_OK;
+}
+
+int m3p_ema_swap(float* p, float* ema, void* w16, const long long* starts, const long long* counts, int n_ranges, void* stream) {
+  if (!p || !ema || ((uintptr_t)p & 15) || ((uintptr_t)ema & 15) || ((uintptr_t)w16 & 7)) return M3P_EINVAL;
+  if (!ema_pieces_ok(starts, counts, n_ranges)) return M3P_EINVAL;
+  int done = 0;
+  while (done < n_ranges) {
+    EmaRanges a;
+    const int b = ema_deal(starts, counts, n_ranges, &done, &a);
+    if (b == 0) continue;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, p, ema, (bf16*)w16, a);
+    M3P_CHECK_LAUNCH();
+  }
+  return M3P_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Non-finite guard (include/m3p_hip.h, m3p_step_guard): the decision and its bookkeeping, one thread, plain stores.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {

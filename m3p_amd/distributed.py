@@ -496,6 +496,17 @@ class DataParallel(torch.nn.Module):
         if hasattr(ar, '_cast_version'):
             ar._cast_version = ar.master._version
 
+    def materialize_ema(self, ema):
+        """Collective (every rank): the same gather for `ema`, the optimizer's exponential moving average of the master - a flat
+        fp32 buffer laid out like it, of which a zero1 rank updates its own bucket shards only (Adam.enable_ema).  The
+        replicated modes have nothing to gather."""
+        if self.mode != 'zero1' or self.single:
+            return
+        assert ema.numel() == self._arena.total and ema.dtype == torch.float32
+        for key, (s, e) in self._ranges.items():
+            a, b = self.shard_of(key)
+            _all_gather_into(ema[s:e], ema[a:b], self.pg).wait()
+
     def params_ready(self, key=None):
         """Make the current stream wait until bucket ``key``'s parameters (None: all of them, and the transposed
         copies) are gathered and cast.  A stream-level wait; free when nothing is pending."""

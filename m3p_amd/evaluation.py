@@ -465,7 +465,18 @@ def evaluate_mt_ic(model, params, iterator, scores, data_set, lang1, lang2):
     return stats.write(scores, name + '_IC_ppl', name + '_IC_acc')
 
 
-def run_all_evals(model, params, get_iterator, epoch):
+def run_all_evals(model, params, get_iterator, epoch, ema=None):
+    """`_run_all_evals`, inside the context manager `ema` when one is given - ``Trainer.ema_weights()``: the model then computes
+    with the exponential moving average of its weights (Adam.enable_ema) and the scores, under their usual names, are the
+    averaged model's.  Entering and leaving that context is a collective under data parallelism, so every rank does both,
+    whether it evaluates or not."""
+    if ema is None:
+        return _run_all_evals(model, params, get_iterator, epoch)
+    with ema:
+        return _run_all_evals(model, params, get_iterator, epoch)
+
+
+def _run_all_evals(model, params, get_iterator, epoch):
     """The scores ``Trainer.save_best_model`` / ``end_epoch`` consume, after every epoch: xevaluator.py:120-235 for the tasks
     built here (``evaluate_clm`` over ``params.clm_steps`` first, as there) plus evaluator.py:250-252's ``evaluate_mlm`` over
     ``params.mlm_steps``, on the 'valid' split.

@@ -148,6 +148,8 @@ SIGNATURES = {
     'm3p_lamb_update_guarded': (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _f, _f, _f, _p, _f, _f, _p, _p, _p]),
     'm3p_lamb_norms_guarded': (_i, [_p, _p, _i, _p, _p, _p]),
     'm3p_lamb_apply_guarded': (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _i, _f, _p, _p]),
+    'm3p_ema_update': (_i, [_p, _p, _p, _p, _i, _f, _p, _p]),
+    'm3p_ema_swap': (_i, [_p, _p, _p, _p, _p, _i, _p]),
     'm3p_itm_score_fwd': (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     'm3p_itm_score_bwd': (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _p]),
     'm3p_gelu_bwd': (_i, [_p, _p, _p, C.c_longlong, _p]),

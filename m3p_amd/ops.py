@@ -1410,6 +1410,31 @@ def adam_step_ranges(p, g, m, v, w16, pieces, lr, beta1, beta2, eps, weight_deca
     L.check(rc, 'm3p_adam_step_ranges')
 
 
+def _ema_pieces(pieces):
+    n = len(pieces)
+    starts = (C.c_longlong * max(n, 1))(*[int(a) for a, _ in pieces])
+    counts = (C.c_longlong * max(n, 1))(*[int(b) - int(a) for a, b in pieces])
+    return starts, counts, n
+
+
+def ema_update(p, ema, pieces, w, skip=None):
+    """ema += w * (p - ema) over the pieces [(start, end)] of two flat fp32 arenas (m3p_ema_update; the rule's fp32 arithmetic
+    is in include/m3p_hip.h).  w: 1 - decay, rounded to fp32 here.  skip: the guard's device word or None."""
+    starts, counts, n = _ema_pieces(pieces)
+    if n == 0:
+        return
+    rc = L.load().m3p_ema_update(p.data_ptr(), ema.data_ptr(), starts, counts, n, float(w), L.ptr(skip), L.stream())
+    L.check(rc, 'm3p_ema_update')
+
+
+def ema_swap(p, ema, w16, pieces):
+    """p <-> ema over the pieces [(start, end)], w16 = bf16(new p) (m3p_ema_swap); w16 may be None."""
+    starts, counts, n = _ema_pieces(pieces)
+    if n == 0:
+        return
+    L.check(L.load().m3p_ema_swap(p.data_ptr(), ema.data_ptr(), L.ptr(w16), starts, counts, n, L.stream()), 'm3p_ema_swap')
+
+
 LAMB_MAX_CLASSES = 32          # M3P_LAMB_MAX_CLASSES of include/m3p_hip.h
 _LAMB_PIECE_BYTES = 32         # M3P_LAMB_PIECE_BYTES
 

@@ -17,11 +17,15 @@ Semantics kept from the reference:
 Beyond the reference: Lamb and its two scheduled forms - Adam's moments with a per-tensor trust ratio, on the same arenas and
 state, three launches per step (m3p_lamb_update / _norms / _apply; the rule is written out in include/m3p_hip.h).  And the
 opt-in non-finite guard (`Adam.guard_nonfinite`, `reconcile`, `roll_back`): a step whose global gradient norm is NaN or
-infinite is skipped on the device, counted there, and taken back out of the host's counts at the next reconcile.
+infinite is skipped on the device, counted there, and taken back out of the host's counts at the next reconcile.  And the
+opt-in exponential moving average of the weights (`Adam.enable_ema`, `ema_weights`, `ema_state`): one more fp32 arena,
+one streaming launch per arena at the end of a step, and a swap of master and bf16 copy for evaluation.
 """
+import contextlib
 import inspect
 import math
 import re
+from logging import getLogger
 
 import torch
 from torch import optim
@@ -29,6 +33,8 @@ from torch import optim
 import os
 
 from . import ops
+
+logger = getLogger()
 
 # developer switch for A/B runs: 0 = the fused Adam pass zeroes the vocabulary gradient like every other range (round 4)
 _LAZY_VOCAB_ZERO = os.environ.get('M3P_LAZY_VOCAB_ZERO', '1') != '0'
@@ -62,6 +68,9 @@ class Adam(optim.Optimizer):
     # so state[p]['step'], num_updates and the lr move with every attempt; reconcile() - the one host read - takes the
     # skipped attempts back out.  Until then bias corrections and schedule run one attempt ahead per unreconciled skip.
     guard_nonfinite = False
+    # Opt-in exponential moving average of the weights (`enable_ema`; Lamb and the scheduled classes inherit it): None = off,
+    # and then step() does nothing but test this attribute.  Else the schedule and its counters (see enable_ema).
+    _ema = None
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
         if not 0.0 <= lr:
@@ -185,6 +194,8 @@ class Adam(optim.Optimizer):
     # ------------------------------------------------------------------ step
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self._ema is not None and self._ema['inside']:
+            raise RuntimeError('step() inside ema_weights(): the parameters hold the averaged weights - leave the context first')
         if self.guard_nonfinite:
             self._open_guarded_step()
         max_norm = self._pending_clip or 0.0
@@ -220,11 +231,206 @@ class Adam(optim.Optimizer):
             # untouched ranges may still hold stale values only if someone wrote them by hand
             arena.after_fused_step(copies_scheduled=gathered)
         self._step_loose(max_norm)
+        if self._ema is not None:
+            self._ema_step()
         if self._skip is not None:
             self._guard_log.append((self._attempts, bumped, [g for g in self.param_groups if 'num_updates' in g]))
             self._attempts += 1
             self._skip = None
         return loss
+
+    # ------------------------------------------------------------------ exponential moving average of the weights
+    def enable_ema(self, decay, every=1, start=0):
+        """Keep ema = decay * ema + (1 - decay) * p of every parameter, updated at the end of the step() calls with index
+        start, start + every, start + 2 * every, ... (calls are counted from this call on, skipped attempts of the non-finite
+        guard included: the host does not know the verdict).  The update is `ema += w * (p - ema)` with w = fp32(1 - decay) in
+        fp32 (include/m3p_hip.h, m3p_ema_update: product and sum fused on the arenas, each rounded for a parameter outside
+        one); the first one, at `start`, is a copy.  Until then
+        the EMA holds the weights as they are now.
+
+        Costs 4 bytes per parameter: one more fp32 arena (`ent['ema']`) beside master, gradient and the two moments, and a
+        clone of every parameter outside an arena.  state[p]['ema'] is a view of it, as exp_avg is of the moment arena.  The
+        WHOLE arena is averaged in one launch per arena, not the active ranges: a parameter that sat out a step still decays
+        towards its value.  Under the sharded data-parallel exchange a rank averages its own shards; `materialize_ema`
+        gathers.  With the guard on, the launch takes the guard's device word: a skipped step leaves the EMA's bits alone."""
+        decay, every, start = float(decay), int(every), int(start)
+        if not 0.0 < decay < 1.0:
+            raise ValueError('Invalid EMA decay: {} (0 < decay < 1)'.format(decay))
+        if every < 1 or start < 0:
+            raise ValueError('Invalid EMA schedule: every = {} (>= 1), start = {} (>= 0)'.format(every, start))
+        if self._ema is not None:
+            raise RuntimeError('enable_ema: already enabled')
+        w = torch.tensor(1.0 - decay, dtype=torch.float64).to(torch.float32).item()      # exactly the fp32 the kernel is given
+        for ent in self._arenas.values():
+            ent['ema'] = ent['arena'].master.clone()
+            # sharded exchange: are the other ranks' shards of the EMA out of date?  (Now: exactly where the master's are.)
+            ent['ema_partial'] = bool(getattr(self._hook(ent['arena']), 'master_partial', False))
+        for group in self.param_groups:
+            for p in group['params']:
+                tag = getattr(p, '_m3p_arena', None)
+                if tag is not None:
+                    arena, name = tag
+                    o, cnt, shape = arena.offsets[name]
+                    self.state[p]['ema'] = self._arenas[id(arena)]['ema'][o:o + cnt].view(shape)
+                else:
+                    self.state[p]['ema'] = p.data.clone()
+        self._ema = dict(decay=decay, w=w, every=every, start=start, calls=0, inside=False)
+
+    def _ema_step(self):
+        """The end of step(): this call's EMA update, if the schedule names it.  One launch per arena over what this rank
+        owns of [0, total); the plain torch form of the same rule for the parameters outside an arena."""
+        st = self._ema
+        index = st['calls']
+        st['calls'] = index + 1
+        if index < st['start'] or (index - st['start']) % st['every'] != 0:
+            return
+        first = index == st['start']
+        for ent in self._arenas.values():
+            arena = ent['arena']
+            pieces = self._owned(arena, 0, arena.total)
+            if first:
+                # (a copy, not a launch with w = 1: e + (p - e) is not p in fp32.  A skipped first step copies the master it
+                #  left alone)
+                for a, b in pieces:
+                    ent['ema'][a:b].copy_(arena.master[a:b])
+            else:
+                ops.ema_update(arena.master, ent['ema'], pieces, st['w'], skip=self._skip)
+            hook = self._hook(arena)
+            ent['ema_partial'] = hook is not None and getattr(hook, 'mode', None) == 'zero1'
+        for group in self.param_groups:
+            for p in group['params']:
+                if getattr(p, '_m3p_arena', None) is not None:
+                    continue
+                e = self._ema_of(p)
+                if first:
+                    e.copy_(p.data)
+                else:
+                    e.add_((p.data - e).mul_(st['w']))
+
+    def materialize_ema(self):
+        """Collective under the sharded data-parallel exchange (every rank): gather the EMA's shards so that every rank holds
+        all of it.  Nothing to do in the replicated modes, or when no update ran since the last gather."""
+        if self._ema is None:
+            raise RuntimeError('materialize_ema: call enable_ema first')
+        for ent in self._arenas.values():
+            hook = self._hook(ent['arena'])
+            if hook is not None and ent['ema_partial']:
+                hook.materialize_ema(ent['ema'])
+            ent['ema_partial'] = False
+
+    def _ema_swap(self):
+        """Weights <-> EMA, everywhere they live: fp32 master and bf16 working copy in one pass (ops.ema_swap), the transposed
+        copies marked stale and the arena's epoch moved (8-bit weight copies and vocab_mean() key on it), parameters outside an
+        arena through copy_ (their _version moves: decoder.ArenaCrossWeights re-makes its copies)."""
+        self.materialize_ema()
+        for ent in self._arenas.values():
+            arena = ent['arena']
+            hook = self._hook(arena)
+            if hook is not None:
+                hook.materialize_master()
+                hook.params_ready(None)
+            ops.ema_swap(arena.master, ent['ema'], arena.w16, [(0, arena.total)])
+            arena.mark_updated_by_fused_optimizer()       # master and w16 written together: only the transposes are stale
+        for group in self.param_groups:
+            for p in group['params']:
+                if getattr(p, '_m3p_arena', None) is None:
+                    e = self._ema_of(p)
+                    raw = p.data.clone()
+                    with torch.no_grad():
+                        p.copy_(e)           # (on the parameter itself, not on .data: p._version moves)
+                    e.copy_(raw)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Context manager (a collective under data parallelism: every rank enters and leaves): inside it the model computes
+        with the averaged weights - master, bf16 copy, transposes and everything keyed on Arena.epoch - and state[p]['ema']
+        holds the raw ones; leaving swaps back, to the bit.  Evaluate and save inside it; do not train: step() raises, and
+        entering with gradients pending (a backward without its step) is refused."""
+        st = self._ema
+        if st is None:
+            raise RuntimeError('ema_weights: call enable_ema first')
+        if st['inside']:
+            raise RuntimeError('ema_weights does not nest')
+        for ent in self._arenas.values():
+            if ent['arena'].touched:
+                raise RuntimeError('ema_weights: gradients are pending (%d parameters touched since the last step or zero_grad): '
+                                   'step or zero_grad first' % len(ent['arena'].touched))
+        self._ema_swap()
+        st['inside'] = True
+        try:
+            yield self
+        finally:
+            st['inside'] = False
+            self._ema_swap()
+
+    def _ema_of(self, p):
+        """The EMA of a parameter of this optimizer, else None: the view of the EMA arena (made afresh - whoever detached
+        state[p]['ema'] for a checkpoint did not detach this), or the clone kept for a parameter outside an arena."""
+        tag = getattr(p, '_m3p_arena', None)
+        if tag is not None:
+            ent = self._arenas.get(id(tag[0]))
+            if ent is None or 'ema' not in ent or p not in self.state:
+                return None
+            o, cnt, shape = tag[0].offsets[tag[1]]
+            return ent['ema'][o:o + cnt].view(shape)
+        return self.state[p].get('ema') if p in self.state else None
+
+    def _ema_named(self, named):
+        if named is not None:
+            return list(named)
+        out = []
+        for gi, group in enumerate(self.param_groups):
+            for pi, p in enumerate(group['params']):
+                tag = getattr(p, '_m3p_arena', None)
+                out.append((tag[1] if tag is not None else 'group%d.%d' % (gi, pi), p))
+        return out
+
+    def ema_state(self, named=None):
+        """{name: fp32 CPU tensor} of the materialised EMA, for checkpoints (a collective under the sharded exchange).
+        named: (name, tensor) pairs that give the keys - e.g. ``model.state_dict(keep_vars=True).items()``, which makes the
+        result load into a model; entries that are not parameters of this optimizer are copied as they are.  Default: the
+        arena's names, and 'group<g>.<i>' for a parameter outside an arena."""
+        if self._ema is None:
+            raise RuntimeError('ema_state: call enable_ema first')
+        if self._ema['inside']:
+            raise RuntimeError('ema_state inside ema_weights(): the buffers are exchanged')
+        self.materialize_ema()
+        out = {}
+        for name, t in self._ema_named(named):
+            e = self._ema_of(t)
+            out[name] = (t if e is None else e).detach().float().cpu().clone()
+        return out
+
+    def load_ema_state(self, d, named=None, warn=True):
+        """Write an `ema_state` back (names as there).  A parameter whose name is missing starts its EMA at its current
+        weights; one warning names how many.  A collective under the sharded exchange."""
+        if self._ema is None:
+            raise RuntimeError('load_ema_state: call enable_ema first')
+        if self._ema['inside']:
+            raise RuntimeError('load_ema_state inside ema_weights(): the buffers are exchanged')
+        for ent in self._arenas.values():
+            hook = self._hook(ent['arena'])
+            if hook is not None:
+                hook.materialize_master()        # (a missing name copies the master: all of it must be current here)
+                hook.params_ready(None)
+        missing, seen = [], set()
+        for name, t in self._ema_named(named):
+            e = self._ema_of(t)
+            if e is None or id(t) in seen:
+                continue
+            if name in d:
+                seen.add(id(t))
+                e.copy_(d[name].to(e.device, torch.float32).view_as(e))
+            else:
+                missing.append((name, t))
+        missing = [(name, t) for name, t in missing if id(t) not in seen]
+        for name, t in missing:
+            self._ema_of(t).copy_(t.data)
+        if missing and warn:
+            logger.warning('load_ema_state: %d parameters are not in the saved EMA and start from their current weights (%s ...)'
+                           % (len(missing), missing[0][0]))
+        for ent in self._arenas.values():
+            ent['ema_partial'] = False
 
     # ------------------------------------------------------------------ non-finite guard
     def _open_guarded_step(self):

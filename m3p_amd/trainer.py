@@ -16,6 +16,7 @@ stay on the device and are only read when ``print_stats`` prints; clip + Adam + 
 one fused kernel pass; DDP is our bucketed reducer (m3p_amd/distributed.py).  ``mt_step`` (:1383-1441) and ``ic_step`` (:1443-1515) are the
 translation / captioning steps on the causal stream.  Not built: the FreeLB / sliding-window steps (out of scope).
 """
+import contextlib
 import math
 import os
 import time
@@ -118,6 +119,17 @@ class Trainer(object):
                 setattr(self, name, wrapped)
                 for opt in self.optimizers.values():
                     opt.grad_scale = 1.0 / wrapped.world
+        # exponential moving average of the weights (not a reference flag): absent = off, so old
+        # params.pkl files load.  Enabled behind the data-parallel broadcast: the EMA starts as a copy of the weights.
+        self.ema_decay = float(getattr(params, 'ema_decay', 0) or 0)
+        self.ema_eval = self.ema_decay > 0 and bool(getattr(params, 'ema_eval', True))
+        self._in_ema = False
+        if self.ema_decay > 0:
+            for opt in self.optimizers.values():
+                if not hasattr(opt, 'enable_ema'):
+                    raise ValueError('ema_decay needs one of the fused optimizers (adam*, lamb*), got %s' % type(opt).__name__)
+            for opt in self.optimizers.values():
+                opt.enable_ema(self.ema_decay, every=int(getattr(params, 'ema_every', 1)), start=int(getattr(params, 'ema_start', 0)))
         # probability of masking out / keeping / randomising the words to predict
         params.pred_probs = torch.FloatTensor([getattr(params, 'word_mask', 0.8), getattr(params, 'word_keep', 0.1),
                                                getattr(params, 'word_rand', 0.1)])
@@ -608,6 +620,44 @@ class Trainer(object):
             hook = getattr(_unwrap(getattr(self, n)), 'ddp_hook', None)
             if hook is not None:
                 hook.materialize_master()
+        if self.ema_decay > 0 and not self._in_ema:       # the EMA's shards likewise: checkpoints carry all of it
+            for opt in self.optimizers.values():
+                opt.materialize_ema()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the models compute with the exponential moving average of their weights (``params.ema_decay``; every
+        optimizer's `Adam.ema_weights`), for evaluation and for saving the model that scored: ``run_all_evals(..., ema=
+        trainer.ema_weights())``.  A collective under data parallelism - every rank enters and leaves.  No training inside."""
+        if self.ema_decay <= 0:
+            raise RuntimeError('ema_weights: params.ema_decay is not set')
+        with contextlib.ExitStack() as stack:
+            for opt in self.optimizers.values():
+                stack.enter_context(opt.ema_weights())
+            self._in_ema = True
+            try:
+                yield self
+            finally:
+                self._in_ema = False
+
+    def _ema_named(self, n):
+        sd = _unwrap(getattr(self, n)).state_dict(keep_vars=True)
+        return list(sd.items())
+
+    def _ema_state_dicts(self):
+        """{'<name>_ema': the materialised EMA of model <name> in state-dict form}.  Inside ema_weights() the parameters hold
+        the EMA (and the optimizers' buffers the raw weights): the key then repeats the model's own entry."""
+        if self._in_ema:
+            return {'%s_ema' % n: sd for n, sd in self._state_dicts().items()}
+        out = {}
+        for n in self.MODEL_NAMES:
+            named = self._ema_named(n)
+            sd = {}
+            for opt in self.optimizers.values():
+                part = opt.ema_state(named)
+                sd.update({k: part[k] for k, v in named if k not in sd or v in opt.state})
+            out['%s_ema' % n] = sd
+        return out
 
     def _state_dicts(self):
         # sharded data parallelism (distributed.py, zero1): since round 4 the forward-side gathers move the bf16 working copy
@@ -650,9 +700,13 @@ class Trainer(object):
         data = {'epoch': self.epoch, 'n_total_iter': self.n_total_iter, 'best_metrics': self.best_metrics,
                 'best_stopping_criterion': self.best_stopping_criterion}
         data.update(self._state_dicts())
+        if self.ema_decay > 0:         # one key per model that the reference's loader ignores; none with EMA off
+            data.update(self._ema_state_dicts())
         if include_optimizers:
             for n, opt in self.optimizers.items():
                 sd = opt.state_dict()
+                if self.ema_decay > 0:               # (the EMA travels once, under '<name>_ema', not per parameter in here too)
+                    sd['state'] = {i: {k: v for k, v in st.items() if k != 'ema'} for i, st in sd['state'].items()}
                 for st in sd['state'].values():      # moments are views of the flat arenas: detach them from it
                     for k, v in st.items():
                         if torch.is_tensor(v):
@@ -681,6 +735,16 @@ class Trainer(object):
             if all(k.startswith('module.') for k in sd):
                 sd = {k[len('module.'):]: v for k, v in sd.items()}
             _unwrap(getattr(self, n)).load_state_dict(sd)
+            if self.ema_decay > 0:
+                ema = data.get('%s_ema' % n)
+                if ema is None:
+                    logger.warning('No "%s_ema" in %s: the EMA starts as a copy of the loaded weights.' % (n, path))
+                    ema = {}
+                elif all(k.startswith('module.') for k in ema):
+                    ema = {k[len('module.'):]: v for k, v in ema.items()}
+                named = self._ema_named(n)
+                for opt in self.optimizers.values():
+                    opt.load_ema_state(ema, named, warn=bool(ema))
         for n, opt in self.optimizers.items():
             saved = data.get('%s_optimizer' % n)
             if saved is None:
@@ -703,8 +767,16 @@ class Trainer(object):
             self.save_model('periodic-%i' % self.epoch)
 
     def save_best_model(self, scores):
-        """:610-625: one 'best-<metric>' model + checkpoint per validation metric that improved."""
+        """:610-625: one 'best-<metric>' model + checkpoint per validation metric that improved.  With ``params.ema_eval`` the
+        scores are the averaged model's (run_all_evals(..., ema=...)), and the files are written from inside ema_weights():
+        they hold the averaged weights, the ones that scored."""
         self._sync_master()
+        if self.ema_eval and not self._in_ema:
+            with self.ema_weights():           # (a collective: entered by every rank, before the master-rank test)
+                return self._save_best_model(scores)
+        return self._save_best_model(scores)
+
+    def _save_best_model(self, scores):
         if not getattr(self.params, 'is_master', True):
             return
         for metric, biggest in self.metrics:
